@@ -16,15 +16,18 @@ driver's form; WORLD_SIZE must equal N), or plainly as `python bench.py --gpus N
 WORLD_SIZE in the environment and N > 1 this process starts N children itself, one per GPU,
 BEFORE anything touches a GPU, relays rank 0's line and exits with their status.
 
-Timing: W untimed warmup steps, then R repetitions (default 5) of EXACTLY K steps, each
-repetition bracketed by a barrier + torch.cuda.synchronize() on both sides, MAX over ranks per
-repetition; `ms_per_step`/`value` are the MEDIAN repetition (min and max are in the line too):
-K steps of a 13 us kernel are over in a fraction of a millisecond, and one such region swings
-by 10 % with launch-train edge effects.
+Timing: a clock preheat on states of its own (the measured states never see it, so what they compute does not
+depend on how long it ran), W untimed warmup steps, then EXACTLY K timed steps bracketed by a barrier +
+torch.cuda.synchronize() on both sides, MAX over ranks; `ms_per_step` = that time / K.  Under --full the timed
+region is repeated R times (default 5) and `ms_per_step`/`value` are the MEDIAN repetition (min and max are in the
+line too): K steps of a 13 us kernel are over in a fraction of a millisecond, and one such region swings by 10 %
+with launch-train edge effects.
 
 Prints ONE JSON line on rank 0 (contract in the task description): value = whole-job input
 Msamples/s, plus "roofline" (algorithmic HBM bytes per launch / launch time measured with HIP
-events on the launch stream, vs the 8 TB/s HBM peak), "parity" (first chunk of up to four
+events on the launch stream, vs the 8 TB/s HBM peak).  `--dump-outputs DIR` writes what the last
+timed step handed its caller (dump_outputs).  A plain run stops there; `--full` adds what takes
+runs of its own: "box" (the clock the chip holds under load), "parity" (first chunk of up to four
 streams checked against the CPU oracle) and, at N=1, "cpu_baseline" (the reference's own C
 timed on the host cores) and the HOST-FED legs, reported beside `value`, never as it: "end_to_end"
 (the host-buffer call a Node caller makes, PCIe included: pageable input, and -- round 6 -- a chunk
@@ -47,9 +50,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "node-speex-resampler_amd", "python"))
-# (the 32-stream pinned legs of end_to_end_streams hold 32 x (4.2 + 4.6) MB of the library's pinned blocks at once: more
-#  than the default cap of 256 MiB on its slabs -- a documented limit of the library, include/speexhip_resampler.h)
-os.environ.setdefault("SPEEXHIP_TAKE_MAX_MB", "1024")
 
 CONFIGS = {
     # name: (channels, in_rate, out_rate, quality) -- BASELINE.json configs[1..3] (+ SURVEY F3)
@@ -65,6 +65,8 @@ VALU_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: fp32 vector peak
 VALU64_PEAK_TFLOPS = 78.6  # fp64 vector peak: v_fma_f64 issues at the rate of v_pk_fma_f32, half the FMAs each
                            # (tools/ubench_fma64.hip, profiles/r04_ubench_fma64.txt)
 PMC_FILE = os.path.join("profiles", "pmc_traffic.json")
+DUMP_BUDGET_BYTES = 56 << 20  # --dump-outputs: output samples written at most (float32)
+DUMP_SEED = 20240601          # the fixed sample of streams (and frames) beyond that budget
 
 
 def wrapper_capacity(chunk_bytes, in_rate, out_rate, channels):
@@ -387,6 +389,40 @@ def cpu_baseline(cfg, frames, budget_s=12.0, max_chunks=32):
                 chunks, frames, ch, dt)}
 
 
+def dump_outputs(out_dir, d_out, used, made, mine):
+    """--dump-outputs DIR: what the last timed step handed its caller -- stream j's first made[j] frames of
+    d_out[j] (int16 samples, or float for --io float, as float32) and the per-stream counters:
+      output.npy    float32 (frames, ch): the dumped pieces, one after the other
+      consumed.npy  float64 (S,): input frames each stream consumed in that step
+      produced.npy  float64 (S,): output frames each stream produced in it
+      pieces.npy    float64 (k, 3): [global stream id, first frame, frames] of each piece of output.npy
+    Every stream in full while that fits in DUMP_BUDGET_BYTES; beyond it a fixed, seeded sample of whole streams
+    (or one seeded window of frames, should a single stream's output exceed the budget alone)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    S, ch = d_out.shape[0], d_out.shape[2]
+    left = DUMP_BUDGET_BYTES // (4 * ch)  # frames
+    order = range(S) if sum(made) <= left else np.random.default_rng(DUMP_SEED).permutation(S)
+    pieces = []
+    for j in order:
+        n = int(made[j])
+        if n <= left:
+            pieces.append((int(j), 0, n))
+            left -= n
+        elif not pieces:
+            f0 = int(np.random.default_rng(DUMP_SEED + int(j)).integers(0, n - left + 1))
+            pieces.append((int(j), f0, left))
+            left = 0
+    pieces.sort()
+    out = (torch.cat([d_out[j, f0:f0 + n] for j, f0, n in pieces]) if pieces else d_out.new_zeros((0, ch)))
+    np.save(os.path.join(out_dir, "output.npy"), out.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(out_dir, "consumed.npy"), np.asarray(used, np.float64))
+    np.save(os.path.join(out_dir, "produced.npy"), np.asarray(made, np.float64))
+    np.save(os.path.join(out_dir, "pieces.npy"), np.asarray([(mine[j], f0, n) for j, f0, n in pieces],
+                                                           np.float64).reshape(-1, 3))
+
+
 def usable_cores():
     """Cores this process may actually use: the affinity mask and the container's CPU quota (cgroup v2 cpu.max, v1
     cfs_quota) bound os.cpu_count() -- a box that shows 256 cores to a container limited to a dozen ran 256 workers at
@@ -488,8 +524,9 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=5,
-                    help="repetitions of the K-step timed region; the median is reported")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of the K-step timed region, the median is reported (default: 1, so that "
+                         "exactly K steps are timed; 5 under --full)")
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--custom", default=None, help="channels,in_rate,out_rate,quality (overrides --config)")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("BENCH_STREAMS", "1")),
@@ -509,11 +546,25 @@ def parse_args(argv=None):
                     help="run the hot path for this long before the W warmup steps: the GPU leaves its idle "
                          "clocks only after some milliseconds of load (measured: the first ~30 ms of a "
                          "launch train run 20-30 %% slower), and W steps of a 15 us kernel are over before that")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: repetitions of the timed region, the "
+                         "chip's clock, parity against the CPU oracle and, at N = 1, the CPU baseline and the "
+                         "host-fed legs (a plain run times the K steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/*.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)  # (child of cpu_baseline_workers)
     ap.add_argument("--host-legs", action="store_true", help=argparse.SUPPRESS)  # (child: the host-fed legs, see host_legs)
     ap.add_argument("--no-parity", action="store_true")
     return ap.parse_args(argv)
+
+
+def timed_reps(args):
+    """Repetitions of the K-step timed region: --reps when given, else one in a plain run (exactly K timed steps)
+    and five under --full."""
+    if args.reps is not None:
+        return max(1, args.reps)
+    return 5 if args.full else 1
 
 
 def launch_ranks(args):
@@ -560,9 +611,15 @@ def launch_ranks(args):
 
 
 def main():
+    # (the 32-stream pinned legs of end_to_end_streams hold 32 x (4.2 + 4.6) MB of the library's pinned blocks at once: more
+    #  than the default cap of 256 MiB on its slabs -- a documented limit of the library, include/speexhip_resampler.h.
+    #  Set here, not at import: a process that only loads this file, as the tests do, keeps the library's default.)
+    os.environ.setdefault("SPEEXHIP_TAKE_MAX_MB", "1024")
     args = parse_args()
     if args.gpus < 1:
         sys.exit("--gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("--steps must be >= 1")
     if args.cpu_worker:
         cpu_worker(args.cpu_worker)
         return
@@ -574,7 +631,8 @@ def main():
     # configs[4]'s CPU column (strong-scaling line at N = 1): min(cores, T) worker processes, started -- and finished --
     # before anything in this process touches a GPU
     cpu_many = None
-    if args.gpus == 1 and args.total_streams > 0 and not args.no_cpu_baseline and "WORLD_SIZE" not in os.environ:
+    if (args.full and args.gpus == 1 and args.total_streams > 0 and not args.no_cpu_baseline
+            and "WORLD_SIZE" not in os.environ):
         cfg0 = tuple(int(v) for v in args.custom.split(",")) if args.custom else CONFIGS[args.config]
         cpu_many = cpu_baseline_workers(cfg0, args.frames, args.total_streams)
 
@@ -646,26 +704,32 @@ def main():
     used, made = step(0)
     torch.cuda.synchronize()
     first_chunks = []
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         for j in sorted(set([0, S // 3, (2 * S) // 3, S - 1])):
             first_chunks.append((mine[j], d_out[0][j, : made[j]].cpu().numpy(), used[j], made[j]))
     # checksum of the first step's outputs (all streams of this rank): deterministic, unlike the
     # buffers after a time-based preheat
     first_sum = int((d_out[0] * (32768.0 if fio else 1)).to(torch.int64).sum().item())
 
-    # clock ramp (untimed, before the warmup steps): same calls as the timed loop
+    # clock ramp (untimed, before the warmup steps): the calls of the timed loop, on states of their own -- the
+    # measured states then run a fixed sequence of calls (first chunk, W warmup steps, the timed steps), and what
+    # the last timed step computes does not depend on how many steps the time-based ramp took
+    heat = speexhip.Batch(S, ch, fi, fo, q, mode=mode) if args.preheat_ms > 0 else None
     t_heat, i_heat = time.perf_counter(), 0
-    while (time.perf_counter() - t_heat) * 1e3 < args.preheat_ms:
+    while heat is not None and (time.perf_counter() - t_heat) * 1e3 < args.preheat_ms:
         for _ in range(64):
-            step(i_heat)
+            b = i_heat % nbuf
+            heat.process_device(d_in[b].data_ptr(), F * ch, F, d_out[b].data_ptr(), cap * ch, cap, sp, float_io=fio)
             i_heat += 1
         torch.cuda.synchronize()
+    if heat is not None:
+        heat.close()
     for i in range(args.warmup):
         step(i + 1)
     torch.cuda.synchronize()
 
-    # R repetitions of exactly K steps; each is bracketed by barrier + synchronize on both sides
-    reps = max(1, args.reps)
+    # R repetitions (one in a plain run) of exactly K steps; each is bracketed by barrier + synchronize on both sides
+    reps = timed_reps(args)
     wall, gpu, issue = [], [], []
     consumed = produced = 0
     it = args.warmup + 1
@@ -695,11 +759,15 @@ def main():
     checksum = dist_util.reduce_int(first_sum, ctl)
 
     rc = 0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out[(it - 1) % nbuf], u, m, mine)
     if rank == 0:
-        try:
-            box_ghz = speexhip.device_clock()  # (after the timed region)
-        except AttributeError:                 # (an older library loaded through SPEEXHIP_LIB_PATH for an A/B)
-            box_ghz = (0.0, 0.0)
+        box_ghz = None
+        if args.full:
+            try:
+                box_ghz = speexhip.device_clock()  # (after the timed region)
+            except AttributeError:                 # (an older library loaded through SPEEXHIP_LIB_PATH for an A/B)
+                box_ghz = (0.0, 0.0)
         elapsed_med = statistics.median(wall)
         value = total_in_samples / elapsed_med / 1e6
         # dominant kernel = the one launch per step; algorithmic bytes per launch:
@@ -770,17 +838,18 @@ def main():
                      "frac": round(tfl / valu_peak, 4), "flops_per_launch": int(flops),
                      "arithmetic": "fp64 vector" if valu_peak == VALU64_PEAK_TFLOPS else "fp32 vector"},
             "checksum": checksum,
+        }
+        if box_ghz is not None:
             # which kind of box this was: the shader clock held under an FIR-like load (the pool's boxes differ by
             # 4-6 %: lines of different leases compare at equal clocks only)
-            "box": {"shader_ghz_under_load": round(box_ghz[0], 3), "slowest_workgroup_ghz": round(box_ghz[1], 3)},
-        }
+            line["box"] = {"shader_ghz_under_load": round(box_ghz[0], 3), "slowest_workgroup_ghz": round(box_ghz[1], 3)}
         if share:
             line["config"]["parallelism"] += "; TEST RUN: all ranks share GPU 0 (BENCH_SHARE_GPU=1, gloo) -- not a measurement"
         if first_chunks:
             line["parity"], ok = parity_block(cfg, F, first_chunks, fio)
             if not ok:
                 rc = 3
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the host-fed legs and the link probe: a child process without torch (host_legs: the runtime a Node / C caller
             # of the drop-in loads); this process is idle meanwhile
             child = subprocess.run([sys.executable, os.path.abspath(__file__), "--host-legs", "--config", args.config,

@@ -273,7 +273,11 @@ def test_bench_stream_sharding_matches_dist_util():
         assert parts == [dist_util.shard_streams(total, world, r) for r in range(world)]
     assert all(len(bench.shard_streams(256, 8, r)) == 32 for r in range(8))
     a = bench.parse_args(["--gpus", "8", "--total-streams", "256"])
-    assert (a.gpus, a.total_streams, a.steps, a.reps) == (8, 256, 200, 5)
+    assert (a.gpus, a.total_streams, a.steps, bench.timed_reps(a)) == (8, 256, 200, 1)
+    assert not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--gpus", "8", "--total-streams", "256", "--full"])
+    assert (a.gpus, a.total_streams, a.steps, bench.timed_reps(a)) == (8, 256, 200, 5)
+    assert bench.timed_reps(bench.parse_args(["--reps", "3"])) == 3
 
 
 class _ChannelModel:
@@ -753,6 +757,9 @@ def test_node_batch_class_and_many_call_check_their_arguments_without_a_gpu():
     processMany, the reference's messages through the batch, the init failure surfacing as Error(strerror) -- and the
     addon loading in a worker_threads Worker (NAPI_MODULE_INIT), with initPromise resolving behind a warm-up that fails
     quietly (no GPU is reported by the first real call, like every error of the reference)."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present")
     index = os.path.join(ROOT, "node-speex-resampler_amd", "index.js")
     if not os.path.exists(os.path.join(ROOT, "node-speex-resampler_amd", "speex_hip_napi.node")):
         pytest.skip("addon not built")

@@ -1273,9 +1273,9 @@ def test_bench_n_rank_path_end_to_end_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["BENCH_SHARE_GPU"] = "1"
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--reps", "2",
-            "--frames", "65536", "--preheat-ms", "20"]
+            "--frames", "65536", "--preheat-ms", "20", "--full"]
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--reps", "2",
-                          "--frames", "65536", "--preheat-ms", "20", "--no-cpu-baseline"], env=env, capture_output=True,
+                          "--frames", "65536", "--preheat-ms", "20", "--no-cpu-baseline", "--full"], env=env, capture_output=True,
                          text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     d1 = json.loads(one.stdout.strip().splitlines()[-1])
@@ -1303,7 +1303,7 @@ def test_bench_n_rank_path_end_to_end_on_one_gpu():
     # BASELINE configs[4] in its full shape -- 8 ranks, 256 streams, 32 per rank, each rank's launch fed through
     # its launches of 32 -- on this one GPU (short chunks): what an 8-GPU node will run (tools/scale.sh)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--total-streams", "256", "--steps", "3",
-                        "--warmup", "1", "--reps", "2", "--frames", "65536", "--preheat-ms", "10"], env=env,
+                        "--warmup", "1", "--reps", "2", "--frames", "65536", "--preheat-ms", "10", "--full"], env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1313,6 +1313,40 @@ def test_bench_n_rank_path_end_to_end_on_one_gpu():
     assert d["config"]["streams_per_gpu"] == 32 and d["config"]["streams_total"] == 256
     assert abs(d["value"] - 256 * 65536 * 2 / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 0.01
     assert d["parity"]["counters_equal"] and d["parity"]["max_abs_diff_lsb"] <= 1
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_one(tmp_path):
+    """A plain bench.py run times exactly --steps steps (one repetition) and leaves the --full blocks out of its line;
+    --dump-outputs writes what the last timed step handed its caller: the same bytes however long the clock preheat
+    ran, and in EXACT mode the oracle's output for that chunk after the same call sequence (first chunk, W warmup
+    steps, K timed steps over the rotating input buffers)."""
+    import json
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    F, K, W = 65536, 7, 3
+    dumps = []
+    for heat in ("20", "80"):
+        out = str(tmp_path / ("heat" + heat))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(K), "--warmup", str(W),
+                            "--frames", str(F), "--mode", "exact", "--preheat-ms", heat, "--dump-outputs", out],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads(r.stdout.strip().splitlines()[-1])
+        assert d["steps"] == K and d["warmup"] == W and d["timing"]["reps"] == 1 and d["ms_per_step"] > 0
+        assert not {"parity", "cpu_baseline", "end_to_end", "box"} & set(d), sorted(d)
+        dumps.append({n: np.load(os.path.join(out, n + ".npy")) for n in ("output", "consumed", "produced", "pieces")})
+    a, b = dumps
+    for n in a:
+        assert a[n].dtype in (np.float32, np.float64) and np.array_equal(a[n], b[n]), n
+    ch, fi, fo, q = 2, 44100, 48000, 7
+    base = orc.lcg_pcm(F * ch, 12345).reshape(F, ch)
+    cap, _ = orc.wrapper_capacity(F * ch * 2, fi, fo, ch)
+    eng = orc.Oracle(ch, fi, fo, q)
+    for i in range(1 + W + K):  # buffer i holds the input rolled by 17 * i frames (bench.py: fewer than 256 buffers here)
+        want, used = eng.process(np.ascontiguousarray(np.roll(base, 17 * i, axis=0)), cap)
+    assert a["pieces"].tolist() == [[0, 0, want.shape[0]]]
+    assert a["consumed"].tolist() == [used] and a["produced"].tolist() == [want.shape[0]]
+    assert np.array_equal(a["output"], want.astype(np.float32))
 
 
 def test_states_recycle_device_resources_through_the_pool():

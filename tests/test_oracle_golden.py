@@ -58,20 +58,24 @@ def test_oracle_error_paths():
     orc.Oracle(1, 8000, 8000, 0)  # quality 0 is accepted (reference resample.c:804)
 
 
-@pytest.mark.skipif(not orc.have_reference(), reason="oracle/_ref not built")
 def test_oracle_equals_reference_build_on_random_configs():
-    rng = np.random.RandomState(1)
-    rates = [8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000, 96000]
-    for trial in range(40):
-        ch = int(rng.randint(1, 5))
-        i, o = int(rng.choice(rates)), int(rng.choice(rates))
-        q = int(rng.randint(0, 11))
+    """40 random configurations x 4 calls: the oracle against the reference's native C -- the digests it recorded
+    (tests/golden/golden_random_configs.json, make_golden_standalone.py), and the live build too when oracle/_ref is
+    there."""
+    import json
+    from make_golden_standalone import random_config_trials, record_digest, run_random_trial
+    with open(os.path.join(ROOT, "tests", "golden", "golden_random_configs.json")) as f:
+        recorded = json.load(f)["trials"]
+    trials = random_config_trials()
+    assert len(trials) == len(recorded) == 40
+    for trial, ((ch, i, o, q, calls), want) in enumerate(zip(trials, recorded)):
+        assert record_digest(run_random_trial(orc.Oracle, ch, i, o, q, calls)) == want, (trial, ch, i, o, q)
+        if not orc.have_reference():
+            continue
         a, r = orc.Oracle(ch, i, o, q), orc.Reference(ch, i, o, q)
         assert np.array_equal(a.table().view(np.uint32), r.table().view(np.uint32))
-        for call in range(4):
-            f = int(rng.choice([0, 1, 100, 777, 3000]))
-            cap = int(rng.choice([0, 10, 1000, 100000]))
-            x = orc.lcg_pcm(f * ch, trial * 10 + call).reshape(f, ch)
+        for f, cap, seed in calls:
+            x = orc.lcg_pcm(f * ch, seed).reshape(f, ch)
             oa, ua = a.process(x, cap)
             orr, ur = r.process(x, cap)
             assert ua == ur and np.array_equal(oa, orr) and a.position() == r.position()
@@ -79,16 +83,24 @@ def test_oracle_equals_reference_build_on_random_configs():
                 assert np.array_equal(a.history(c), r.history(c))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/resources"), reason="reference fixtures absent")
 def test_oracle_on_the_reference_fixture_files(golden):
-    """The reference's own resources/*.pcm (not copied into this repo): digests from SURVEY section 4."""
-    for r in golden["resources"]:
-        raw = np.fromfile(os.path.join("/root/reference/resources", r["file"]), dtype=np.uint8)
+    """The reference's own resources/*.pcm: the first 64 KiB of each, stored under tests/golden/resources/, against
+    the output frames and sha1 the reference's native C gives on them (golden_resources.json), for every
+    configuration golden.json lists for the whole files (whose digests are from SURVEY section 4)."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "golden_resources.json")) as f:
+        fx = json.load(f)
+    assert [{k: c[k] for k in ("file", "channels", "in_rate", "out_rate", "quality")} for c in fx["cases"]] == \
+        [{k: r[k] for k in ("file", "channels", "in_rate", "out_rate", "quality")} for r in golden["resources"]]
+    for r in fx["cases"]:
+        raw = np.fromfile(os.path.join(ROOT, "tests", "golden", "resources", r["file"]), dtype=np.uint8)
+        assert raw.size == fx["excerpt_bytes"] and sha1(raw) == fx["files"][r["file"]], r["file"]
         raw = raw[: raw.size - raw.size % (2 * r["channels"])]
         x = raw.view(np.int16).reshape(-1, r["channels"])
+        assert x.shape[0] == r["in_frames"]
         spec = dict(channels=r["channels"], in_rate=r["in_rate"], out_rate=r["out_rate"], chunks="whole")
         out, _ = drive(orc.Oracle(r["channels"], r["in_rate"], r["out_rate"], r["quality"]), spec, x)
-        assert out.shape[0] == r["out_frames"] and sha1(out) == r["sha1"], r["file"]
+        assert out.shape[0] == r["out_frames"] and sha1(out) == r["sha1"], r
         # the reference test's only assertion (src/test.ts:40): durations agree within 10 ms
         assert abs(x.shape[0] / r["in_rate"] - out.shape[0] / r["out_rate"]) < 0.01
 
@@ -128,28 +140,25 @@ def test_oracle_mid_stream_control_matches_the_reference_goldens(golden):
     assert n_pending > 100  # the scripts really exercise the pending-frame paths
 
 
-@pytest.mark.skipif(not orc.have_reference(), reason="oracle/_ref not built")
 def test_oracle_equals_reference_build_on_random_control_scripts():
-    """Same ops on the reference build and on the restatement, beyond the committed scripts
-    (full output bytes and histories compared, not digests)."""
+    """Same ops on the reference build and on the restatement, beyond the committed scripts: against the digests
+    the reference recorded (tests/golden/golden_random_configs.json, make_golden_standalone.py) and, when
+    oracle/_ref is there, against the live build (full output bytes and histories compared, not digests)."""
+    import json
     from make_golden import apply_op
-    for seed in range(25):
-        r = np.random.RandomState(seed)
-        ch = int(r.choice([1, 2, 5]))
-        args = (ch, int(r.choice([8000, 11025, 44100, 48000])), int(r.choice([8000, 16000, 48000])),
-                int(r.randint(0, 11)))
+    from make_golden_standalone import random_control_scripts, record_digest, run_control_script
+    with open(os.path.join(ROOT, "tests", "golden", "golden_random_configs.json")) as f:
+        recorded = json.load(f)["control_scripts"]
+    scripts = random_control_scripts()
+    assert len(scripts) == len(recorded) == 25
+    for seed, ((args, ops), want) in enumerate(zip(scripts, recorded)):
+        assert record_digest(run_control_script(orc.Oracle, args, ops)) == want, (seed, args)
+    if not orc.have_reference():
+        return
+    for seed, (args, ops) in enumerate(scripts):
+        ch = args[0]
         a, b = orc.Reference(*args), orc.Oracle(*args)
-        for _ in range(20):
-            pick = r.randint(0, 6)
-            if pick < 3:
-                op = ["int" if r.rand() < 0.5 else "float", int(r.randint(0, 1500)), int(r.randint(0, 3000)),
-                      int(r.randint(1, 1 << 30))]
-            elif pick == 3:
-                op = ["rate", int(r.choice([8000, 11025, 44100, 48000])), int(r.choice([8000, 16000, 48000]))]
-            elif pick == 4:
-                op = ["quality", int(r.randint(0, 11))]
-            else:
-                op = [["skip"], ["reset"]][int(r.randint(0, 2))]
+        for op in ops:
             ra, ya = apply_op(a, op, ch)
             rb, yb = apply_op(b, op, ch)
             assert ra == rb, (seed, op)

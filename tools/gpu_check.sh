@@ -13,10 +13,10 @@ if [ "$MODE" = "full" ]; then
 else
   timeout 900 python -m pytest tests -m gpu -q -x -k "golden or baseline or batched or configs4 or node" > $O/pytest_gpu.txt 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.txt
 fi
-timeout 300 python bench.py > $O/bench1.txt 2>&1; echo "rc=$?" >> $O/bench1.txt
-timeout 300 python bench.py --steps 20 --warmup 5 > $O/bench1_driver_form.txt 2>&1
-timeout 300 python bench.py --steps 100 --warmup 20 --streams 32 --no-cpu-baseline > $O/bench_s32.txt 2>&1
-timeout 300 python bench.py --steps 100 --warmup 20 --total-streams 32 --no-cpu-baseline > $O/bench_total32.txt 2>&1
+timeout 300 python bench.py --full > $O/bench1.txt 2>&1; echo "rc=$?" >> $O/bench1.txt
+timeout 300 python bench.py --full --steps 20 --warmup 5 > $O/bench1_driver_form.txt 2>&1
+timeout 300 python bench.py --full --steps 100 --warmup 20 --streams 32 --no-cpu-baseline > $O/bench_s32.txt 2>&1
+timeout 300 python bench.py --full --steps 100 --warmup 20 --total-streams 32 --no-cpu-baseline > $O/bench_total32.txt 2>&1
 timeout 300 python bench.py --gpus 2 > $O/bench_gpus2_on_1gpu_box.txt 2>&1; echo "rc=$? (must be non-zero on a 1-GPU box, with no JSON line)" >> $O/bench_gpus2_on_1gpu_box.txt
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/prof1

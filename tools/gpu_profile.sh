@@ -86,37 +86,37 @@ fi  # LINES_ONLY
 cd $R
 # bench lines AFTER the PMC passes: every line carries the traffic of this very collection
 : > $O/r${N}_bench_lines.jsonl
-python bench.py >> $O/r${N}_bench_lines.jsonl 2> $O/bench_default.err
-python bench.py --streams 32 --steps 100 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
-python bench.py --total-streams 32 --steps 100 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
+python bench.py --full >> $O/r${N}_bench_lines.jsonl 2> $O/bench_default.err
+python bench.py --full --streams 32 --steps 100 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
+python bench.py --full --total-streams 32 --steps 100 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
 for CFG in cfg3 cfg4 f3; do
-  python bench.py --config $CFG --steps 300 >> $O/r${N}_bench_lines.jsonl 2>/dev/null
-  python bench.py --config $CFG --streams 32 --steps 60 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
+  python bench.py --full --config $CFG --steps 300 >> $O/r${N}_bench_lines.jsonl 2>/dev/null
+  python bench.py --full --config $CFG --streams 32 --steps 60 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
 done
-python bench.py --mode exact --steps 200 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
-python bench.py --config cfg3 --mode exact --steps 100 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
-python bench.py --config cfg3 --mode exact --streams 32 --steps 20 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
+python bench.py --full --mode exact --steps 200 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
+python bench.py --full --config cfg3 --mode exact --steps 100 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
+python bench.py --full --config cfg3 --mode exact --streams 32 --steps 20 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
 for S in 1 32; do
-  python bench.py --config cfg3 --mode fast_f32 --streams $S --steps 60 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
-  python bench.py --custom 2,44100,48000,10 --streams $S --steps 60 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
+  python bench.py --full --config cfg3 --mode fast_f32 --streams $S --steps 60 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
+  python bench.py --full --custom 2,44100,48000,10 --streams $S --steps 60 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
 done
-python bench.py --io float --steps 300 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
-python bench.py --io float --streams 32 --steps 60 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
+python bench.py --full --io float --steps 300 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
+python bench.py --full --io float --streams 32 --steps 60 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
 # mono (not a BASELINE config; the store path of round 3): 44.1k->48k q7, int16 and float
 for IO in int16 float; do
-  python bench.py --custom 1,44100,48000,7 --io $IO --steps 300 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
-  python bench.py --custom 1,44100,48000,7 --io $IO --streams 32 --steps 60 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
+  python bench.py --full --custom 1,44100,48000,7 --io $IO --steps 300 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
+  python bench.py --full --custom 1,44100,48000,7 --io $IO --streams 32 --steps 60 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
 done
 # round 6: the default mode is the pinned summation order (fast_fixed); the opt-in mode with tap-range shares (fast) beside
 # it at the BASELINE configs; configs[4] whole on one GPU with its CPU column on min(cores, 256) worker processes
 for CFG in cfg2 cfg3 cfg4; do
   for S in 1 32; do
-    python bench.py --config $CFG --mode fast --streams $S --steps 60 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
+    python bench.py --full --config $CFG --mode fast --streams $S --steps 60 --no-cpu-baseline >> $O/r${N}_bench_lines.jsonl 2>/dev/null
   done
 done
 SPEEXHIP_PY_NO_TORCH=1 python tools/pinned_path_bench.py > $O/r${N}_pinned_path.json 2>/dev/null   # (the runtime a Node / C caller loads)
-python bench.py --total-streams 256 --steps 10 --warmup 2 > $O/r${N}_bench_total256.json 2>/dev/null
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_form.json 2>/dev/null
+python bench.py --full --total-streams 256 --steps 10 --warmup 2 > $O/r${N}_bench_total256.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_form.json 2>/dev/null
 python tools/call_stamps.py > $O/r${N}_call_stamps.txt 2>/dev/null
 python tools/first_call.py > $O/r${N}_first_call.txt 2>/dev/null
 FIRST_CALL_WARMUP=1 python tools/first_call.py > $O/r${N}_first_call_warm.txt 2>/dev/null

@@ -39,7 +39,7 @@ collect)
   bash tools/gpu_profile.sh $N > $O/r${N}_profile_log.txt 2>&1; tail -45 $O/r${N}_profile_log.txt
   timeout 1200 python tools/perf_floor.py --measure --merge > $O/r${N}_perf_floor.txt 2>&1; tail -5 $O/r${N}_perf_floor.txt
   cp profiles/perf_floor.json profiles/pmc_traffic.json $O/
-  timeout 300 python bench.py --steps 20 --warmup 5 > $O/r${N}_bench_driver_form.json 2> $O/r${N}_bench.err; echo "bench rc=$?";;
+  timeout 300 python bench.py --full --steps 20 --warmup 5 > $O/r${N}_bench_driver_form.json 2> $O/r${N}_bench.err; echo "bench rc=$?";;
 bounds)
   rm -f $O/r${N}_cfg4_bound.txt $O/r${N}_headline_r.txt $O/r${N}_slide_bound.txt
   for S in 32 1; do
@@ -57,7 +57,7 @@ lib-ab)  # NAME config...   (BASE = the other library)
   [ -f "$BASE" ] || { echo "lease.sh lib-ab: BASE=$BASE is not a library" >&2; exit 2; }
   for REP in 1 2; do for C in "$@"; do
     tools/ab.sh -o $OUT -f "'launch_us %s (min %s) valu %s fast_path %s parity %s' % (d['roofline']['launch_us'], d['roofline']['launch_us_min'], d['valu']['frac'], d['config']['fast_path'], d['parity'].get('max_abs_diff_lsb', d['parity'].get('max_abs_diff')))" \
-      -- "SPEEXHIP_LIB_PATH=$R/$BASE" "SPEEXHIP_LIB_PATH=$PKG/libspeexhip.so" -- python bench.py $C --streams ${STREAMS:-32} --steps 40 --warmup 5 --reps 3 --mode fast_fixed --no-cpu-baseline
+      -- "SPEEXHIP_LIB_PATH=$R/$BASE" "SPEEXHIP_LIB_PATH=$PKG/libspeexhip.so" -- python bench.py --full $C --streams ${STREAMS:-32} --steps 40 --warmup 5 --reps 3 --mode fast_fixed --no-cpu-baseline
   done; done;;
 pinned)
   # Which HIP runtime a process loads matters to the host-fed path: python + torch brings torch's bundled libamdhip64, a
