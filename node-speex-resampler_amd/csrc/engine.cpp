@@ -2,6 +2,7 @@
 #include "engine.h"
 
 #include "devices.h"
+#include "host_transfer.h"
 #include "pool.h"
 #include "unit_workers.h"
 
@@ -141,14 +142,13 @@ int ctl_download(void *dst, const char *base, size_t total, size_t off, size_t l
 }
 
 const size_t kLdsBudget = 150 * 1024;  // of the CU's 160 KiB
-const size_t kDirectCopyBytes = 256 * 1024;  // host buffers at least this big skip the pinned bounce buffer
 // A piecewise host call (take_in_pieces) takes 2 MB of input per piece, at most four: a piece costs ~15 us (an event,
 // a cross-stream wait, a launch) and buys the overlap of its launch -- the result leaving through PCIe -- with the next
 // piece's copy.  2^20 stereo frames (4.2 MB in): 1 / 2 / 3 / 4 pieces 0.1935 / 0.1879 / 0.198 / 0.224 ms per call; 8
 // channels (16.8 MB in), four pieces: 0.617 -> 0.517 ms.
 const size_t kPieceBytes = static_cast<size_t>(2) << 20;
-const size_t kZeroCopyBelow = 720 * 1024;    // ... and calls whose buffers are smaller than this run on pinned memory alone
 
+inline size_t align64(size_t v) { return (v + 63) & ~static_cast<size_t>(63); }
 inline bool buffers_overlap(const void *a, size_t na, const void *b, size_t nb) {
   const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
   return x < y + nb && y < x + na;
@@ -179,16 +179,14 @@ void *pinned_view(const void *p, size_t bytes) {
   return last != nullptr && static_cast<size_t>(last - first) == bytes - 1 ? first : nullptr;
 }
 
-// The wait of a host-buffer call whose kernels read and write pinned memory: hipStreamSynchronize after a small launch
-// costs 11-12 us on this stack; a 32-bit stream write behind the kernel (hipStreamWriteValue32: performed once
-// everything before it on the stream has completed) into pinned memory, polled by the caller, 8.8 (tools/ubench_sync.hip).
-// The pool's streams are shared by all states -- behind another state's long launch the word will not come soon -- so the
-// spin is bounded (`spin_us`, `pause` between the reads) and then the thread sleeps in the runtime, which also reports
-// the error if that is what happened.  *word must not equal seq when the call is made.
+// The polled wait of a host-buffer call (host_transfer.h, Wait): a 32-bit stream write behind the kernel
+// (hipStreamWriteValue32: performed once everything before it on the stream has completed) into pinned memory, polled by
+// the caller.  The pool's streams are shared by all states -- behind another state's long launch the word will not come
+// soon -- so the spin is bounded (`spin_us`, `pause` between the reads) and then the thread sleeps in the runtime, which
+// also reports the error if that is what happened.  *word must not equal seq when the call is made.
 int wait_done(hipStream_t stream, volatile uint32_t *word, uint32_t seq, uint32_t spin_us) {
-  static const bool poll_done = SPEEXHIP_DIAG_ENV("SPEEXHIP_NO_POLL") == nullptr;  // (A/B)
   bool signalled = false;
-  if (poll_done && hipStreamWriteValue32(stream, const_cast<uint32_t *>(word), seq, 0) == hipSuccess) {
+  if (hipStreamWriteValue32(stream, const_cast<uint32_t *>(word), seq, 0) == hipSuccess) {
     const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(spin_us);
     for (uint32_t spins = 0; !signalled; spins++) {
       signalled = __atomic_load_n(const_cast<const uint32_t *>(word), __ATOMIC_ACQUIRE) == seq;
@@ -202,10 +200,57 @@ int wait_done(hipStream_t stream, volatile uint32_t *word, uint32_t seq, uint32_
   if (!signalled) HIP_TRY(hipStreamSynchronize(stream));
   return SPEEXHIP_ERR_SUCCESS;
 }
-// A/B (diagnostics build): a large pinned input through the copy engines in pieces (take_in_pieces) instead of read in place
-bool pinned_in_pieces() { return diag_int(SPEEXHIP_DIAG_ENV("SPEEXHIP_PINNED_IN_PIECES"), 0) != 0; }
-// how long such a call may spin: 300 us for the launch itself plus what `bytes` take to cross PCIe (~40 GB/s), 2 ms at most
-uint32_t spin_budget_us(size_t bytes) { return static_cast<uint32_t>(std::min<size_t>(2000, 300 + bytes / 40000)); }
+// The wait `w` chose.  A polled one arms the completion word at `word` -- 64 bytes of pinned memory the call's kernels do
+// not write: the tail of a pinned result buffer (tail_word) or the bytes behind the samples of a take block -- with a
+// value other than `seq` and waits for the stream to write `seq` there.
+int wait_call(hipStream_t stream, const Wait &w, void *word, uint32_t seq) {
+  if (w.sync) {
+    HIP_TRY(hipStreamSynchronize(stream));
+    return SPEEXHIP_ERR_SUCCESS;
+  }
+  volatile uint32_t *done = static_cast<volatile uint32_t *>(word);
+  *done = seq - 1;
+  return wait_done(stream, done, seq, w.spin_us());
+}
+inline char *tail_word(char *buf, size_t cap) { return buf == nullptr ? nullptr : buf + ((cap - 64) & ~static_cast<size_t>(63)); }
+// bytes of a side that pass through a device / a pinned staging buffer
+inline size_t device_part(Via v, size_t bytes) { return v == Via::Copy || v == Via::Staged ? bytes : 0; }
+inline size_t pinned_part(Via v, size_t bytes) { return v == Via::Bounce || v == Via::Staged ? bytes : 0; }
+
+// Grows a staging buffer of the host-buffer calls to `want` bytes: grow-only (like the wrapper's heap buffers,
+// src/index.ts:71-87); the calls are synchronous, so nothing in flight uses a buffer that goes back to the pool here.
+int grow_stage(int device, char **buf, size_t *cap_now, size_t want, bool pinned) {
+  if (want <= *cap_now) return SPEEXHIP_ERR_SUCCESS;
+  if (pinned)
+    pool::pinned_put(*buf);
+  else
+    pool::device_put(device, *buf);
+  *buf = nullptr;
+  *cap_now = 0;
+  const size_t cap = pool::size_class(std::max<size_t>(want, 8192));
+  if (pinned)
+    HIP_TRY(pool::pinned_get(reinterpret_cast<void **>(buf), cap));
+  else
+    HIP_TRY(pool::device_get(device, reinterpret_cast<void **>(buf), cap));
+  *cap_now = cap;
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+// The position fields of a descriptor: `n_out` outputs of filter `f` from `at`, `consumed` frames of V past the history,
+// `hist_frames` frames of history read and `hist_keep` left behind.
+void set_position(StreamDesc &d, const FilterSpec &f, const StreamPos &at, uint32_t n_out, uint32_t consumed,
+                  uint32_t hist_frames, uint32_t hist_keep) {
+  d.n_out = n_out;
+  d.consumed = consumed;
+  d.hist_frames = hist_frames;
+  d.hist_keep = hist_keep;
+  d.last0 = at.last;
+  d.frac0 = at.frac;
+  d.k_shift = phase_index_of(f.num, f.den, at.frac);
+  d.base_shift = at.last - static_cast<int32_t>((static_cast<uint64_t>(d.k_shift) * f.num) / f.den);
+  d.tile_begin = 0;
+  d.m_total = static_cast<uint32_t>((static_cast<uint64_t>(d.k_shift) + n_out + f.den - 1) / f.den);
+}
 }  // namespace
 
 // SPEEXHIP_INIT_TRACE=1: where a state's creation goes, step by step (stderr; tools/first_call.py)
@@ -982,12 +1027,8 @@ int Batch::run_channel(uint32_t c, const void *d_in, uint32_t in_stride, uint32_
   d.out = d_out;
   d.hist_next = d_hist_[hist_cur_ ^ 1] + c;
   d.in_frames = in_frames;
-  d.n_out = plan.produced;
-  d.consumed = walked;
-  d.hist_frames = filter_.taps - 1 + plan.begin.magic;
-  d.hist_keep = filter_.taps - 1 + plan.end.magic;
-  d.last0 = plan.begin.last;
-  d.frac0 = plan.begin.frac;
+  // (launch_exact and its kernel read none of k_shift, base_shift, tile_begin, m_total)
+  set_position(d, filter_, plan.begin, plan.produced, walked, filter_.taps - 1 + plan.begin.magic, filter_.taps - 1 + plan.end.magic);
   const ExactStrides strides = {in_stride, out_stride, channels_};
   ExactGeometry geo = exact_geo_ch_;
   if (zero_mode_) {  // the window geometry belongs to the filter that is no longer in force
@@ -1107,17 +1148,8 @@ int Batch::run_plans(const void *d_in, uint64_t in_stride, const uint32_t *in_fr
       d.out = static_cast<char *>(d_out) + s * out_stride * es;
       d.hist_next = d_hist_[hist_cur_ ^ 1] + s * hist_elems_;
       d.in_frames = in_frames[s];
-      d.n_out = plan.produced;
-      d.consumed = plan.magic_used + plan.consumed;  // frames of V past the history
-      d.hist_frames = filter_.taps - 1 + plan.begin.magic;
-      d.hist_keep = filter_.taps - 1 + plan.end.magic;
-      d.last0 = plan.begin.last;
-      d.frac0 = plan.begin.frac;
-      d.k_shift = phase_index_of(filter_.num, filter_.den, plan.begin.frac);
-      d.base_shift = plan.begin.last -
-                     static_cast<int32_t>((static_cast<uint64_t>(d.k_shift) * filter_.num) / filter_.den);
-      d.tile_begin = 0;
-      d.m_total = static_cast<uint32_t>((static_cast<uint64_t>(d.k_shift) + d.n_out + filter_.den - 1) / filter_.den);
+      set_position(d, filter_, plan.begin, plan.produced, plan.magic_used + plan.consumed, filter_.taps - 1 + plan.begin.magic,
+                   filter_.taps - 1 + plan.end.magic);
       max_out = std::max(max_out, plan.produced);
       any_work = any_work || plan.produced != 0 || d.consumed != 0;
     }
@@ -1159,33 +1191,28 @@ void Batch::int16_call_done(const CallPlan *plans, uint32_t n) {
   float_seen_ = false;
 }
 
-// Staging buffers of the host-buffer calls, each grow-only (like the wrapper's heap buffers,
-// src/index.ts:71-87) and taken only when a call needs it: small calls run on the pinned pair alone,
-// large ones on the device pair alone (the runtime copies straight from / to the caller's memory).
-// The calls are synchronous, so nothing in flight uses a buffer that goes back to the pool here.
+// Staging buffers of the host-buffer calls (grow_stage), each taken only when a call needs it: small calls run on the
+// pinned pair alone, large ones on the device pair alone (the runtime copies straight from / to the caller's memory).
 int Batch::ensure_stage(size_t dev_in, size_t dev_out, size_t pin_in, size_t pin_out) {
   if (own_stream_ == nullptr) HIP_TRY(pool::stream_get(device_, &own_stream_));
-  auto grow = [&](char **buf, size_t *cap_now, size_t want, bool pinned) -> int {
-    if (want <= *cap_now) return SPEEXHIP_ERR_SUCCESS;
-    if (pinned)
-      pool::pinned_put(*buf);
-    else
-      pool::device_put(device_, *buf);
-    *buf = nullptr;
-    *cap_now = 0;
-    const size_t cap = pool::size_class(std::max<size_t>(want, 8192));
-    if (pinned)
-      HIP_TRY(pool::pinned_get(reinterpret_cast<void **>(buf), cap));
-    else
-      HIP_TRY(pool::device_get(device_, reinterpret_cast<void **>(buf), cap));
-    *cap_now = cap;
-    return SPEEXHIP_ERR_SUCCESS;
-  };
-  int rc = grow(&d_stage_in_, &stage_in_cap_, dev_in, false);
-  if (rc == SPEEXHIP_ERR_SUCCESS) rc = grow(&d_stage_out_, &stage_out_cap_, dev_out, false);
-  if (rc == SPEEXHIP_ERR_SUCCESS) rc = grow(&h_pin_in_, &pin_in_cap_, pin_in, true);
-  if (rc == SPEEXHIP_ERR_SUCCESS) rc = grow(&h_pin_out_, &pin_out_cap_, pin_out, true);
+  int rc = grow_stage(device_, &d_stage_in_, &stage_in_cap_, dev_in, false);
+  if (rc == SPEEXHIP_ERR_SUCCESS) rc = grow_stage(device_, &d_stage_out_, &stage_out_cap_, dev_out, false);
+  if (rc == SPEEXHIP_ERR_SUCCESS) rc = grow_stage(device_, &h_pin_in_, &pin_in_cap_, pin_in, true);
+  if (rc == SPEEXHIP_ERR_SUCCESS) rc = grow_stage(device_, &h_pin_out_, &pin_out_cap_, pin_out, true);
   return rc;
+}
+
+// Brings a host input onto the device the way `via` says (host_transfer.h) and sets *src to what the kernels read:
+// nullptr for an absent or empty input.
+int Batch::stage_input(Via via, const void *in, size_t bytes, const void *pin, const void **src) {
+  *src = nullptr;
+  if (via == Via::InPlace) *src = pin;
+  if (via == Via::None || via == Via::InPlace || bytes == 0) return SPEEXHIP_ERR_SUCCESS;
+  if (via == Via::Bounce || via == Via::Staged) std::memcpy(h_pin_in_, in, bytes);
+  if (via == Via::Copy) HIP_TRY(hipMemcpyAsync(d_stage_in_, in, bytes, hipMemcpyHostToDevice, own_stream_));
+  if (via == Via::Staged) HIP_TRY(hipMemcpyAsync(d_stage_in_, h_pin_in_, bytes, hipMemcpyHostToDevice, own_stream_));
+  *src = via == Via::Bounce ? h_pin_in_ : d_stage_in_;
+  return SPEEXHIP_ERR_SUCCESS;
 }
 
 // The second stream of a piecewise call: one of the pool's shared streams that is NOT this state's own one (on the
@@ -1276,16 +1303,8 @@ int Batch::take_in_pieces(const void *in, uint32_t *in_len, uint32_t *out_len, b
     d.out = static_cast<char *>(blk) + static_cast<size_t>(done_out) * channels_ * es;
     d.hist_next = d_hist_[hist_cur_ ^ 1];
     d.in_frames = frames;
-    d.n_out = n_out;
-    d.consumed = plan.magic_used + plan.consumed;
-    d.hist_frames = hist_frames;
-    d.hist_keep = last ? filter_.taps - 1 + plan.end.magic : 0;  // (the history moves once, with the last piece)
-    d.last0 = at.last;
-    d.frac0 = at.frac;
-    d.k_shift = phase_index_of(filter_.num, filter_.den, at.frac);
-    d.base_shift = at.last - static_cast<int32_t>((static_cast<uint64_t>(d.k_shift) * filter_.num) / filter_.den);
-    d.tile_begin = 0;
-    d.m_total = static_cast<uint32_t>((static_cast<uint64_t>(d.k_shift) + d.n_out + filter_.den - 1) / filter_.den);
+    // (the history moves once, with the last piece)
+    set_position(d, filter_, at, n_out, plan.magic_used + plan.consumed, hist_frames, last ? filter_.taps - 1 + plan.end.magic : 0);
     rc = launch_chunk(pack.d, pack, 1, n_out, float_io, own_stream_);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
     done_out = upto;
@@ -1340,40 +1359,30 @@ int Batch::process_host_take(const void *in, uint32_t *in_len, uint32_t *out_len
   // Round 6: an input the caller left in pinned memory (speexhip_block_acquire, or memory it pinned itself) is read where
   // it lies -- ONE launch whose loads and stores cross PCIe in opposite directions at the same time, no staging copy, no
   // second stream (the pieces above overlap the two directions only partly and pay ~15 us per piece for it).
+  // The result is the block (InPlace); the input takes the rule of host_transfer.h.
   const void *pin_in = (split || zero_mode_ || in == nullptr) ? nullptr : pinned_view(in, in_bytes);
+  const Via in_via = route_side(in_bytes, in != nullptr, pin_in != nullptr,
+                                small_call(in != nullptr && pin_in == nullptr ? in_bytes : 0, 0));
   if (split || zero_mode_) {
     rc = process_host(in, in_len, blk, out_len, float_io);
     if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
-  } else if ((pin_in == nullptr || pinned_in_pieces()) && pieces >= 2 && in != nullptr && in_bytes >= kZeroCopyBelow && frames < 0x40000000u && have_copy_stream()) {
+  } else if (in_via == Via::Copy && pieces >= 2 && frames < 0x40000000u && have_copy_stream()) {
     rc = take_in_pieces(in, in_len, out_len, float_io, blk, pieces);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   } else {
     DrainOnExit drain(&own_stream_);
-    const bool direct_in = pin_in == nullptr && in_bytes >= kZeroCopyBelow;
-    rc = ensure_stage(direct_in ? in_bytes : 0, 0, (direct_in || pin_in != nullptr) ? 0 : in_bytes, 0);
+    rc = ensure_stage(device_part(in_via, in_bytes), 0, pinned_part(in_via, in_bytes), 0);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
     const void *src = nullptr;
-    if (pin_in != nullptr) {
-      src = pin_in;
-    } else if (in != nullptr && in_bytes != 0) {
-      if (direct_in) {
-        HIP_TRY(hipMemcpyAsync(d_stage_in_, in, in_bytes, hipMemcpyHostToDevice, own_stream_));
-        src = d_stage_in_;
-      } else {
-        std::memcpy(h_pin_in_, in, in_bytes);
-        src = h_pin_in_;
-      }
-    }
-    volatile uint32_t *done = reinterpret_cast<volatile uint32_t *>(static_cast<char *>(blk) + ((out_bytes + 63) & ~static_cast<size_t>(63)));
-    *done = 0;
+    rc = stage_input(in_via, in, in_bytes, pin_in, &src);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+    Wait wait;
+    wait.add(in_via, in_bytes);
+    wait.add(Via::InPlace, out_bytes);
     rc = process_device(src, 0, in_len, blk, 0, out_len, float_io, own_stream_);
     if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
-    if (direct_in) {
-      HIP_TRY(hipStreamSynchronize(own_stream_));
-    } else {
-      const int wrc = wait_done(own_stream_, done, 1u, spin_budget_us(pin_in != nullptr ? in_bytes + out_bytes : 0));
-      if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
-    }
+    const int wrc = wait_call(own_stream_, wait, static_cast<char *>(blk) + align64(out_bytes), 1u);
+    if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
     drain.armed = false;
   }
   if (*out_len == 0) return rc;  // (the guard returns the block)
@@ -1398,121 +1407,17 @@ int Batch::process_host(const void *in, uint32_t *in_len, void *out, uint32_t *o
   const size_t out_bytes = static_cast<size_t>(will_make) * channels_ * es;
   int rc = SPEEXHIP_ERR_SUCCESS;
   DrainOnExit drain(&own_stream_);
-  // Large buffers go straight from / to the caller's pageable memory: the HIP runtime stages such
-  // copies itself and does it 2.2-2.5x faster than memcpy -> pinned -> DMA in one thread (2^20
-  // stereo frames: 0.46 -> 0.21 ms per call, 8 channels 1.57 -> 0.63 ms).  Small ones go through
-  // the pinned bounce buffers (below).
-  // What was tried in round 2 to get below this (2^20 stereo frames, 207 us per call; tools/ubench_copy.hip):
-  // PCIe is full duplex -- both copies at once from pinned memory take 103 us instead of 175 -- but
-  //   * H2D / kernel / D2H of 2-8 pieces on three streams chained by events: +30 us per piece (a
-  //     cross-stream wait costs ~14 us on this stack and nothing overlapped);
-  //   * pieces alternating on two independent in-order streams: 189 us at 2 pieces, more beyond (a
-  //     copy-engine <-> kernel hand-over costs ~10 us, and kernels of two streams never ran side by side);
-  //   * the caller's buffers pinned for the call (hipHostRegister, ~5 us) and read / written by the
-  //     kernels straight through PCIe, one launch: 166 us -- and, one run in three, a stretch of stale
-  //     zeros near the end of the output when buffers at recycled addresses were pinned again.  Not
-  //     shippable; removed.
-  // So the call stays three in-order steps on one stream.
-  const bool direct_in = in_bytes >= kDirectCopyBytes, direct_out = out_bytes >= kDirectCopyBytes && !split;
-  // Small calls -- a Transform's 64 KiB chunks, a realtime caller's 10-20 ms frames -- are all latency:
-  // the kernels read the pinned bounce buffer and write the pinned result buffer straight through PCIe
-  // (pool-owned hipHostMalloc memory, coherent; one launch and one wait instead of copy / launch / copy
-  // / wait): 480-960 stereo frames 26.5 -> 22.7 us per call, 16384 frames 41.7 -> 30.1, 65536 frames
-  // 70.4 -> 53.7 (tools/small_call_latency.py).  SPEEXHIP_ZERO_COPY_BELOW=0 turns it off (A/B).
-  // Where it stops paying (profiles/r03_zero_copy_sweep.txt, per call, pinned alone vs copies): 256 KB of input
-  // 49 vs 65 us (stereo), 49 vs 66 (mono), 46 vs 65 (8 channels); 512 KB 76 vs 95, 76 vs 95, 72 vs 90; 1 MB
-  // 167 vs 145, 169 vs 144, 132 vs 150: the single-threaded memcpy into and out of the bounce buffers grows at
-  // 0.18 us per KB against 0.10 for the runtime's own staged copies -- they cross near 740 KB.  (Until late in
-  // round 3 the limit was 256 KB, which sent a 65536-frame stereo chunk down the slower way.)
-  static const size_t zero_copy_below = [] {
-    const char *e = SPEEXHIP_DIAG_ENV("SPEEXHIP_ZERO_COPY_BELOW");
-    return e != nullptr ? static_cast<size_t>(std::strtoull(e, nullptr, 10)) : kZeroCopyBelow;
-  }();
-  // Round 6: buffers the caller keeps in pinned memory (speexhip_block_acquire, hipHostMalloc, hipHostRegister) are used
-  // where they lie (pinned_view): a pinned input is read by the kernel through PCIe, a pinned output written by it -- with
-  // both pinned the call is one launch and one wait, the two crossings side by side.  The other side, if pageable, keeps its
-  // own rule: small through the bounce buffer, large by the runtime's staged copy.
-  if (!split) {
-    const void *pin_in = in != nullptr ? pinned_view(in, in_bytes) : nullptr;
-    void *pin_out = pinned_view(out, out_bytes);
-    // (a result that overlaps its chunk: the chunk is taken in whole before anything is written, as on pageable buffers)
-    if (pin_in != nullptr && pin_out != nullptr && buffers_overlap(in, in_bytes, out, out_bytes)) pin_in = nullptr;
-    if (pin_in != nullptr || pin_out != nullptr) {
-      const bool have_in = in != nullptr && in_bytes != 0;
-      const bool bounce_in = have_in && pin_in == nullptr && in_bytes < zero_copy_below;
-      const bool copy_in = have_in && pin_in == nullptr && !bounce_in;
-      const bool bounce_out = pin_out == nullptr && out_bytes < zero_copy_below;
-      const bool copy_out = pin_out == nullptr && !bounce_out;
-      rc = ensure_stage(copy_in ? in_bytes : 0, copy_out ? out_bytes : 0, bounce_in ? in_bytes : 0, (bounce_out ? out_bytes : 0) + 64);
-      if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-      const void *src = nullptr;
-      if (pin_in != nullptr) {
-        src = pin_in;
-      } else if (bounce_in) {
-        std::memcpy(h_pin_in_, in, in_bytes);
-        src = h_pin_in_;
-      } else if (copy_in) {
-        HIP_TRY(hipMemcpyAsync(d_stage_in_, in, in_bytes, hipMemcpyHostToDevice, own_stream_));
-        src = d_stage_in_;
-      } else if (in != nullptr) {
-        src = h_pin_out_;  // (an empty chunk, not silence: no frame is read, any non-null address serves)
-      }
-      void *dst = pin_out != nullptr ? pin_out : bounce_out ? static_cast<void *>(h_pin_out_) : static_cast<void *>(d_stage_out_);
-      volatile uint32_t *done = reinterpret_cast<volatile uint32_t *>(h_pin_out_ + ((pin_out_cap_ - 64) & ~static_cast<size_t>(63)));
-      const uint32_t seq = ++done_seq_;
-      *done = seq - 1;
-      rc = process_device(src, 0, in_len, dst, 0, out_len, float_io, own_stream_);
-      if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
-      const size_t made = static_cast<size_t>(*out_len) * channels_ * es;
-      if (copy_in || copy_out) {
-        if (copy_out && made != 0) HIP_TRY(hipMemcpyAsync(out, d_stage_out_, made, hipMemcpyDeviceToHost, own_stream_));
-        HIP_TRY(hipStreamSynchronize(own_stream_));
-      } else {
-        const int wrc = wait_done(own_stream_, done, seq, spin_budget_us((pin_in != nullptr ? in_bytes : 0) + (pin_out != nullptr ? out_bytes : 0)));
-        if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
-      }
-      drain.armed = false;
-      if (bounce_out && made != 0) std::memcpy(out, h_pin_out_, made);
-      return rc;
-    }
-  }
-  if (!split && in_bytes < zero_copy_below && out_bytes < zero_copy_below) {
-    // (+ 64 bytes: the completion word below lives behind the samples, in the same pinned block)
-    rc = ensure_stage(0, 0, in_bytes, out_bytes + 64);
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-    if (in != nullptr && in_bytes != 0) std::memcpy(h_pin_in_, in, in_bytes);
-    // The wait: hipStreamSynchronize after a tiny launch costs 11-12 us on this stack; a 32-bit stream write behind
-    // the kernel (hipStreamWriteValue32: performed once everything before it on the stream has completed) into
-    // pinned memory, polled by the caller, 8.8 (tools/ubench_sync.hip).  A launch that has not signalled after
-    // 300 us is waited for -- and its error, if that is what happened, reported -- the ordinary way.
-    volatile uint32_t *done = reinterpret_cast<volatile uint32_t *>(h_pin_out_ + ((pin_out_cap_ - 64) & ~static_cast<size_t>(63)));
-    const uint32_t seq = ++done_seq_;
-    *done = seq - 1;
-    rc = process_device(in != nullptr ? h_pin_in_ : nullptr, 0, in_len, h_pin_out_, 0, out_len, float_io, own_stream_);
-    if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
-    const int wrc = wait_done(own_stream_, done, seq, 300);  // (the word: see wait_done)
-    if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
-    drain.armed = false;
-    const size_t made = static_cast<size_t>(*out_len) * channels_ * es;
-    if (made != 0) std::memcpy(out, h_pin_out_, made);
-    return rc;
-  }
-  rc = ensure_stage(in_bytes, out_bytes, direct_in ? 0 : in_bytes, direct_out ? 0 : out_bytes);
-  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  if (in != nullptr && in_bytes != 0) {
-    if (direct_in) {
-      HIP_TRY(hipMemcpyAsync(d_stage_in_, in, in_bytes, hipMemcpyHostToDevice, own_stream_));
-    } else {
-      std::memcpy(h_pin_in_, in, in_bytes);
-      HIP_TRY(hipMemcpyAsync(d_stage_in_, h_pin_in_, in_bytes, hipMemcpyHostToDevice, own_stream_));
-    }
-  }
   if (split) {
     // channels at different positions write different numbers of frames: fetch the whole block
     // and hand the caller only the samples each channel really wrote
+    const Via in_via = route_side(in_bytes, in != nullptr, false, false);
+    rc = ensure_stage(in_bytes, out_bytes, pinned_part(in_via, in_bytes), out_bytes);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+    const void *src = nullptr;
+    rc = stage_input(in_via, in, in_bytes, nullptr, &src);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
     std::vector<CallPlan> plans;
-    rc = process_split(in != nullptr ? d_stage_in_ : nullptr, in_len, d_stage_out_, out_len, float_io, own_stream_,
-                       &plans);
+    rc = process_split(src, in_len, d_stage_out_, out_len, float_io, own_stream_, &plans);
     if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
     uint32_t most = 0;
     for (const CallPlan &pl : plans) most = std::max(most, pl.produced);
@@ -1526,15 +1431,35 @@ int Batch::process_host(const void *in, uint32_t *in_len, void *out, uint32_t *o
                     h_pin_out_ + (static_cast<size_t>(j) * channels_ + c) * es, es);
     return rc;
   }
-  rc = process_device(in != nullptr ? d_stage_in_ : nullptr, 0, in_len, d_stage_out_, 0, out_len, float_io,
-                      own_stream_);
+  // Both sides by the rule of host_transfer.h.  (A pinned result that overlaps its chunk: the chunk is taken in whole
+  // before anything is written, as on pageable buffers.)
+  const void *pin_in = in != nullptr ? pinned_view(in, in_bytes) : nullptr;
+  void *pin_out = pinned_view(out, out_bytes);
+  if (pin_in != nullptr && pin_out != nullptr && buffers_overlap(in, in_bytes, out, out_bytes)) pin_in = nullptr;
+  const bool small = small_call(in != nullptr && pin_in == nullptr ? in_bytes : 0, pin_out == nullptr ? out_bytes : 0);
+  const Via in_via = route_side(in_bytes, in != nullptr, pin_in != nullptr, small);
+  const Via out_via = route_side(out_bytes, true, pin_out != nullptr, small);
+  Wait wait;
+  wait.add(in_via, in_bytes);
+  wait.add(out_via, out_bytes);
+  // (+ 64 bytes for a polled wait: its completion word lives behind the samples, in the pinned result buffer)
+  rc = ensure_stage(device_part(in_via, in_bytes), device_part(out_via, out_bytes), pinned_part(in_via, in_bytes),
+                    pinned_part(out_via, out_bytes) + (wait.sync ? 0 : 64));
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  const void *src = nullptr;
+  rc = stage_input(in_via, in, in_bytes, pin_in, &src);
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  if (src == nullptr && in != nullptr) src = h_pin_out_;  // (an empty chunk, not silence: no frame is read, any non-null address serves)
+  void *dst = out_via == Via::InPlace ? pin_out : out_via == Via::Bounce ? static_cast<void *>(h_pin_out_) : static_cast<void *>(d_stage_out_);
+  rc = process_device(src, 0, in_len, dst, 0, out_len, float_io, own_stream_);
   if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
   const size_t made = static_cast<size_t>(*out_len) * channels_ * es;
-  if (made != 0)
-    HIP_TRY(hipMemcpyAsync(direct_out ? out : h_pin_out_, d_stage_out_, made, hipMemcpyDeviceToHost, own_stream_));
-  HIP_TRY(hipStreamSynchronize(own_stream_));
+  if (device_part(out_via, made) != 0)
+    HIP_TRY(hipMemcpyAsync(out_via == Via::Copy ? out : h_pin_out_, d_stage_out_, made, hipMemcpyDeviceToHost, own_stream_));
+  const int wrc = wait_call(own_stream_, wait, tail_word(h_pin_out_, pin_out_cap_), ++done_seq_);
+  if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
   drain.armed = false;
-  if (made != 0 && !direct_out) std::memcpy(out, h_pin_out_, made);
+  if (pinned_part(out_via, made) != 0) std::memcpy(out, h_pin_out_, made);
   return rc;
 }
 
@@ -1760,23 +1685,6 @@ ManyStage &many_stage(int device, int lane) {
   if (m == nullptr) m = new ManyStage();
   return *m;
 }
-int grow_stage(int device, char **buf, size_t *cap_now, size_t want, bool pinned) {
-  if (want <= *cap_now) return SPEEXHIP_ERR_SUCCESS;
-  if (pinned)
-    pool::pinned_put(*buf);
-  else
-    pool::device_put(device, *buf);
-  *buf = nullptr;
-  *cap_now = 0;
-  const size_t cap = pool::size_class(std::max<size_t>(want, 8192));
-  if (pinned)
-    HIP_TRY(pool::pinned_get(reinterpret_cast<void **>(buf), cap));
-  else
-    HIP_TRY(pool::device_get(device, reinterpret_cast<void **>(buf), cap));
-  *cap_now = cap;
-  return SPEEXHIP_ERR_SUCCESS;
-}
-inline size_t align64(size_t v) { return (v + 63) & ~static_cast<size_t>(63); }
 
 // The stage's copy stream: a stream of its own that carries host -> device copies and NOTHING else, made and primed here.
 // Why (late in round 6; profiles/r06_engine_log.txt, r06_pinned_in_leg.txt): the runtime picks a copy engine per stream --
@@ -1833,14 +1741,14 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
     uint32_t i;
     Batch *b;
     CallPlan plan;
-    size_t in_bytes, out_bytes, in_off, out_off;  // bytes that travel through the stage (0: a pinned buffer, used in place)
+    size_t in_bytes, out_bytes, in_off, out_off;
     const void *pin_in;                           // round 6: the caller's own buffers where they are pinned memory
     void *pin_out;                                // (pinned_view): the kernels read / write them directly
+    Via in_via, out_via;                          // host_transfer.h
     bool work;
   };
   std::vector<Item> items(idx.size());
-  size_t total_in = 0, total_out = 0, pinned_bytes = 0;
-  bool all_big = true;
+  size_t total_in = 0, total_out = 0;  // pageable bytes, as laid out in the stage
   for (size_t k = 0; k < idx.size(); k++) {
     Item &it = items[k];
     it.i = idx[k];
@@ -1861,45 +1769,50 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
     if (it.pin_in != nullptr && it.pin_out == nullptr && it.out_bytes >= kDirectCopyBytes &&
         diag_int(SPEEXHIP_DIAG_ENV("SPEEXHIP_PIN_IN_COPY"), 1) != 0)  // (A/B: 0 = read in place even then)
       it.pin_in = nullptr;
-    // (experiment, diagnostics: large chunks AND results in pinned memory by the copy engines as well, pipelined)
-    if (it.pin_in != nullptr && it.pin_out != nullptr && it.in_bytes >= kDirectCopyBytes && it.out_bytes >= kDirectCopyBytes &&
-        diag_int(SPEEXHIP_DIAG_ENV("SPEEXHIP_PIN_BOTH_COPY"), 0) != 0)
-      it.pin_in = nullptr, it.pin_out = nullptr;
-    if (it.pin_in != nullptr) pinned_bytes += it.in_bytes, it.in_bytes = 0;
-    if (it.pin_out != nullptr) pinned_bytes += it.out_bytes, it.out_bytes = 0;
     it.work = it.plan.produced != 0 || it.plan.magic_used + it.plan.consumed != 0;
-    total_in += align64(it.in_bytes);
-    total_out += align64(it.out_bytes);
-    if (it.work && (it.in_bytes < kDirectCopyBytes || it.out_bytes < kDirectCopyBytes)) all_big = false;
+    total_in += align64(it.pin_in != nullptr ? 0 : it.in_bytes);
+    total_out += align64(it.pin_out != nullptr ? 0 : it.out_bytes);
   }
-  // Small calls (a server's 10-20 ms frames, a Transform's 64 KiB chunks) are all latency: the kernels read and write
-  // pinned memory straight through PCIe, one wait (process_host's small-call path).  Larger ones: inputs of >= 256 KB
-  // go from the caller's pageable memory by the runtime's own staged copies, smaller ones are gathered in the pinned
-  // buffer and travel as ONE copy; the same on the way out.
-  const bool zero_copy = total_in < kZeroCopyBelow && total_out < kZeroCopyBelow;
-  // layout: the small buffers first (one contiguous range = one copy), then the large ones
-  size_t small_in = 0, small_out = 0, off_in = 0, off_out = 0;
+  // Every side by the rule of host_transfer.h, the call's pageable totals deciding whether it is small.  Small calls (a
+  // server's 10-20 ms frames, a Transform's 64 KiB chunks) run on pinned memory alone; larger ones gather their Staged
+  // buffers in the pinned buffer, which travels as ONE copy each way.
+  const bool small = small_call(total_in, total_out);
+  Wait wait;
+  bool all_big = true;  // every working state Copy both ways: the pipelined path (below)
+  for (Item &it : items) {
+    it.in_via = route_side(it.in_bytes, in[it.i] != nullptr, it.pin_in != nullptr, small);
+    it.out_via = route_side(it.out_bytes, true, it.pin_out != nullptr, small);
+    wait.add(it.in_via, it.in_bytes);
+    wait.add(it.out_via, it.out_bytes);
+    if (it.work && (it.in_via != Via::Copy || it.out_via != Via::Copy)) all_big = false;
+  }
+  // layout: the gathered buffers first (one contiguous range = one copy), then the Copy ones
+  auto through_stage = [](Via v, size_t bytes) { return v == Via::InPlace ? 0 : bytes; };
+  size_t gathered_in = 0, gathered_out = 0, off_in = 0, off_out = 0;
   for (int pass = 0; pass < 2; pass++)
     for (Item &it : items) {
-      const bool big_in = !zero_copy && it.in_bytes >= kDirectCopyBytes, big_out = !zero_copy && it.out_bytes >= kDirectCopyBytes;
-      if (big_in == (pass == 1)) {
+      if ((it.in_via == Via::Copy) == (pass == 1)) {
         it.in_off = off_in;
-        off_in += align64(it.in_bytes);
-        if (pass == 0) small_in = off_in;
+        off_in += align64(through_stage(it.in_via, it.in_bytes));
+        if (pass == 0) gathered_in = off_in;
       }
-      if (big_out == (pass == 1)) {
+      if ((it.out_via == Via::Copy) == (pass == 1)) {
         it.out_off = off_out;
-        off_out += align64(it.out_bytes);
-        if (pass == 0) small_out = off_out;
+        off_out += align64(through_stage(it.out_via, it.out_bytes));
+        if (pass == 0) gathered_out = off_out;
       }
     }
-  int rc = grow_stage(device, &ms.h_in, &ms.h_in_cap, zero_copy ? total_in : small_in, true);
-  if (rc == SPEEXHIP_ERR_SUCCESS) rc = grow_stage(device, &ms.h_out, &ms.h_out_cap, (zero_copy ? total_out : small_out) + 128, true);
-  if (rc == SPEEXHIP_ERR_SUCCESS && !zero_copy) rc = grow_stage(device, &ms.d_in, &ms.d_in_cap, total_in, false);
-  if (rc == SPEEXHIP_ERR_SUCCESS && !zero_copy) rc = grow_stage(device, &ms.d_out, &ms.d_out_cap, total_out, false);
+  int rc = grow_stage(device, &ms.h_in, &ms.h_in_cap, gathered_in, true);
+  if (rc == SPEEXHIP_ERR_SUCCESS) rc = grow_stage(device, &ms.h_out, &ms.h_out_cap, gathered_out + 128, true);
+  if (rc == SPEEXHIP_ERR_SUCCESS && !small) rc = grow_stage(device, &ms.d_in, &ms.d_in_cap, total_in, false);
+  if (rc == SPEEXHIP_ERR_SUCCESS && !small) rc = grow_stage(device, &ms.d_out, &ms.d_out_cap, total_out, false);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  char *src_base = zero_copy ? ms.h_in : ms.d_in, *dst_base = zero_copy ? ms.h_out : ms.d_out;
+  char *src_base = small ? ms.h_in : ms.d_in, *dst_base = small ? ms.h_out : ms.d_out;
 
+  // Large calls in pieces (below): a launch then carries about 16 MB of input, so that the transfer of the next
+  // piece and the results of the previous one have something to overlap with.
+  static const int env_pipe = diag_int(SPEEXHIP_DIAG_ENV("SPEEXHIP_MANY_PIPELINE"), -1);  // A/B: 0 off
+  const bool pipelined = all_big && env_pipe != 0 && total_in >= (static_cast<size_t>(32) << 20);
   // launches: the states that share (tables, mode, window format) go together, at most 32 per launch
   std::vector<std::vector<Item *>> launches;
   {
@@ -1910,10 +1823,6 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
       if (!it.work) continue;  // nothing to run: the state stays where it is
       groups[std::make_tuple(static_cast<const void *>(it.b->tables_.get()), it.b->mode_, it.b->float_seen_)].push_back(&it);
     }
-    // Large calls in pieces (below): a launch then carries about 16 MB of input, so that the transfer of the next
-    // piece and the results of the previous one have something to overlap with.
-    static const int env_pipe = SPEEXHIP_DIAG_ENV("SPEEXHIP_MANY_PIPELINE") ? std::atoi(SPEEXHIP_DIAG_ENV("SPEEXHIP_MANY_PIPELINE")) : -1;  // A/B: 0 off
-    const bool pipelined = !zero_copy && all_big && env_pipe != 0 && total_in >= (static_cast<size_t>(32) << 20);
     for (auto &kv : groups) {
       std::vector<Item *> &g = kv.second;
       size_t per = kMaxPackedStreams;
@@ -1952,16 +1861,8 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
       d.out = it.pin_out != nullptr ? it.pin_out : dst_base + it.out_off;
       d.hist_next = b->d_hist_[b->hist_cur_ ^ 1];
       d.in_frames = in_len[it.i];
-      d.n_out = it.plan.produced;
-      d.consumed = it.plan.magic_used + it.plan.consumed;
-      d.hist_frames = f.taps - 1 + it.plan.begin.magic;
-      d.hist_keep = f.taps - 1 + it.plan.end.magic;
-      d.last0 = it.plan.begin.last;
-      d.frac0 = it.plan.begin.frac;
-      d.k_shift = phase_index_of(f.num, f.den, it.plan.begin.frac);
-      d.base_shift = it.plan.begin.last - static_cast<int32_t>((static_cast<uint64_t>(d.k_shift) * f.num) / f.den);
-      d.tile_begin = 0;
-      d.m_total = static_cast<uint32_t>((static_cast<uint64_t>(d.k_shift) + d.n_out + f.den - 1) / f.den);
+      set_position(d, f, it.plan.begin, it.plan.produced, it.plan.magic_used + it.plan.consumed, f.taps - 1 + it.plan.begin.magic,
+                   f.taps - 1 + it.plan.end.magic);
       max_out = std::max(max_out, it.plan.produced);
     }
     const int lrc = g[0]->b->launch_chunk(pack.d, pack, cnt, max_out, float_io, stream);
@@ -1982,8 +1883,7 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
       if (!it.work) commit_item(it);
   };
 
-  static const int env_pipe2 = SPEEXHIP_DIAG_ENV("SPEEXHIP_MANY_PIPELINE") ? std::atoi(SPEEXHIP_DIAG_ENV("SPEEXHIP_MANY_PIPELINE")) : -1;
-  if (!zero_copy && all_big && env_pipe2 != 0 && total_in >= (static_cast<size_t>(32) << 20) && launches.size() >= 2) {
+  if (pipelined && launches.size() >= 2) {
     // Large calls, pipelined (round 5).  PCIe is full duplex, but the runtime's pageable copies keep the thread that
     // issues them busy until they are staged, so one thread alone moves inputs, computes, and moves results strictly
     // one after the other: 32 streams x 2^20 stereo frames 5.8 ms, of which 0.2 are the kernel.  Here the calling
@@ -2082,39 +1982,29 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
 
   for (const Item &it : items) {
     if (it.in_bytes == 0) continue;
-    if (zero_copy || it.in_bytes < kDirectCopyBytes)
-      std::memcpy(ms.h_in + it.in_off, in[it.i], it.in_bytes);
-    else
+    if (it.in_via == Via::Bounce || it.in_via == Via::Staged) std::memcpy(ms.h_in + it.in_off, in[it.i], it.in_bytes);
+    if (it.in_via == Via::Copy)
       HIP_TRY(hipMemcpyAsync(ms.d_in + it.in_off, in[it.i], it.in_bytes, hipMemcpyHostToDevice, ms.stream));
   }
-  if (!zero_copy && small_in != 0) HIP_TRY(hipMemcpyAsync(ms.d_in, ms.h_in, small_in, hipMemcpyHostToDevice, ms.stream));
+  // (not small: the gathered range holds the Staged buffers)
+  if (!small && gathered_in != 0) HIP_TRY(hipMemcpyAsync(ms.d_in, ms.h_in, gathered_in, hipMemcpyHostToDevice, ms.stream));
   for (const std::vector<Item *> &g : launches) {
     rc = launch(g, ms.stream);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
   commit();
   // results back
-  if (zero_copy) {
-    volatile uint32_t *done = reinterpret_cast<volatile uint32_t *>(ms.h_out + ((ms.h_out_cap - 64) & ~static_cast<size_t>(63)));
-    const uint32_t seq = ++ms.seq;
-    *done = seq - 1;
-    if (!launches.empty()) {
-      const int wrc = wait_done(ms.stream, done, seq, spin_budget_us(pinned_bytes));
-      if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
-    }
-    drain.armed = false;
-    for (const Item &it : items)
-      if (it.out_bytes != 0) std::memcpy(out[it.i], ms.h_out + it.out_off, it.out_bytes);
-    return SPEEXHIP_ERR_SUCCESS;
-  }
-  if (small_out != 0) HIP_TRY(hipMemcpyAsync(ms.h_out, ms.d_out, small_out, hipMemcpyDeviceToHost, ms.stream));
+  if (!small && gathered_out != 0) HIP_TRY(hipMemcpyAsync(ms.h_out, ms.d_out, gathered_out, hipMemcpyDeviceToHost, ms.stream));
   for (const Item &it : items)
-    if (it.out_bytes >= kDirectCopyBytes)
+    if (it.out_via == Via::Copy)
       HIP_TRY(hipMemcpyAsync(out[it.i], ms.d_out + it.out_off, it.out_bytes, hipMemcpyDeviceToHost, ms.stream));
-  HIP_TRY(hipStreamSynchronize(ms.stream));
+  if (wait.sync || !launches.empty()) {
+    const int wrc = wait_call(ms.stream, wait, tail_word(ms.h_out, ms.h_out_cap), ++ms.seq);
+    if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
+  }
   drain.armed = false;
   for (const Item &it : items)
-    if (it.out_bytes != 0 && it.out_bytes < kDirectCopyBytes) std::memcpy(out[it.i], ms.h_out + it.out_off, it.out_bytes);
+    if (pinned_part(it.out_via, it.out_bytes) != 0) std::memcpy(out[it.i], ms.h_out + it.out_off, it.out_bytes);
   return SPEEXHIP_ERR_SUCCESS;
 }
 

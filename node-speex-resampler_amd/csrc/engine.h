@@ -11,6 +11,7 @@
 #include "../../include/speexhip_resampler.h"
 #include "device_types.h"
 #include "filter_design.h"
+#include "host_transfer.h"
 #include "kernels.h"
 #include "stream_plan.h"
 
@@ -156,6 +157,7 @@ class Batch {
   int quiesce();  // waits for this batch's own enqueued work (never for the whole device)
   uint32_t block_in() const { return line_ - (filter_.taps - 1); }
   int ensure_stage(size_t dev_in, size_t dev_out, size_t pin_in, size_t pin_out);
+  int stage_input(Via via, const void *in, size_t bytes, const void *pin, const void **src);
   int run_plans(const void *d_in, uint64_t in_stride, const uint32_t *in_frames, void *d_out,
                 uint64_t out_stride, const CallPlan *plans, bool float_io, hipStream_t stream);
   int launch_chunk(const StreamDesc *descs, const DescPack &pack, uint32_t n, uint32_t max_out, bool float_io,

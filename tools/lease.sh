@@ -72,14 +72,12 @@ import speexhip
 for mb in (4, 64):
     print('pcie probe %d MiB: h2d %.1f d2h %.1f both-each %.1f GB/s' % ((mb,) + speexhip.pcie_peak(mb << 20)))
 print('libamdhip64 loaded:', sorted(set(l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l)))" 2>&1 | tee -a $OUT
-    tools/ab.sh -o $OUT -- "" "SPEEXHIP_PINNED_IN_PIECES=1 SPEEXHIP_PIECES=2" "SPEEXHIP_PINNED_IN_PIECES=1 SPEEXHIP_PIECES=4" "SPEEXHIP_PIECES=1" "SPEEXHIP_PIECES=2" \
-      "SPEEXHIP_PIECES=4" -- python tools/pinned_one.py cfg2 1048576
+    tools/ab.sh -o $OUT -- "" "SPEEXHIP_PIECES=1" "SPEEXHIP_PIECES=2" "SPEEXHIP_PIECES=4" -- python tools/pinned_one.py cfg2 1048576
     python tools/pinned_path_bench.py cfg2 > $O/r${N}_pinned_path_notorch$NT.json 2>&1
   done
   export SPEEXHIP_PY_NO_TORCH=1
   for CFG in cfg2 cfg3; do
-    tools/ab.sh -o $O/r${N}_pinned_ab.txt -- "" "SPEEXHIP_PINNED_IN_PIECES=1 SPEEXHIP_PIECES=2" "SPEEXHIP_PINNED_IN_PIECES=1 SPEEXHIP_PIECES=4" "SPEEXHIP_PINNED_IN_PIECES=1 SPEEXHIP_PIECES=8" \
-      "SPEEXHIP_TILE_PERIODS=32" "SPEEXHIP_TILE_PERIODS=16" "SPEEXHIP_TILE_PERIODS=8" "SPEEXHIP_MODE=fast_fixed SPEEXHIP_TILE_PERIODS=16" -- python tools/pinned_one.py $CFG 1048576
+    tools/ab.sh -o $O/r${N}_pinned_ab.txt -- "" "SPEEXHIP_TILE_PERIODS=32" "SPEEXHIP_TILE_PERIODS=16" "SPEEXHIP_TILE_PERIODS=8" "SPEEXHIP_MODE=fast_fixed SPEEXHIP_TILE_PERIODS=16" -- python tools/pinned_one.py $CFG 1048576
   done
   # the many-states call: lanes and what a pinned input beside pageable results does
   tools/ab.sh -o $O/r${N}_lanes_ab.txt -f "{k: {a: b['ms'] for a, b in v.items() if a in ('pageable', 'pinned_in', 'pinned_in_pinned_out')} for k, v in d.items() if k.startswith('many32_1048576')}" \

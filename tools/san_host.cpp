@@ -1,11 +1,13 @@
 // tools/san_host.cpp -- the host-only half of the product (filter_design.cpp, stream_plan.cpp) under ASan + UBSan:
-// every rate pair of a grid incl. absurd ones, random positions / pending frames / capacities up to 2^32.
+// every rate pair of a grid incl. absurd ones, random positions / pending frames / capacities up to 2^32; and the
+// host-buffer staging rule (host_transfer.h) against its table.
 // Built and run by tests/test_cpu_sanitizers.py (GPU sanitizers are not available on the pool).
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 #include "devices.h"
 #include "filter_design.h"
+#include "host_transfer.h"
 #include "stream_plan.h"
 using namespace speexhip;
 int main() {
@@ -60,6 +62,52 @@ int main() {
     if (d < -1 || d >= 8) { printf("BAD placement\n"); return 1; }
     placements++;
   }
-  printf("sanitizer run ok: %ld filters, %ld plans, %ld placements\n", filters, plans, placements);
+  // the host-buffer staging rule (host_transfer.h): a single-state call, both sides
+  const size_t K = 1024, M = 1024 * 1024, Z = kZeroCopyBelow, D = kDirectCopyBytes;
+  struct Row {
+    size_t in;
+    bool in_present, in_pinned;
+    size_t out;
+    bool out_pinned;
+    Via want_in, want_out;
+    bool want_sync;
+    uint32_t want_spin;  // (polled rows)
+  };
+  const Row rows[] = {
+      {64 * K, true, false, 70 * K, false, Via::Bounce, Via::Bounce, false, 300},
+      {500 * K, true, false, 500 * K, false, Via::Bounce, Via::Bounce, false, 300},
+      {100 * K, true, false, 800 * K, false, Via::Staged, Via::Copy, true, 0},
+      {800 * K, true, false, 100 * K, false, Via::Copy, Via::Staged, true, 0},
+      {4 * M, true, false, 4506 * K, false, Via::Copy, Via::Copy, true, 0},
+      {D, true, false, Z, false, Via::Copy, Via::Copy, true, 0},  // (D inclusive; out exactly Z: not small)
+      {D - 1, true, false, Z, false, Via::Staged, Via::Copy, true, 0},
+      {D, true, false, Z - 1, false, Via::Bounce, Via::Bounce, false, 300},
+      {4 * M, true, true, 4506 * K, true, Via::InPlace, Via::InPlace, false, spin_budget_us(4 * M + 4506 * K)},
+      {4 * M, true, true, 500 * K, false, Via::InPlace, Via::Bounce, false, spin_budget_us(4 * M)},
+      {4 * M, true, true, 800 * K, false, Via::InPlace, Via::Copy, true, 0},
+      {500 * K, true, false, 1 * M, true, Via::Bounce, Via::InPlace, false, spin_budget_us(1 * M)},
+      {1 * M, true, false, 1 * M, true, Via::Copy, Via::InPlace, true, 0},
+      {0, false, false, 64 * K, false, Via::None, Via::Bounce, false, 300},
+      {4 * M, false, false, 64 * K, false, Via::None, Via::Bounce, false, 300},  // (absent input: 0 pageable bytes)
+  };
+  long routes = 0;
+  for (const Row &r : rows) {
+    const bool small = small_call(r.in_present && !r.in_pinned ? r.in : 0, r.out_pinned ? 0 : r.out);
+    const Via vin = route_side(r.in, r.in_present, r.in_pinned, small), vout = route_side(r.out, true, r.out_pinned, small);
+    Wait w;
+    w.add(vin, r.in);
+    w.add(vout, r.out);
+    if (vin != r.want_in || vout != r.want_out || w.sync != r.want_sync || (!w.sync && w.spin_us() != r.want_spin)) {
+      printf("BAD route: in %zu out %zu -> %d / %d sync %d spin %u\n", r.in, r.out, static_cast<int>(vin), static_cast<int>(vout),
+             w.sync, w.spin_us());
+      return 1;
+    }
+    routes++;
+  }
+  if (small_call(0, Z) || !small_call(Z - 1, Z - 1) || spin_budget_us(4 * M + 4506 * K) <= 300 || spin_budget_us(1ull << 40) != 2000) {
+    printf("BAD thresholds\n");
+    return 1;
+  }
+  printf("sanitizer run ok: %ld filters, %ld plans, %ld placements, %ld routes\n", filters, plans, placements, routes);
   return 0;
 }
