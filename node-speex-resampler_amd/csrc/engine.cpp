@@ -142,6 +142,7 @@ int ctl_download(void *dst, const char *base, size_t total, size_t off, size_t l
 }
 
 const size_t kLdsBudget = 150 * 1024;  // of the CU's 160 KiB
+static_assert(kStagedLdsBytes <= kLdsBudget, "the period kernel's staged-store instance asks for more LDS than the budget");
 // A piecewise host call (take_in_pieces) takes 2 MB of input per piece, at most four: a piece costs ~15 us (an event,
 // a cross-stream wait, a launch) and buys the overlap of its launch -- the result leaving through PCIe -- with the next
 // piece's copy.  2^20 stereo frames (4.2 MB in): 1 / 2 / 3 / 4 pieces 0.1935 / 0.1879 / 0.198 / 0.224 ms per call; 8

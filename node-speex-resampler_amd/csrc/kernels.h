@@ -105,6 +105,9 @@ struct PeriodPlan {         // per filter, fixed at init
 // a multiple of 5 that is at least 10 (whole groups of five phases); returns true and fills *view (a copy of f, table
 // included) when this (filter, channel count) wants it, false (view untouched) otherwise.
 bool period_view(const FilterSpec &f, uint32_t channels, FilterSpec *view);
+// LDS of a workgroup of the period kernel's staged-store instance (round 7, kernels_period_impl.h: StagedImage): the
+// window at the front, the output image at the end -- the planners' whole budget (engine.cpp, kLdsBudget)
+constexpr uint32_t kStagedLdsBytes = 150 * 1024;
 PeriodPlan plan_period(const FilterSpec &f, uint32_t channels, size_t lds_budget, bool w16 = false, bool a64 = false,
                        bool pp = false);
 PeriodPlan plan_period_r(const FilterSpec &f, uint32_t channels, size_t lds_budget, uint32_t r, bool w16 = false,

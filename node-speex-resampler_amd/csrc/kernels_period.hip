@@ -402,7 +402,7 @@ struct PeriodShape {
 hipError_t launch_period_plan(const FilterSpec &f, const PeriodPlan &t, const float *d_rows, uint32_t channels,
                               const StreamDesc *h_descs, const DescPack *pack,
                               uint32_t n_streams, bool float_io, hipStream_t stream, PeriodShape *probe = nullptr,
-                              bool fixed_shape = false);
+                              bool fixed_shape = false, bool fine = false);
 }  // namespace
 
 // Which window for an int16 launch of a ratio that has both?  The int16 window's tiles hold twice the periods
@@ -537,7 +537,8 @@ hipError_t launch_period(const FilterSpec &f, const PeriodPlan &t, const float *
     const uint32_t max_periods = periods_of_launch(f, h_descs, n_streams);
     const uint32_t tiles = (max_periods + t.lane_periods - 1) / t.lane_periods;
     if (split_count(t, tiles, n_streams, 2 * device_compute_units()) > 1)
-      return launch_period_plan(f, *fine, d_rows_fine, channels, h_descs, pack, n_streams, float_io, stream, nullptr, fixed_shape);
+      return launch_period_plan(f, *fine, d_rows_fine, channels, h_descs, pack, n_streams, float_io, stream, nullptr, fixed_shape,
+                                true);
   }
   return launch_period_plan(f, t, d_rows, channels, h_descs, pack, n_streams, float_io, stream, nullptr, fixed_shape);
 }
@@ -545,7 +546,8 @@ hipError_t launch_period(const FilterSpec &f, const PeriodPlan &t, const float *
 namespace {
 hipError_t launch_period_plan(const FilterSpec &f, const PeriodPlan &plan, const float *d_rows, uint32_t channels,
                               const StreamDesc *h_descs, const DescPack *pack,
-                              uint32_t n_streams, bool float_io, hipStream_t stream, PeriodShape *probe, bool fixed_shape) {
+                              uint32_t n_streams, bool float_io, hipStream_t stream, PeriodShape *probe, bool fixed_shape,
+                              bool fine) {
   PeriodPlan t = plan;
 #ifdef SPEEXHIP_DIAG
   {  // A/B: fewer periods per tile than the plan's (more, smaller workgroups over the same LDS allocation)
@@ -782,20 +784,39 @@ hipError_t launch_period_plan(const FilterSpec &f, const PeriodPlan &plan, const
   uint32_t grid_x = (max_periods == 0 ? 0 : tiles) + 1;
   if (splits > 1 && n_streams == 1) grid_x = (grid_x + 7) / 8 * 8;
   const dim3 grid(grid_x, n_streams, splits);
+  // Staged stores (fir_tile_staged, kernels_period_impl.h): the fine plan's stereo launch of ONE generation -- every
+  // workgroup, history blocks included, on a CU of its own, so the larger LDS allocation costs no residency --, each
+  // wave one phase group (no walk), no tap-range shares, and output buffers whose frames are whole dwords.  There the
+  // stores and the end-of-kernel write-back were 1.75-2.1 us of the 11.8 us of BASELINE configs[1]'s one-stream launch, 1.45
+  // with the image (profiles/r07_phases_cfg2_s1.txt); the launch 11.85 -> 11.44 us by kernel trace, float I/O 13.7 -> 12.7
+  // by HIP events (r07_staged_ab.txt: the image and the nt stores pay only together).  Launches of several generations keep the per-lane stores: the other workgroup
+  // on the CU hides them.
+  static const bool staged_off = SPEEXHIP_DIAG_ENV("SPEEXHIP_NO_STAGED") != nullptr;  // diagnostics: A/B
+  bool staged = fine && !staged_off && t.r == 5 && t.ct == 2 && t.cgroups == 1 && !t.pp && !t.a64 && !t.w16 && t.pad == 0 &&
+                t.lane_periods <= 64 && p.ksplit == 1 && wave_groups <= 16 && wave_groups * splits >= t.groups &&
+                static_cast<uint64_t>(grid_x) * n_streams * splits <= device_compute_units() &&
+                t.window_bytes <= (float_io ? StagedImage<float>::kAt : StagedImage<int16_t>::kAt);
+  for (uint32_t i = 0; staged && i < n_streams; i++)
+    if ((reinterpret_cast<uintptr_t>(h_descs[i].out) & 3u) != 0) staged = false;  // (2-byte aligned int16: store_group)
   // diagnostics: one line per launch shape on stderr
   static const bool verbose = SPEEXHIP_DIAG_ENV("SPEEXHIP_PLAN_VERBOSE") != nullptr;
   if (verbose) {
     static uint64_t last = 0;
-    const uint64_t key = (static_cast<uint64_t>(tiles) << 40) ^ (static_cast<uint64_t>(n_streams) << 24) ^ (splits << 16) ^ (t.r << 8) ^ p.ksplit ^ (t.w16 ? 1u << 31 : 0u);
+    const uint64_t key = (static_cast<uint64_t>(tiles) << 40) ^ (static_cast<uint64_t>(n_streams) << 24) ^ (splits << 16) ^ (t.r << 8) ^ p.ksplit ^
+                         (t.w16 ? 1u << 31 : 0u) ^ (staged ? 1u << 30 : 0u);
     if (key != last) {
       last = key;
-      std::fprintf(stderr, "period launch: r=%u%s groups=%u lane_periods=%u tiles=%u streams=%u splits=%u wave_groups=%u parts=%u threads=%u window=%zu B\n",
-                   t.r, t.w16 ? " (int16 window)" : "", t.groups, t.lane_periods, tiles, n_streams, splits, wave_groups, p.ksplit, threads, t.window_bytes);
+      std::fprintf(stderr, "period launch: r=%u%s groups=%u lane_periods=%u tiles=%u streams=%u splits=%u wave_groups=%u parts=%u threads=%u window=%zu B staged=%d\n",
+                   t.r, t.w16 ? " (int16 window)" : "", t.groups, t.lane_periods, tiles, n_streams, splits, wave_groups, p.ksplit, threads, t.window_bytes,
+                   staged ? 1 : 0);
     }
   }
   // (an int16 window -- t.w16 -- exists for int16 calls on the layouts the ISA loop is generated for: ONE or CGV)
   if (t.w16 && float_io) return hipErrorInvalidValue;
   if (!t.float_ok) return hipErrorInvalidValue;  // (a plan that only carries its int16 plan: engine.cpp never launches it)
+  if (staged)
+    return float_io ? launch_rc<5, 2, true, false, float, 0, false, false, 0, true>(p, pack, grid, threads, kStagedLdsBytes, stream)
+                    : launch_rc<5, 2, true, false, int16_t, 0, false, false, 0, true>(p, pack, grid, threads, kStagedLdsBytes, stream);
   if (t.a64)  // kernels_period64.hip / kernels_period64_w16.hip
     return t.w16 ? dispatch_period64_w16(t, p, pack, grid, threads, float_io, stream)
                  : dispatch_period64(t, p, pack, grid, threads, float_io, stream);

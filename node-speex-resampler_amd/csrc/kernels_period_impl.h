@@ -398,7 +398,8 @@ __device__ __forceinline__ void fir_group64(const PeriodParams &p, const double 
 // Round / interleave / store the R phases of group g for this lane's period: R consecutive
 // frames per lane, 4 bytes each per channel pair.  With two workgroups per CU the stores
 // overlap the other workgroup's FMAs (an LDS transpose for fully coalesced stores measured
-// slower).
+// slower there).  A stereo launch of ONE generation has nothing to hide them behind: it writes
+// through an LDS image instead (fir_tile_staged, round 7).
 template <int R, int CT, bool ONE_GROUP, typename T>
 __device__ __forceinline__ void store_group(const PeriodParams &p, const StreamDesc &d, const LaneCtx &c,
                                             uint32_t g, const f32x2 (&acc)[R]) {
@@ -524,6 +525,17 @@ __device__ __forceinline__ void store_group(const PeriodParams &p, const StreamD
       //  But a lane's 16-byte pieces lie 640 bytes apart, and written through each is a fabric write of its own where
       //  L2 would have merged eight of them into a line: one stream 11.9 -> 15.7 us, 4 streams 33.4 -> 42.3,
       //  32 streams 206 -> 250 (same box, profiles/r05_ab_sc1.txt).)
+#ifdef SPEEXHIP_DIAG
+      if (SPEEXHIP_DIAG_SKIP(p, 1024u)) {  // (control for the staged stores: these per-lane runs as nt stores)
+#pragma unroll
+        for (int i = 0; i + 4 <= R; i += 4)
+          __builtin_nontemporal_store(u32x4_a4{v[i], v[i + 1], v[i + 2], v[i + 3]}, (g_u32x4_a4 *)(od + i));
+        if constexpr (R % 4 >= 2)
+          __builtin_nontemporal_store(u32x2_a4{v[R / 4 * 4], v[R / 4 * 4 + 1]}, (g_u32x2_a4 *)(od + R / 4 * 4));
+        if constexpr (R % 2 != 0) __builtin_nontemporal_store(v[R - 1], od + (R - 1));
+        return;
+      }
+#endif
 #pragma unroll
       for (int i = 0; i + 4 <= R; i += 4) *(g_u32x4_a4 *)(od + i) = u32x4_a4{v[i], v[i + 1], v[i + 2], v[i + 3]};
       if constexpr (R % 4 >= 2) *(g_u32x2_a4 *)(od + R / 4 * 4) = u32x2_a4{v[R / 4 * 4], v[R / 4 * 4 + 1]};
@@ -903,6 +915,104 @@ __device__ __forceinline__ void fir_tile(const PeriodParams &p0, const StreamDes
   }
 }
 
+// ---- staged stores (round 7) ------------------------------------------------------------------------
+// A launch that is ONE generation of workgroups (the one-stream `fine` plan: 224 workgroups, one per CU) has no second
+// workgroup on a CU whose FMAs could hide the stores, and its 224 workgroups leave their FIR loops within ~0.3 us of
+// each other.  Per lane, store_group writes a period's R = 5 frames as one 20-byte run, and neighbouring lanes' runs lie
+// den frames apart: each store instruction asks L2 for 64 partial lines, ~460 000 requests per launch for 4.6 MB.  Here
+// the waves put their frames into an image in LDS instead -- row = period of the tile, the share's wave_groups x R
+// consecutive phases in it -- and after one barrier all the lanes of the workgroup write each row's run of output as
+// 16-byte pieces at 16-byte addresses, eight lanes to a 128-byte line.  The bytes and the places written are store_group's
+// (the call's first period cut by k_shift, its last cut by n_out, the padding phases past den), only the instructions
+// that write them differ.  Its own instance (resample_period<..., ST = true>): launch_period_plan takes it for stereo
+// R = 5 launches of one generation whose waves own one phase group each.
+template <typename T>
+struct StagedImage {
+  // 16 waves x R = 5 frames of one (int16 x 2) or two (float x 2) dwords per row, + 1 dword: with an odd row stride
+  // the lanes of a wave -- one row each -- write distinct banks (ds_write: bank = dword address mod 32)
+  static constexpr uint32_t kRowDwords = 16 * 5 * (sizeof(T) == 4 ? 2 : 1) + 1;
+  static constexpr uint32_t kBytes = 64 * kRowDwords * 4;  // one row per lane of a wave
+  static constexpr uint32_t kAt = (kStagedLdsBytes - kBytes) / 16 * 16;  // byte offset in LDS, behind the window
+};
+
+template <int R, int CT, typename T>
+__device__ __forceinline__ void fir_tile_staged(const PeriodParams &p0, KParams pp, const float *__restrict__ rows, KDesc dp,
+                                                float *xs, uint32_t xshift, uint32_t m_lo, uint32_t m_cnt, uint32_t wave,
+                                                uint32_t lane, uint32_t zsplit) {
+  static_assert(R == 5 && CT == 2, "written for stereo groups of five phases");
+  using Img = StagedImage<T>;
+  constexpr uint32_t kDpf = sizeof(T) == 4 ? 2u : 1u;  // dwords per frame
+  uint32_t *img = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(xs) + Img::kAt);
+  const uint32_t g = zsplit * p0.wave_groups + wave;
+  // every wave comes to the barrier below: the staging helpers and the waves past the last group skip only the FIR
+  if (wave < p0.wave_groups && g < p0.groups) {
+    const LaneCtx c = lane_ctx<CT, true, false>(p0, xshift, m_lo, m_cnt, lane);
+    f32x2 acc[R];
+#pragma unroll
+    for (int i = 0; i < R; i++) acc[i] = f32x2{0.f, 0.f};
+    fir_group<R, CT, false, CT, false>(p0, rows, xs, c, g, SPEEXHIP_DIAG_SKIP(p0, 4u), acc);
+    // (the image lies behind the window: no barrier in front of these writes)
+    uint32_t *row = img + lane * Img::kRowDwords + wave * (R * kDpf);
+#pragma unroll
+    for (int i = 0; i < R; i++) {
+      if constexpr (sizeof(T) == 4) {
+        row[2 * i] = __float_as_uint(acc[i].x);
+        row[2 * i + 1] = __float_as_uint(acc[i].y);
+      } else {
+        row[i] = round_pack_pcm(acc[i].x, acc[i].y);
+      }
+    }
+  }
+  __syncthreads();
+  const PeriodParams q = load_k(pp);
+  const StreamDesc d = load_k(dp);
+  if (SPEEXHIP_DIAG_SKIP(q, 8u)) return;
+  if (q.prio & 2u) __builtin_amdgcn_s_setprio(2);
+  // the share's phases [ph_lo, ph_lo + ph_n) of each of the tile's m_cnt periods: row r is frames [f0, f0 + ph_n) of the
+  // call, f0 = (m_lo + r) den + ph_lo - k_shift, of which [0, n_out) are written
+  constexpr uint32_t kFb = 4u * kDpf;  // bytes per frame
+  const uint32_t ph_lo = zsplit * q.wave_groups * R;
+  const uint32_t ph_n = ph_lo < q.den ? min(q.wave_groups * R, q.den - ph_lo) : 0u;
+  const uint32_t pieces = (ph_n * kFb + 15u) / 16u + 1u;  // 16-byte blocks a row's run can touch at any alignment
+  const uint64_t out = reinterpret_cast<uint64_t>(d.out);  // (4-byte aligned: launch_period_plan)
+#pragma clang loop unroll(disable)
+  for (uint32_t t = threadIdx.x; t < m_cnt * pieces; t += q.threads) {
+    const uint32_t r = t / pieces, k = t - r * pieces;
+    const int64_t f0 = static_cast<int64_t>(m_lo + r) * q.den + ph_lo - d.k_shift;
+    const int64_t f_lo = max(f0, static_cast<int64_t>(0));
+    const int64_t f_hi = min(f0 + static_cast<int64_t>(ph_n), static_cast<int64_t>(d.n_out));
+    if (f_lo >= f_hi) continue;
+    const uint64_t a_lo = out + static_cast<uint64_t>(f_lo) * kFb, a_hi = out + static_cast<uint64_t>(f_hi) * kFb;
+    const uint64_t blk = (a_lo & ~static_cast<uint64_t>(15)) + 16u * k;
+    if (blk >= a_hi) continue;
+    const uint64_t s = max(blk, a_lo), e = min(blk + 16u, a_hi);
+    // dword of the row that byte s holds
+    const uint32_t col = static_cast<uint32_t>((static_cast<int64_t>(s - out) - f0 * kFb) >> 2);
+    const uint32_t *src = img + r * Img::kRowDwords + col;
+    if (e - s == 16u) {
+      const u32x4 v = u32x4{src[0], src[1], src[2], src[3]};
+      // (nt: same box, one stream of cfg2, rocprofv3-free HIP events: plain stores 11.83 us, nt 11.35, write-through
+      //  -- sc1 -- 15.8; the per-lane stores of store_group gain nothing from nt: profiles/r07_staged_ab.txt, C and D)
+#ifdef SPEEXHIP_DIAG
+      // (A/B of the store's cache policy: SPEEXHIP_SKIP bit 256 = plain stores, bit 512 = write-through)
+      if (SPEEXHIP_DIAG_SKIP(q, 256u)) {
+        *reinterpret_cast<G<u32x4> *>(blk) = v;
+        continue;
+      }
+      if (SPEEXHIP_DIAG_SKIP(q, 512u)) {
+        asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(blk), "v"(v) : "memory");
+        continue;
+      }
+#endif
+      __builtin_nontemporal_store(v, reinterpret_cast<G<u32x4> *>(blk));
+    } else {  // the head or the tail of a run: 4, 8 or 12 bytes
+#pragma unroll
+      for (uint32_t j = 0; j < 3; j++)
+        if (s + 4u * j < e) reinterpret_cast<g_u32 *>(s)[j] = src[j];
+    }
+  }
+}
+
 // ---- tap-range shares (round 3, second take) -------------------------------------------------------
 // A launch that cannot fill the chip runs its tiles in shares of a few phase groups each, and a share's
 // few FIR waves then sit one to a SIMD: a wave alone waits out every scalar-load round trip (14-19 cycles
@@ -1118,7 +1228,8 @@ __device__ __forceinline__ void touch_rows(const PeriodParams &p, const float *_
 //
 // Workgroup = one tile (blockIdx.x) of one stream (blockIdx.y), optionally one of gridDim.z
 // shares of its phase groups.
-template <int R, int CT, bool ONE_GROUP, bool PADDED, typename T, int CGF = 0, bool W16 = false, bool KS = false, int AM = 0>
+template <int R, int CT, bool ONE_GROUP, bool PADDED, typename T, int CGF = 0, bool W16 = false, bool KS = false, int AM = 0,
+          bool ST = false>
 __global__ __launch_bounds__(1024, (R == 10 && !KS) ? 8 : 4) __attribute__((amdgpu_num_sgpr(80))) void resample_period(
     PeriodParams p, const float *__restrict__ rows, DescPack pack) {
   extern __shared__ __attribute__((aligned(16))) float xs[];
@@ -1223,6 +1334,12 @@ __global__ __launch_bounds__(1024, (R == 10 && !KS) ? 8 : 4) __attribute__((amdg
       fir_tile_parts<R, CT, ONE_GROUP, PADDED, T, CGF, W16, AM == 2>(&ka->p, rows, dp, xs, wg.xshift, m_lo, m_cnt, wave,
                                                                     threadIdx.x & 63u, blockIdx.z);
     return;
+  } else if constexpr (ST) {  // staged stores (fir_tile_staged): every wave of the workgroup takes part in them
+    static_assert(ONE_GROUP && !PADDED && !W16 && AM == 0, "staged stores: stereo frames on the float window");
+    const __attribute__((address_space(4))) KernArgs *ka =
+        (const __attribute__((address_space(4))) KernArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+    fir_tile_staged<R, CT, T>(p, &ka->p, rows, &ka->pack.d[blockIdx.y], xs, wg.xshift, m_lo, m_cnt, wave, threadIdx.x & 63u,
+                              blockIdx.z);
   } else {
   if (wave >= p.wave_groups) return;  // staging helpers (see launch_period): no phase group of their own
   const __attribute__((address_space(4))) KernArgs *ka =
@@ -1233,7 +1350,8 @@ __global__ __launch_bounds__(1024, (R == 10 && !KS) ? 8 : 4) __attribute__((amdg
   }
 }
 
-template <int R, int CT, bool ONE_GROUP, bool PADDED, typename T, int CGF = 0, bool W16 = false, bool KS = false, int AM = 0>
+template <int R, int CT, bool ONE_GROUP, bool PADDED, typename T, int CGF = 0, bool W16 = false, bool KS = false, int AM = 0,
+          bool ST = false>
 hipError_t launch_rc(const PeriodParams &p, const DescPack *pack, dim3 grid, uint32_t threads, size_t lds_bytes,
                      hipStream_t stream) {
 #ifdef SPEEXHIP_CXX_FIR_LOOP
@@ -1245,8 +1363,8 @@ hipError_t launch_rc(const PeriodParams &p, const DescPack *pack, dim3 grid, uin
     return hipErrorInvalidValue;
   } else {
     static std::atomic<uint64_t> seen{0};
-    opt_in_lds_on_this_device(resample_period<R, CT, ONE_GROUP, PADDED, T, CGF, W16, KS, AM>, seen);
-    hipLaunchKernelGGL((resample_period<R, CT, ONE_GROUP, PADDED, T, CGF, W16, KS, AM>), grid, dim3(threads), lds_bytes, stream,
+    opt_in_lds_on_this_device(resample_period<R, CT, ONE_GROUP, PADDED, T, CGF, W16, KS, AM, ST>, seen);
+    hipLaunchKernelGGL((resample_period<R, CT, ONE_GROUP, PADDED, T, CGF, W16, KS, AM, ST>), grid, dim3(threads), lds_bytes, stream,
                        p, p.rows, *pack);
     return hipGetLastError();
   }
