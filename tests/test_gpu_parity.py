@@ -28,6 +28,8 @@ MISMATCH_RATE = 4e-3   # (5e-3 until round 5; 3.5e-3 met a 3.53e-3 on 23 000 sam
 
 
 DIAG_LIB = os.path.join(ROOT, "node-speex-resampler_amd", "ab", "libspeexhip_diag.so")
+# the exact-model tests of the period kernel run in the diagnostics children below as well (instances only they can force)
+EXACT_MODEL_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_gpu_exact_model.py")
 
 
 def diag_env(**switches):
@@ -308,25 +310,29 @@ def test_node_drop_in_harness():
         assert "ALL NODE TESTS PASSED" in res.stdout
 
 
+# the slide kernel's (num, den, channel parity) instances (tests/test_gpu_exact_model.py runs the same lists)
+SLIDE_CASES = [(1, 24000, 48000, 10), (2, 24000, 48000, 10), (1, 16000, 48000, 5), (2, 16000, 48000, 7),
+               (1, 8000, 48000, 8), (2, 8000, 48000, 3), (1, 12000, 48000, 9), (4, 11025, 44100, 4),
+               (1, 48000, 48000, 6), (2, 24000, 24000, 5), (3, 22050, 44100, 6), (6, 8000, 16000, 0),
+               # num > 1: 2:1, 3:1, 4:1 decimation, 3:2, 2:3
+               (2, 96000, 48000, 7), (1, 48000, 24000, 10), (2, 48000, 16000, 5), (1, 48000, 16000, 8),
+               (2, 48000, 12000, 4), (1, 32000, 8000, 6), (2, 48000, 32000, 7), (1, 48000, 32000, 3),
+               (2, 32000, 48000, 9), (1, 32000, 48000, 5),
+               # den = 5: 1:5, 2:5, 3:5, 4:5, stereo (five accumulator pairs) and mono / 3 ch (den padded to 6)
+               (2, 8000, 40000, 7), (1, 8000, 40000, 5), (2, 16000, 40000, 10), (1, 16000, 40000, 3),
+               (2, 24000, 40000, 6), (3, 24000, 40000, 4), (2, 32000, 40000, 8), (1, 32000, 40000, 9),
+               # 5:2, 5:3, 5:4
+               (2, 40000, 16000, 5), (1, 40000, 16000, 7), (2, 40000, 24000, 4), (1, 40000, 24000, 6),
+               (2, 40000, 32000, 10), (1, 40000, 32000, 2),
+               # 8:3, 6:5, 5:6 (one period per lane for the last two)
+               (2, 32000, 12000, 7), (1, 64000, 24000, 5), (4, 32000, 12000, 3), (2, 48000, 40000, 6),
+               (1, 48000, 40000, 9), (3, 48000, 40000, 4), (2, 40000, 48000, 8), (1, 40000, 48000, 5), (6, 40000, 48000, 2)]
+
+
 def test_small_ratio_sliding_window_kernel_variants():
     """kernels_slide.hip: every (num, den, channel parity) instantiation -- channel-pair and
     phase-pair packing, P = 8 and P = 4, num = 1..4 -- in multi-call streams, vs the oracle."""
-    cases = [(1, 24000, 48000, 10), (2, 24000, 48000, 10), (1, 16000, 48000, 5), (2, 16000, 48000, 7),
-             (1, 8000, 48000, 8), (2, 8000, 48000, 3), (1, 12000, 48000, 9), (4, 11025, 44100, 4),
-             (1, 48000, 48000, 6), (2, 24000, 24000, 5), (3, 22050, 44100, 6), (6, 8000, 16000, 0),
-             # num > 1: 2:1, 3:1, 4:1 decimation, 3:2, 2:3
-             (2, 96000, 48000, 7), (1, 48000, 24000, 10), (2, 48000, 16000, 5), (1, 48000, 16000, 8),
-             (2, 48000, 12000, 4), (1, 32000, 8000, 6), (2, 48000, 32000, 7), (1, 48000, 32000, 3),
-             (2, 32000, 48000, 9), (1, 32000, 48000, 5),
-             # den = 5: 1:5, 2:5, 3:5, 4:5, stereo (five accumulator pairs) and mono / 3 ch (den padded to 6)
-             (2, 8000, 40000, 7), (1, 8000, 40000, 5), (2, 16000, 40000, 10), (1, 16000, 40000, 3),
-             (2, 24000, 40000, 6), (3, 24000, 40000, 4), (2, 32000, 40000, 8), (1, 32000, 40000, 9),
-             # 5:2, 5:3, 5:4
-             (2, 40000, 16000, 5), (1, 40000, 16000, 7), (2, 40000, 24000, 4), (1, 40000, 24000, 6),
-             (2, 40000, 32000, 10), (1, 40000, 32000, 2),
-             # 8:3, 6:5, 5:6 (one period per lane for the last two)
-             (2, 32000, 12000, 7), (1, 64000, 24000, 5), (4, 32000, 12000, 3), (2, 48000, 40000, 6),
-             (1, 48000, 40000, 9), (3, 48000, 40000, 4), (2, 40000, 48000, 8), (1, 40000, 48000, 5), (6, 40000, 48000, 2)]
+    cases = SLIDE_CASES
     for (ch, i, o, q) in cases:
         ref = orc.Oracle(ch, i, o, q)
         r = speexhip.Resampler(ch, i, o, q)
@@ -423,12 +429,16 @@ def test_eight_channel_padded_window_and_odd_channel_counts():
         r.close()
 
 
+# filters no fast kernel can hold: (channels, in, out, quality, frames)
+EXACT_FALLBACK_CASES = [(1, 192000, 1000, 10, 120000), (2, 192000, 1000, 8, 90000)]
+
+
 def test_extreme_ratios_take_the_exact_kernel_even_in_fast_mode():
     """Filters no fast kernel can hold (192:1 at quality 10: 49 152 taps, a window beyond the LDS) must still be right:
     the fast modes fall back to the bit-exact kernel (fast_path == 0), staged in LDS or streaming straight from L2 when
     the filter does not fit.  (Until round 6 this list also held 11:1, 7:6 and 64:1: they run the period kernel on a
     folded view now -- test_small_denominator_ratios_run_the_period_kernel_on_a_folded_view.)"""
-    for (ch, i, o, q, frames) in [(1, 192000, 1000, 10, 120000), (2, 192000, 1000, 8, 90000)]:
+    for (ch, i, o, q, frames) in EXACT_FALLBACK_CASES:
         ref = orc.Oracle(ch, i, o, q)
         r = speexhip.Resampler(ch, i, o, q)
         assert r.info()["fast_path"] == 0, (ch, i, o, q)
@@ -441,17 +451,21 @@ def test_extreme_ratios_take_the_exact_kernel_even_in_fast_mode():
         r.close()
 
 
+# ratios with den <= 6 outside the slide kernel's shapes: the period kernel on a folded view
+FOLDED_CASES = [(1, 88000, 8000, 5), (2, 56000, 48000, 4), (2, 96000, 1500, 3), (2, 72000, 16000, 7), (1, 64000, 12000, 7),
+                (2, 200000, 8000, 5), (1, 56000, 48000, 10), (3, 88000, 8000, 6), (8, 56000, 48000, 5), (4, 72000, 16000, 9),
+                (2, 28000, 8000, 6), (6, 88000, 8000, 3), (1, 56000, 48000, 0),
+                # 24:1 of 6 144 taps x 8 channels: too long for a slide workgroup, folded to 240:10 over the int16 window (fp32 chain)
+                (8, 192000, 8000, 10)]
+
+
 def test_small_denominator_ratios_run_the_period_kernel_on_a_folded_view():
     """Round 6 (VERDICT r5 #7a).  Ratios with den <= 6 outside the slide kernel's shapes -- 7:6, 11:1, 9:2, 16:3, 25:1,
     64:1, 7:2 -- ran the exact kernel (~5x slower).  A resampler's outputs repeat with period den, hence also with period
     k * den: they run the period kernel as 35:30, 110:10, 45:10, 80:15 ... (FilterSpec::fold, period_view), the same taps
     per output.  fast_path 2 (5 where the reference sums in fp64), every sample within +-1 LSB over several calls of ragged
     sizes, counters, position and history equal; float entry point and a many-states launch too; EXACT mode unchanged."""
-    cases = [(1, 88000, 8000, 5), (2, 56000, 48000, 4), (2, 96000, 1500, 3), (2, 72000, 16000, 7), (1, 64000, 12000, 7),
-             (2, 200000, 8000, 5), (1, 56000, 48000, 10), (3, 88000, 8000, 6), (8, 56000, 48000, 5), (4, 72000, 16000, 9),
-             (2, 28000, 8000, 6), (6, 88000, 8000, 3), (1, 56000, 48000, 0),
-             # 24:1 of 6 144 taps x 8 channels: too long for a slide workgroup, folded to 240:10 over the int16 window (fp32 chain)
-             (8, 192000, 8000, 10)]
+    cases = FOLDED_CASES
     for (ch, i, o, q) in cases:
         ref = orc.Oracle(ch, i, o, q)
         r = speexhip.Resampler(ch, i, o, q)
@@ -496,22 +510,26 @@ def test_small_denominator_ratios_run_the_period_kernel_on_a_folded_view():
             st.close()
 
 
+# integer decimation on the slide kernel
+N_TO_ONE_CASES = [(1, 48000, 8000, 5), (2, 48000, 8000, 7), (2, 96000, 16000, 3), (1, 40000, 8000, 10),
+                  (2, 40000, 8000, 4), (3, 48000, 8000, 6),
+                  # 8:1 and 12:1: the long decimation filters of 96k / 192k sources (1024 - 3072 taps)
+                  (2, 192000, 24000, 7), (1, 96000, 12000, 10), (2, 96000, 8000, 5), (1, 192000, 16000, 10),
+                  (4, 192000, 16000, 3),
+                  # 7:1, 9:1, 10:1
+                  (2, 56000, 8000, 6), (1, 56000, 8000, 9), (2, 72000, 8000, 4), (1, 72000, 8000, 7),
+                  (2, 44100, 4410, 8), (1, 80000, 8000, 10),
+                  # 16:1, 20:1, 24:1: one period per lane, up to 6144 taps
+                  (2, 128000, 8000, 7), (1, 128000, 8000, 10),
+                  (2, 160000, 8000, 4), (3, 160000, 8000, 6), (2, 192000, 8000, 10), (1, 192000, 8000, 7),
+                  (4, 192000, 8000, 3)]
+
+
 def test_n_to_one_decimation_takes_the_slide_kernel():
     """48k -> 8k, 96k -> 16k (6:1), 40k -> 8k (5:1), 192k -> 24k (8:1), 96k -> 8k / 192k -> 16k (12:1):
     integer down-sampling runs the small-ratio fast kernel, stereo (channel pairs) and mono (phase
     pairs), with filters of up to 3072 taps."""
-    for (ch, i, o, q) in [(1, 48000, 8000, 5), (2, 48000, 8000, 7), (2, 96000, 16000, 3), (1, 40000, 8000, 10),
-                          (2, 40000, 8000, 4), (3, 48000, 8000, 6),
-                          # 8:1 and 12:1: the long decimation filters of 96k / 192k sources (1024 - 3072 taps)
-                          (2, 192000, 24000, 7), (1, 96000, 12000, 10), (2, 96000, 8000, 5), (1, 192000, 16000, 10),
-                          (4, 192000, 16000, 3),
-                          # 7:1, 9:1, 10:1
-                          (2, 56000, 8000, 6), (1, 56000, 8000, 9), (2, 72000, 8000, 4), (1, 72000, 8000, 7),
-                          (2, 44100, 4410, 8), (1, 80000, 8000, 10),
-                          # 16:1, 20:1, 24:1: one period per lane, up to 6144 taps
-                          (2, 128000, 8000, 7), (1, 128000, 8000, 10),
-                          (2, 160000, 8000, 4), (3, 160000, 8000, 6), (2, 192000, 8000, 10), (1, 192000, 8000, 7),
-                          (4, 192000, 8000, 3)]:
+    for (ch, i, o, q) in N_TO_ONE_CASES:
         ref = orc.Oracle(ch, i, o, q)
         r = speexhip.Resampler(ch, i, o, q)
         assert r.info()["fast_path"] == (4 if q >= 9 else 3), (ch, i, o, q)
@@ -754,29 +772,33 @@ def test_chunk_coalescing_equals_the_separate_calls(mode):
         r.close()
 
 
+# every LDS layout decision of the period kernel on its own ratio
+LAYOUT_CASES = [(2, 48000, 44100, 5), (2, 48000, 44100, 10), (1, 48000, 44100, 7), (4, 48000, 44100, 5),
+                (6, 44100, 48000, 7), (2, 96000, 44100, 7), (2, 32000, 44100, 7), (2, 44100, 32000, 7),
+                (3, 48000, 44100, 4), (2, 11025, 48000, 6), (2, 48000, 11025, 3), (2, 44100, 8000, 5),
+                (7, 22050, 16000, 8), (2, 88200, 96000, 9),
+                # round 3: int16 calls of these run over an int16 LDS window (twice the periods per tile)
+                (2, 48000, 11025, 7), (4, 48000, 11025, 7), (2, 44100, 16000, 7), (1, 48000, 11025, 7), (2, 44100, 8000, 10),
+                (8, 48000, 11025, 5), (6, 44100, 16000, 6),
+                # round 5: three channels' two-period plan over an int16 window; the widest windows (num = 1280), of which
+                # seven channels fit a ninth of a tile's periods
+                (3, 48000, 11025, 7), (3, 32000, 11025, 7), (7, 32000, 11025, 7), (5, 96000, 11025, 6), (4, 32000, 11025, 7),
+                # frames of 10 / 12 / 16 channels (5, 6, 8 channel pairs; kernels_period_frames.hip): unpadded, padded, groups of 5,
+                # wide windows (int16 window under SPEEXHIP_W16_ALWAYS, test_int16_window_on_small_launches_too)
+                (10, 44100, 48000, 7), (12, 48000, 44100, 5), (16, 44100, 48000, 4), (12, 44100, 8000, 6), (10, 48000, 11025, 7),
+                (16, 48000, 11025, 5), (12, 32000, 44100, 8), (16, 96000, 11025, 7), (12, 96000, 11025, 8),
+                # round 6: frames WITHOUT an ISA loop (C++ loop) -- their int16 window under SPEEXHIP_W16_ALWAYS too
+                (9, 48000, 11025, 7), (11, 44100, 16000, 6), (13, 48000, 11025, 5), (14, 96000, 11025, 4), (15, 44100, 8000, 7),
+                (17, 48000, 11025, 7), (20, 44100, 16000, 5), (18, 32000, 44100, 7), (9, 44100, 48000, 7)]
+
+
 def test_window_layout_variants_of_the_period_kernel():
     """Every LDS layout decision of the period kernel on its own ratio: bank padding with one and
     with several period boundaries per group (num % 4 == 0), fewer periods per tile so that two
     workgroups share a CU, partly filled waves for very wide windows (num = 320, 441, 640), odd
     channel counts (two periods per lane) and a split tile with staging helper waves.  fast_path must
     stay 2 and every sample within +-1 LSB, multi-call, history equal."""
-    cases = [(2, 48000, 44100, 5), (2, 48000, 44100, 10), (1, 48000, 44100, 7), (4, 48000, 44100, 5),
-             (6, 44100, 48000, 7), (2, 96000, 44100, 7), (2, 32000, 44100, 7), (2, 44100, 32000, 7),
-             (3, 48000, 44100, 4), (2, 11025, 48000, 6), (2, 48000, 11025, 3), (2, 44100, 8000, 5),
-             (7, 22050, 16000, 8), (2, 88200, 96000, 9),
-             # round 3: int16 calls of these run over an int16 LDS window (twice the periods per tile)
-             (2, 48000, 11025, 7), (4, 48000, 11025, 7), (2, 44100, 16000, 7), (1, 48000, 11025, 7), (2, 44100, 8000, 10),
-             (8, 48000, 11025, 5), (6, 44100, 16000, 6),
-             # round 5: three channels' two-period plan over an int16 window; the widest windows (num = 1280), of which
-             # seven channels fit a ninth of a tile's periods
-             (3, 48000, 11025, 7), (3, 32000, 11025, 7), (7, 32000, 11025, 7), (5, 96000, 11025, 6), (4, 32000, 11025, 7),
-             # frames of 10 / 12 / 16 channels (5, 6, 8 channel pairs; kernels_period_frames.hip): unpadded, padded, groups of 5,
-             # wide windows (int16 window under SPEEXHIP_W16_ALWAYS, test_int16_window_on_small_launches_too)
-             (10, 44100, 48000, 7), (12, 48000, 44100, 5), (16, 44100, 48000, 4), (12, 44100, 8000, 6), (10, 48000, 11025, 7),
-             (16, 48000, 11025, 5), (12, 32000, 44100, 8), (16, 96000, 11025, 7), (12, 96000, 11025, 8),
-             # round 6: frames WITHOUT an ISA loop (C++ loop) -- their int16 window under SPEEXHIP_W16_ALWAYS too
-             (9, 48000, 11025, 7), (11, 44100, 16000, 6), (13, 48000, 11025, 5), (14, 96000, 11025, 4), (15, 44100, 8000, 7),
-             (17, 48000, 11025, 7), (20, 44100, 16000, 5), (18, 32000, 44100, 7), (9, 44100, 48000, 7)]
+    cases = LAYOUT_CASES
     for (ch, i, o, q) in cases:
         ref = orc.Oracle(ch, i, o, q)
         r = speexhip.Resampler(ch, i, o, q)
@@ -800,8 +822,8 @@ def test_int16_window_on_small_launches_too():
     import subprocess
     import sys
     env = diag_env(SPEEXHIP_MODE="fast", SPEEXHIP_W16_ALWAYS="1")
-    res = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.abspath(__file__), "-k",
-                          "window_layout_variants or int16_window_plan_serves or edge_cases"],
+    res = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.abspath(__file__), EXACT_MODEL_FILE, "-k",
+                          "window_layout_variants or int16_window_plan_serves or edge_cases or exact_model_period_layouts"],
                          env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
 
@@ -1729,6 +1751,16 @@ def test_fp64_accumulate_is_closer_to_the_reference_than_the_fp32_chain():
     assert rates[speexhip.MODE_FAST] <= 0.5 * rates[speexhip.MODE_FAST_F32] + 1e-4
 
 
+# the fp64-accumulate period kernel's layouts
+PERIOD64_CASES = [(1, 44100, 48000, 10), (2, 44100, 48000, 10), (2, 44100, 48000, 9), (2, 48000, 44100, 10),
+                  (1, 48000, 44100, 9), (4, 44100, 48000, 10), (6, 48000, 44100, 9), (8, 48000, 44100, 10),
+                  (8, 44100, 48000, 9), (2, 48000, 11025, 10), (1, 44100, 8000, 9), (2, 44100, 8000, 10),
+                  (2, 32000, 44100, 10), (1, 22050, 16000, 9), (2, 88200, 48000, 10), (2, 16000, 44100, 9),
+                  # round 5: frames of three, five and seven channels (single-channel lanes, FirLoopAsm64<R, 1, 3 | 5 | 7>)
+                  (3, 44100, 48000, 10), (3, 48000, 44100, 9), (5, 44100, 48000, 9), (5, 48000, 11025, 10),
+                  (7, 48000, 44100, 10), (7, 44100, 8000, 9), (3, 44100, 8000, 10)]
+
+
 def test_fp64_accumulate_period_kernel_on_every_layout():
     """Round 4: the period kernel with an fp64 accumulator (kernels_period64.hip, FirLoopAsm64): quality 9 and 10 on
     ratios with den >= 7 -- mono (two periods per lane), stereo, 4 / 6 / 8 channels, plain and padded windows, the
@@ -1737,13 +1769,7 @@ def test_fp64_accumulate_period_kernel_on_every_layout():
     ISA loop (9 channels and more) keep the fp32 chain and say so."""
     import torch
     worst = 0.0
-    cases = [(1, 44100, 48000, 10), (2, 44100, 48000, 10), (2, 44100, 48000, 9), (2, 48000, 44100, 10),
-             (1, 48000, 44100, 9), (4, 44100, 48000, 10), (6, 48000, 44100, 9), (8, 48000, 44100, 10),
-             (8, 44100, 48000, 9), (2, 48000, 11025, 10), (1, 44100, 8000, 9), (2, 44100, 8000, 10),
-             (2, 32000, 44100, 10), (1, 22050, 16000, 9), (2, 88200, 48000, 10), (2, 16000, 44100, 9),
-             # round 5: frames of three, five and seven channels (single-channel lanes, FirLoopAsm64<R, 1, 3 | 5 | 7>)
-             (3, 44100, 48000, 10), (3, 48000, 44100, 9), (5, 44100, 48000, 9), (5, 48000, 11025, 10),
-             (7, 48000, 44100, 10), (7, 44100, 8000, 9), (3, 44100, 8000, 10)]
+    cases = PERIOD64_CASES
     for (ch, i, o, q) in cases:
         ref = orc.Oracle(ch, i, o, q)
         r = speexhip.Resampler(ch, i, o, q)
@@ -1877,10 +1903,10 @@ def test_phase_pair_plans_for_mono_on_every_launch():
     import subprocess
     import sys
     env = diag_env(SPEEXHIP_MODE="fast", SPEEXHIP_PP="1")
-    res = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.abspath(__file__), "-k",
+    res = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.abspath(__file__), EXACT_MODEL_FILE, "-k",
                           "(mono or every_golden_case or many_rates or window_layout_variants or edge_cases or tap_range_shares "
-                          "or int16_window_plan_serves or history_after or float_entry or control_scripts_fast or many_generation) "
-                          "and not phase_pair"],   # (not this test again)
+                          "or int16_window_plan_serves or history_after or float_entry or control_scripts_fast or many_generation "
+                          "or exact_model_period_layouts) and not phase_pair"],   # (not this test again)
                          env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
     # ... and by the rule: a batch of a wide-window decimator runs over them, one big stream does not; both match
