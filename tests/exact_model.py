@@ -18,6 +18,11 @@ give it the concatenation of what each call consumed and the number of outputs m
 capacity-bound streams need no history logic.  The control calls (set_rate, set_quality, skip_zeros) change the line
 and are out of scope.
 
+Input (tests/float_inputs.py).  The model takes any float32 line: a product of two 24-bit numbers is exact in a double
+and the rational arbiter settles the rest, so real float data -- full mantissas, fractions, channels and passages 2^20
+apart in loudness, samples far outside the int16 range -- is judged by the same three checks and the same bounds as
+int16-valued data.  Only gradual underflow (kind D) needs a term of its own: bound32 / bound64 (underflow=True).
+
 Checks, with e = (got - truth) / (u mag) over the samples with mag > 0:
   (a) hard, per sample: hard_float / hard_int16;
   (b) accuracy against a yardstick on the same input: rms(e) (compare with the oracle's or chain32's);
@@ -58,6 +63,26 @@ def phase_rows(o):
     j = np.arange(n)
     for phase in range(den):
         w = blend_weights((phase * o.oversample) % den, den)
+        t = 4 + (j + 1) * o.oversample - (phase * o.oversample) // den
+        rows[phase] = w[0] * table[t - 2] + w[1] * table[t - 1] + w[2] * table[t] + w[3] * table[t + 1]
+    return rows
+
+
+def reference_abs_rows(o):
+    """sum_i |w_i| |t_i[phase, j]|: what the REFERENCE's interpolating kernels are conditioned by.  They do not sum over
+    the blended row: they run four dot products over the table (resample.c:463-481) and blend the four sums, so their
+    rounding error scales with sum_i |w_i| sum_j |t_i| |x| -- which is `mag` within a few per cent where neighbouring
+    samples are equally loud, and many times `mag` where one loud sample sits on a zero crossing of the blended row
+    (float_inputs kind B).  The product blends the ROWS (in double) and runs one dot product: its bound is over `mag`.
+    Direct kinds: |rows|."""
+    table = np.abs(o.table().astype(np.float64))
+    n, den = o.taps, o.den
+    if o.kind.startswith("direct"):
+        return table.reshape(den, n).copy()
+    rows = np.empty((den, n), np.float64)
+    j = np.arange(n)
+    for phase in range(den):
+        w = np.abs(blend_weights((phase * o.oversample) % den, den))
         t = 4 + (j + 1) * o.oversample - (phase * o.oversample) // den
         rows[phase] = w[0] * table[t - 2] + w[1] * table[t - 1] + w[2] * table[t] + w[3] * table[t + 1]
     return rows
@@ -148,15 +173,21 @@ def chain32(model, x, n_out, rows=None, shift=None):
     return s
 
 
-def bound32(truth, mag, taps):
+UNDERFLOW = 2.0 ** -149     # the spacing of float32 below 2^-126
+
+
+def bound32(truth, mag, taps, underflow=False):
     """(a) for fp32-accumulate instances: the textbook bound of a length-`taps` fp32 dot product in any order, with or
-    without FMA, over rows rounded once to fp32, then narrowed"""
-    return (taps + 2) * U * mag + 0.5 * ulp32(truth)
+    without FMA, over rows rounded once to fp32, then narrowed.
+    `underflow` (opt-in, input kind D): the textbook bound charges every rounding u x |value|, which is nothing for a
+    value in the subnormal range -- there each of the up to 2 taps roundings (products and sums) may be off by half the
+    subnormal spacing, 2^-150, whatever the value: taps 2^-149 in all."""
+    return (taps + 2) * U * mag + 0.5 * ulp32(truth) + (taps * UNDERFLOW if underflow else 0.0)
 
 
-def bound64(truth, mag, taps):
-    """what an fp64-accumulate instance may be off by after narrowing to float32"""
-    return taps * 2.0 ** -52 * mag + 0.5 * ulp32(truth)
+def bound64(truth, mag, taps, underflow=False):
+    """what an fp64-accumulate instance may be off by after narrowing to float32 (`underflow`: as bound32's)"""
+    return taps * 2.0 ** -52 * mag + 0.5 * ulp32(truth) + (taps * UNDERFLOW if underflow else 0.0)
 
 
 def errors(got, truth, mag):
@@ -193,16 +224,17 @@ def _worst_phase(model, bad):
         int(bad.sum()), int(vals[np.argmax(counts)]), int(counts.max()), [int(v) for v in k[:6]])
 
 
-def hard_float(model, x, got, truth, mag, bits, tile=None):
+def hard_float(model, x, got, truth, mag, bits, tile=None, underflow=False):
     """(a) on a float call's output -> list of failure messages (empty: passed).
     bits 32: |got - truth| <= (taps + 2) u mag + 1/2 ulp32(truth).
     bits 64: got is a float32 neighbour of truth, and the correctly rounded one unless truth lies within
-             taps 2^-52 mag of the midpoint of its two neighbours."""
+             taps 2^-52 mag of the midpoint of its two neighbours.
+    underflow (input kind D): |got - truth| <= the instance's bound with its underflow term, for either `bits`."""
     got = np.asarray(got)
     assert got.dtype == np.float32 and got.shape == truth.shape, (got.dtype, got.shape, truth.shape)
     g = got.astype(np.float64)
-    if bits == 32:
-        slack = bound32(truth, mag, model.taps)
+    if bits == 32 or underflow:
+        slack = (bound32 if bits == 32 else bound64)(truth, mag, model.taps, underflow)
         bad = ~(np.abs(g - truth) <= slack)
 
         def still_bad(k, c):
@@ -268,10 +300,13 @@ def _settle(model, bad, still_bad, got, truth, mag, tile):
 MARGIN = 1.5    # (b): rms(e_kernel) <= MARGIN rms(e_yardstick); an fp64-accumulate instance gets 1.0 against the oracle
 
 
-def judge_float(model, x, got, truth, mag, bits, yardstick, margin=MARGIN, tile=None):
+def judge_float(model, x, got, truth, mag, bits, yardstick, margin=MARGIN, tile=None, underflow=False):
     """(a), (b) and (c) on one float comparison -> (failures, stats).  `yardstick`: the float32 output of the oracle or
-    of chain32 on the same input (None: (b) is not judged)."""
-    fails = ["(a) " + m for m in hard_float(model, x, got, truth, mag, bits, tile)]
+    of chain32 on the same input (None: (b) is not judged).  underflow: (a) alone, with the bounds' underflow term --
+    e = error / (u mag) means nothing where the error is an absolute 2^-150 per rounding."""
+    fails = ["(a) " + m for m in hard_float(model, x, got, truth, mag, bits, tile, underflow)]
+    if underflow:
+        return fails, {"n": int((mag > 0).sum()), "rms": 0.0, "max": 0.0, "z": 0.0}
     e = errors(got, truth, mag)
     stats = {"n": int(e.size), "rms": rms(e), "max": float(np.abs(e).max(initial=0.0))}
     if yardstick is not None:

@@ -12,7 +12,10 @@ e = (got - truth) / (u mag),
 Each case runs one int16 and one float stream (the same int16-valued samples, as tools/num_check.py does) of ragged calls
 with a 1-frame and an empty call; the long call carries a stretch of silence longer than the filter, where single edge
 taps decide whole samples.  The case lists are test_gpu_parity.py's.  Run with -s for the per-family figures.
+test_gpu_exact_model_float.py runs the same lists with real float data on the float stream (the sample-maker argument of
+_one_state and _batch).
 """
+import os
 from math import gcd
 
 import numpy as np
@@ -57,22 +60,34 @@ def _samples(frames, ch, seed, taps, tone=False):
     return em.with_silence(x, taps) if frames > 2 * taps + 64 else x
 
 
-def _judge(family, name, model, bits, fed, got16, gotf, wantf):
-    """(a) on the int16 stream, (a) (b) (c) on the float stream; both streams consumed the same samples `fed`"""
-    truth, mag = model.truth(fed, gotf.shape[0])
-    assert got16.shape == gotf.shape, (name, got16.shape, gotf.shape)
-    fails = ["int16 (a) " + m for m in em.hard_int16(model, fed, got16, truth, mag, bits, tile=model.num)]
-    if bits == 64:
+def _judge(family, name, model, bits, fed, got16, gotf, wantf, fedf=None, underflow=False):
+    """(a) on the int16 stream, (a) (b) (c) on the float stream.  Both streams consumed the same samples `fed`, unless the
+    float stream had a sample maker of its own: `fedf` is what it consumed then (got16 None: there was no int16 stream).
+    underflow: the float stream is judged by (a) alone, with the bounds' underflow term (float_inputs kind D)."""
+    fails, differing = [], None
+    if got16 is not None:
+        assert got16.shape == gotf.shape, (name, got16.shape, gotf.shape)
+        truth, mag = model.truth(fed, got16.shape[0])
+        fails = ["int16 (a) " + m for m in em.hard_int16(model, fed, got16, truth, mag, bits, tile=model.num)]
+        differing = float((got16.astype(np.int64) != em.halfup(truth)).mean()) if got16.size else 0.0
+    if fedf is None:
+        fedf = fed
+    else:
+        truth, mag = model.truth(fedf, gotf.shape[0])
+    if underflow:
+        yard, margin = None, em.MARGIN
+    elif bits == 64:
         yard, margin = wantf, 1.0           # no worse than the reference's double kernels
     elif model.double_kind:
-        yard, margin = em.chain32(model, fed, gotf.shape[0]), MARGINS.get(family, em.MARGIN)
+        yard, margin = em.chain32(model, fedf, gotf.shape[0]), MARGINS.get(family, em.MARGIN)
     else:
         yard, margin = wantf, MARGINS.get(family, em.MARGIN)
-    ffails, stats = em.judge_float(model, fed, gotf, truth, mag, bits, yard, margin, tile=model.num)
-    differing = float((got16.astype(np.int64) != em.halfup(truth)).mean()) if got16.size else 0.0
-    _note(family, stats, differing)
-    print("%s %s bits %d: n %d rms(e) %.3f yardstick %.3f max|e| %.2f bias %.1f sigma, int16 off halfup(truth) %.2e" % (
-        family, name, bits, stats["n"], stats["rms"], stats.get("yard", 0.0), stats["max"], stats["z"], differing))
+    ffails, stats = em.judge_float(model, fedf, gotf, truth, mag, bits, yard, margin, tile=model.num, underflow=underflow)
+    _note(family, None if underflow else stats, differing)
+    print("%s %s bits %d: n %d rms(e) %.3f yardstick %.3f max|e| %.2f bias %.1f sigma%s%s" % (
+        family, name, bits, stats["n"], stats["rms"], stats.get("yard", 0.0), stats["max"], stats["z"],
+        "" if differing is None else ", int16 off halfup(truth) %.2e" % differing,
+        " ((a) alone, with the underflow term)" if underflow else ""))
     assert not fails + ffails, (family, name, fails + ffails)
 
 
@@ -82,12 +97,14 @@ def _expect_bits(info, model):
     return bits
 
 
-def _one_state(family, ch, i, o, q, fast_path, sizes=(1, 21011, 0, 9000), mode=None, bound_call=None, seed=40):
-    """One int16 and one float stream of `sizes` frames per call through two states of one filter."""
+def _one_state(family, ch, i, o, q, fast_path, sizes=(1, 21011, 0, 9000), mode=None, bound_call=None, seed=40,
+               float_samples=None, streams=("int16", "float"), underflow=False, label=""):
+    """One int16 and one float stream of `sizes` frames per call through two states of one filter.  float_samples(frames,
+    ch, seed, taps) makes the float stream's samples (default: the int16 stream's own, as float32)."""
     model = em.Model(ch, i, o, q)
-    name = "%s mode %s" % ((ch, i, o, q), mode)
+    name = "%s mode %s%s" % ((ch, i, o, q), mode, label)
     outs = {}
-    for kind in ("int16", "float"):
+    for kind in streams:
         r, ref = speexhip.Resampler(ch, i, o, q, mode=mode), orc.Oracle(ch, i, o, q)
         info = r.info()
         assert info["fast_path"] == fast_path, (name, info["fast_path"])
@@ -97,6 +114,8 @@ def _one_state(family, ch, i, o, q, fast_path, sizes=(1, 21011, 0, 9000), mode=N
             x = _samples(frames, ch, seed + 7 * call + ch, model.taps, tone=call == 3)
             cap = max(1, frames * o // i // 2) if call == bound_call else BIG
             if kind == "float":
+                if float_samples is not None:
+                    x = float_samples(frames, ch, seed + 7 * call + ch, model.taps)
                 y, u = r.process_float(x.astype(np.float32), cap)
                 w, wu = ref.process_float(x.astype(np.float32), cap)
             else:
@@ -106,16 +125,23 @@ def _one_state(family, ch, i, o, q, fast_path, sizes=(1, 21011, 0, 9000), mode=N
             got.append(y), want.append(w), fed.append(x[:u])
         outs[kind] = (np.concatenate(got), np.concatenate(want), np.concatenate(fed))
         r.close()
-    assert np.array_equal(outs["int16"][2], outs["float"][2]), name
-    _judge(family, name, model, bits, outs["int16"][2], outs["int16"][0], outs["float"][0], outs["float"][1])
+    if float_samples is None:
+        assert np.array_equal(outs["int16"][2], outs["float"][2]), name
+        _judge(family, name, model, bits, outs["int16"][2], outs["int16"][0], outs["float"][0], outs["float"][1])
+    else:
+        i16 = outs.get("int16", (None, None, None))
+        _judge(family, name, model, bits, i16[2], i16[0], outs["float"][0], outs["float"][1], fedf=outs["float"][2],
+               underflow=underflow)
     return outs
 
 
-def _batch(family, ch, i, o, q, S, F, fast_path, mode=None, picks=None, int16_window=None):
-    """S streams x two ragged calls through Batch.process_device, int16 and float; three streams judged."""
+def _batch(family, ch, i, o, q, S, F, fast_path, mode=None, picks=None, int16_window=None, float_samples=None,
+           streams=("int16", "float"), underflow=False, label=""):
+    """S streams x two ragged calls through Batch.process_device, int16 and float; three streams judged.
+    float_samples: as _one_state's."""
     import torch
     model = em.Model(ch, i, o, q)
-    name = "%s x %d streams x %d" % ((ch, i, o, q), S, F)
+    name = "%s x %d streams x %d%s" % ((ch, i, o, q), S, F, label)
     if int16_window is not None:
         g = gcd(i, o)
         shape = speexhip.debug_launch_shape(i // g, o // g, q, ch, S, F)
@@ -123,16 +149,22 @@ def _batch(family, ch, i, o, q, S, F, fast_path, mode=None, picks=None, int16_wi
     picks = sorted(set(picks or (0, S // 2, S - 1)))
     base = em.with_silence(orc.lcg_pcm(F * ch, 700 + ch + q).reshape(F, ch), model.taps)
     xs = np.stack([np.roll(base, 13 * s, axis=0) for s in range(S)])
+    xsf = None
+    if float_samples is not None:
+        basef = float_samples(F, ch, 700 + ch + q, model.taps)
+        xsf = np.stack([np.roll(basef, 13 * s, axis=0) for s in range(S)])
     cap = F * o // i + 64
     sp = torch.cuda.current_stream().cuda_stream
     outs = {}
-    for kind in ("int16", "float"):
+    for kind in streams:
         fl = kind == "float"
+        if fl and xsf is not None:
+            xs = xsf
         b = speexhip.Batch(S, ch, i, o, q, mode=mode)
         info = b.info()
         assert info["fast_path"] == fast_path, (name, info["fast_path"])
         bits = _expect_bits(info, model)
-        d_in = torch.from_numpy(xs.astype(np.float32) if fl else xs).cuda()
+        d_in = torch.from_numpy(np.ascontiguousarray(xs, np.float32) if fl else xs).cuda()
         d_out = torch.zeros((S, cap, ch), dtype=torch.float32 if fl else torch.int16, device="cuda")
         refs = {s: orc.Oracle(ch, i, o, q) for s in picks}
         acc = {s: ([], [], []) for s in picks}
@@ -149,6 +181,11 @@ def _batch(family, ch, i, o, q, S, F, fast_path, mode=None, picks=None, int16_wi
         outs[kind] = {s: tuple(np.concatenate(v) for v in acc[s]) for s in picks}
         b.close()
     for s in picks:
+        if float_samples is not None:
+            i16 = outs["int16"][s] if "int16" in outs else (None, None, None)
+            _judge(family, "%s stream %d" % (name, s), model, bits, i16[2], i16[0], outs["float"][s][0], outs["float"][s][1],
+                   fedf=outs["float"][s][2], underflow=underflow)
+            continue
         assert np.array_equal(outs["int16"][s][2], outs["float"][s][2])
         _judge(family, "%s stream %d" % (name, s), model, bits, outs["int16"][s][2], outs["int16"][s][0], outs["float"][s][0],
                outs["float"][s][1])
@@ -256,26 +293,31 @@ def test_exact_model_mono_phase_pair_plans_by_the_rule():
     _report("phase pairs")
 
 
+FAST_SHARES_CASES = [(2, 48000, 11025, 7, 2), (2, 44100, 8000, 5, 2), (4, 48000, 11025, 7, 2), (2, 192000, 24000, 7, 3),
+                     (1, 192000, 8000, 7, 3), (1, 96000, 12000, 10, 4), (2, 48000, 11025, 10, 5), (2, 44100, 8000, 10, 5),
+                     (12, 96000, 11025, 8, 2)]
+FAST_F32_CASES = [(1, 24000, 48000, 10, 3), (2, 44100, 48000, 10, 2), (2, 48000, 44100, 9, 2), (1, 48000, 8000, 10, 3),
+                  (2, 48000, 11025, 10, 2), (2, 16000, 48000, 9, 3)]
+BASELINE_ROWS = [("cfg2", 2, 44100, 48000, 7, 2), ("cfg3", 1, 24000, 48000, 10, 4), ("cfg4", 8, 48000, 44100, 5, 2),
+                 ("f3", 1, 24000, 48000, 5, 3)]
+
+
 def test_exact_model_fast_mode_tap_range_shares():
     """MODE_FAST: small launches of long filters add their sums in tap-range shares (re-associated: still inside (a), and
     (b) leaves them their margin)."""
-    for (ch, i, o, q, fp) in [(2, 48000, 11025, 7, 2), (2, 44100, 8000, 5, 2), (4, 48000, 11025, 7, 2), (2, 192000, 24000, 7, 3),
-                              (1, 192000, 8000, 7, 3), (1, 96000, 12000, 10, 4), (2, 48000, 11025, 10, 5), (2, 44100, 8000, 10, 5),
-                              (12, 96000, 11025, 8, 2)]:
+    for (ch, i, o, q, fp) in FAST_SHARES_CASES:
         _one_state("FAST shares", ch, i, o, q, fp, sizes=(3, 60011, 0, 41234), mode=speexhip.MODE_FAST)
     _report("FAST shares")
 
 
 def test_exact_model_fast_f32_mode_on_the_double_kinds():
     """MODE_FAST_F32: the fp32 chain on quality 9 and 10, judged as what it says it is -- against chain32."""
-    for (ch, i, o, q, fp) in [(1, 24000, 48000, 10, 3), (2, 44100, 48000, 10, 2), (2, 48000, 44100, 9, 2), (1, 48000, 8000, 10, 3),
-                              (2, 48000, 11025, 10, 2), (2, 16000, 48000, 9, 3)]:
+    for (ch, i, o, q, fp) in FAST_F32_CASES:
         _one_state("FAST_F32", ch, i, o, q, fp, mode=speexhip.MODE_FAST_F32)
     _report("FAST_F32")
 
 
-@pytest.mark.parametrize("name,ch,i,o,q,fast_path", [("cfg2", 2, 44100, 48000, 7, 2), ("cfg3", 1, 24000, 48000, 10, 4),
-                                                     ("cfg4", 8, 48000, 44100, 5, 2), ("f3", 1, 24000, 48000, 5, 3)])
+@pytest.mark.parametrize("name,ch,i,o,q,fast_path", BASELINE_ROWS)
 def test_exact_model_baseline_rows_at_full_size_in_the_default_mode(name, ch, i, o, q, fast_path):
     """BASELINE.json configs[1..3] and SURVEY F3, one 2^20-frame call, NO mode named."""
     frames = 1 << 20
@@ -307,3 +349,8 @@ def test_exact_model_is_wired_into_the_diagnostics_children():
     for fn in (par.test_int16_window_on_small_launches_too, par.test_phase_pair_plans_for_mono_on_every_launch):
         src = inspect.getsource(fn)
         assert "exact_model_period_layouts" in src and "EXACT_MODEL_FILE" in src, fn.__name__
+    # ... and the mixed int16 / float streams of test_gpu_exact_model_float.py, whose one-state entry points meet the int16
+    # window nowhere else
+    src = inspect.getsource(par.test_int16_window_on_small_launches_too)
+    assert "exact_model_mixed_entry_points" in src and "EXACT_MODEL_FLOAT_FILE" in src
+    assert par.EXACT_MODEL_FLOAT_FILE.endswith("test_gpu_exact_model_float.py") and os.path.exists(par.EXACT_MODEL_FLOAT_FILE)

@@ -30,6 +30,7 @@ MISMATCH_RATE = 4e-3   # (5e-3 until round 5; 3.5e-3 met a 3.53e-3 on 23 000 sam
 DIAG_LIB = os.path.join(ROOT, "node-speex-resampler_amd", "ab", "libspeexhip_diag.so")
 # the exact-model tests of the period kernel run in the diagnostics children below as well (instances only they can force)
 EXACT_MODEL_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_gpu_exact_model.py")
+EXACT_MODEL_FLOAT_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_gpu_exact_model_float.py")
 
 
 def diag_env(**switches):
@@ -822,8 +823,10 @@ def test_int16_window_on_small_launches_too():
     import subprocess
     import sys
     env = diag_env(SPEEXHIP_MODE="fast", SPEEXHIP_W16_ALWAYS="1")
-    res = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.abspath(__file__), EXACT_MODEL_FILE, "-k",
-                          "window_layout_variants or int16_window_plan_serves or edge_cases or exact_model_period_layouts"],
+    res = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.abspath(__file__), EXACT_MODEL_FILE,
+                          EXACT_MODEL_FLOAT_FILE, "-k",
+                          "window_layout_variants or int16_window_plan_serves or edge_cases or exact_model_period_layouts "
+                          "or exact_model_mixed_entry_points"],
                          env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
 
