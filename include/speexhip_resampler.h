@@ -370,6 +370,49 @@ SPEEXHIP_API int speexhip_batch_process_interleaved_float_device(
     SpeexHipBatch *b, const float *d_in, uint64_t in_stream_stride, uint32_t *in_len, float *d_out,
     uint64_t out_stream_stride, uint32_t *out_len, void *hip_stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Planar audio: one plane per channel instead of interleaved frames (Web Audio's getChannelData,
+ * ffmpeg's s16p / fltp, a tensor shaped (channels, time)).  A planar call IS the interleaved call
+ * on the same frames: the same counters, the same samples in every mode, the same state left
+ * behind -- so interleaved, planar and per-channel calls may be mixed freely on one state.  It runs
+ * the same kernels as the interleaved call between two transposing passes on the device.
+ *
+ * Lengths are frames per channel, with the in / out meaning of the interleaved calls; strides are in
+ * elements (samples of the call's type).  Planes need no alignment beyond their element type; any
+ * plane stride >= the frame count serves.  speexhip_resampler_peek sizes the output planes exactly
+ * as it sizes an interleaved buffer.
+ *
+ * Host planes (synchronous): in[c] / out[c] = plane of channel c; in == NULL is silence.  Returns
+ * INVALID_ARG when out, an element of out or an element of in is NULL, PTR_OVERLAP when the frames
+ * the call writes to an output plane overlap another plane of the call; the state is untouched in
+ * both cases.  A state whose
+ * channels the per-channel calls moved apart is handled channel after channel and reports the
+ * lengths of the last channel, like the interleaved call.
+ *
+ * ABI note: 0.4 -> 0.5 adds these six entry points; SpeexHipInfo and the error codes are unchanged. */
+SPEEXHIP_API int speexhip_resampler_process_planar_int(SpeexHipResamplerState *st, const int16_t *const *in,
+                                                       uint32_t *in_len, int16_t *const *out, uint32_t *out_len);
+SPEEXHIP_API int speexhip_resampler_process_planar_float(SpeexHipResamplerState *st, const float *const *in,
+                                                         uint32_t *in_len, float *const *out, uint32_t *out_len);
+/* Device planes (asynchronous on hip_stream, ordered like the interleaved device calls): plane c
+ * starts at d_in + c * in_plane_stride / d_out + c * out_plane_stride; d_in == NULL is silence. */
+SPEEXHIP_API int speexhip_resampler_process_planar_int_device(SpeexHipResamplerState *st, const int16_t *d_in,
+                                                              uint64_t in_plane_stride, uint32_t *in_len,
+                                                              int16_t *d_out, uint64_t out_plane_stride,
+                                                              uint32_t *out_len, void *hip_stream);
+SPEEXHIP_API int speexhip_resampler_process_planar_float_device(SpeexHipResamplerState *st, const float *d_in,
+                                                                uint64_t in_plane_stride, uint32_t *in_len,
+                                                                float *d_out, uint64_t out_plane_stride,
+                                                                uint32_t *out_len, void *hip_stream);
+/* ... of every stream of a batch: plane c of stream s starts at d_in + s * in_stream_stride +
+ * c * in_plane_stride (a tensor shaped (batch, channels, time)); in_len / out_len hold one entry per stream. */
+SPEEXHIP_API int speexhip_batch_process_planar_int_device(
+    SpeexHipBatch *b, const int16_t *d_in, uint64_t in_stream_stride, uint64_t in_plane_stride, uint32_t *in_len,
+    int16_t *d_out, uint64_t out_stream_stride, uint64_t out_plane_stride, uint32_t *out_len, void *hip_stream);
+SPEEXHIP_API int speexhip_batch_process_planar_float_device(
+    SpeexHipBatch *b, const float *d_in, uint64_t in_stream_stride, uint64_t in_plane_stride, uint32_t *in_len,
+    float *d_out, uint64_t out_stream_stride, uint64_t out_plane_stride, uint32_t *out_len, void *hip_stream);
+
 /* Mid-stream control for every stream of a batch (same semantics as the single-stream calls). */
 SPEEXHIP_API int speexhip_batch_set_rate_frac(SpeexHipBatch *b, uint32_t ratio_num, uint32_t ratio_den,
                                               uint32_t in_rate, uint32_t out_rate);

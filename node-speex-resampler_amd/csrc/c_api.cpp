@@ -532,6 +532,51 @@ int speexhip_batch_process_interleaved_int_device(SpeexHipBatch *b, const int16_
                                   static_cast<hipStream_t>(hip_stream)); });
 }
 
+int speexhip_resampler_process_planar_int(SpeexHipResamplerState *st, const int16_t *const *in, uint32_t *in_len,
+                                          int16_t *const *out, uint32_t *out_len) {
+  if (st == nullptr || in_len == nullptr || out_len == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return st->batch->process_planar_host(reinterpret_cast<const void *const *>(in), in_len,
+                                        reinterpret_cast<void *const *>(out), out_len, false); });
+}
+int speexhip_resampler_process_planar_float(SpeexHipResamplerState *st, const float *const *in, uint32_t *in_len,
+                                            float *const *out, uint32_t *out_len) {
+  if (st == nullptr || in_len == nullptr || out_len == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return st->batch->process_planar_host(reinterpret_cast<const void *const *>(in), in_len,
+                                        reinterpret_cast<void *const *>(out), out_len, true); });
+}
+int speexhip_resampler_process_planar_int_device(SpeexHipResamplerState *st, const int16_t *d_in, uint64_t in_plane_stride,
+                                                 uint32_t *in_len, int16_t *d_out, uint64_t out_plane_stride,
+                                                 uint32_t *out_len, void *hip_stream) {
+  if (st == nullptr || in_len == nullptr || out_len == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return st->batch->process_planar_device(d_in, 0, in_plane_stride, in_len, d_out, 0, out_plane_stride,
+                                        out_len, false, static_cast<hipStream_t>(hip_stream)); });
+}
+int speexhip_resampler_process_planar_float_device(SpeexHipResamplerState *st, const float *d_in, uint64_t in_plane_stride,
+                                                   uint32_t *in_len, float *d_out, uint64_t out_plane_stride,
+                                                   uint32_t *out_len, void *hip_stream) {
+  if (st == nullptr || in_len == nullptr || out_len == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return st->batch->process_planar_device(d_in, 0, in_plane_stride, in_len, d_out, 0, out_plane_stride,
+                                        out_len, true, static_cast<hipStream_t>(hip_stream)); });
+}
+int speexhip_batch_process_planar_int_device(SpeexHipBatch *b, const int16_t *d_in, uint64_t in_stream_stride,
+                                             uint64_t in_plane_stride, uint32_t *in_len, int16_t *d_out,
+                                             uint64_t out_stream_stride, uint64_t out_plane_stride, uint32_t *out_len,
+                                             void *hip_stream) {
+  if (b == nullptr || in_len == nullptr || out_len == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return b->batch->process_planar_device(d_in, in_stream_stride, in_plane_stride, in_len, d_out,
+                                       out_stream_stride, out_plane_stride, out_len, false,
+                                       static_cast<hipStream_t>(hip_stream)); });
+}
+int speexhip_batch_process_planar_float_device(SpeexHipBatch *b, const float *d_in, uint64_t in_stream_stride,
+                                               uint64_t in_plane_stride, uint32_t *in_len, float *d_out,
+                                               uint64_t out_stream_stride, uint64_t out_plane_stride, uint32_t *out_len,
+                                               void *hip_stream) {
+  if (b == nullptr || in_len == nullptr || out_len == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return b->batch->process_planar_device(d_in, in_stream_stride, in_plane_stride, in_len, d_out,
+                                       out_stream_stride, out_plane_stride, out_len, true,
+                                       static_cast<hipStream_t>(hip_stream)); });
+}
+
 int speexhip_design_filter(uint32_t in_rate, uint32_t out_rate, int quality, SpeexHipInfo *info,
                            float *table, uint32_t table_capacity) {
   if (in_rate == 0 || out_rate == 0) return SPEEXHIP_ERR_INVALID_ARG;
@@ -620,6 +665,6 @@ int speexhip_plan_filter_change(uint32_t old_filt_len, uint32_t new_filt_len, ui
   return SPEEXHIP_ERR_SUCCESS;
 }
 
-const char *speexhip_version(void) { return "speexhip 0.4.0 gfx950"; }
+const char *speexhip_version(void) { return "speexhip 0.5.0 gfx950"; }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 #include "engine.h"
 
 #include "devices.h"
+#include "engine_detail.h"
 #include "host_transfer.h"
 #include "pool.h"
 #include "unit_workers.h"
@@ -22,47 +23,18 @@
 namespace speexhip {
 namespace {
 thread_local std::string g_last_error = "no HIP error recorded";
+}  // namespace
 
+namespace detail {
 bool hip_failed(hipError_t e, const char *what) {
   if (e == hipSuccess) return false;
   g_last_error = std::string("HIP device error: ") + what + ": " + hipGetErrorString(e);
   return true;
 }
-#define HIP_TRY(expr)                                            \
-  do {                                                           \
-    if (hip_failed((expr), #expr)) return SPEEXHIP_ERR_DEVICE;   \
-  } while (0)
+}  // namespace detail
+using namespace detail;  // (engine_detail.h: HIP_TRY, ON_DEVICE, DeviceScope, DrainOnExit, the staging helpers)
 
-// Every entry point runs on the batch's own device whatever the calling thread's current one is,
-// and leaves the thread's current device as it found it.
-class DeviceScope {
- public:
-  explicit DeviceScope(int logical_device) {  // (devices.h: logical ordinals; physical = logical unless aliased)
-    const int device = devices::physical(logical_device);
-    if (hipGetDevice(&prev_) != hipSuccess) prev_ = device;
-    if (prev_ != device) err_ = hipSetDevice(device);
-    // (a failed call leaves its code behind as the thread's "last error", and the launchers read that after their
-    //  next launch: hipLaunchKernelGGL + hipGetLastError would report THIS failure for a launch that worked)
-    if (err_ != hipSuccess) (void)hipGetLastError();
-  }
-  ~DeviceScope() {
-    if (prev_ != device_now()) (void)hipSetDevice(prev_);
-  }
-  hipError_t error() const { return err_; }
-
- private:
-  static int device_now() {
-    int d = 0;
-    (void)hipGetDevice(&d);
-    return d;
-  }
-  int prev_ = 0;
-  hipError_t err_ = hipSuccess;
-};
-#define ON_DEVICE()                 \
-  DeviceScope device_scope(device_); \
-  HIP_TRY(device_scope.error())
-
+namespace {
 std::atomic<int> g_fail_allocs{0};
 
 // Device allocation of the filter installs: ALLOC_FAILED when the device is out of memory (or the
@@ -89,18 +61,6 @@ int dev_alloc(int device, void **ptr, size_t bytes) {
   if (hip_failed(e, "hipMalloc")) return SPEEXHIP_ERR_DEVICE;
   return SPEEXHIP_ERR_SUCCESS;
 }
-
-// The host-buffer calls are synchronous, and their staging buffers and the (shared) stream go on to the
-// next call or to another state: on EVERY exit nothing they enqueued may still be in flight.  The normal
-// path waits explicitly (and checks the result); this guard covers the early error returns.
-struct DrainOnExit {
-  hipStream_t *stream;  // (pointer: the stream is taken from the pool after the guard is set up)
-  bool armed = true;
-  explicit DrainOnExit(hipStream_t *s) : stream(s) {}
-  ~DrainOnExit() {
-    if (armed && *stream != nullptr) (void)hipStreamSynchronize(*stream);
-  }
-};
 
 // Control-plane copies (histories of a filter change, table uploads).  The runtime performs copies of
 // <= 16 KiB with a blit KERNEL, and a kernel of this stream is dispatched only once the kernels other
@@ -149,12 +109,6 @@ static_assert(kStagedLdsBytes <= kLdsBudget, "the period kernel's staged-store i
 // channels (16.8 MB in), four pieces: 0.617 -> 0.517 ms.
 const size_t kPieceBytes = static_cast<size_t>(2) << 20;
 
-inline size_t align64(size_t v) { return (v + 63) & ~static_cast<size_t>(63); }
-inline bool buffers_overlap(const void *a, size_t na, const void *b, size_t nb) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y + nb && y < x + na;
-}
-
 // Round 6 -- pinned host buffers are used in place.  Where the kernels reach a HOST buffer directly: the address the
 // device sees when all of [p, p + bytes) is pinned memory -- a block of the library's slabs (speexhip_block_acquire, a
 // result block of ..._take: a range check, no runtime call), or, for buffers of kDirectCopyBytes and more, memory the
@@ -201,10 +155,11 @@ int wait_done(hipStream_t stream, volatile uint32_t *word, uint32_t seq, uint32_
   if (!signalled) HIP_TRY(hipStreamSynchronize(stream));
   return SPEEXHIP_ERR_SUCCESS;
 }
+}  // namespace
 // The wait `w` chose.  A polled one arms the completion word at `word` -- 64 bytes of pinned memory the call's kernels do
 // not write: the tail of a pinned result buffer (tail_word) or the bytes behind the samples of a take block -- with a
 // value other than `seq` and waits for the stream to write `seq` there.
-int wait_call(hipStream_t stream, const Wait &w, void *word, uint32_t seq) {
+int detail::wait_call(hipStream_t stream, const Wait &w, void *word, uint32_t seq) {
   if (w.sync) {
     HIP_TRY(hipStreamSynchronize(stream));
     return SPEEXHIP_ERR_SUCCESS;
@@ -213,14 +168,9 @@ int wait_call(hipStream_t stream, const Wait &w, void *word, uint32_t seq) {
   *done = seq - 1;
   return wait_done(stream, done, seq, w.spin_us());
 }
-inline char *tail_word(char *buf, size_t cap) { return buf == nullptr ? nullptr : buf + ((cap - 64) & ~static_cast<size_t>(63)); }
-// bytes of a side that pass through a device / a pinned staging buffer
-inline size_t device_part(Via v, size_t bytes) { return v == Via::Copy || v == Via::Staged ? bytes : 0; }
-inline size_t pinned_part(Via v, size_t bytes) { return v == Via::Bounce || v == Via::Staged ? bytes : 0; }
-
 // Grows a staging buffer of the host-buffer calls to `want` bytes: grow-only (like the wrapper's heap buffers,
 // src/index.ts:71-87); the calls are synchronous, so nothing in flight uses a buffer that goes back to the pool here.
-int grow_stage(int device, char **buf, size_t *cap_now, size_t want, bool pinned) {
+int detail::grow_stage(int device, char **buf, size_t *cap_now, size_t want, bool pinned) {
   if (want <= *cap_now) return SPEEXHIP_ERR_SUCCESS;
   if (pinned)
     pool::pinned_put(*buf);
@@ -236,6 +186,7 @@ int grow_stage(int device, char **buf, size_t *cap_now, size_t want, bool pinned
   *cap_now = cap;
   return SPEEXHIP_ERR_SUCCESS;
 }
+namespace {
 
 // The position fields of a descriptor: `n_out` outputs of filter `f` from `at`, `consumed` frames of V past the history,
 // `hist_frames` frames of history read and `hist_keep` left behind.
@@ -914,6 +865,8 @@ Batch::~Batch() {
   pool::device_put(device_, d_hist_[1]);
   pool::device_put(device_, d_stage_in_);
   pool::device_put(device_, d_stage_out_);
+  pool::device_put(device_, d_planar_in_);
+  pool::device_put(device_, d_planar_out_);
   pool::pinned_put(h_pin_in_);
   pool::pinned_put(h_pin_out_);
   for (int i = 0; i < kMaxPieces; i++) pool::event_put(device_, piece_ev_[i]);
@@ -1046,12 +999,16 @@ int Batch::run_channel(uint32_t c, const void *d_in, uint32_t in_stride, uint32_
   return SPEEXHIP_ERR_SUCCESS;
 }
 
-// The interleaved call on a stream whose channels stand at different positions: channel by
-// channel with the caller's lengths restored before each, the lengths of the LAST channel
-// reported (resample.c:1061-1082).  d_in / d_out: interleaved device buffers.
+// A call on a stream whose channels stand at different positions: channel by channel with the caller's lengths
+// restored before each, the lengths of the LAST channel reported (resample.c:1061-1082).  Channel c starts
+// `layout.in_channel` / `layout.out_channel` samples into the device buffers and its samples lie `in_sample` /
+// `out_sample` apart there: an interleaved buffer is {1, 1, channels, channels}, planes {in_plane_stride,
+// out_plane_stride, 1, 1}.
 int Batch::process_split(const void *d_in, uint32_t *in_len, void *d_out, uint32_t *out_len, bool float_io,
-                         hipStream_t stream, std::vector<CallPlan> *plans_out) {
+                         hipStream_t stream, std::vector<CallPlan> *plans_out, const SplitLayout *layout) {
   const size_t es = float_io ? sizeof(float) : sizeof(int16_t);
+  const SplitLayout interleaved = {1, 1, channels_, channels_};
+  const SplitLayout &at = layout != nullptr ? *layout : interleaved;
   EntryRules rules;
   rules.block_in = block_in();
   rules.float_entry = float_io;
@@ -1059,8 +1016,8 @@ int Batch::process_split(const void *d_in, uint32_t *in_len, void *d_out, uint32
   if (want_in != 0 && want_out != 0) started_[0] = 1;
   for (uint32_t c = 0; c < channels_; c++) {
     const CallPlan plan = plan_call(filter_.num, filter_.den, want_in, want_out, P(0, c), rules);
-    const int rc = run_channel(c, d_in ? static_cast<const char *>(d_in) + c * es : nullptr, channels_, want_in,
-                               static_cast<char *>(d_out) + c * es, channels_, plan, float_io, stream);
+    const int rc = run_channel(c, d_in ? static_cast<const char *>(d_in) + c * at.in_channel * es : nullptr, at.in_sample, want_in,
+                               static_cast<char *>(d_out) + c * at.out_channel * es, at.out_sample, plan, float_io, stream);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
     P(0, c) = plan.end;
     *in_len = plan.consumed;
@@ -1640,6 +1597,7 @@ int warm_device(int device) {
   warm_unit_period_w16g(s);
   warm_unit_slide_f32(s);
   warm_unit_slide64_f32(s);
+  warm_unit_planar(s);
   HIP_TRY(hipStreamSynchronize(s));
   return SPEEXHIP_ERR_SUCCESS;
 }

@@ -70,6 +70,17 @@ class Batch {
   // (process_interleaved_float); strides are in samples of that type.
   int process_device(const void *d_in, uint64_t in_stride, uint32_t *in_len, void *d_out,
                      uint64_t out_stride, uint32_t *out_len, bool float_io, hipStream_t stream);
+  // The same call on channel planes (planar.cpp): plane c of stream s starts at d_in + s * in_stream_stride +
+  // c * in_plane_stride (elements; a plane stride >= the frame count), likewise on the output side.  It IS the
+  // interleaved call on the same frames -- counters, samples and the state left behind -- between two transposing
+  // kernels (kernels_planar.hip) and per-state scratch images; a mono plane goes straight to process_device.
+  int process_planar_device(const void *d_in, uint64_t in_stream_stride, uint64_t in_plane_stride, uint32_t *in_len,
+                            void *d_out, uint64_t out_stream_stride, uint64_t out_plane_stride, uint32_t *out_len,
+                            bool float_io, hipStream_t stream);
+  // ... and on host planes (one pointer per channel; in_planes == nullptr: silence) of a single-stream batch;
+  // synchronous.  Each plane moves by the rule of host_transfer.h.
+  int process_planar_host(const void *const *in_planes, uint32_t *in_len, void *const *out_planes, uint32_t *out_len,
+                          bool float_io);
   // Host-buffer call for a single-stream batch; synchronous (H2D, kernels, D2H).
   int process_host(const void *in, uint32_t *in_len, void *out, uint32_t *out_len, bool float_io);
   // The same call with the result left in a pinned block of the pool that the caller then OWNS (release_block):
@@ -151,8 +162,13 @@ class Batch {
   uint32_t max_magic(uint32_t s) const;
   int run_channel(uint32_t c, const void *d_in, uint32_t in_stride, uint32_t in_frames, void *d_out,
                   uint32_t out_stride, const CallPlan &plan, bool float_io, hipStream_t stream);
+  struct SplitLayout {  // where process_split finds channel c and its samples (elements)
+    uint64_t in_channel, out_channel;
+    uint32_t in_sample, out_sample;
+  };
   int process_split(const void *d_in, uint32_t *in_len, void *d_out, uint32_t *out_len, bool float_io,
-                    hipStream_t stream, std::vector<CallPlan> *plans_out);
+                    hipStream_t stream, std::vector<CallPlan> *plans_out, const SplitLayout *layout = nullptr);
+  int ensure_planar_scratch(size_t in_bytes, size_t out_bytes);
   int fetch_history(std::vector<float> *host);
   int quiesce();  // waits for this batch's own enqueued work (never for the whole device)
   uint32_t block_in() const { return line_ - (filter_.taps - 1); }
@@ -239,6 +255,9 @@ class Batch {
   hipEvent_t piece_ev_[kMaxPieces] = {};
   char *d_stage_in_ = nullptr, *d_stage_out_ = nullptr;
   char *h_pin_in_ = nullptr, *h_pin_out_ = nullptr;
+  // planar calls (planar.cpp): the interleaved images either side of the existing launch; per state, grow-only
+  char *d_planar_in_ = nullptr, *d_planar_out_ = nullptr;
+  size_t planar_in_cap_ = 0, planar_out_cap_ = 0;  // bytes
   uint32_t done_seq_ = 0;  // completion word of the small host-buffer calls (engine.cpp, process_host)
   size_t stage_in_cap_ = 0, stage_out_cap_ = 0, pin_in_cap_ = 0, pin_out_cap_ = 0;  // bytes
 };

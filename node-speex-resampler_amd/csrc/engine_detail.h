@@ -1,0 +1,80 @@
+// engine_detail.h -- what the engine's translation units (engine.cpp, planar.cpp) share beside engine.h: the HIP error
+// macros, the device scope of an entry point and the staging helpers of the host-buffer calls (product code).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/speexhip_resampler.h"
+#include "devices.h"
+#include "host_transfer.h"
+
+namespace speexhip {
+namespace detail {
+
+// false on hipSuccess; otherwise records the text speexhip_resampler_strerror(SPEEXHIP_ERR_DEVICE) reports
+bool hip_failed(hipError_t e, const char *what);
+#define HIP_TRY(expr)                                                                  \
+  do {                                                                                 \
+    if (::speexhip::detail::hip_failed((expr), #expr)) return SPEEXHIP_ERR_DEVICE;     \
+  } while (0)
+
+// Every entry point runs on the batch's own device whatever the calling thread's current one is,
+// and leaves the thread's current device as it found it.
+class DeviceScope {
+ public:
+  explicit DeviceScope(int logical_device) {  // (devices.h: logical ordinals; physical = logical unless aliased)
+    const int device = devices::physical(logical_device);
+    if (hipGetDevice(&prev_) != hipSuccess) prev_ = device;
+    if (prev_ != device) err_ = hipSetDevice(device);
+    // (a failed call leaves its code behind as the thread's "last error", and the launchers read that after their
+    //  next launch: hipLaunchKernelGGL + hipGetLastError would report THIS failure for a launch that worked)
+    if (err_ != hipSuccess) (void)hipGetLastError();
+  }
+  ~DeviceScope() {
+    if (prev_ != device_now()) (void)hipSetDevice(prev_);
+  }
+  hipError_t error() const { return err_; }
+
+ private:
+  static int device_now() {
+    int d = 0;
+    (void)hipGetDevice(&d);
+    return d;
+  }
+  int prev_ = 0;
+  hipError_t err_ = hipSuccess;
+};
+#define ON_DEVICE()                                   \
+  ::speexhip::detail::DeviceScope device_scope(device_); \
+  HIP_TRY(device_scope.error())
+
+// The host-buffer calls are synchronous, and their staging buffers and the (shared) stream go on to the
+// next call or to another state: on EVERY exit nothing they enqueued may still be in flight.  The normal
+// path waits explicitly (and checks the result); this guard covers the early error returns.
+struct DrainOnExit {
+  hipStream_t *stream;  // (pointer: the stream is taken from the pool after the guard is set up)
+  bool armed = true;
+  explicit DrainOnExit(hipStream_t *s) : stream(s) {}
+  ~DrainOnExit() {
+    if (armed && *stream != nullptr) (void)hipStreamSynchronize(*stream);
+  }
+};
+
+inline size_t align64(size_t v) { return (v + 63) & ~static_cast<size_t>(63); }
+inline bool buffers_overlap(const void *a, size_t na, const void *b, size_t nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + nb && y < x + na;
+}
+inline char *tail_word(char *buf, size_t cap) { return buf == nullptr ? nullptr : buf + ((cap - 64) & ~static_cast<size_t>(63)); }
+// bytes of a side that pass through a device / a pinned staging buffer
+inline size_t device_part(Via v, size_t bytes) { return v == Via::Copy || v == Via::Staged ? bytes : 0; }
+inline size_t pinned_part(Via v, size_t bytes) { return v == Via::Bounce || v == Via::Staged ? bytes : 0; }
+
+// engine.cpp: the wait a host-buffer call's `Wait` chose, and the grow-only staging buffers
+int wait_call(hipStream_t stream, const Wait &w, void *word, uint32_t seq);
+int grow_stage(int device, char **buf, size_t *cap_now, size_t want, bool pinned);
+
+}  // namespace detail
+}  // namespace speexhip

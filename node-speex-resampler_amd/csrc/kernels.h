@@ -47,6 +47,7 @@ void warm_unit_period_odd(hipStream_t s);
 void warm_unit_period_frames(hipStream_t s);
 void warm_unit_period64_w16(hipStream_t s);
 void warm_unit_period_w16g(hipStream_t s);
+void warm_unit_planar(hipStream_t s);
 
 // compute units of the calling thread's current device (cached per device id)
 inline uint32_t device_compute_units() {
@@ -164,5 +165,25 @@ void build_slide64_rows(const FilterSpec &f, const SlidePlan &t, std::vector<dou
 hipError_t launch_slide64(const FilterSpec &f, const SlidePlan &t, const double *d_rows, uint32_t channels,
                           const StreamDesc *h_descs, const DescPack *pack,
                           uint32_t n_streams, bool float_io, hipStream_t stream, bool fixed_shape = false);
+
+// ---- channel planes <-> interleaved frames (kernels_planar.hip): the two passes either side of a planar call ------
+struct PlanarStream {       // one stream's share of a transposing launch
+  const void *planes;       // plane 0 (gather: read, scatter: written); plane c starts plane_stride elements further
+  uint64_t plane_stride;    // elements between two planes (>= frames)
+  void *inter;              // the interleaved image (gather: written, scatter: read); 16-byte aligned
+  uint32_t frames;          // frames per channel to move; 0 (or planes == NULL) = nothing
+  uint32_t reserved;
+};
+struct PlanarPack {         // like DescPack: up to 32 streams, in the kernel-argument segment
+  PlanarStream s[kMaxPackedStreams];
+};
+// frames of a workgroup's tile: 16 bytes per lane and plane, 256 lanes
+inline uint32_t planar_tile_frames(bool float_io) { return float_io ? 1024u : 2048u; }
+// planes -> interleaved (gather) / interleaved -> planes (scatter) for streams [0, n) of `pack`; max_frames = the
+// largest PlanarStream::frames among them
+hipError_t launch_planar_gather(const PlanarPack &pack, uint32_t n, uint32_t channels, uint32_t max_frames, bool float_io,
+                                hipStream_t stream);
+hipError_t launch_planar_scatter(const PlanarPack &pack, uint32_t n, uint32_t channels, uint32_t max_frames, bool float_io,
+                                 hipStream_t stream);
 
 }  // namespace speexhip

@@ -106,6 +106,13 @@ declare class SpeexResampler {
     /** interleaved float32 PCM in and out (speex_resampler_process_interleaved_float) */
     processChunkFloat(chunk: Buffer): Buffer;
 
+    /**
+     * planar PCM: one Int16Array or one Float32Array per channel (all of one kind and length) in, typed arrays of the
+     * same kind out; same state, capacity rule and samples as processChunk / processChunkFloat on the interleaved frames
+     */
+    processChunkPlanar(channels: Int16Array[]): Int16Array[];
+    processChunkPlanar(channels: Float32Array[]): Float32Array[];
+
     /** mid-stream control (speex_resampler_set_rate / set_quality / skip_zeros / reset_mem) */
     setRate(inRate: number, outRate: number): void;
     setQuality(quality: number): void;

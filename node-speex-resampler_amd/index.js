@@ -202,6 +202,29 @@ class SpeexResampler {
     return speexModule.processFloat(this._resamplerPtr, chunk, f, cap);
   }
 
+  /**
+   * Planar audio (Web Audio's getChannelData, a decoder's s16p / fltp): `channels` is an array of Int16Array or an
+   * array of Float32Array, one per channel, all of equal length; the result is an array of the same kind, one typed
+   * array per channel.  Same stream state and the same grow-only capacity rule as processChunk / processChunkFloat on
+   * the interleaved frames -- and the same samples.
+   */
+  processChunkPlanar(channels) {
+    if (!speexModule) {
+      throw new Error('You need to wait for SpeexResampler.initPromise before calling this method');
+    }
+    this._refuseWhileAsyncPending('processChunkPlanar');
+    const first = Array.isArray(channels) ? channels[0] : undefined;
+    const bytesPerSample = first instanceof Float32Array ? Float32Array.BYTES_PER_ELEMENT : Uint16Array.BYTES_PER_ELEMENT;
+    const sameKind = first instanceof Float32Array || first instanceof Int16Array;
+    if (!sameKind || channels.length !== this.channels ||
+        channels.some((p) => p.constructor !== first.constructor || p.length !== first.length)) {
+      throw new Error('Chunk length should be a multiple of channels * ' + bytesPerSample + ' bytes');
+    }
+    // the interleaved chunk of these frames, as far as the capacity rule is concerned
+    const [, cap] = this._prepare({ length: first.length * this.channels * bytesPerSample }, bytesPerSample);
+    return speexModule.processPlanar(this._resamplerPtr, channels, cap);
+  }
+
   /** Mid-stream control (SURVEY 8f row N3; speex_resampler_set_rate / set_quality / ...). */
   setRate(inRate, outRate) {
     this._refuseWhileAsyncPending('setRate');

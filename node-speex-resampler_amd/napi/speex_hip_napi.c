@@ -263,6 +263,96 @@ static napi_value process_common(napi_env env, napi_callback_info info, size_t s
 static napi_value Process(napi_env env, napi_callback_info info) { return process_common(env, info, 2); }
 static napi_value ProcessFloat(napi_env env, napi_callback_info info) { return process_common(env, info, 4); }
 
+/* processPlanar(handle, planes: Int16Array[] | Float32Array[], outCapacityFrames) -> typed arrays of the same kind,
+ * one per channel: speexhip_resampler_process_planar_int / _float on the arrays' own memory, the result written
+ * straight into fresh typed arrays of exactly the frames the call makes (peek, as in process_common). */
+static napi_value ProcessPlanar(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  uint32_t n = 0, out_len = 0;
+  bool is_array = false;
+  if (napi_is_array(env, argv[1], &is_array) != napi_ok || !is_array || napi_get_array_length(env, argv[1], &n) != napi_ok || n == 0) {
+    napi_throw_type_error(env, NULL, "channels must be an array of Int16Array or of Float32Array");
+    return NULL;
+  }
+  NAPI_OK(napi_get_value_uint32(env, argv[2], &out_len));
+  const void **in = (const void **)calloc(n, sizeof(void *));
+  void **out = (void **)calloc(n, sizeof(void *));
+  napi_value result = NULL;
+  const char *fail = NULL;
+  int type_error = 0;
+  napi_typedarray_type kind = napi_int16_array;
+  size_t frames = 0;
+  Handle *h = NULL;
+  if (in == NULL || out == NULL) fail = speexhip_resampler_strerror(SPEEXHIP_ERR_ALLOC_FAILED);
+  for (uint32_t c = 0; fail == NULL && c < n; c++) {
+    napi_value v;
+    napi_typedarray_type t;
+    size_t len = 0;
+    void *data = NULL;
+    bool typed = false;
+    if (napi_get_element(env, argv[1], c, &v) != napi_ok || napi_is_typedarray(env, v, &typed) != napi_ok || !typed ||
+        napi_get_typedarray_info(env, v, &t, &len, &data, NULL, NULL) != napi_ok ||
+        (t != napi_int16_array && t != napi_float32_array) || (c != 0 && t != kind)) {
+      fail = "channels must be an array of Int16Array or of Float32Array";
+      type_error = 1;
+    } else if (c != 0 && len != frames) {
+      fail = "channels must all have the same length";
+    } else {
+      kind = t;
+      frames = len;
+      in[c] = data != NULL ? data : (const void *)in; /* (an empty array: nothing is read, but NULL means "no plane") */
+    }
+  }
+  SpeexHipResamplerState *st = NULL;
+  if (fail == NULL) {
+    st = lock_state(env, argv[0], &h);
+    if (st == NULL) {
+      free(in);
+      free(out);
+      return NULL;
+    }
+    SpeexHipInfo si;
+    speexhip_resampler_get_info(st, &si);
+    if (si.nb_channels != n) fail = "one typed array per channel is expected";
+  }
+  if (fail == NULL) {
+    const int is_float = kind == napi_float32_array;
+    const size_t es = is_float ? 4 : 2;
+    uint32_t in_len = (uint32_t)frames, will_use = 0, will_make = 0;
+    speexhip_resampler_peek(st, in_len, out_len, is_float, &will_use, &will_make);
+    uint64_t nowhere = 0;
+    if (napi_create_array_with_length(env, n, &result) != napi_ok) fail = "speexhip N-API failure: napi_create_array_with_length";
+    for (uint32_t c = 0; fail == NULL && c < n; c++) {
+      napi_value ab, ta;
+      void *dst = NULL;
+      if (napi_create_arraybuffer(env, (size_t)will_make * es, &dst, &ab) != napi_ok ||
+          napi_create_typedarray(env, kind, will_make, ab, 0, &ta) != napi_ok || napi_set_element(env, result, c, ta) != napi_ok)
+        fail = "speexhip N-API failure: creating the result arrays";
+      out[c] = will_make != 0 && dst != NULL ? dst : (void *)&nowhere;
+    }
+    if (fail == NULL) {
+      /* out_len stays the caller's capacity (process_common); the library writes exactly will_make frames */
+      uint32_t cap = out_len;
+      const int rc = is_float ? speexhip_resampler_process_planar_float(st, (const float *const *)in, &in_len, (float *const *)out, &cap)
+                              : speexhip_resampler_process_planar_int(st, (const int16_t *const *)in, &in_len, (int16_t *const *)out, &cap);
+      if (rc != 0 || cap != will_make) fail = speexhip_resampler_strerror(rc != 0 ? rc : SPEEXHIP_ERR_BAD_STATE);
+    }
+  }
+  if (h != NULL) UNLOCK(h);
+  free(in);
+  free(out);
+  if (fail != NULL) {
+    if (type_error)
+      napi_throw_type_error(env, NULL, fail);
+    else
+      napi_throw_error(env, NULL, fail);
+    return NULL;
+  }
+  return result;
+}
+
 /* processChunks(handle, chunks: Buffer[], inFrames: number[], outCapacities: number[]) -> Buffer[]
  * n consecutive process() calls as one transfer + one launch
  * (speexhip_resampler_process_chunks_int); the i-th Buffer is what the i-th call returns. */
@@ -1118,6 +1208,7 @@ NAPI_MODULE_INIT() {
       {"destroy", NULL, Destroy, NULL, NULL, NULL, napi_default, NULL},
       {"process", NULL, Process, NULL, NULL, NULL, napi_default, NULL},
       {"processFloat", NULL, ProcessFloat, NULL, NULL, NULL, napi_default, NULL},
+      {"processPlanar", NULL, ProcessPlanar, NULL, NULL, NULL, napi_default, NULL},
       {"processChunks", NULL, ProcessChunks, NULL, NULL, NULL, napi_default, NULL},
       {"processAsync", NULL, ProcessAsync, NULL, NULL, NULL, napi_default, NULL},
       {"processChunksAsync", NULL, ProcessChunksAsync, NULL, NULL, NULL, napi_default, NULL},

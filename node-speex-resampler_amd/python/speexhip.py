@@ -57,6 +57,10 @@ EXPORTS = [
     "speexhip_resampler_get_info2", "speexhip_debug_placement", "speexhip_warmup",
     # round 6: pinned blocks the caller fills (inputs used in place)
     "speexhip_block_acquire", "speexhip_debug_pcie_peak", "speexhip_debug_placement_live", "speexhip_debug_live_states",
+    # planar (one plane per channel) calls
+    "speexhip_resampler_process_planar_int", "speexhip_resampler_process_planar_float",
+    "speexhip_resampler_process_planar_int_device", "speexhip_resampler_process_planar_float_device",
+    "speexhip_batch_process_planar_int_device", "speexhip_batch_process_planar_float_device",
 ]
 
 
@@ -222,6 +226,17 @@ def lib():
             L.speexhip_debug_live_states.argtypes = [i32]
             L.speexhip_debug_pcie_peak.restype = i32
             L.speexhip_debug_pcie_peak.argtypes = [C.c_uint64, i32, C.POINTER(C.c_double)]
+        if hasattr(L, "speexhip_resampler_process_planar_int") or "SPEEXHIP_LIB_PATH" not in os.environ:
+            u64 = C.c_uint64
+            for f in (L.speexhip_resampler_process_planar_int, L.speexhip_resampler_process_planar_float):
+                f.restype = i32
+                f.argtypes = [p, C.POINTER(C.c_void_p), pu32, C.POINTER(C.c_void_p), pu32]
+            for f in (L.speexhip_resampler_process_planar_int_device, L.speexhip_resampler_process_planar_float_device):
+                f.restype = i32
+                f.argtypes = [p, p, u64, pu32, p, u64, pu32, p]
+            for f in (L.speexhip_batch_process_planar_int_device, L.speexhip_batch_process_planar_float_device):
+                f.restype = i32
+                f.argtypes = [p, p, u64, u64, pu32, p, u64, u64, pu32, p]
         _lib = L
     return _lib
 
@@ -646,6 +661,49 @@ class Resampler:
             raise RuntimeError(strerror(rc))
         return out[: ol.value].copy(), il.value
 
+    def planar_call(self, kind, planes, cap, null_frames=0, out_planes=None):
+        """The host planar C call itself: planes = sequence of 1-D arrays (one per channel; None = silence of
+        null_frames frames), out_planes = arrays to write (default: fresh ones of `cap` frames, sentinel-filled).
+        Returns (rc, consumed, produced, out_planes)."""
+        dt, fill = (np.int16, self.SENTINEL_I16) if kind == "int" else (np.float32, self.SENTINEL_F32)
+        ins = None
+        if planes is None:
+            n = int(null_frames)
+        else:
+            planes = [np.asarray(q, dtype=dt) for q in planes]
+            assert all(q.ndim == 1 and (q.size < 2 or q.strides[0] == q.itemsize) for q in planes)
+            n = planes[0].shape[0]
+            ins = (C.c_void_p * len(planes))(*[q.ctypes.data for q in planes])
+        if out_planes is None:
+            out_planes = [np.full(max(int(cap), 1), fill, dt) for _ in range(self.channels)]
+        outs = (C.c_void_p * len(out_planes))(*[None if q is None else q.ctypes.data for q in out_planes])
+        il, ol = C.c_uint32(n), C.c_uint32(int(cap))
+        fn = (lib().speexhip_resampler_process_planar_int if kind == "int"
+              else lib().speexhip_resampler_process_planar_float)
+        rc = fn(self._h, ins, C.byref(il), outs, C.byref(ol))
+        return rc, il.value, ol.value, out_planes
+
+    def process_planar(self, x, out_capacity, float_io=False, null_frames=0):
+        """x: [C, F] array or a list of C 1-D arrays (None: null_frames frames of silence) -- one plane per channel,
+        no transposition on the caller's side.  Returns ([C, produced] array, frames consumed)."""
+        planes = None if x is None else [np.ascontiguousarray(q) for q in x]
+        rc, used, made, outs = self.planar_call("float" if float_io else "int", planes, out_capacity, null_frames)
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return np.stack([q[:made] for q in outs]), used
+
+    def process_planar_device(self, d_in_ptr, in_plane_stride, in_frames, d_out_ptr, out_plane_stride, out_capacity,
+                              stream_ptr=0, float_io=False):
+        """device planes: plane c at d_in_ptr + c * in_plane_stride elements; (consumed, produced)"""
+        il, ol = C.c_uint32(in_frames), C.c_uint32(out_capacity)
+        fn = (lib().speexhip_resampler_process_planar_float_device if float_io
+              else lib().speexhip_resampler_process_planar_int_device)
+        rc = fn(self._h, C.c_void_p(d_in_ptr), in_plane_stride, C.byref(il), C.c_void_p(d_out_ptr), out_plane_stride,
+                C.byref(ol), C.c_void_p(stream_ptr))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return il.value, ol.value
+
     def peek(self, in_frames, out_capacity, float_entry=False):
         """(consumed, produced) of the next call, state untouched"""
         c, p_ = C.c_uint32(), C.c_uint32()
@@ -755,6 +813,51 @@ class Batch:
         if rc:
             raise RuntimeError(strerror(rc))
         return list(il), list(ol)
+
+    def process_planar_device(self, d_in_ptr, in_stream_stride, in_plane_stride, in_frames, d_out_ptr,
+                              out_stream_stride, out_plane_stride, out_capacity, stream_ptr=0, float_io=False):
+        """The same call on channel planes: plane c of stream s at d_in_ptr + s * in_stream_stride +
+        c * in_plane_stride elements (a (B, C, T) tensor's strides)."""
+        n = self.n_streams
+        il = (C.c_uint32 * n)(*([in_frames] * n if np.isscalar(in_frames) else in_frames))
+        ol = (C.c_uint32 * n)(*([out_capacity] * n if np.isscalar(out_capacity) else out_capacity))
+        fn = (lib().speexhip_batch_process_planar_float_device if float_io
+              else lib().speexhip_batch_process_planar_int_device)
+        rc = fn(self._h, C.c_void_p(d_in_ptr), in_stream_stride, in_plane_stride, il, C.c_void_p(d_out_ptr),
+                out_stream_stride, out_plane_stride, ol, C.c_void_p(stream_ptr))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return list(il), list(ol)
+
+    def process_tensor(self, x, out_capacity=None, in_frames=None):
+        """x: a CUDA tensor (B, C, T) or (C, T), int16 or float32, whose last dimension is dense (any other strides).
+        Runs on torch's current stream.  in_frames: frames per stream (default T for all); out_capacity: frames the
+        result may hold per stream (default: what T frames can produce).  Returns (tensor of the same rank with
+        T_out = max(produced), list of frames produced per stream)."""
+        import torch
+        if not x.is_cuda or x.dtype not in (torch.int16, torch.float32) or x.dim() not in (2, 3):
+            raise ValueError("process_tensor wants a CUDA tensor (B, C, T) or (C, T) of int16 or float32")
+        xb = x if x.dim() == 3 else x.unsqueeze(0)
+        B, Cn, T = xb.shape
+        if B != self.n_streams or Cn != self.channels:
+            raise ValueError("tensor of %d streams x %d channels for a batch of %d x %d" % (B, Cn, self.n_streams, self.channels))
+        if T > 1 and xb.stride(-1) != 1:
+            raise ValueError("the last dimension of the tensor must be dense (stride 1)")
+        float_io = x.dtype == torch.float32
+        i = self.info()
+        if out_capacity is None:
+            out_capacity = (T * i["den_rate"] + i["num_rate"] - 1) // i["num_rate"] + 1
+        # (rows of whole 128-byte lines: planes whose base and stride are multiples of 16 bytes take the kernels' 16-bytes-
+        #  per-lane path; the result is a view of the padded buffer)
+        pitch = (max(int(out_capacity), 1) + 63) & ~63
+        out = torch.empty((B, Cn, pitch), dtype=x.dtype, device=x.device)
+        # (a dimension of size 1 may carry any stride: planes and streams are then never stepped over)
+        _, made = self.process_planar_device(
+            xb.data_ptr(), xb.stride(0) if B > 1 else 0, xb.stride(1), T if in_frames is None else in_frames,
+            out.data_ptr(), out.stride(0), out.stride(1), int(out_capacity), torch.cuda.current_stream(x.device).cuda_stream,
+            float_io)
+        out = out[:, :, : max(made)]
+        return (out if x.dim() == 3 else out[0]), made
 
     def close(self):
         if getattr(self, "_h", None):
