@@ -413,6 +413,65 @@ SPEEXHIP_API int speexhip_batch_process_planar_float_device(
     SpeexHipBatch *b, const float *d_in, uint64_t in_stream_stride, uint64_t in_plane_stride, uint32_t *in_len,
     float *d_out, uint64_t out_stream_stride, uint64_t out_plane_stride, uint32_t *out_len, void *hip_stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sample formats: a formatted call names the format of its input and of its output independently
+ * (a decoder's s16le in, Web Audio's float32 in +-1.0 out; 24-bit WAV / FLAC; 8-bit telephony).
+ * The library's internal unit is the reference's: one int16 step = 1.0f, what the float entry point
+ * takes and gives.  Every format has a full scale FS:
+ *
+ *   format  storage                     FS    to the internal float x           from a FIR value y
+ *   U8      1 byte, offset binary       2^7   (u - 128) * 256                   halfup(y / 256) + 128, clamped to 0..255
+ *   S16     2 bytes LE                  2^15  s                                 halfup(y), clamped
+ *   S24     3 bytes LE, packed          2^23  s / 256                           halfup(y * 256), clamped to -2^23..2^23-1
+ *   S32     4 bytes LE                  2^31  float(s) (nearest even) / 65536   halfup(y * 65536), clamped
+ *   F32     float, int16 units          2^15  as is                             as is
+ *   F32N    float, +-1.0 full scale     1     x * 32768                         y / 32768
+ *
+ * halfup(v) = floor(v + 0.5), evaluated exactly (ties go up, negative ones too: -2.5 -> -2).  The
+ * integer formats saturate, +inf / -inf go to their rails and NaN becomes the format's zero (128 for
+ * U8); the float formats never saturate.  U8 and packed S24 buffers need no alignment, the others that
+ * of their element.
+ *
+ * A formatted call IS the float call (..._process_interleaved_float*) on the converted input,
+ * followed by the output conversion: the same counters (speexhip_resampler_peek with float_entry = 1
+ * sizes it), the same state and history left behind, in every mode; a state whose channels the
+ * per-channel calls moved apart and the zero fallback behave as in the float call (the fallback's
+ * silence is the format's zero).  Both conversions run on the device, either side of the float
+ * call's own launch.  Three pairs launch nothing extra: S16 -> S16 is the int16 call, bit for bit and
+ * with its counter rules; F32 -> F32 is the float call; F32N -> F32N is the float call on the same
+ * bytes (a power-of-two scale commutes exactly with the FIR, short of overflow and underflow).
+ * Formatted, interleaved, planar and per-channel calls may be mixed on one state.
+ *
+ * ABI note: 0.5 -> 0.6 adds the enum and these four entry points; SpeexHipInfo and the error codes
+ * are unchanged. */
+enum {
+  SPEEXHIP_FMT_U8 = 0,
+  SPEEXHIP_FMT_S16 = 1,
+  SPEEXHIP_FMT_S24 = 2,
+  SPEEXHIP_FMT_S32 = 3,
+  SPEEXHIP_FMT_F32 = 4,
+  SPEEXHIP_FMT_F32N = 5
+};
+/* Bytes of one sample of a format (host only); 0 for an unknown format. */
+SPEEXHIP_API uint32_t speexhip_sample_bytes(int fmt);
+/* Host buffers, synchronous; lengths are frames per channel as in the interleaved calls, in == NULL
+ * is silence.  The raw bytes of both sides travel by the rule of the other host calls (pageable,
+ * speexhip_block_acquire blocks and caller-pinned buffers used in place).  An unknown format or
+ * out == NULL returns INVALID_ARG with the state untouched. */
+SPEEXHIP_API int speexhip_resampler_process_interleaved_fmt(SpeexHipResamplerState *st, int in_fmt, const void *in,
+                                                            uint32_t *in_len, int out_fmt, void *out,
+                                                            uint32_t *out_len);
+/* Device buffers, asynchronous on hip_stream, ordered like the other device calls. */
+SPEEXHIP_API int speexhip_resampler_process_interleaved_fmt_device(SpeexHipResamplerState *st, int in_fmt,
+                                                                   const void *d_in, uint32_t *in_len, int out_fmt,
+                                                                   void *d_out, uint32_t *out_len, void *hip_stream);
+/* ... of every stream of a batch; strides are in samples of the respective format (a packed S24
+ * sample is 3 bytes). */
+SPEEXHIP_API int speexhip_batch_process_interleaved_fmt_device(SpeexHipBatch *b, int in_fmt, const void *d_in,
+                                                               uint64_t in_stream_stride, uint32_t *in_len,
+                                                               int out_fmt, void *d_out, uint64_t out_stream_stride,
+                                                               uint32_t *out_len, void *hip_stream);
+
 /* Mid-stream control for every stream of a batch (same semantics as the single-stream calls). */
 SPEEXHIP_API int speexhip_batch_set_rate_frac(SpeexHipBatch *b, uint32_t ratio_num, uint32_t ratio_den,
                                               uint32_t in_rate, uint32_t out_rate);

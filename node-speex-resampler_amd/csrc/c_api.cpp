@@ -577,6 +577,43 @@ int speexhip_batch_process_planar_float_device(SpeexHipBatch *b, const float *d_
                                        static_cast<hipStream_t>(hip_stream)); });
 }
 
+uint32_t speexhip_sample_bytes(int fmt) {
+  switch (fmt) {
+    case SPEEXHIP_FMT_U8: return 1;
+    case SPEEXHIP_FMT_S16: return 2;
+    case SPEEXHIP_FMT_S24: return 3;
+    case SPEEXHIP_FMT_S32:
+    case SPEEXHIP_FMT_F32:
+    case SPEEXHIP_FMT_F32N: return 4;
+    default: return 0;
+  }
+}
+int speexhip_resampler_process_interleaved_fmt(SpeexHipResamplerState *st, int in_fmt, const void *in, uint32_t *in_len,
+                                               int out_fmt, void *out, uint32_t *out_len) {
+  if (st == nullptr || in_len == nullptr || out_len == nullptr || out == nullptr || speexhip_sample_bytes(in_fmt) == 0 ||
+      speexhip_sample_bytes(out_fmt) == 0)
+    return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return st->batch->process_fmt_host(in_fmt, in, in_len, out_fmt, out, out_len); });
+}
+int speexhip_resampler_process_interleaved_fmt_device(SpeexHipResamplerState *st, int in_fmt, const void *d_in,
+                                                      uint32_t *in_len, int out_fmt, void *d_out, uint32_t *out_len,
+                                                      void *hip_stream) {
+  if (st == nullptr || in_len == nullptr || out_len == nullptr || d_out == nullptr || speexhip_sample_bytes(in_fmt) == 0 ||
+      speexhip_sample_bytes(out_fmt) == 0)
+    return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return st->batch->process_fmt_device(in_fmt, d_in, 0, in_len, out_fmt, d_out, 0, out_len,
+                                     static_cast<hipStream_t>(hip_stream)); });
+}
+int speexhip_batch_process_interleaved_fmt_device(SpeexHipBatch *b, int in_fmt, const void *d_in, uint64_t in_stream_stride,
+                                                  uint32_t *in_len, int out_fmt, void *d_out, uint64_t out_stream_stride,
+                                                  uint32_t *out_len, void *hip_stream) {
+  if (b == nullptr || in_len == nullptr || out_len == nullptr || d_out == nullptr || speexhip_sample_bytes(in_fmt) == 0 ||
+      speexhip_sample_bytes(out_fmt) == 0)
+    return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return b->batch->process_fmt_device(in_fmt, d_in, in_stream_stride, in_len, out_fmt, d_out,
+                                    out_stream_stride, out_len, static_cast<hipStream_t>(hip_stream)); });
+}
+
 int speexhip_design_filter(uint32_t in_rate, uint32_t out_rate, int quality, SpeexHipInfo *info,
                            float *table, uint32_t table_capacity) {
   if (in_rate == 0 || out_rate == 0) return SPEEXHIP_ERR_INVALID_ARG;
@@ -665,6 +702,6 @@ int speexhip_plan_filter_change(uint32_t old_filt_len, uint32_t new_filt_len, ui
   return SPEEXHIP_ERR_SUCCESS;
 }
 
-const char *speexhip_version(void) { return "speexhip 0.5.0 gfx950"; }
+const char *speexhip_version(void) { return "speexhip 0.6.0 gfx950"; }
 
 }  // extern "C"

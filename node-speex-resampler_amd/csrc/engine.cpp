@@ -156,6 +156,7 @@ int wait_done(hipStream_t stream, volatile uint32_t *word, uint32_t seq, uint32_
   return SPEEXHIP_ERR_SUCCESS;
 }
 }  // namespace
+void *detail::pinned_view_of(const void *p, size_t bytes) { return pinned_view(p, bytes); }
 // The wait `w` chose.  A polled one arms the completion word at `word` -- 64 bytes of pinned memory the call's kernels do
 // not write: the tail of a pinned result buffer (tail_word) or the bytes behind the samples of a take block -- with a
 // value other than `seq` and waits for the stream to write `seq` there.
@@ -1598,6 +1599,7 @@ int warm_device(int device) {
   warm_unit_slide_f32(s);
   warm_unit_slide64_f32(s);
   warm_unit_planar(s);
+  warm_unit_convert(s);
   HIP_TRY(hipStreamSynchronize(s));
   return SPEEXHIP_ERR_SUCCESS;
 }

@@ -81,6 +81,16 @@ class Batch {
   // synchronous.  Each plane moves by the rule of host_transfer.h.
   int process_planar_host(const void *const *in_planes, uint32_t *in_len, void *const *out_planes, uint32_t *out_len,
                           bool float_io);
+  // Formatted calls (formats.cpp; SPEEXHIP_FMT_*): the float call on the converted input followed by the output
+  // conversion -- convert_in / convert_out (kernels_convert.hip) either side of process_device(float) on the state's
+  // scratch images (the planar calls' ones: calls on a state are ordered).  S16 -> S16, F32 -> F32 and F32N -> F32N go
+  // straight to process_device.  Strides are in samples of the side's format.  plans_out: the plan of every channel of
+  // a state whose channels stand apart (empty otherwise).
+  int process_fmt_device(int in_fmt, const void *d_in, uint64_t in_stride, uint32_t *in_len, int out_fmt, void *d_out,
+                         uint64_t out_stride, uint32_t *out_len, hipStream_t stream,
+                         std::vector<CallPlan> *plans_out = nullptr);
+  // ... on host buffers of a single-stream batch; synchronous.  The raw bytes move by the rule of host_transfer.h.
+  int process_fmt_host(int in_fmt, const void *in, uint32_t *in_len, int out_fmt, void *out, uint32_t *out_len);
   // Host-buffer call for a single-stream batch; synchronous (H2D, kernels, D2H).
   int process_host(const void *in, uint32_t *in_len, void *out, uint32_t *out_len, bool float_io);
   // The same call with the result left in a pinned block of the pool that the caller then OWNS (release_block):

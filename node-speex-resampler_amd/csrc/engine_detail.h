@@ -75,6 +75,8 @@ inline size_t pinned_part(Via v, size_t bytes) { return v == Via::Bounce || v ==
 // engine.cpp: the wait a host-buffer call's `Wait` chose, and the grow-only staging buffers
 int wait_call(hipStream_t stream, const Wait &w, void *word, uint32_t seq);
 int grow_stage(int device, char **buf, size_t *cap_now, size_t want, bool pinned);
+// engine.cpp, pinned_view: the address the device sees when all of [p, p + bytes) is pinned memory, else nullptr
+void *pinned_view_of(const void *p, size_t bytes);
 
 }  // namespace detail
 }  // namespace speexhip

@@ -48,6 +48,7 @@ void warm_unit_period_frames(hipStream_t s);
 void warm_unit_period64_w16(hipStream_t s);
 void warm_unit_period_w16g(hipStream_t s);
 void warm_unit_planar(hipStream_t s);
+void warm_unit_convert(hipStream_t s);
 
 // compute units of the calling thread's current device (cached per device id)
 inline uint32_t device_compute_units() {
@@ -185,5 +186,22 @@ hipError_t launch_planar_gather(const PlanarPack &pack, uint32_t n, uint32_t cha
                                 hipStream_t stream);
 hipError_t launch_planar_scatter(const PlanarPack &pack, uint32_t n, uint32_t channels, uint32_t max_frames, bool float_io,
                                  hipStream_t stream);
+
+// ---- sample formats <-> the internal float image (kernels_convert.hip): the two passes either side of a formatted call
+struct ConvertStream {      // one stream's share of a converting launch
+  const void *src;          // convert_in: storage of the call's format, convert_out: the float image; NULL = nothing
+  void *dst;                // convert_in: the float image, convert_out: storage
+  uint64_t n;               // samples to convert
+  uint32_t step;            // elements between two samples, in both buffers (1; the channel count when one channel of
+                            // interleaved frames is converted: a state whose channels stand apart)
+  uint32_t reserved;
+};
+struct ConvertPack {        // like DescPack: up to 32 streams, in the kernel-argument segment
+  ConvertStream s[kMaxPackedStreams];
+};
+// streams [0, n) of `pack` from / into format fmt (SPEEXHIP_FMT_*, not F32: that IS the image's format); max_samples =
+// the largest ConvertStream::n among them
+hipError_t launch_convert_in(int fmt, const ConvertPack &pack, uint32_t n, uint64_t max_samples, hipStream_t stream);
+hipError_t launch_convert_out(int fmt, const ConvertPack &pack, uint32_t n, uint64_t max_samples, hipStream_t stream);
 
 }  // namespace speexhip

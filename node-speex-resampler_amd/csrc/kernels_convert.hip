@@ -1,0 +1,217 @@
+// kernels_convert.hip -- sample formats <-> the internal float image: the two passes either side of a formatted call
+// (engine.h, process_fmt_device).  convert_in<F> reads storage of format F (u8, s16, packed s24, s32, float in +-1.0)
+// and writes the float image the FIR kernels read, in the library's unit (one int16 step = 1.0f); convert_out<F> reads
+// the image they wrote and stores format F, rounding half up and saturating the integer formats.  Elementwise.
+//
+// Grid = (tile, stream); the streams' arguments (ConvertPack) travel in the kernel-argument segment.  A tile is 4096
+// samples: 256 lanes x 16.
+//
+// Vector path (whole tiles; storage and image 16-byte aligned; step 1 -- decided per workgroup from the stream's
+// arguments, so it is wave-uniform): every access is 16 bytes per lane.  A lane owns G consecutive samples per pass --
+// G = 16 for u8 (one 16-byte piece of storage, four of the image) and packed s24 (three pieces of storage, unpacked /
+// packed in registers with byte shifts across dword pairs, four of the image), 8 for s16, 4 for the 4-byte formats --
+// and a workgroup makes 16 / G passes, lane t on group pass * 256 + t.
+//
+// Element path (any byte address for u8 / s24, any element-aligned one for the rest; partial tiles; strided samples of
+// a state whose channels stand apart): sample by sample, s24 byte by byte, consecutive lanes on consecutive samples.
+//
+// The image convert_in writes is read by the very next kernel and convert_out's source was written by the previous
+// one: plain loads and stores throughout, so that the images can stay in L2 / Infinity Cache.
+//
+// Rounding (include/speexhip_resampler.h): halfup(v) = floor(v + 0.5) on v = y * 2^k, evaluated in fp64 -- the product is
+// exact there, and v + 0.5 is exact wherever its floor depends on it.  NaN becomes the format's zero, +-inf the rails.
+#include <hip/hip_runtime.h>
+
+#include "../../include/speexhip_resampler.h"
+#include "kernels.h"
+
+namespace speexhip {
+
+SPEEXHIP_WARM_UNIT(convert)
+
+namespace {
+
+constexpr uint32_t kLanes = 256;
+constexpr uint32_t kTile = 4096;  // samples per workgroup
+
+constexpr uint32_t bytes_of(int f) {
+  return f == SPEEXHIP_FMT_U8 ? 1u : f == SPEEXHIP_FMT_S16 ? 2u : f == SPEEXHIP_FMT_S24 ? 3u : 4u;
+}
+// samples a lane owns per pass of the vector path: whole 16-byte pieces on both sides
+constexpr uint32_t group_of(int f) { return f == SPEEXHIP_FMT_U8 || f == SPEEXHIP_FMT_S24 ? 16u : f == SPEEXHIP_FMT_S16 ? 8u : 4u; }
+
+// ---- one sample --------------------------------------------------------------------------------------------------
+// `raw` = the sample's storage bits in the low bytes of a dword
+template <int F>
+__device__ __forceinline__ float to_internal(uint32_t raw) {
+  if (F == SPEEXHIP_FMT_U8) return (static_cast<float>(raw & 0xffu) - 128.0f) * 256.0f;
+  if (F == SPEEXHIP_FMT_S16) return static_cast<float>(static_cast<int16_t>(raw));
+  if (F == SPEEXHIP_FMT_S24) return static_cast<float>(static_cast<int32_t>(raw << 8) >> 8) * (1.0f / 256.0f);
+  if (F == SPEEXHIP_FMT_S32) return static_cast<float>(static_cast<int32_t>(raw)) * (1.0f / 65536.0f);
+  return __uint_as_float(raw) * 32768.0f;  // F32N
+}
+
+template <int F>
+__device__ __forceinline__ uint32_t from_internal(float y) {
+  if (F == SPEEXHIP_FMT_F32N) return __float_as_uint(y * (1.0f / 32768.0f));
+  constexpr double scale = F == SPEEXHIP_FMT_U8 ? 1.0 / 256.0 : F == SPEEXHIP_FMT_S16 ? 1.0 : F == SPEEXHIP_FMT_S24 ? 256.0 : 65536.0;
+  constexpr double bias = F == SPEEXHIP_FMT_U8 ? 128.0 : 0.0;
+  constexpr double lo = F == SPEEXHIP_FMT_U8 ? 0.0 : F == SPEEXHIP_FMT_S16 ? -32768.0 : F == SPEEXHIP_FMT_S24 ? -8388608.0 : -2147483648.0;
+  constexpr double hi = F == SPEEXHIP_FMT_U8 ? 255.0 : F == SPEEXHIP_FMT_S16 ? 32767.0 : F == SPEEXHIP_FMT_S24 ? 8388607.0 : 2147483647.0;
+  if (y != y) return static_cast<uint32_t>(static_cast<int32_t>(bias));
+  const double r = floor(static_cast<double>(y) * scale + 0.5) + bias;
+  return static_cast<uint32_t>(static_cast<int32_t>(fmin(fmax(r, lo), hi)));
+}
+
+// ---- 16 bytes per lane ---------------------------------------------------------------------------------------------
+// sample j (compile-time) of a lane's group, from / into the group's storage words
+template <int F>
+__device__ __forceinline__ uint32_t raw_of(const uint32_t *w, uint32_t j) {
+  constexpr uint32_t bits = 8 * bytes_of(F), words = group_of(F) * bytes_of(F) / 4;
+  const uint32_t k = j * bits / 32, shift = j * bits % 32;
+  const uint64_t pair = w[k] | (static_cast<uint64_t>(k + 1 < words ? w[k + 1] : 0u) << 32);
+  return static_cast<uint32_t>(pair >> shift);
+}
+template <int F>
+__device__ __forceinline__ void put_raw(uint32_t *w, uint32_t j, uint32_t raw) {
+  constexpr uint32_t bits = 8 * bytes_of(F), words = group_of(F) * bytes_of(F) / 4;
+  const uint32_t k = j * bits / 32, shift = j * bits % 32;
+  const uint64_t pair = static_cast<uint64_t>(bits == 32 ? raw : raw & ((1u << (bits & 31)) - 1u)) << shift;
+  w[k] |= static_cast<uint32_t>(pair);
+  if (k + 1 < words) w[k + 1] |= static_cast<uint32_t>(pair >> 32);
+}
+
+template <int F, bool kOut>
+__device__ __forceinline__ void vector_tile(const ConvertStream &s, uint64_t tile0) {
+  constexpr uint32_t B = bytes_of(F), G = group_of(F), words = G * B / 4;
+  const char *src = static_cast<const char *>(s.src);
+  char *dst = static_cast<char *>(s.dst);
+#pragma unroll
+  for (uint32_t pass = 0; pass < kTile / (kLanes * G); pass++) {
+    const uint64_t first = tile0 + static_cast<uint64_t>(pass * kLanes + threadIdx.x) * G;  // the lane's first sample
+    uint32_t w[words];
+    float e[G];
+    if (!kOut) {
+      const uint4 *in = reinterpret_cast<const uint4 *>(src + first * B);
+#pragma unroll
+      for (uint32_t i = 0; i < words / 4; i++) {
+        const uint4 v = in[i];
+        w[4 * i] = v.x, w[4 * i + 1] = v.y, w[4 * i + 2] = v.z, w[4 * i + 3] = v.w;
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < G; j++) e[j] = to_internal<F>(raw_of<F>(w, j));
+      float4 *out = reinterpret_cast<float4 *>(dst + first * sizeof(float));
+#pragma unroll
+      for (uint32_t i = 0; i < G / 4; i++) out[i] = make_float4(e[4 * i], e[4 * i + 1], e[4 * i + 2], e[4 * i + 3]);
+    } else {
+      const float4 *in = reinterpret_cast<const float4 *>(src + first * sizeof(float));
+#pragma unroll
+      for (uint32_t i = 0; i < G / 4; i++) {
+        const float4 v = in[i];
+        e[4 * i] = v.x, e[4 * i + 1] = v.y, e[4 * i + 2] = v.z, e[4 * i + 3] = v.w;
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < words; i++) w[i] = 0;
+#pragma unroll
+      for (uint32_t j = 0; j < G; j++) put_raw<F>(w, j, from_internal<F>(e[j]));
+      uint4 *out = reinterpret_cast<uint4 *>(dst + first * B);
+#pragma unroll
+      for (uint32_t i = 0; i < words / 4; i++) out[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+    }
+  }
+}
+
+// ---- sample by sample ----------------------------------------------------------------------------------------------
+template <int F>
+__device__ __forceinline__ uint32_t load_raw(const char *p) {
+  if (F == SPEEXHIP_FMT_U8) return *reinterpret_cast<const uint8_t *>(p);
+  if (F == SPEEXHIP_FMT_S16) return *reinterpret_cast<const uint16_t *>(p);
+  if (F == SPEEXHIP_FMT_S24) {
+    const uint8_t *b = reinterpret_cast<const uint8_t *>(p);
+    return b[0] | (static_cast<uint32_t>(b[1]) << 8) | (static_cast<uint32_t>(b[2]) << 16);
+  }
+  return *reinterpret_cast<const uint32_t *>(p);
+}
+template <int F>
+__device__ __forceinline__ void store_raw(char *p, uint32_t raw) {
+  if (F == SPEEXHIP_FMT_U8) {
+    *reinterpret_cast<uint8_t *>(p) = static_cast<uint8_t>(raw);
+  } else if (F == SPEEXHIP_FMT_S16) {
+    *reinterpret_cast<uint16_t *>(p) = static_cast<uint16_t>(raw);
+  } else if (F == SPEEXHIP_FMT_S24) {
+    uint8_t *b = reinterpret_cast<uint8_t *>(p);
+    b[0] = static_cast<uint8_t>(raw), b[1] = static_cast<uint8_t>(raw >> 8), b[2] = static_cast<uint8_t>(raw >> 16);
+  } else {
+    *reinterpret_cast<uint32_t *>(p) = raw;
+  }
+}
+
+// samples [tile0, tile0 + n) of the stream; sample k lies k * step elements into both buffers
+template <int F, bool kOut>
+__device__ __forceinline__ void element_tile(const ConvertStream &s, uint64_t tile0, uint32_t n) {
+  constexpr uint32_t B = bytes_of(F);
+  const char *src = static_cast<const char *>(s.src);
+  char *dst = static_cast<char *>(s.dst);
+  for (uint32_t i = threadIdx.x; i < n; i += kLanes) {
+    const uint64_t at = (tile0 + i) * s.step;
+    if (!kOut)
+      *reinterpret_cast<float *>(dst + at * sizeof(float)) = to_internal<F>(load_raw<F>(src + at * B));
+    else
+      store_raw<F>(dst + at * B, from_internal<F>(*reinterpret_cast<const float *>(src + at * sizeof(float))));
+  }
+}
+
+template <int F, bool kOut>
+__device__ __forceinline__ void convert_tile(const ConvertPack &pack) {
+  const ConvertStream &s = pack.s[blockIdx.y];
+  const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kTile;
+  if (s.src == nullptr || tile0 >= s.n) return;  // (nothing to convert, or a shorter stream of the launch)
+  const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(kTile), s.n - tile0));
+  const bool aligned = ((reinterpret_cast<uintptr_t>(s.src) | reinterpret_cast<uintptr_t>(s.dst)) & 15u) == 0;
+  if (n == kTile && aligned && s.step == 1)
+    vector_tile<F, kOut>(s, tile0);
+  else
+    element_tile<F, kOut>(s, tile0, n);
+}
+
+template <int F>
+__global__ __launch_bounds__(kLanes) void convert_in(const ConvertPack pack) {
+  convert_tile<F, false>(pack);
+}
+template <int F>
+__global__ __launch_bounds__(kLanes) void convert_out(const ConvertPack pack) {
+  convert_tile<F, true>(pack);
+}
+
+#define CONVERT_LAUNCH(F)                                                           \
+  if (kOut)                                                                         \
+    hipLaunchKernelGGL((convert_out<F>), grid, block, 0, stream, pack);             \
+  else                                                                              \
+    hipLaunchKernelGGL((convert_in<F>), grid, block, 0, stream, pack);              \
+  break
+template <bool kOut>
+hipError_t launch_convert(int fmt, const ConvertPack &pack, uint32_t n, uint64_t max_samples, hipStream_t stream) {
+  if (n == 0 || max_samples == 0) return hipSuccess;
+  const dim3 grid(static_cast<uint32_t>((max_samples + kTile - 1) / kTile), n), block(kLanes);
+  switch (fmt) {
+    case SPEEXHIP_FMT_U8: CONVERT_LAUNCH(SPEEXHIP_FMT_U8);
+    case SPEEXHIP_FMT_S16: CONVERT_LAUNCH(SPEEXHIP_FMT_S16);
+    case SPEEXHIP_FMT_S24: CONVERT_LAUNCH(SPEEXHIP_FMT_S24);
+    case SPEEXHIP_FMT_S32: CONVERT_LAUNCH(SPEEXHIP_FMT_S32);
+    case SPEEXHIP_FMT_F32N: CONVERT_LAUNCH(SPEEXHIP_FMT_F32N);
+    default: return hipErrorInvalidValue;  // (F32 is the image's own format: nothing to convert)
+  }
+  return hipGetLastError();
+}
+#undef CONVERT_LAUNCH
+
+}  // namespace
+
+hipError_t launch_convert_in(int fmt, const ConvertPack &pack, uint32_t n, uint64_t max_samples, hipStream_t stream) {
+  return launch_convert<false>(fmt, pack, n, max_samples, stream);
+}
+hipError_t launch_convert_out(int fmt, const ConvertPack &pack, uint32_t n, uint64_t max_samples, hipStream_t stream) {
+  return launch_convert<true>(fmt, pack, n, max_samples, stream);
+}
+
+}  // namespace speexhip

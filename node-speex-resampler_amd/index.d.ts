@@ -11,6 +11,12 @@ import { Transform, TransformCallback } from 'stream';
  * MI355X with the seven files of the reference's test (1.7 MB each, 64 KiB chunks, profiles/r02_node_bench.json),
  * the plain pipe takes 0.76-1.49 ms per file.  The options below buy something else than throughput.
  */
+/**
+ * sample formats of processChunkFormat: 's24le' is packed (3 bytes per sample), 'f32le' is float32 in int16 units (what
+ * processChunkFloat takes), 'f32le-normalized' float32 with +-1.0 full scale (Web Audio)
+ */
+export type SampleFormat = 'u8' | 's16le' | 's24le' | 's32le' | 'f32le' | 'f32le-normalized';
+
 export interface SpeexResamplerTransformOptions {
     /**
      * Hold up to n chunks and resample them in one GPU launch (same bytes out).  Trades LATENCY -- the first
@@ -112,6 +118,12 @@ declare class SpeexResampler {
      */
     processChunkPlanar(channels: Int16Array[]): Int16Array[];
     processChunkPlanar(channels: Float32Array[]): Float32Array[];
+
+    /**
+     * interleaved PCM of one sample format in, another out (SampleFormat); the conversions run on the GPU: it is
+     * processChunkFloat on the converted samples, then rounding half up and saturating into an integer outFormat
+     */
+    processChunkFormat(chunk: Buffer, inFormat: SampleFormat, outFormat: SampleFormat): Buffer;
 
     /** mid-stream control (speex_resampler_set_rate / set_quality / skip_zeros / reset_mem) */
     setRate(inRate: number, outRate: number): void;

@@ -12,6 +12,15 @@ const path = require('path');
 // Counterpart of `SpeexWasm()` (reference src/index.ts:18-19): a promise for the native
 // module; `speexModule` is only set once it resolves, so calling processChunk before
 // awaiting initPromise throws exactly like the reference does.
+// processChunkFormat: the names of the sample formats (SPEEXHIP_FMT_* ids, bytes per sample)
+const SAMPLE_FORMATS = {
+  'u8': { id: 0, bytes: 1 },
+  's16le': { id: 1, bytes: 2 },
+  's24le': { id: 2, bytes: 3 },
+  's32le': { id: 3, bytes: 4 },
+  'f32le': { id: 4, bytes: 4 },
+  'f32le-normalized': { id: 5, bytes: 4 },
+};
 let speexModule;
 const globalModulePromise = new Promise((resolve, reject) => {
   try {
@@ -223,6 +232,34 @@ class SpeexResampler {
     // the interleaved chunk of these frames, as far as the capacity rule is concerned
     const [, cap] = this._prepare({ length: first.length * this.channels * bytesPerSample }, bytesPerSample);
     return speexModule.processPlanar(this._resamplerPtr, channels, cap);
+  }
+
+  /**
+   * Sample formats named independently for the input and the result: 'u8' | 's16le' | 's24le' (packed, 3 bytes) |
+   * 's32le' | 'f32le' (float32 in int16 units, as processChunkFloat) | 'f32le-normalized' (float32 in +-1.0, Web Audio).
+   * `chunk` is a Buffer of interleaved frames in inFormat; the result is a Buffer in outFormat.  It is processChunkFloat
+   * on the converted samples followed by the output conversion (round half up, saturating), both done on the GPU:
+   * a decoder's s16le goes in and Web Audio's float32 comes out with no loop over the samples in JavaScript.  Same
+   * stream state and grow-only capacity rule as processChunkFloat on the same frames (processChunk for s16le -> s16le).
+   */
+  processChunkFormat(chunk, inFormat, outFormat) {
+    if (!speexModule) {
+      throw new Error('You need to wait for SpeexResampler.initPromise before calling this method');
+    }
+    this._refuseWhileAsyncPending('processChunkFormat');
+    const fin = SAMPLE_FORMATS[inFormat];
+    const fout = SAMPLE_FORMATS[outFormat];
+    if (!fin || !fout) {
+      throw new Error('Unknown sample format: ' + (fin ? outFormat : inFormat));
+    }
+    if (chunk.length % (this.channels * fin.bytes) !== 0) {
+      throw new Error('Chunk length should be a multiple of channels * ' + fin.bytes + ' bytes');
+    }
+    // the capacity rule of the call this one is: processChunk for s16le -> s16le, processChunkFloat on these frames otherwise
+    const frames = (chunk.length / this.channels / fin.bytes) | 0;
+    const asBytes = fin.id === 1 && fout.id === 1 ? Uint16Array.BYTES_PER_ELEMENT : Float32Array.BYTES_PER_ELEMENT;
+    const [, cap] = this._prepare({ length: frames * this.channels * asBytes }, asBytes);
+    return speexModule.processFormat(this._resamplerPtr, chunk, fin.id, fout.id, frames, cap);
   }
 
   /** Mid-stream control (SURVEY 8f row N3; speex_resampler_set_rate / set_quality / ...). */

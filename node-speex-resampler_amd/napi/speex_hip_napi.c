@@ -353,6 +353,58 @@ static napi_value ProcessPlanar(napi_env env, napi_callback_info info) {
   return result;
 }
 
+/* processFormat(handle, chunk: Buffer|null, inFormat, outFormat, inFrames, outCapacityFrames) -> Buffer of the frames
+ * written, in outFormat: speexhip_resampler_process_interleaved_fmt on the Buffer's own memory, the result written straight
+ * into a fresh Buffer of exactly the frames the call makes (peek with the entry whose counters the pair has). */
+static napi_value ProcessFormat(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  void *in_data = NULL;
+  size_t in_bytes = 0;
+  if (!buffer_or_null(env, argv[1], &in_data, &in_bytes)) {
+    napi_throw_type_error(env, NULL, "chunk must be a Buffer or null");
+    return NULL;
+  }
+  int32_t in_fmt = -1, out_fmt = -1;
+  uint32_t in_len = 0, out_len = 0;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &in_fmt));
+  NAPI_OK(napi_get_value_int32(env, argv[3], &out_fmt));
+  NAPI_OK(napi_get_value_uint32(env, argv[4], &in_len));
+  NAPI_OK(napi_get_value_uint32(env, argv[5], &out_len));
+  const size_t bin = speexhip_sample_bytes(in_fmt), bout = speexhip_sample_bytes(out_fmt);
+  if (bin == 0 || bout == 0) {
+    napi_throw_range_error(env, NULL, "unknown sample format");
+    return NULL;
+  }
+  Handle *h = NULL;
+  SpeexHipResamplerState *st = lock_state(env, argv[0], &h);
+  if (st == NULL) return NULL;
+  SpeexHipInfo si;
+  speexhip_resampler_get_info(st, &si);
+  if (in_data != NULL && (size_t)in_len * si.nb_channels * bin > in_bytes) {
+    UNLOCK(h);
+    napi_throw_range_error(env, NULL, "input frame count exceeds the chunk");
+    return NULL;
+  }
+  /* (s16 -> s16 is the int16 call, with its counters; every other pair has the float call's) */
+  const int float_entry = !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
+  uint32_t will_use = 0, will_make = 0;
+  speexhip_resampler_peek(st, in_len, out_len, float_entry, &will_use, &will_make);
+  napi_value out;
+  void *dst = NULL;
+  NAPI_OK_LOCKED(h, napi_create_buffer(env, (size_t)will_make * si.nb_channels * bout, &dst, &out));
+  uint64_t nowhere = 0;
+  if (dst == NULL) dst = &nowhere; /* empty Buffer: nothing will be written, but NULL means "no buffer" */
+  const int rc = speexhip_resampler_process_interleaved_fmt(st, in_fmt, in_data, &in_len, out_fmt, dst, &out_len);
+  UNLOCK(h);
+  if (rc != 0 || out_len != will_make) {
+    napi_throw_error(env, NULL, speexhip_resampler_strerror(rc != 0 ? rc : SPEEXHIP_ERR_BAD_STATE));
+    return NULL;
+  }
+  return out;
+}
+
 /* processChunks(handle, chunks: Buffer[], inFrames: number[], outCapacities: number[]) -> Buffer[]
  * n consecutive process() calls as one transfer + one launch
  * (speexhip_resampler_process_chunks_int); the i-th Buffer is what the i-th call returns. */
@@ -1209,6 +1261,7 @@ NAPI_MODULE_INIT() {
       {"process", NULL, Process, NULL, NULL, NULL, napi_default, NULL},
       {"processFloat", NULL, ProcessFloat, NULL, NULL, NULL, napi_default, NULL},
       {"processPlanar", NULL, ProcessPlanar, NULL, NULL, NULL, napi_default, NULL},
+      {"processFormat", NULL, ProcessFormat, NULL, NULL, NULL, napi_default, NULL},
       {"processChunks", NULL, ProcessChunks, NULL, NULL, NULL, napi_default, NULL},
       {"processAsync", NULL, ProcessAsync, NULL, NULL, NULL, napi_default, NULL},
       {"processChunksAsync", NULL, ProcessChunksAsync, NULL, NULL, NULL, napi_default, NULL},

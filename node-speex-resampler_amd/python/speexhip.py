@@ -20,6 +20,10 @@ KERNEL_NAMES = ("direct_single", "direct_double", "interpolate_single", "interpo
 ERR_SUCCESS, ERR_ALLOC_FAILED, ERR_BAD_STATE, ERR_INVALID_ARG, ERR_PTR_OVERLAP, ERR_OVERFLOW = 0, 1, 2, 3, 4, 5
 ERR_DEVICE = 6
 ERR_NO_BLOCK = 7  # the ..._take calls: no pinned result block free right now, state untouched
+# sample formats of the formatted calls (SPEEXHIP_FMT_*); S24 is packed: 3 bytes per sample, a uint8 array here
+FMT_U8, FMT_S16, FMT_S24, FMT_S32, FMT_F32, FMT_F32N = range(6)
+FMT_BYTES = (1, 2, 3, 4, 4, 4)
+FMT_DTYPE = (np.uint8, np.int16, np.uint8, np.int32, np.float32, np.float32)  # numpy storage type of each format
 
 EXPORTS = [
     "speexhip_resampler_init", "speexhip_resampler_destroy",
@@ -61,6 +65,9 @@ EXPORTS = [
     "speexhip_resampler_process_planar_int", "speexhip_resampler_process_planar_float",
     "speexhip_resampler_process_planar_int_device", "speexhip_resampler_process_planar_float_device",
     "speexhip_batch_process_planar_int_device", "speexhip_batch_process_planar_float_device",
+    # sample formats: u8, packed s24, s32, float in +-1.0; input and output named independently
+    "speexhip_sample_bytes", "speexhip_resampler_process_interleaved_fmt",
+    "speexhip_resampler_process_interleaved_fmt_device", "speexhip_batch_process_interleaved_fmt_device",
 ]
 
 
@@ -237,6 +244,16 @@ def lib():
             for f in (L.speexhip_batch_process_planar_int_device, L.speexhip_batch_process_planar_float_device):
                 f.restype = i32
                 f.argtypes = [p, p, u64, u64, pu32, p, u64, u64, pu32, p]
+        if hasattr(L, "speexhip_sample_bytes") or "SPEEXHIP_LIB_PATH" not in os.environ:
+            u64 = C.c_uint64
+            L.speexhip_sample_bytes.restype = u32
+            L.speexhip_sample_bytes.argtypes = [i32]
+            L.speexhip_resampler_process_interleaved_fmt.restype = i32
+            L.speexhip_resampler_process_interleaved_fmt.argtypes = [p, i32, p, pu32, i32, p, pu32]
+            L.speexhip_resampler_process_interleaved_fmt_device.restype = i32
+            L.speexhip_resampler_process_interleaved_fmt_device.argtypes = [p, i32, p, pu32, i32, p, pu32, p]
+            L.speexhip_batch_process_interleaved_fmt_device.restype = i32
+            L.speexhip_batch_process_interleaved_fmt_device.argtypes = [p, i32, p, u64, pu32, i32, p, u64, pu32, p]
         _lib = L
     return _lib
 
@@ -704,6 +721,46 @@ class Resampler:
             raise RuntimeError(strerror(rc))
         return il.value, ol.value
 
+    SENTINEL_BYTE = 0xA5
+
+    def fmt_call(self, x, in_fmt, out_fmt, cap, null_frames=0):
+        """The host formatted C call itself.  x: array of the format's storage type (FMT_DTYPE; packed S24 as uint8,
+        3 bytes per sample) holding whole frames, or None = silence of null_frames frames.  Returns (rc, consumed,
+        produced, out): `out` is the whole buffer of `cap` frames in the output format's storage type, flat, every
+        byte pre-filled with SENTINEL_BYTE."""
+        if x is None:
+            ptr, n = None, int(null_frames)
+        else:
+            x = np.ascontiguousarray(x, dtype=FMT_DTYPE[in_fmt]).reshape(-1)
+            n = x.nbytes // (FMT_BYTES[in_fmt] * self.channels)
+            assert n * FMT_BYTES[in_fmt] * self.channels == x.nbytes, "whole frames only"
+            ptr = C.c_void_p(x.ctypes.data)
+        raw = np.full(max(int(cap), 1) * self.channels * FMT_BYTES[out_fmt], self.SENTINEL_BYTE, np.uint8)
+        il, ol = C.c_uint32(n), C.c_uint32(int(cap))
+        rc = lib().speexhip_resampler_process_interleaved_fmt(self._h, in_fmt, ptr, C.byref(il), out_fmt,
+                                                              C.c_void_p(raw.ctypes.data), C.byref(ol))
+        return rc, il.value, ol.value, raw.view(FMT_DTYPE[out_fmt])
+
+    def process_fmt(self, x, in_fmt, out_fmt, capacity, null_frames=0):
+        """Formatted call on host buffers: x in format in_fmt (FMT_*; S24 as a uint8 array of 3 * n bytes; None: silence),
+        the result in out_fmt.  It is the float call on the converted input followed by the output conversion, both on the
+        device.  Returns (flat array of produced * channels samples in the output format's storage type, consumed)."""
+        rc, used, made, out = self.fmt_call(x, in_fmt, out_fmt, capacity, null_frames)
+        if rc:
+            raise RuntimeError(strerror(rc))
+        per = self.channels * (3 if out_fmt == FMT_S24 else 1)
+        return out[: made * per].copy(), used
+
+    def process_fmt_device(self, in_fmt, d_in_ptr, in_frames, out_fmt, d_out_ptr, out_capacity, stream_ptr=0):
+        """device buffers of the named formats; (consumed, produced)"""
+        il, ol = C.c_uint32(in_frames), C.c_uint32(out_capacity)
+        rc = lib().speexhip_resampler_process_interleaved_fmt_device(
+            self._h, in_fmt, C.c_void_p(d_in_ptr), C.byref(il), out_fmt, C.c_void_p(d_out_ptr), C.byref(ol),
+            C.c_void_p(stream_ptr))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return il.value, ol.value
+
     def peek(self, in_frames, out_capacity, float_entry=False):
         """(consumed, produced) of the next call, state untouched"""
         c, p_ = C.c_uint32(), C.c_uint32()
@@ -829,12 +886,59 @@ class Batch:
             raise RuntimeError(strerror(rc))
         return list(il), list(ol)
 
-    def process_tensor(self, x, out_capacity=None, in_frames=None):
+    def process_fmt_device(self, in_fmt, d_in_ptr, in_stride, in_frames, out_fmt, d_out_ptr, out_stride, out_capacity,
+                           stream_ptr=0):
+        """Formatted call of every stream: interleaved device buffers of formats in_fmt / out_fmt (FMT_*), strides in
+        samples of the respective format (a packed S24 sample is 3 bytes)."""
+        n = self.n_streams
+        il = (C.c_uint32 * n)(*([in_frames] * n if np.isscalar(in_frames) else in_frames))
+        ol = (C.c_uint32 * n)(*([out_capacity] * n if np.isscalar(out_capacity) else out_capacity))
+        rc = lib().speexhip_batch_process_interleaved_fmt_device(
+            self._h, in_fmt, C.c_void_p(d_in_ptr), in_stride, il, out_fmt, C.c_void_p(d_out_ptr), out_stride, ol,
+            C.c_void_p(stream_ptr))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return list(il), list(ol)
+
+    def _process_tensor_fmt(self, x, out_capacity, in_frames, out_dtype, normalized):
+        """process_tensor beyond int16 -> int16 and float32 -> float32: interleaved frames (..., T, C) through the
+        formatted call.  uint8 = U8, int16 = S16, int32 = S32, float32 = F32 (normalized: +-1.0 full scale)."""
+        import torch
+        fmt_of = {torch.uint8: FMT_U8, torch.int16: FMT_S16, torch.int32: FMT_S32,
+                  torch.float32: FMT_F32N if normalized else FMT_F32}
+        out_dtype = x.dtype if out_dtype is None else out_dtype
+        if x.dtype not in fmt_of or out_dtype not in fmt_of:
+            raise ValueError("process_tensor converts between uint8, int16, int32 and float32 tensors")
+        xb = x if x.dim() == 3 else x.unsqueeze(0)
+        B, T, Cn = xb.shape
+        if B != self.n_streams or Cn != self.channels:
+            raise ValueError("tensor of %d streams x %d channels for a batch of %d x %d" % (B, Cn, self.n_streams, self.channels))
+        if not xb[0].is_contiguous():
+            raise ValueError("the frames of a stream must be dense (T, C)")
+        i = self.info()
+        if out_capacity is None:
+            out_capacity = (T * i["den_rate"] + i["num_rate"] - 1) // i["num_rate"] + 1
+        out = torch.empty((B, max(int(out_capacity), 1), Cn), dtype=out_dtype, device=x.device)
+        _, made = self.process_fmt_device(
+            fmt_of[x.dtype], xb.data_ptr(), xb.stride(0) if B > 1 else 0, T if in_frames is None else in_frames,
+            fmt_of[out_dtype], out.data_ptr(), out.stride(0), int(out_capacity),
+            torch.cuda.current_stream(x.device).cuda_stream)
+        out = out[:, : max(made)]
+        return (out if x.dim() == 3 else out[0]), made
+
+    def process_tensor(self, x, out_capacity=None, in_frames=None, out_dtype=None, normalized=False):
         """x: a CUDA tensor (B, C, T) or (C, T), int16 or float32, whose last dimension is dense (any other strides).
         Runs on torch's current stream.  in_frames: frames per stream (default T for all); out_capacity: frames the
         result may hold per stream (default: what T frames can produce).  Returns (tensor of the same rank with
-        T_out = max(produced), list of frames produced per stream)."""
+        T_out = max(produced), list of frames produced per stream).
+
+        Other sample types -- a uint8 (offset binary) or int32 tensor, out_dtype= another type than x's, or
+        normalized=True (float32 in +-1.0 instead of int16 units) -- take the formatted call, which works on
+        interleaved frames: x is then (B, T, C) or (T, C), dense, and so is the result."""
         import torch
+        if x.is_cuda and x.dim() in (2, 3) and (
+                x.dtype in (torch.uint8, torch.int32) or normalized or (out_dtype is not None and out_dtype != x.dtype)):
+            return self._process_tensor_fmt(x, out_capacity, in_frames, out_dtype, normalized)
         if not x.is_cuda or x.dtype not in (torch.int16, torch.float32) or x.dim() not in (2, 3):
             raise ValueError("process_tensor wants a CUDA tensor (B, C, T) or (C, T) of int16 or float32")
         xb = x if x.dim() == 3 else x.unsqueeze(0)

@@ -6,7 +6,8 @@ Random (channels, in_rate, out_rate, quality) -- common audio rates, rates that 
 ratios (the slide kernel's shapes), near-unity and coprime oddballs (long periods, the exact kernel) --
 driven through a random call sequence: chunk sizes from 0 to a few hundred thousand frames, output
 capacities that are sometimes too small (unconsumed input, reference resample.c:1061-1082), int16 and
-float calls mixed on one state, per-channel calls with strides (after which the interleaved calls run
+float calls mixed on one state, formatted calls (a random pair of sample formats: the float call on the converted samples,
+converted back -- bytes in EXACT mode, the float bound scaled to the output format otherwise), per-channel calls with strides (after which the interleaved calls run
 channel by channel), runs of coalesced chunks, occasional set_rate / set_quality / skip_zeros / reset_mem
 in between.
 EXACT mode must be bit-identical (samples, counters, positions); FAST mode within +-1 LSB (int16) /
@@ -30,7 +31,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "node-speex-resampler_amd", "python"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle as orc  # noqa: E402
+import sample_formats as sf  # noqa: E402  (tests/: the numpy statement of the sample formats)
 import speexhip  # noqa: E402
 
 COMMON = [8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000]
@@ -178,6 +181,47 @@ def one_trial(seed, max_frames, many_channels=False):
                 return "%s: buffers differ in %d places" % (tag, int((a[3] != b[3]).sum())), what
             if got_r.positions() != ref.positions():
                 return "%s: positions %s, oracle %s" % (tag, got_r.positions(), ref.positions()), what
+            continue
+        if as_float and rng.rand() < 0.4:
+            # a formatted call: the samples stored in a random format, the result asked for in another -- against the
+            # oracle's float call on the converted samples, converted by tests/sample_formats.py
+            in_fmt, out_fmt = int(rng.randint(0, 6)), int(rng.randint(0, 6))
+            raw = sf.from_internal(in_fmt, x.astype(np.float32))
+            xin = sf.to_internal(in_fmt, raw).reshape(-1, ch)
+            if in_fmt == out_fmt == sf.S16:
+                a = ref.raw_call("int", raw, cap)
+            else:
+                a = ref.raw_call("float", raw if in_fmt == out_fmt == sf.F32N else xin, cap)
+            b = got_r.fmt_call(raw, in_fmt, out_fmt, cap)
+            tag = "call %d (formatted %s -> %s, %d frames, cap %d)" % (call, sf.NAMES[in_fmt], sf.NAMES[out_fmt], frames, cap)
+            if a[:3] != b[:3]:
+                return "%s: rc/used/made %s, oracle %s" % (tag, b[:3], a[:3]), what
+            if got_r.positions() != ref.positions():
+                return "%s: positions %s, oracle %s" % (tag, got_r.positions(), ref.positions()), what
+            y = a[3][: a[2]].reshape(-1)
+            same_bytes = in_fmt == out_fmt and in_fmt in (sf.S16, sf.F32, sf.F32N)
+            want = y if same_bytes else sf.from_internal(out_fmt, y)
+            got = b[3][: want.size]
+            if want.size == 0:
+                continue
+            if mode == speexhip.MODE_EXACT:
+                if got.tobytes() != want.tobytes():
+                    return "%s: EXACT differs" % tag, what
+                continue
+            # the float bound below, in int16 steps, times the output format's steps per int16 step (+ 1 step of rounding)
+            if xin.size:
+                peak_in = max(peak_in, float(np.abs(xin.astype(np.float64)).max()))
+            bound = 4e-6 * max(1.0, float(np.abs(y.astype(np.float64)).max()) * (32768.0 if same_bytes and in_fmt == sf.F32N else 1.0),
+                               peak_in) * 8 * max(1.0, (ref.taps / 256.0) ** 0.5)
+            if out_fmt in (sf.F32, sf.F32N):
+                err = float(np.abs(got.astype(np.float64) - want.astype(np.float64)).max()) * (32768.0 if out_fmt == sf.F32N else 1.0)
+                if err > bound:
+                    return "%s: float error %.3g, bound %.3g" % (tag, err, bound), what
+            else:
+                steps = {sf.U8: 1.0 / 256.0, sf.S16: 1.0, sf.S24: 256.0, sf.S32: 65536.0}[out_fmt]
+                d = np.abs(sf.integers(out_fmt, got) - sf.integers(out_fmt, want)).max()
+                if d > bound * steps + 1:
+                    return "%s: off by %d steps, bound %.3g" % (tag, d, bound * steps + 1), what
             continue
         if as_float:
             want, wu = ref.process_float(x, cap)
