@@ -472,6 +472,64 @@ SPEEXHIP_API int speexhip_batch_process_interleaved_fmt_device(SpeexHipBatch *b,
                                                                int out_fmt, void *d_out, uint64_t out_stream_stride,
                                                                uint32_t *out_len, void *hip_stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Channel mixing: a mixed call is a formatted call whose input and output frames may hold another
+ * number of channels than the state, with a matrix on that side.  The state keeps its channel count C
+ * from init: the number of channels the FIR runs on and the history holds.  Each side names
+ *
+ *   in_channels,  in_mix   row-major C x in_channels floats in HOST memory; NULL = no input mix,
+ *                          and in_channels must then equal C
+ *   out_channels, out_mix  row-major out_channels x C floats in host memory; NULL = no output mix,
+ *                          and out_channels must then equal C
+ *
+ * so the caller places the mix by choosing C: a downmix at the input (a state of the small count: the
+ * FIR does the least work), an upmix at the output, or both (6 -> 2 -> 2).  The matrices are read
+ * during the call and not kept.  The call is, in order: to_internal(in_fmt) per sample as in the
+ * formatted call; the input mix per frame; THE FLOAT CALL of the state on that image (its counters,
+ * and the same history and position left behind, in every mode); the output mix per frame;
+ * from_internal(out_fmt) per sample (half-up, saturating, NaN -> the format's zero).
+ *
+ * The mix of one frame x of n samples by a matrix M, exactly: output o is
+ *   acc = (double)M[o][0] * (double)x[0];  acc = acc + (double)M[o][i] * (double)x[i]  for i = 1 .. n-1
+ * in ascending order, then one rounding of acc to fp32 (nearest even).  Every term is included (a zero
+ * coefficient is not skipped) and nothing is clamped on the float image: only the integer output
+ * formats saturate, in from_internal.
+ *
+ * Lengths are frames, as in the other calls; speexhip_resampler_peek with float_entry = 1 sizes a
+ * mixed call.  A side with a matrix supports C <= 8 and a caller-side count of 1..8; anything else,
+ * an unknown format or out == NULL returns INVALID_ARG.  With both matrices NULL the call IS the
+ * formatted call (S16 -> S16 being the int16 call with its counter rules); with a matrix on either
+ * side the float entry's rules hold for every format pair, S16 -> S16 included.  A state whose
+ * channels the per-channel calls moved apart returns BAD_STATE (its channels produce different
+ * numbers of frames, so an output frame is not defined).  The zero fallback behaves as in the float
+ * call: its zeros go through the output mix and the output conversion.  Every argument error leaves
+ * the state, *in_len and *out_len untouched.  Both mixes run on the device, each folded into the pass
+ * that converts its side: a mixed call launches no more kernels than the formatted call.  Mixed,
+ * formatted, interleaved, planar and per-channel calls may be mixed on one state.
+ *
+ * ABI note: 0.6 -> 0.7 adds these three entry points; SpeexHipInfo, the enum and the error codes are
+ * unchanged. */
+/* Host buffers, synchronous, routed like speexhip_resampler_process_interleaved_fmt; an input frame
+ * holds in_channels samples of in_fmt, an output frame out_channels samples of out_fmt. */
+SPEEXHIP_API int speexhip_resampler_process_interleaved_mix(SpeexHipResamplerState *st, int in_fmt, uint32_t in_channels,
+                                                            const float *in_mix, const void *in, uint32_t *in_len,
+                                                            int out_fmt, uint32_t out_channels, const float *out_mix,
+                                                            void *out, uint32_t *out_len);
+/* Device buffers, asynchronous on hip_stream, ordered like the other device calls. */
+SPEEXHIP_API int speexhip_resampler_process_interleaved_mix_device(SpeexHipResamplerState *st, int in_fmt,
+                                                                   uint32_t in_channels, const float *in_mix,
+                                                                   const void *d_in, uint32_t *in_len, int out_fmt,
+                                                                   uint32_t out_channels, const float *out_mix,
+                                                                   void *d_out, uint32_t *out_len, void *hip_stream);
+/* ... of every stream of a batch; strides are in samples of the respective format, a frame of a side
+ * holds that side's channel count, and the one pair of matrices serves all streams. */
+SPEEXHIP_API int speexhip_batch_process_interleaved_mix_device(SpeexHipBatch *b, int in_fmt, uint32_t in_channels,
+                                                               const float *in_mix, const void *d_in,
+                                                               uint64_t in_stream_stride, uint32_t *in_len, int out_fmt,
+                                                               uint32_t out_channels, const float *out_mix, void *d_out,
+                                                               uint64_t out_stream_stride, uint32_t *out_len,
+                                                               void *hip_stream);
+
 /* Mid-stream control for every stream of a batch (same semantics as the single-stream calls). */
 SPEEXHIP_API int speexhip_batch_set_rate_frac(SpeexHipBatch *b, uint32_t ratio_num, uint32_t ratio_den,
                                               uint32_t in_rate, uint32_t out_rate);

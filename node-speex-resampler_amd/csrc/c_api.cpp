@@ -614,6 +614,37 @@ int speexhip_batch_process_interleaved_fmt_device(SpeexHipBatch *b, int in_fmt, 
                                     out_stream_stride, out_len, static_cast<hipStream_t>(hip_stream)); });
 }
 
+int speexhip_resampler_process_interleaved_mix(SpeexHipResamplerState *st, int in_fmt, uint32_t in_channels,
+                                               const float *in_mix, const void *in, uint32_t *in_len, int out_fmt,
+                                               uint32_t out_channels, const float *out_mix, void *out, uint32_t *out_len) {
+  if (st == nullptr || in_len == nullptr || out_len == nullptr || out == nullptr || speexhip_sample_bytes(in_fmt) == 0 ||
+      speexhip_sample_bytes(out_fmt) == 0)
+    return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return st->batch->process_mix_host(in_fmt, in_channels, in_mix, in, in_len, out_fmt, out_channels,
+                                                          out_mix, out, out_len); });
+}
+int speexhip_resampler_process_interleaved_mix_device(SpeexHipResamplerState *st, int in_fmt, uint32_t in_channels,
+                                                      const float *in_mix, const void *d_in, uint32_t *in_len, int out_fmt,
+                                                      uint32_t out_channels, const float *out_mix, void *d_out,
+                                                      uint32_t *out_len, void *hip_stream) {
+  if (st == nullptr || in_len == nullptr || out_len == nullptr || d_out == nullptr || speexhip_sample_bytes(in_fmt) == 0 ||
+      speexhip_sample_bytes(out_fmt) == 0)
+    return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return st->batch->process_mix_device(in_fmt, in_channels, in_mix, d_in, 0, in_len, out_fmt,
+                                     out_channels, out_mix, d_out, 0, out_len, static_cast<hipStream_t>(hip_stream)); });
+}
+int speexhip_batch_process_interleaved_mix_device(SpeexHipBatch *b, int in_fmt, uint32_t in_channels, const float *in_mix,
+                                                  const void *d_in, uint64_t in_stream_stride, uint32_t *in_len, int out_fmt,
+                                                  uint32_t out_channels, const float *out_mix, void *d_out,
+                                                  uint64_t out_stream_stride, uint32_t *out_len, void *hip_stream) {
+  if (b == nullptr || in_len == nullptr || out_len == nullptr || d_out == nullptr || speexhip_sample_bytes(in_fmt) == 0 ||
+      speexhip_sample_bytes(out_fmt) == 0)
+    return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return b->batch->process_mix_device(in_fmt, in_channels, in_mix, d_in, in_stream_stride, in_len,
+                                    out_fmt, out_channels, out_mix, d_out, out_stream_stride, out_len,
+                                    static_cast<hipStream_t>(hip_stream)); });
+}
+
 int speexhip_design_filter(uint32_t in_rate, uint32_t out_rate, int quality, SpeexHipInfo *info,
                            float *table, uint32_t table_capacity) {
   if (in_rate == 0 || out_rate == 0) return SPEEXHIP_ERR_INVALID_ARG;
@@ -702,6 +733,6 @@ int speexhip_plan_filter_change(uint32_t old_filt_len, uint32_t new_filt_len, ui
   return SPEEXHIP_ERR_SUCCESS;
 }
 
-const char *speexhip_version(void) { return "speexhip 0.6.0 gfx950"; }
+const char *speexhip_version(void) { return "speexhip 0.7.0 gfx950"; }
 
 }  // extern "C"

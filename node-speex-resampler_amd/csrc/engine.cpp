@@ -1600,6 +1600,7 @@ int warm_device(int device) {
   warm_unit_slide64_f32(s);
   warm_unit_planar(s);
   warm_unit_convert(s);
+  warm_unit_mix(s);
   HIP_TRY(hipStreamSynchronize(s));
   return SPEEXHIP_ERR_SUCCESS;
 }

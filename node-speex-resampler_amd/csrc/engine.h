@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -91,6 +92,18 @@ class Batch {
                          std::vector<CallPlan> *plans_out = nullptr);
   // ... on host buffers of a single-stream batch; synchronous.  The raw bytes move by the rule of host_transfer.h.
   int process_fmt_host(int in_fmt, const void *in, uint32_t *in_len, int out_fmt, void *out, uint32_t *out_len);
+  // Mixed calls (mix.cpp): a formatted call whose sides may carry a channel matrix in host memory -- in_mix, row-major
+  // channels() x in_channels, applied to every input frame before the float call; out_mix, row-major out_channels x
+  // channels(), applied to every frame it produced.  NULL = no mix on that side (its channel count is then channels()).
+  // A side with a matrix runs mix_in / mix_out (kernels_mix.hip) in place of convert_in / convert_out; the float call
+  // between them is process_device(float) on the scratch images of channels() channels.  Both NULL: process_fmt_device.
+  // Strides are in samples of the side's format, a frame of a side holding that side's channel count.
+  int process_mix_device(int in_fmt, uint32_t in_channels, const float *in_mix, const void *d_in, uint64_t in_stride,
+                         uint32_t *in_len, int out_fmt, uint32_t out_channels, const float *out_mix, void *d_out,
+                         uint64_t out_stride, uint32_t *out_len, hipStream_t stream);
+  // ... on host buffers of a single-stream batch; synchronous, routed like process_fmt_host.
+  int process_mix_host(int in_fmt, uint32_t in_channels, const float *in_mix, const void *in, uint32_t *in_len, int out_fmt,
+                       uint32_t out_channels, const float *out_mix, void *out, uint32_t *out_len);
   // Host-buffer call for a single-stream batch; synchronous (H2D, kernels, D2H).
   int process_host(const void *in, uint32_t *in_len, void *out, uint32_t *out_len, bool float_io);
   // The same call with the result left in a pinned block of the pool that the caller then OWNS (release_block):
@@ -179,6 +192,13 @@ class Batch {
   int process_split(const void *d_in, uint32_t *in_len, void *d_out, uint32_t *out_len, bool float_io,
                     hipStream_t stream, std::vector<CallPlan> *plans_out, const SplitLayout *layout = nullptr);
   int ensure_planar_scratch(size_t in_bytes, size_t out_bytes);
+  // formats.cpp, shared by the formatted and the mixed calls: the converting pass of a side without a matrix over every
+  // stream (stream s: lens[s] frames of channels() samples at src + s * src_step, dst + s * dst_step bytes; to_image:
+  // convert_in, otherwise convert_out), and the routing of a single-stream call's host buffers around a device call.
+  int convert_streams(bool to_image, int fmt, const void *src, size_t src_step, void *dst, size_t dst_step, const uint32_t *lens,
+                      hipStream_t stream);
+  int routed_host_call(const void *in, size_t in_bytes, void *out, size_t out_bytes, size_t out_frame_bytes,
+                       const uint32_t *out_len, const std::function<int(const void *, void *)> &device_call);
   int fetch_history(std::vector<float> *host);
   int quiesce();  // waits for this batch's own enqueued work (never for the whole device)
   uint32_t block_in() const { return line_ - (filter_.taps - 1); }

@@ -5,6 +5,7 @@
 // planar and per-channel calls mix freely on one state.
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <vector>
 
 #include "engine.h"
@@ -32,6 +33,31 @@ inline bool same_bytes_pair(int in_fmt, int out_fmt) {
   return in_fmt == out_fmt && (in_fmt == SPEEXHIP_FMT_S16 || in_fmt == SPEEXHIP_FMT_F32 || in_fmt == SPEEXHIP_FMT_F32N);
 }
 }  // namespace
+
+// The converting pass of a side without a matrix over every stream of the batch, <= 32 streams per launch: stream s is
+// lens[s] frames of channels() samples at src + s * src_step and dst + s * dst_step (bytes).  to_image: convert_in (storage
+// -> float image), otherwise convert_out.  Shared with the mixed calls (mix.cpp).
+int Batch::convert_streams(bool to_image, int fmt, const void *src, size_t src_step, void *dst, size_t dst_step,
+                           const uint32_t *lens, hipStream_t stream) {
+  const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
+  for (uint32_t s0 = 0; s0 < n_streams_; s0 += kChunk) {
+    const uint32_t n = std::min(kChunk, n_streams_ - s0);
+    ConvertPack pack;
+    std::memset(&pack, 0, sizeof(pack));
+    uint64_t most = 0;
+    for (uint32_t j = 0; j < n; j++) {
+      const uint32_t s = s0 + j;
+      pack.s[j].src = static_cast<const char *>(src) + s * src_step;
+      pack.s[j].dst = static_cast<char *>(dst) + s * dst_step;
+      pack.s[j].n = static_cast<uint64_t>(lens[s]) * channels_;
+      pack.s[j].step = 1;
+      most = std::max(most, pack.s[j].n);
+    }
+    const hipError_t e = to_image ? launch_convert_in(fmt, pack, n, most, stream) : launch_convert_out(fmt, pack, n, most, stream);
+    if (hip_failed(e, "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+  }
+  return SPEEXHIP_ERR_SUCCESS;
+}
 
 int Batch::process_fmt_device(int in_fmt, const void *d_in, uint64_t in_stride, uint32_t *in_len, int out_fmt, void *d_out,
                               uint64_t out_stride, uint32_t *out_len, hipStream_t stream, std::vector<CallPlan> *plans_out) {
@@ -72,20 +98,9 @@ int Batch::process_fmt_device(int in_fmt, const void *d_in, uint64_t in_stride, 
     rc = chain_to(stream);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
-  for (uint32_t s0 = 0; conv_in && s0 < n_streams_; s0 += kChunk) {
-    const uint32_t n = std::min(kChunk, n_streams_ - s0);
-    ConvertPack pack;
-    std::memset(&pack, 0, sizeof(pack));
-    uint64_t most = 0;
-    for (uint32_t j = 0; j < n; j++) {
-      const uint32_t s = s0 + j;
-      pack.s[j].src = static_cast<const char *>(d_in) + s * in_stride * bin;
-      pack.s[j].dst = d_planar_in_ + s * in_pitch * sizeof(float);
-      pack.s[j].n = static_cast<uint64_t>(in_len[s]) * channels_;
-      pack.s[j].step = 1;
-      most = std::max(most, pack.s[j].n);
-    }
-    if (hip_failed(launch_convert_in(in_fmt, pack, n, most, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+  if (conv_in) {
+    rc = convert_streams(true, in_fmt, d_in, in_stride * bin, d_planar_in_, in_pitch * sizeof(float), in_len, stream);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
   // (a present but empty input is not silence: no frame is read, any non-null address serves)
   const void *image_in = conv_in ? static_cast<const void *>(d_planar_in_) : d_in;
@@ -117,21 +132,49 @@ int Batch::process_fmt_device(int in_fmt, const void *d_in, uint64_t in_stride, 
       if (hip_failed(launch_convert_out(out_fmt, pack, n, most, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
     }
   }
-  for (uint32_t s0 = 0; conv_out && !split && s0 < n_streams_; s0 += kChunk) {
-    const uint32_t n = std::min(kChunk, n_streams_ - s0);
-    ConvertPack pack;
-    std::memset(&pack, 0, sizeof(pack));
-    uint64_t most = 0;
-    for (uint32_t j = 0; j < n; j++) {
-      const uint32_t s = s0 + j;
-      pack.s[j].src = d_planar_out_ + s * out_pitch * sizeof(float);
-      pack.s[j].dst = static_cast<char *>(d_out) + s * out_stride * bout;
-      pack.s[j].n = static_cast<uint64_t>(out_len[s]) * channels_;  // (out_len: what the float call produced)
-      pack.s[j].step = 1;
-      most = std::max(most, pack.s[j].n);
-    }
-    if (hip_failed(launch_convert_out(out_fmt, pack, n, most, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+  if (conv_out && !split) {
+    // (out_len: what the float call produced)
+    const int crc = convert_streams(false, out_fmt, d_planar_out_, out_pitch * sizeof(float), d_out, out_stride * bout, out_len,
+                                    stream);
+    if (crc != SPEEXHIP_ERR_SUCCESS) return crc;
   }
+  return rc;
+}
+
+// A single-stream call on host buffers around a device call: the raw bytes of both sides move by the rule of
+// host_transfer.h -- in place when pinned, through the bounce buffers when small, by the runtime's staged copy when large.
+// device_call(src, dst) enqueues the work on own_stream_ and sets *out_len to the frames produced, out_frame_bytes each.
+// Shared by the formatted and the mixed host calls.
+int Batch::routed_host_call(const void *in, size_t in_bytes, void *out, size_t out_bytes, size_t out_frame_bytes,
+                            const uint32_t *out_len, const std::function<int(const void *, void *)> &device_call) {
+  int rc = SPEEXHIP_ERR_SUCCESS;
+  DrainOnExit drain(&own_stream_);
+  const void *pin_in = in != nullptr ? pinned_view_of(in, in_bytes) : nullptr;
+  void *pin_out = pinned_view_of(out, out_bytes);
+  if (pin_in != nullptr && pin_out != nullptr && buffers_overlap(in, in_bytes, out, out_bytes)) pin_in = nullptr;
+  const bool small = small_call(in != nullptr && pin_in == nullptr ? in_bytes : 0, pin_out == nullptr ? out_bytes : 0);
+  const Via in_via = route_side(in_bytes, in != nullptr, pin_in != nullptr, small);
+  const Via out_via = route_side(out_bytes, true, pin_out != nullptr, small);
+  Wait wait;
+  wait.add(in_via, in_bytes);
+  wait.add(out_via, out_bytes);
+  rc = ensure_stage(device_part(in_via, in_bytes), device_part(out_via, out_bytes), pinned_part(in_via, in_bytes),
+                    pinned_part(out_via, out_bytes) + (wait.sync ? 0 : 64));
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  const void *src = nullptr;
+  rc = stage_input(in_via, in, in_bytes, pin_in, &src);
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  if (src == nullptr && in != nullptr) src = h_pin_out_;  // (an empty chunk, not silence)
+  void *dst = out_via == Via::InPlace ? pin_out : out_via == Via::Bounce ? static_cast<void *>(h_pin_out_) : static_cast<void *>(d_stage_out_);
+  rc = device_call(src, dst);
+  if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
+  const size_t made = static_cast<size_t>(*out_len) * out_frame_bytes;
+  if (device_part(out_via, made) != 0)
+    HIP_TRY(hipMemcpyAsync(out_via == Via::Copy ? out : h_pin_out_, d_stage_out_, made, hipMemcpyDeviceToHost, own_stream_));
+  const int wrc = wait_call(own_stream_, wait, tail_word(h_pin_out_, pin_out_cap_), ++done_seq_);
+  if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
+  drain.armed = false;
+  if (pinned_part(out_via, made) != 0) std::memcpy(out, h_pin_out_, made);
   return rc;
 }
 
@@ -150,10 +193,10 @@ int Batch::process_fmt_host(int in_fmt, const void *in, uint32_t *in_len, int ou
     will_make = std::max(will_make, produced_closed_form(filter_.num, filter_.den, frames, *out_len, P(0, c)));
   const size_t in_bytes = static_cast<size_t>(frames) * channels_ * bin;
   const size_t out_bytes = static_cast<size_t>(will_make) * channels_ * bout;
-  int rc = SPEEXHIP_ERR_SUCCESS;
-  DrainOnExit drain(&own_stream_);
-  std::vector<CallPlan> plans;
   if (split) {
+    int rc = SPEEXHIP_ERR_SUCCESS;
+    DrainOnExit drain(&own_stream_);
+    std::vector<CallPlan> plans;
     // channels at different positions write different numbers of frames: fetch the whole block and hand the caller
     // only the samples each channel really wrote (as process_host does)
     const Via in_via = route_side(in_bytes, in != nullptr, false, false);
@@ -177,33 +220,9 @@ int Batch::process_fmt_host(int in_fmt, const void *in, uint32_t *in_len, int ou
                     h_pin_out_ + (static_cast<size_t>(j) * channels_ + c) * bout, bout);
     return rc;
   }
-  const void *pin_in = in != nullptr ? pinned_view_of(in, in_bytes) : nullptr;
-  void *pin_out = pinned_view_of(out, out_bytes);
-  if (pin_in != nullptr && pin_out != nullptr && buffers_overlap(in, in_bytes, out, out_bytes)) pin_in = nullptr;
-  const bool small = small_call(in != nullptr && pin_in == nullptr ? in_bytes : 0, pin_out == nullptr ? out_bytes : 0);
-  const Via in_via = route_side(in_bytes, in != nullptr, pin_in != nullptr, small);
-  const Via out_via = route_side(out_bytes, true, pin_out != nullptr, small);
-  Wait wait;
-  wait.add(in_via, in_bytes);
-  wait.add(out_via, out_bytes);
-  rc = ensure_stage(device_part(in_via, in_bytes), device_part(out_via, out_bytes), pinned_part(in_via, in_bytes),
-                    pinned_part(out_via, out_bytes) + (wait.sync ? 0 : 64));
-  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  const void *src = nullptr;
-  rc = stage_input(in_via, in, in_bytes, pin_in, &src);
-  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  if (src == nullptr && in != nullptr) src = h_pin_out_;  // (an empty chunk, not silence)
-  void *dst = out_via == Via::InPlace ? pin_out : out_via == Via::Bounce ? static_cast<void *>(h_pin_out_) : static_cast<void *>(d_stage_out_);
-  rc = process_fmt_device(in_fmt, src, 0, in_len, out_fmt, dst, 0, out_len, own_stream_);
-  if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
-  const size_t made = static_cast<size_t>(*out_len) * channels_ * bout;
-  if (device_part(out_via, made) != 0)
-    HIP_TRY(hipMemcpyAsync(out_via == Via::Copy ? out : h_pin_out_, d_stage_out_, made, hipMemcpyDeviceToHost, own_stream_));
-  const int wrc = wait_call(own_stream_, wait, tail_word(h_pin_out_, pin_out_cap_), ++done_seq_);
-  if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
-  drain.armed = false;
-  if (pinned_part(out_via, made) != 0) std::memcpy(out, h_pin_out_, made);
-  return rc;
+  return routed_host_call(in, in_bytes, out, out_bytes, channels_ * bout, out_len, [&](const void *src, void *dst) {
+    return process_fmt_device(in_fmt, src, 0, in_len, out_fmt, dst, 0, out_len, own_stream_);
+  });
 }
 
 }  // namespace speexhip

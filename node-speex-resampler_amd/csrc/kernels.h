@@ -49,6 +49,7 @@ void warm_unit_period64_w16(hipStream_t s);
 void warm_unit_period_w16g(hipStream_t s);
 void warm_unit_planar(hipStream_t s);
 void warm_unit_convert(hipStream_t s);
+void warm_unit_mix(hipStream_t s);
 
 // compute units of the calling thread's current device (cached per device id)
 inline uint32_t device_compute_units() {
@@ -203,5 +204,26 @@ struct ConvertPack {        // like DescPack: up to 32 streams, in the kernel-ar
 // the largest ConvertStream::n among them
 hipError_t launch_convert_in(int fmt, const ConvertPack &pack, uint32_t n, uint64_t max_samples, hipStream_t stream);
 hipError_t launch_convert_out(int fmt, const ConvertPack &pack, uint32_t n, uint64_t max_samples, hipStream_t stream);
+
+// ---- channel mix folded into the conversion (kernels_mix.hip): the pass of a mixed call's side that has a matrix ------
+// mix_in: storage of the call's format, src_channels per frame -> the float image, dst_channels per frame;
+// mix_out: the float image -> storage.  One frame of the destination = the matrix times the frame of the source, every
+// output summed in fp64 in ascending index order and rounded once to fp32 (include/speexhip_resampler.h).
+constexpr uint32_t kMixMaxChannels = 8;   // per side of a matrix: its coefficients travel in the kernel-argument segment
+struct MixStream {          // one stream's share of a mixing launch
+  const void *src;          // mix_in: storage, mix_out: the float image; NULL = nothing
+  void *dst;                // mix_in: the float image, mix_out: storage
+  uint32_t frames;          // frames to mix
+  uint32_t reserved;
+};
+struct MixPack {            // like ConvertPack: up to 32 streams and the matrix, in the kernel-argument segment
+  MixStream s[kMaxPackedStreams];
+  float m[kMixMaxChannels * kMixMaxChannels];  // row-major dst_channels x src_channels
+  uint32_t src_channels, dst_channels;
+};
+// streams [0, n) of `pack`; fmt = the storage side's format (any SPEEXHIP_FMT_*, F32 included); max_frames = the largest
+// MixStream::frames among them
+hipError_t launch_mix_in(int fmt, const MixPack &pack, uint32_t n, uint32_t max_frames, hipStream_t stream);
+hipError_t launch_mix_out(int fmt, const MixPack &pack, uint32_t n, uint32_t max_frames, hipStream_t stream);
 
 }  // namespace speexhip

@@ -18,11 +18,12 @@
 // The image convert_in writes is read by the very next kernel and convert_out's source was written by the previous
 // one: plain loads and stores throughout, so that the images can stay in L2 / Infinity Cache.
 //
-// Rounding (include/speexhip_resampler.h): halfup(v) = floor(v + 0.5) on v = y * 2^k, evaluated in fp64 -- the product is
-// exact there, and v + 0.5 is exact wherever its floor depends on it.  NaN becomes the format's zero, +-inf the rails.
+// The formats themselves -- one sample to and from the image, rounding half up, and the loads / stores of one sample --
+// are stated in format_device.h, which the mixing kernels (kernels_mix.hip) share.
 #include <hip/hip_runtime.h>
 
 #include "../../include/speexhip_resampler.h"
+#include "format_device.h"
 #include "kernels.h"
 
 namespace speexhip {
@@ -31,37 +32,13 @@ SPEEXHIP_WARM_UNIT(convert)
 
 namespace {
 
+using namespace fmtdev;  // to_internal / from_internal, load_raw / store_raw, bytes_of
+
 constexpr uint32_t kLanes = 256;
 constexpr uint32_t kTile = 4096;  // samples per workgroup
 
-constexpr uint32_t bytes_of(int f) {
-  return f == SPEEXHIP_FMT_U8 ? 1u : f == SPEEXHIP_FMT_S16 ? 2u : f == SPEEXHIP_FMT_S24 ? 3u : 4u;
-}
 // samples a lane owns per pass of the vector path: whole 16-byte pieces on both sides
 constexpr uint32_t group_of(int f) { return f == SPEEXHIP_FMT_U8 || f == SPEEXHIP_FMT_S24 ? 16u : f == SPEEXHIP_FMT_S16 ? 8u : 4u; }
-
-// ---- one sample --------------------------------------------------------------------------------------------------
-// `raw` = the sample's storage bits in the low bytes of a dword
-template <int F>
-__device__ __forceinline__ float to_internal(uint32_t raw) {
-  if (F == SPEEXHIP_FMT_U8) return (static_cast<float>(raw & 0xffu) - 128.0f) * 256.0f;
-  if (F == SPEEXHIP_FMT_S16) return static_cast<float>(static_cast<int16_t>(raw));
-  if (F == SPEEXHIP_FMT_S24) return static_cast<float>(static_cast<int32_t>(raw << 8) >> 8) * (1.0f / 256.0f);
-  if (F == SPEEXHIP_FMT_S32) return static_cast<float>(static_cast<int32_t>(raw)) * (1.0f / 65536.0f);
-  return __uint_as_float(raw) * 32768.0f;  // F32N
-}
-
-template <int F>
-__device__ __forceinline__ uint32_t from_internal(float y) {
-  if (F == SPEEXHIP_FMT_F32N) return __float_as_uint(y * (1.0f / 32768.0f));
-  constexpr double scale = F == SPEEXHIP_FMT_U8 ? 1.0 / 256.0 : F == SPEEXHIP_FMT_S16 ? 1.0 : F == SPEEXHIP_FMT_S24 ? 256.0 : 65536.0;
-  constexpr double bias = F == SPEEXHIP_FMT_U8 ? 128.0 : 0.0;
-  constexpr double lo = F == SPEEXHIP_FMT_U8 ? 0.0 : F == SPEEXHIP_FMT_S16 ? -32768.0 : F == SPEEXHIP_FMT_S24 ? -8388608.0 : -2147483648.0;
-  constexpr double hi = F == SPEEXHIP_FMT_U8 ? 255.0 : F == SPEEXHIP_FMT_S16 ? 32767.0 : F == SPEEXHIP_FMT_S24 ? 8388607.0 : 2147483647.0;
-  if (y != y) return static_cast<uint32_t>(static_cast<int32_t>(bias));
-  const double r = floor(static_cast<double>(y) * scale + 0.5) + bias;
-  return static_cast<uint32_t>(static_cast<int32_t>(fmin(fmax(r, lo), hi)));
-}
 
 // ---- 16 bytes per lane ---------------------------------------------------------------------------------------------
 // sample j (compile-time) of a lane's group, from / into the group's storage words
@@ -122,30 +99,6 @@ __device__ __forceinline__ void vector_tile(const ConvertStream &s, uint64_t til
 }
 
 // ---- sample by sample ----------------------------------------------------------------------------------------------
-template <int F>
-__device__ __forceinline__ uint32_t load_raw(const char *p) {
-  if (F == SPEEXHIP_FMT_U8) return *reinterpret_cast<const uint8_t *>(p);
-  if (F == SPEEXHIP_FMT_S16) return *reinterpret_cast<const uint16_t *>(p);
-  if (F == SPEEXHIP_FMT_S24) {
-    const uint8_t *b = reinterpret_cast<const uint8_t *>(p);
-    return b[0] | (static_cast<uint32_t>(b[1]) << 8) | (static_cast<uint32_t>(b[2]) << 16);
-  }
-  return *reinterpret_cast<const uint32_t *>(p);
-}
-template <int F>
-__device__ __forceinline__ void store_raw(char *p, uint32_t raw) {
-  if (F == SPEEXHIP_FMT_U8) {
-    *reinterpret_cast<uint8_t *>(p) = static_cast<uint8_t>(raw);
-  } else if (F == SPEEXHIP_FMT_S16) {
-    *reinterpret_cast<uint16_t *>(p) = static_cast<uint16_t>(raw);
-  } else if (F == SPEEXHIP_FMT_S24) {
-    uint8_t *b = reinterpret_cast<uint8_t *>(p);
-    b[0] = static_cast<uint8_t>(raw), b[1] = static_cast<uint8_t>(raw >> 8), b[2] = static_cast<uint8_t>(raw >> 16);
-  } else {
-    *reinterpret_cast<uint32_t *>(p) = raw;
-  }
-}
-
 // samples [tile0, tile0 + n) of the stream; sample k lies k * step elements into both buffers
 template <int F, bool kOut>
 __device__ __forceinline__ void element_tile(const ConvertStream &s, uint64_t tile0, uint32_t n) {

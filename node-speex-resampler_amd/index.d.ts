@@ -125,6 +125,17 @@ declare class SpeexResampler {
      */
     processChunkFormat(chunk: Buffer, inFormat: SampleFormat, outFormat: SampleFormat): Buffer;
 
+    /**
+     * processChunkFormat with a channel mix on either side, done on the GPU in the passes that convert the samples.  The
+     * instance's `channels` is the count the resampler runs on.  inMix: `channels` rows, one column per channel of the
+     * chunk, applied to every input frame before the filter; outMix: one row per channel of the result, `channels`
+     * columns, applied to every frame the filter made; null = no mix on that side.  Up to 8 x 8.  Stereo to mono:
+     * [[0.5, 0.5]] as inMix of a mono instance; mono to stereo: [[1], [1]] as outMix.  Each output is summed in double
+     * precision in ascending order and rounded once to float32.
+     */
+    processChunkMix(chunk: Buffer, inFormat: SampleFormat, outFormat: SampleFormat, inMix: number[][] | null,
+      outMix: number[][] | null): Buffer;
+
     /** mid-stream control (speex_resampler_set_rate / set_quality / skip_zeros / reset_mem) */
     setRate(inRate: number, outRate: number): void;
     setQuality(quality: number): void;

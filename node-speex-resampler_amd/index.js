@@ -262,6 +262,50 @@ class SpeexResampler {
     return speexModule.processFormat(this._resamplerPtr, chunk, fin.id, fout.id, frames, cap);
   }
 
+  /**
+   * processChunkFormat with a channel mix on either side, done on the GPU in the same two passes that convert the samples.
+   * This instance's `channels` is the count the resampler runs on; inMix (rows = channels, columns = the chunk's channel
+   * count) turns every input frame into a frame of the resampler, outMix (rows = the result's channel count, columns =
+   * channels) every frame it made into an output frame; null = no mix on that side.  48 kHz stereo s16le to 16 kHz mono
+   * float for a speech model: new SpeexResampler(1, 48000, 16000).processChunkMix(chunk, 's16le', 'f32le-normalized',
+   * [[0.5, 0.5]], null) -- the filter runs on one channel, not two.  Up to 8 channels on either side of a matrix.
+   */
+  processChunkMix(chunk, inFormat, outFormat, inMix, outMix) {
+    if (!speexModule) {
+      throw new Error('You need to wait for SpeexResampler.initPromise before calling this method');
+    }
+    this._refuseWhileAsyncPending('processChunkMix');
+    const fin = SAMPLE_FORMATS[inFormat];
+    const fout = SAMPLE_FORMATS[outFormat];
+    if (!fin || !fout) {
+      throw new Error('Unknown sample format: ' + (fin ? outFormat : inFormat));
+    }
+    if (inMix == null && outMix == null) return this.processChunkFormat(chunk, inFormat, outFormat);
+    // rows x columns, rectangular, 1..8 either way
+    const flat = (m, rows, cols, name) => {
+      if (m == null) return null;
+      const ok = Array.isArray(m) && m.length >= 1 && m.length <= 8 && (rows === undefined || m.length === rows) &&
+        m.every((r) => Array.isArray(r) && r.length >= 1 && r.length <= 8 && r.length === m[0].length &&
+          (cols === undefined || r.length === cols) && r.every((v) => typeof v === 'number'));
+      if (!ok || this.channels > 8) {
+        throw new Error(name + ' should be ' + (rows === undefined ? 'rows of ' + cols : rows + ' rows of') +
+          ' numbers, at most 8 x 8');
+      }
+      return Float32Array.from(m.flat());
+    };
+    const mi = flat(inMix, this.channels, undefined, 'inMix');
+    const mo = flat(outMix, undefined, this.channels, 'outMix');
+    const inChannels = mi ? inMix[0].length : this.channels;
+    const outChannels = mo ? outMix.length : this.channels;
+    if (chunk.length % (inChannels * fin.bytes) !== 0) {
+      throw new Error('Chunk length should be a multiple of channels * ' + fin.bytes + ' bytes');
+    }
+    // the capacity rule of processChunkFloat on these frames of the resampler's channel count
+    const frames = (chunk.length / inChannels / fin.bytes) | 0;
+    const [, cap] = this._prepare({ length: frames * this.channels * Float32Array.BYTES_PER_ELEMENT }, Float32Array.BYTES_PER_ELEMENT);
+    return speexModule.processMix(this._resamplerPtr, chunk, fin.id, fout.id, frames, cap, inChannels, mi, outChannels, mo);
+  }
+
   /** Mid-stream control (SURVEY 8f row N3; speex_resampler_set_rate / set_quality / ...). */
   setRate(inRate, outRate) {
     this._refuseWhileAsyncPending('setRate');

@@ -405,6 +405,90 @@ static napi_value ProcessFormat(napi_env env, napi_callback_info info) {
   return out;
 }
 
+/* a mixed call's matrix: null -> (NULL, 0 values), a Float32Array -> its data */
+static bool mix_matrix(napi_env env, napi_value v, const float **m, size_t *n) {
+  napi_valuetype t;
+  *m = NULL;
+  *n = 0;
+  if (napi_typeof(env, v, &t) != napi_ok) return false;
+  if (t == napi_null || t == napi_undefined) return true;
+  bool is_ta = false;
+  if (napi_is_typedarray(env, v, &is_ta) != napi_ok || !is_ta) return false;
+  napi_typedarray_type kind;
+  void *data = NULL;
+  if (napi_get_typedarray_info(env, v, &kind, n, &data, NULL, NULL) != napi_ok || kind != napi_float32_array) return false;
+  *m = (const float *)data;
+  return true;
+}
+
+/* processMix(handle, chunk: Buffer|null, inFormat, outFormat, inFrames, outCapacityFrames, inChannels,
+ * inMix: Float32Array|null, outChannels, outMix: Float32Array|null) -> Buffer of the frames written, out_channels samples of
+ * outFormat each: speexhip_resampler_process_interleaved_mix on the Buffer's own memory, the result written straight into a
+ * fresh Buffer of exactly the frames the call makes.  The matrices are row-major (index.js flattens them). */
+static napi_value ProcessMix(napi_env env, napi_callback_info info) {
+  size_t argc = 10;
+  napi_value argv[10];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  void *in_data = NULL;
+  size_t in_bytes = 0;
+  if (!buffer_or_null(env, argv[1], &in_data, &in_bytes)) {
+    napi_throw_type_error(env, NULL, "chunk must be a Buffer or null");
+    return NULL;
+  }
+  int32_t in_fmt = -1, out_fmt = -1;
+  uint32_t in_len = 0, out_len = 0, in_channels = 0, out_channels = 0;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &in_fmt));
+  NAPI_OK(napi_get_value_int32(env, argv[3], &out_fmt));
+  NAPI_OK(napi_get_value_uint32(env, argv[4], &in_len));
+  NAPI_OK(napi_get_value_uint32(env, argv[5], &out_len));
+  NAPI_OK(napi_get_value_uint32(env, argv[6], &in_channels));
+  NAPI_OK(napi_get_value_uint32(env, argv[8], &out_channels));
+  const float *in_mix = NULL, *out_mix = NULL;
+  size_t in_mix_n = 0, out_mix_n = 0;
+  if (!mix_matrix(env, argv[7], &in_mix, &in_mix_n) || !mix_matrix(env, argv[9], &out_mix, &out_mix_n)) {
+    napi_throw_type_error(env, NULL, "a mix must be a Float32Array or null");
+    return NULL;
+  }
+  const size_t bin = speexhip_sample_bytes(in_fmt), bout = speexhip_sample_bytes(out_fmt);
+  if (bin == 0 || bout == 0) {
+    napi_throw_range_error(env, NULL, "unknown sample format");
+    return NULL;
+  }
+  Handle *h = NULL;
+  SpeexHipResamplerState *st = lock_state(env, argv[0], &h);
+  if (st == NULL) return NULL;
+  SpeexHipInfo si;
+  speexhip_resampler_get_info(st, &si);
+  if ((in_mix != NULL && in_mix_n != (size_t)si.nb_channels * in_channels) ||
+      (out_mix != NULL && out_mix_n != (size_t)si.nb_channels * out_channels)) {
+    UNLOCK(h);
+    napi_throw_range_error(env, NULL, "mix size does not match the channel counts");
+    return NULL;
+  }
+  if (in_data != NULL && (size_t)in_len * in_channels * bin > in_bytes) {
+    UNLOCK(h);
+    napi_throw_range_error(env, NULL, "input frame count exceeds the chunk");
+    return NULL;
+  }
+  /* (without a matrix s16 -> s16 is the int16 call, with its counters; everything else has the float call's) */
+  const int float_entry = in_mix != NULL || out_mix != NULL || !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
+  uint32_t will_use = 0, will_make = 0;
+  speexhip_resampler_peek(st, in_len, out_len, float_entry, &will_use, &will_make);
+  napi_value out;
+  void *dst = NULL;
+  NAPI_OK_LOCKED(h, napi_create_buffer(env, (size_t)will_make * out_channels * bout, &dst, &out));
+  uint64_t nowhere = 0;
+  if (dst == NULL) dst = &nowhere; /* empty Buffer: nothing will be written, but NULL means "no buffer" */
+  const int rc = speexhip_resampler_process_interleaved_mix(st, in_fmt, in_channels, in_mix, in_data, &in_len, out_fmt,
+                                                            out_channels, out_mix, dst, &out_len);
+  UNLOCK(h);
+  if (rc != 0 || out_len != will_make) {
+    napi_throw_error(env, NULL, speexhip_resampler_strerror(rc != 0 ? rc : SPEEXHIP_ERR_BAD_STATE));
+    return NULL;
+  }
+  return out;
+}
+
 /* processChunks(handle, chunks: Buffer[], inFrames: number[], outCapacities: number[]) -> Buffer[]
  * n consecutive process() calls as one transfer + one launch
  * (speexhip_resampler_process_chunks_int); the i-th Buffer is what the i-th call returns. */
@@ -1262,6 +1346,7 @@ NAPI_MODULE_INIT() {
       {"processFloat", NULL, ProcessFloat, NULL, NULL, NULL, napi_default, NULL},
       {"processPlanar", NULL, ProcessPlanar, NULL, NULL, NULL, napi_default, NULL},
       {"processFormat", NULL, ProcessFormat, NULL, NULL, NULL, napi_default, NULL},
+      {"processMix", NULL, ProcessMix, NULL, NULL, NULL, napi_default, NULL},
       {"processChunks", NULL, ProcessChunks, NULL, NULL, NULL, napi_default, NULL},
       {"processAsync", NULL, ProcessAsync, NULL, NULL, NULL, napi_default, NULL},
       {"processChunksAsync", NULL, ProcessChunksAsync, NULL, NULL, NULL, napi_default, NULL},

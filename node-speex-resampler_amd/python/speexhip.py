@@ -68,7 +68,26 @@ EXPORTS = [
     # sample formats: u8, packed s24, s32, float in +-1.0; input and output named independently
     "speexhip_sample_bytes", "speexhip_resampler_process_interleaved_fmt",
     "speexhip_resampler_process_interleaved_fmt_device", "speexhip_batch_process_interleaved_fmt_device",
+    # channel mixing in the formatted calls: a matrix before the FIR and / or after it
+    "speexhip_resampler_process_interleaved_mix", "speexhip_resampler_process_interleaved_mix_device",
+    "speexhip_batch_process_interleaved_mix_device",
 ]
+
+
+def _mix_matrix(m, channels, is_input):
+    """a mixed call's matrix as (row-major float32 array or None, the caller-side channel count): in_mix is
+    channels x in_channels, out_mix is out_channels x channels"""
+    if m is None:
+        return None, channels
+    a = np.ascontiguousarray(m, dtype=np.float32)
+    if a.ndim != 2 or a.shape[0 if is_input else 1] != channels:
+        raise ValueError("%s must be %s for a state of %d channels" % (
+            ("in_mix", "(channels x in_channels)") if is_input else ("out_mix", "(out_channels x channels)"), channels))
+    return a, a.shape[1 if is_input else 0]
+
+
+def _mix_ptr(a):
+    return None if a is None else C.c_void_p(a.ctypes.data)
 
 
 class Info(C.Structure):
@@ -254,6 +273,15 @@ def lib():
             L.speexhip_resampler_process_interleaved_fmt_device.argtypes = [p, i32, p, pu32, i32, p, pu32, p]
             L.speexhip_batch_process_interleaved_fmt_device.restype = i32
             L.speexhip_batch_process_interleaved_fmt_device.argtypes = [p, i32, p, u64, pu32, i32, p, u64, pu32, p]
+        if hasattr(L, "speexhip_resampler_process_interleaved_mix") or "SPEEXHIP_LIB_PATH" not in os.environ:
+            u64 = C.c_uint64
+            L.speexhip_resampler_process_interleaved_mix.restype = i32
+            L.speexhip_resampler_process_interleaved_mix.argtypes = [p, i32, u32, p, p, pu32, i32, u32, p, p, pu32]
+            L.speexhip_resampler_process_interleaved_mix_device.restype = i32
+            L.speexhip_resampler_process_interleaved_mix_device.argtypes = [p, i32, u32, p, p, pu32, i32, u32, p, p, pu32, p]
+            L.speexhip_batch_process_interleaved_mix_device.restype = i32
+            L.speexhip_batch_process_interleaved_mix_device.argtypes = [p, i32, u32, p, p, u64, pu32, i32, u32, p, p, u64,
+                                                                        pu32, p]
         _lib = L
     return _lib
 
@@ -761,6 +789,52 @@ class Resampler:
             raise RuntimeError(strerror(rc))
         return il.value, ol.value
 
+    def mix_call(self, x, in_fmt, out_fmt, in_mix, out_mix, cap, null_frames=0):
+        """The host mixed C call itself.  in_mix: None or (channels x in_channels), out_mix: None or (out_channels x
+        channels), applied to every frame before / after the float call.  x: array of in_fmt's storage type holding
+        whole frames of in_channels samples, or None = silence of null_frames frames.  Returns (rc, consumed, produced,
+        out): `out` is the whole buffer of `cap` frames of out_channels samples in the output format's storage type,
+        flat, every byte pre-filled with SENTINEL_BYTE."""
+        mi, n_in = _mix_matrix(in_mix, self.channels, True)
+        mo, n_out = _mix_matrix(out_mix, self.channels, False)
+        if x is None:
+            ptr, n = None, int(null_frames)
+        else:
+            x = np.ascontiguousarray(x, dtype=FMT_DTYPE[in_fmt]).reshape(-1)
+            n = x.nbytes // (FMT_BYTES[in_fmt] * n_in)
+            assert n * FMT_BYTES[in_fmt] * n_in == x.nbytes, "whole frames only"
+            ptr = C.c_void_p(x.ctypes.data)
+        raw = np.full(max(int(cap), 1) * n_out * FMT_BYTES[out_fmt], self.SENTINEL_BYTE, np.uint8)
+        il, ol = C.c_uint32(n), C.c_uint32(int(cap))
+        rc = lib().speexhip_resampler_process_interleaved_mix(
+            self._h, in_fmt, n_in, _mix_ptr(mi), ptr, C.byref(il), out_fmt, n_out, _mix_ptr(mo),
+            C.c_void_p(raw.ctypes.data), C.byref(ol))
+        return rc, il.value, ol.value, raw.view(FMT_DTYPE[out_fmt])
+
+    def process_mix(self, x, in_fmt, out_fmt, capacity, in_mix=None, out_mix=None, null_frames=0):
+        """Mixed call on host buffers: the formatted call with a channel matrix on either side -- in_mix (channels x
+        in_channels) turns every input frame into a frame of the state before the FIR, out_mix (out_channels x channels)
+        every frame it produced into an output frame; both on the device, folded into the conversions.  Returns (flat
+        array of produced * out_channels samples in the output format's storage type, consumed)."""
+        rc, used, made, out = self.mix_call(x, in_fmt, out_fmt, in_mix, out_mix, capacity, null_frames)
+        if rc:
+            raise RuntimeError(strerror(rc))
+        n_out = self.channels if out_mix is None else len(out_mix)
+        return out[: made * n_out * (3 if out_fmt == FMT_S24 else 1)].copy(), used
+
+    def process_mix_device(self, in_fmt, d_in_ptr, in_frames, out_fmt, d_out_ptr, out_capacity, in_mix=None, out_mix=None,
+                           stream_ptr=0):
+        """device buffers of the named formats and channel counts; (consumed, produced)"""
+        mi, n_in = _mix_matrix(in_mix, self.channels, True)
+        mo, n_out = _mix_matrix(out_mix, self.channels, False)
+        il, ol = C.c_uint32(in_frames), C.c_uint32(out_capacity)
+        rc = lib().speexhip_resampler_process_interleaved_mix_device(
+            self._h, in_fmt, n_in, _mix_ptr(mi), C.c_void_p(d_in_ptr), C.byref(il), out_fmt, n_out, _mix_ptr(mo),
+            C.c_void_p(d_out_ptr), C.byref(ol), C.c_void_p(stream_ptr))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return il.value, ol.value
+
     def peek(self, in_frames, out_capacity, float_entry=False):
         """(consumed, produced) of the next call, state untouched"""
         c, p_ = C.c_uint32(), C.c_uint32()
@@ -900,9 +974,27 @@ class Batch:
             raise RuntimeError(strerror(rc))
         return list(il), list(ol)
 
-    def _process_tensor_fmt(self, x, out_capacity, in_frames, out_dtype, normalized):
+    def process_mix_device(self, in_fmt, d_in_ptr, in_stride, in_frames, out_fmt, d_out_ptr, out_stride, out_capacity,
+                           in_mix=None, out_mix=None, stream_ptr=0):
+        """Mixed call of every stream: the formatted call with in_mix (channels x in_channels) before the FIR and / or
+        out_mix (out_channels x channels) after it; one pair of matrices for all streams.  Strides in samples of the
+        respective format, a frame of a side holding that side's channel count."""
+        n = self.n_streams
+        mi, n_in = _mix_matrix(in_mix, self.channels, True)
+        mo, n_out = _mix_matrix(out_mix, self.channels, False)
+        il = (C.c_uint32 * n)(*([in_frames] * n if np.isscalar(in_frames) else in_frames))
+        ol = (C.c_uint32 * n)(*([out_capacity] * n if np.isscalar(out_capacity) else out_capacity))
+        rc = lib().speexhip_batch_process_interleaved_mix_device(
+            self._h, in_fmt, n_in, _mix_ptr(mi), C.c_void_p(d_in_ptr), in_stride, il, out_fmt, n_out, _mix_ptr(mo),
+            C.c_void_p(d_out_ptr), out_stride, ol, C.c_void_p(stream_ptr))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return list(il), list(ol)
+
+    def _process_tensor_fmt(self, x, out_capacity, in_frames, out_dtype, normalized, in_mix=None, out_mix=None):
         """process_tensor beyond int16 -> int16 and float32 -> float32: interleaved frames (..., T, C) through the
-        formatted call.  uint8 = U8, int16 = S16, int32 = S32, float32 = F32 (normalized: +-1.0 full scale)."""
+        formatted call (the mixed call when a matrix is given: x then holds in_channels per frame and the result
+        out_channels).  uint8 = U8, int16 = S16, int32 = S32, float32 = F32 (normalized: +-1.0 full scale)."""
         import torch
         fmt_of = {torch.uint8: FMT_U8, torch.int16: FMT_S16, torch.int32: FMT_S32,
                   torch.float32: FMT_F32N if normalized else FMT_F32}
@@ -911,22 +1003,30 @@ class Batch:
             raise ValueError("process_tensor converts between uint8, int16, int32 and float32 tensors")
         xb = x if x.dim() == 3 else x.unsqueeze(0)
         B, T, Cn = xb.shape
-        if B != self.n_streams or Cn != self.channels:
-            raise ValueError("tensor of %d streams x %d channels for a batch of %d x %d" % (B, Cn, self.n_streams, self.channels))
+        n_in = self.channels if in_mix is None else _mix_matrix(in_mix, self.channels, True)[1]
+        n_out = self.channels if out_mix is None else _mix_matrix(out_mix, self.channels, False)[1]
+        if B != self.n_streams or Cn != n_in:
+            raise ValueError("tensor of %d streams x %d channels for a batch of %d x %d" % (B, Cn, self.n_streams, n_in))
         if not xb[0].is_contiguous():
             raise ValueError("the frames of a stream must be dense (T, C)")
         i = self.info()
         if out_capacity is None:
             out_capacity = (T * i["den_rate"] + i["num_rate"] - 1) // i["num_rate"] + 1
-        out = torch.empty((B, max(int(out_capacity), 1), Cn), dtype=out_dtype, device=x.device)
-        _, made = self.process_fmt_device(
-            fmt_of[x.dtype], xb.data_ptr(), xb.stride(0) if B > 1 else 0, T if in_frames is None else in_frames,
-            fmt_of[out_dtype], out.data_ptr(), out.stride(0), int(out_capacity),
-            torch.cuda.current_stream(x.device).cuda_stream)
+        out = torch.empty((B, max(int(out_capacity), 1), n_out), dtype=out_dtype, device=x.device)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        if in_mix is None and out_mix is None:
+            _, made = self.process_fmt_device(
+                fmt_of[x.dtype], xb.data_ptr(), xb.stride(0) if B > 1 else 0, T if in_frames is None else in_frames,
+                fmt_of[out_dtype], out.data_ptr(), out.stride(0), int(out_capacity), stream)
+        else:
+            _, made = self.process_mix_device(
+                fmt_of[x.dtype], xb.data_ptr(), xb.stride(0) if B > 1 else 0, T if in_frames is None else in_frames,
+                fmt_of[out_dtype], out.data_ptr(), out.stride(0), int(out_capacity), in_mix, out_mix, stream)
         out = out[:, : max(made)]
         return (out if x.dim() == 3 else out[0]), made
 
-    def process_tensor(self, x, out_capacity=None, in_frames=None, out_dtype=None, normalized=False):
+    def process_tensor(self, x, out_capacity=None, in_frames=None, out_dtype=None, normalized=False, in_mix=None,
+                       out_mix=None):
         """x: a CUDA tensor (B, C, T) or (C, T), int16 or float32, whose last dimension is dense (any other strides).
         Runs on torch's current stream.  in_frames: frames per stream (default T for all); out_capacity: frames the
         result may hold per stream (default: what T frames can produce).  Returns (tensor of the same rank with
@@ -934,8 +1034,15 @@ class Batch:
 
         Other sample types -- a uint8 (offset binary) or int32 tensor, out_dtype= another type than x's, or
         normalized=True (float32 in +-1.0 instead of int16 units) -- take the formatted call, which works on
-        interleaved frames: x is then (B, T, C) or (T, C), dense, and so is the result."""
+        interleaved frames: x is then (B, T, C) or (T, C), dense, and so is the result.
+
+        in_mix (channels x in_channels) / out_mix (out_channels x channels): the mixed call, also on interleaved
+        frames -- x is (B, T, in_channels) and the result (B, T', out_channels), of any of the sample types above."""
         import torch
+        if in_mix is not None or out_mix is not None:
+            if not x.is_cuda or x.dim() not in (2, 3):
+                raise ValueError("process_tensor wants a CUDA tensor (B, T, C) or (T, C) for a mixed call")
+            return self._process_tensor_fmt(x, out_capacity, in_frames, out_dtype, normalized, in_mix, out_mix)
         if x.is_cuda and x.dim() in (2, 3) and (
                 x.dtype in (torch.uint8, torch.int32) or normalized or (out_dtype is not None and out_dtype != x.dtype)):
             return self._process_tensor_fmt(x, out_capacity, in_frames, out_dtype, normalized)
