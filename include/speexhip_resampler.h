@@ -530,6 +530,63 @@ SPEEXHIP_API int speexhip_batch_process_interleaved_mix_device(SpeexHipBatch *b,
                                                                uint64_t out_stream_stride, uint32_t *out_len,
                                                                void *hip_stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Dither: the integer output formats (U8, S16, S24, S32) of the formatted and mixed calls are
+ * quantised with a bare half-up rounding unless the state has dither on.  Requantising without
+ * dither makes an error that follows the signal (harmonic distortion); with dither it is noise.  The
+ * generator is counter based: the noise of an output sample is a pure function of (seed, idx), idx
+ * being the sample's index in its stream, so the bytes of a stream still do not depend on how it is
+ * cut into calls, on what shares its launch, or on the GPU.  Off by default; with the kind NONE
+ * every call is exactly what it is without this section, shortcuts and kernels included.
+ *
+ *   mix32(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16      (uint32, wrapping)
+ *   idx  = (position + f) * C_out + c      uint64, wrapping; f = output frame of this call, c = channel within the
+ *                                          OUTPUT frame, C_out = samples per output frame (out_channels of a mixed
+ *                                          call, else the state's channel count)
+ *   w    = mix32( lo32(idx) ^ mix32( hi32(idx) ^ hi32(seed) ) ^ lo32(seed) )
+ *   a    = w & 0xffff,  b = w >> 16
+ *   d    = 0                                   SPEEXHIP_DITHER_NONE
+ *   d    = (a + 0.5) / 65536 - 0.5             SPEEXHIP_DITHER_RECTANGULAR   uniform in (-0.5, 0.5) LSB
+ *   d    = (a - b) / 65536                     SPEEXHIP_DITHER_TRIANGULAR    triangular in (-1, 1) LSB, variance 1/6
+ *
+ * d is in units of one LSB of the output format.  A FIR value y goes to an integer format of scale
+ * 2^k (the table's "from a FIR value" column) as, in fp64 and evaluated as written,
+ *
+ *   v = (double)y * 2^k  (exact);   t = v + d  (one rounding);   q = floor(t + 0.5)  (one rounding)
+ *
+ * then the U8 offset and the clamp to the format's range; NaN becomes the format's zero and +-inf go
+ * to the rails, as without dither.  With d = 0 these are the undithered bytes.  (For S32 the noise
+ * lies below the fp32 mantissa of y; it is allowed all the same: one rule for the four formats.)
+ *
+ * Dither is a property of the state and applies to the formatted and mixed calls only -- host,
+ * device and batch forms.  The int16, float, planar, per-channel, chunks, many and take calls neither
+ * dither nor move the position.  `position` is the index of the stream's next output frame:
+ * set_dither sets it (a stream can be resumed in a new state), and while the kind is not NONE every
+ * formatted or mixed call advances it by the frames it produced, whatever the output format.  Then
+ *   - integer output formats are dithered, the float ones (F32, F32N) written as ever;
+ *   - S16 -> S16 is no longer the int16 call: it runs as the float call between the two conversions,
+ *     with the float entry's counter rules (as a mixed call with a matrix does);
+ *   - the zero fallback's zeros are dithered like any other value;
+ *   - a state whose channels the per-channel calls moved apart returns BAD_STATE, untouched.
+ * In a batch, stream s draws from seed + s * 0x9E3779B97F4A7C15 (mod 2^64) at its own position;
+ * batch_set_dither sets every stream's position, batch_get_dither reports stream s's own seed.
+ * An unknown kind returns INVALID_ARG and leaves the state as it was.  set_rate, set_quality,
+ * reset_mem and skip_zeros touch neither kind, seed nor position.
+ *
+ * ABI note: 0.7 + dither adds the enum and these five entry points; SpeexHipInfo, the error codes and
+ * the version string are unchanged. */
+enum { SPEEXHIP_DITHER_NONE = 0, SPEEXHIP_DITHER_RECTANGULAR = 1, SPEEXHIP_DITHER_TRIANGULAR = 2 };
+SPEEXHIP_API int speexhip_resampler_set_dither(SpeexHipResamplerState *st, int kind, uint64_t seed, uint64_t position);
+/* Any of kind, seed, position may be NULL. */
+SPEEXHIP_API int speexhip_resampler_get_dither(SpeexHipResamplerState *st, int *kind, uint64_t *seed,
+                                               uint64_t *position);
+SPEEXHIP_API int speexhip_batch_set_dither(SpeexHipBatch *b, int kind, uint64_t seed, uint64_t position);
+SPEEXHIP_API int speexhip_batch_get_dither(SpeexHipBatch *b, uint32_t stream, int *kind, uint64_t *seed,
+                                           uint64_t *position);
+/* Host only, no GPU: d[i] = the d above for idx = first_index + i (wrapping), i < n -- the very
+ * statement the kernels compile, for the tests to hold against their model. */
+SPEEXHIP_API int speexhip_debug_dither(int kind, uint64_t seed, uint64_t first_index, uint32_t n, double *d);
+
 /* Mid-stream control for every stream of a batch (same semantics as the single-stream calls). */
 SPEEXHIP_API int speexhip_batch_set_rate_frac(SpeexHipBatch *b, uint32_t ratio_num, uint32_t ratio_den,
                                               uint32_t in_rate, uint32_t out_rate);

@@ -7,6 +7,7 @@
 
 #include "../../include/speexhip_resampler.h"
 #include "devices.h"
+#include "dither.h"
 #include "engine.h"
 #include "pool.h"
 
@@ -643,6 +644,24 @@ int speexhip_batch_process_interleaved_mix_device(SpeexHipBatch *b, int in_fmt, 
   return guarded([&] { return b->batch->process_mix_device(in_fmt, in_channels, in_mix, d_in, in_stream_stride, in_len,
                                     out_fmt, out_channels, out_mix, d_out, out_stream_stride, out_len,
                                     static_cast<hipStream_t>(hip_stream)); });
+}
+
+int speexhip_resampler_set_dither(SpeexHipResamplerState *st, int kind, uint64_t seed, uint64_t position) {
+  return guarded([&] { return st ? st->batch->set_dither(kind, seed, position) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_resampler_get_dither(SpeexHipResamplerState *st, int *kind, uint64_t *seed, uint64_t *position) {
+  return guarded([&] { return st ? st->batch->get_dither(0, kind, seed, position) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_batch_set_dither(SpeexHipBatch *b, int kind, uint64_t seed, uint64_t position) {
+  return guarded([&] { return b ? b->batch->set_dither(kind, seed, position) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_batch_get_dither(SpeexHipBatch *b, uint32_t stream, int *kind, uint64_t *seed, uint64_t *position) {
+  return guarded([&] { return b ? b->batch->get_dither(stream, kind, seed, position) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_debug_dither(int kind, uint64_t seed, uint64_t first_index, uint32_t n, double *d) {
+  if (!speexhip::dither::known_kind(kind) || (d == nullptr && n != 0)) return SPEEXHIP_ERR_INVALID_ARG;
+  for (uint32_t i = 0; i < n; i++) d[i] = speexhip::dither::noise(kind, seed, first_index + i);
+  return SPEEXHIP_ERR_SUCCESS;
 }
 
 int speexhip_design_filter(uint32_t in_rate, uint32_t out_rate, int quality, SpeexHipInfo *info,

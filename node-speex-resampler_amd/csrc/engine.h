@@ -104,6 +104,14 @@ class Batch {
   // ... on host buffers of a single-stream batch; synchronous, routed like process_fmt_host.
   int process_mix_host(int in_fmt, uint32_t in_channels, const float *in_mix, const void *in, uint32_t *in_len, int out_fmt,
                        uint32_t out_channels, const float *out_mix, void *out, uint32_t *out_len);
+  // Dither of the integer output formats of the formatted and mixed calls (dither.h; include/speexhip_resampler.h,
+  // "Dither"): a property of the state, off by default.  kind = SPEEXHIP_DITHER_*; stream s draws from
+  // dither::stream_seed(seed, s); position = index of the next output frame of every stream.  While the kind is not NONE
+  // every formatted or mixed call advances each stream's position by the frames it produced, S16 -> S16 runs as the float
+  // call between convert_in and the dithered convert_out, and a state whose channels stand apart returns BAD_STATE.  No
+  // other call reads or moves any of this, and no control call (set_rate, set_quality, reset_mem, skip_zeros) touches it.
+  int set_dither(int kind, uint64_t seed, uint64_t position);
+  int get_dither(uint32_t stream, int *kind, uint64_t *seed, uint64_t *position) const;  // seed: the stream's own
   // Host-buffer call for a single-stream batch; synchronous (H2D, kernels, D2H).
   int process_host(const void *in, uint32_t *in_len, void *out, uint32_t *out_len, bool float_io);
   // The same call with the result left in a pinned block of the pool that the caller then OWNS (release_block):
@@ -195,8 +203,13 @@ class Batch {
   // formats.cpp, shared by the formatted and the mixed calls: the converting pass of a side without a matrix over every
   // stream (stream s: lens[s] frames of channels() samples at src + s * src_step, dst + s * dst_step bytes; to_image:
   // convert_in, otherwise convert_out), and the routing of a single-stream call's host buffers around a device call.
+  // dithered (convert_out only, an integer format): convert_out_dither at the streams' dither positions.
   int convert_streams(bool to_image, int fmt, const void *src, size_t src_step, void *dst, size_t dst_step, const uint32_t *lens,
-                      hipStream_t stream);
+                      hipStream_t stream, bool dithered = false);
+  bool dither_on() const { return dither_kind_ != SPEEXHIP_DITHER_NONE; }
+  // the DitherPack of streams [s0, s0 + n): first = position * per_frame (per_frame = 1: the position itself)
+  DitherPack dither_pack(uint32_t s0, uint32_t n, uint32_t per_frame) const;
+  void dither_advance(const uint32_t *produced);  // after a formatted or mixed call with dither on
   int routed_host_call(const void *in, size_t in_bytes, void *out, size_t out_bytes, size_t out_frame_bytes,
                        const uint32_t *out_len, const std::function<int(const void *, void *)> &device_call);
   int fetch_history(std::vector<float> *host);
@@ -288,6 +301,9 @@ class Batch {
   // planar calls (planar.cpp): the interleaved images either side of the existing launch; per state, grow-only
   char *d_planar_in_ = nullptr, *d_planar_out_ = nullptr;
   size_t planar_in_cap_ = 0, planar_out_cap_ = 0;  // bytes
+  int dither_kind_ = SPEEXHIP_DITHER_NONE;  // set_dither
+  uint64_t dither_seed_ = 0;
+  std::vector<uint64_t> dither_pos_;        // per stream: index of its next output frame (empty until set_dither: 0)
   uint32_t done_seq_ = 0;  // completion word of the small host-buffer calls (engine.cpp, process_host)
   size_t stage_in_cap_ = 0, stage_out_cap_ = 0, pin_in_cap_ = 0, pin_out_cap_ = 0;  // bytes
 };

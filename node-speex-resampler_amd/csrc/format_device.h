@@ -43,6 +43,24 @@ __device__ __forceinline__ uint32_t from_internal(float y) {
   return static_cast<uint32_t>(static_cast<int32_t>(fmin(fmax(r, lo), hi)));
 }
 
+// ... with dither (dither.h): d, in LSB of the integer format F, joins v before the half-up rounding -- v = y * 2^k (exact),
+// t = v + d (one fp64 rounding), floor(t + 0.5) (one more), as written: nothing contracted, nothing re-associated.  With
+// d = 0 these are from_internal's bits.
+template <int F>
+__device__ __forceinline__ uint32_t from_internal_dither(float y, double d) {
+  static_assert(F == SPEEXHIP_FMT_U8 || F == SPEEXHIP_FMT_S16 || F == SPEEXHIP_FMT_S24 || F == SPEEXHIP_FMT_S32,
+                "the integer formats are dithered, the float ones written as they are");
+  constexpr double scale = F == SPEEXHIP_FMT_U8 ? 1.0 / 256.0 : F == SPEEXHIP_FMT_S16 ? 1.0 : F == SPEEXHIP_FMT_S24 ? 256.0 : 65536.0;
+  constexpr double bias = F == SPEEXHIP_FMT_U8 ? 128.0 : 0.0;
+  constexpr double lo = F == SPEEXHIP_FMT_U8 ? 0.0 : F == SPEEXHIP_FMT_S16 ? -32768.0 : F == SPEEXHIP_FMT_S24 ? -8388608.0 : -2147483648.0;
+  constexpr double hi = F == SPEEXHIP_FMT_U8 ? 255.0 : F == SPEEXHIP_FMT_S16 ? 32767.0 : F == SPEEXHIP_FMT_S24 ? 8388607.0 : 2147483647.0;
+  if (y != y) return static_cast<uint32_t>(static_cast<int32_t>(bias));
+  const double v = static_cast<double>(y) * scale;
+  const double t = v + d;
+  const double r = floor(t + 0.5) + bias;
+  return static_cast<uint32_t>(static_cast<int32_t>(fmin(fmax(r, lo), hi)));
+}
+
 // ---- one sample at its address (any byte address for u8 / s24, an element-aligned one for the rest) -----------------
 template <int F>
 __device__ __forceinline__ uint32_t load_raw(const char *p) {

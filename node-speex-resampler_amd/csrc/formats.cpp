@@ -8,6 +8,7 @@
 #include <functional>
 #include <vector>
 
+#include "dither.h"
 #include "engine.h"
 #include "engine_detail.h"
 #include "pool.h"
@@ -32,13 +33,46 @@ inline size_t fmt_bytes(int fmt) {
 inline bool same_bytes_pair(int in_fmt, int out_fmt) {
   return in_fmt == out_fmt && (in_fmt == SPEEXHIP_FMT_S16 || in_fmt == SPEEXHIP_FMT_F32 || in_fmt == SPEEXHIP_FMT_F32N);
 }
+inline bool integer_fmt(int fmt) {
+  return fmt == SPEEXHIP_FMT_U8 || fmt == SPEEXHIP_FMT_S16 || fmt == SPEEXHIP_FMT_S24 || fmt == SPEEXHIP_FMT_S32;
+}
 }  // namespace
+
+// ---- dither (engine.h) -------------------------------------------------------------------------------------------------
+int Batch::set_dither(int kind, uint64_t seed, uint64_t position) {
+  if (!dither::known_kind(kind)) return SPEEXHIP_ERR_INVALID_ARG;
+  dither_kind_ = kind;
+  dither_seed_ = seed;
+  dither_pos_.assign(n_streams_, position);
+  return SPEEXHIP_ERR_SUCCESS;
+}
+int Batch::get_dither(uint32_t stream, int *kind, uint64_t *seed, uint64_t *position) const {
+  if (stream >= n_streams_) return SPEEXHIP_ERR_INVALID_ARG;
+  if (kind != nullptr) *kind = dither_kind_;
+  if (seed != nullptr) *seed = dither::stream_seed(dither_seed_, stream);
+  if (position != nullptr) *position = dither_pos_.empty() ? 0 : dither_pos_[stream];
+  return SPEEXHIP_ERR_SUCCESS;
+}
+DitherPack Batch::dither_pack(uint32_t s0, uint32_t n, uint32_t per_frame) const {
+  DitherPack d;
+  std::memset(&d, 0, sizeof(d));
+  d.kind = dither_kind_;
+  for (uint32_t j = 0; j < n; j++) {
+    d.s[j].seed = dither::stream_seed(dither_seed_, s0 + j);
+    d.s[j].first = (dither_pos_.empty() ? 0 : dither_pos_[s0 + j]) * per_frame;  // (mod 2^64, like idx)
+  }
+  return d;
+}
+void Batch::dither_advance(const uint32_t *produced) {
+  if (dither_pos_.empty()) dither_pos_.assign(n_streams_, 0);
+  for (uint32_t s = 0; s < n_streams_; s++) dither_pos_[s] += produced[s];
+}
 
 // The converting pass of a side without a matrix over every stream of the batch, <= 32 streams per launch: stream s is
 // lens[s] frames of channels() samples at src + s * src_step and dst + s * dst_step (bytes).  to_image: convert_in (storage
 // -> float image), otherwise convert_out.  Shared with the mixed calls (mix.cpp).
 int Batch::convert_streams(bool to_image, int fmt, const void *src, size_t src_step, void *dst, size_t dst_step,
-                           const uint32_t *lens, hipStream_t stream) {
+                           const uint32_t *lens, hipStream_t stream, bool dithered) {
   const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
   for (uint32_t s0 = 0; s0 < n_streams_; s0 += kChunk) {
     const uint32_t n = std::min(kChunk, n_streams_ - s0);
@@ -53,7 +87,9 @@ int Batch::convert_streams(bool to_image, int fmt, const void *src, size_t src_s
       pack.s[j].step = 1;
       most = std::max(most, pack.s[j].n);
     }
-    const hipError_t e = to_image ? launch_convert_in(fmt, pack, n, most, stream) : launch_convert_out(fmt, pack, n, most, stream);
+    const hipError_t e = to_image   ? launch_convert_in(fmt, pack, n, most, stream)
+                         : dithered ? launch_convert_out_dither(fmt, pack, dither_pack(s0, n, channels_), n, most, stream)
+                                    : launch_convert_out(fmt, pack, n, most, stream);
     if (hip_failed(e, "kernel launch")) return SPEEXHIP_ERR_DEVICE;
   }
   return SPEEXHIP_ERR_SUCCESS;
@@ -67,14 +103,21 @@ int Batch::process_fmt_device(int in_fmt, const void *d_in, uint64_t in_stride, 
   EntryRules rules;
   rules.block_in = block_in();
   bool split = false;
+  const bool dith = dither_on();
   for (uint32_t s = 0; s < n_streams_; s++)
     if (!uniform(s)) {
-      if (n_streams_ != 1) return SPEEXHIP_ERR_BAD_STATE;
+      // (with dither on: channels that stand apart produce different numbers of frames, a position is not defined)
+      if (n_streams_ != 1 || dith) return SPEEXHIP_ERR_BAD_STATE;
       split = true;
     }
   // (F32N -> F32N: a power-of-two scale commutes exactly with the FIR, so the float call on the same bytes)
-  if (same_bytes_pair(in_fmt, out_fmt))
-    return process_device(d_in, in_stride, in_len, d_out, out_stride, out_len, in_fmt != SPEEXHIP_FMT_S16, stream);
+  // With dither on S16 -> S16 is no such pair -- it runs as the float call between convert_in and the dithered
+  // convert_out -- and the float pairs, written as ever, still count their frames.
+  if (same_bytes_pair(in_fmt, out_fmt) && !(dith && in_fmt == SPEEXHIP_FMT_S16)) {
+    const int rc = process_device(d_in, in_stride, in_len, d_out, out_stride, out_len, in_fmt != SPEEXHIP_FMT_S16, stream);
+    if (dith && (rc == SPEEXHIP_ERR_SUCCESS || rc == SPEEXHIP_ERR_ALLOC_FAILED)) dither_advance(out_len);
+    return rc;
+  }
   rules.float_entry = true;
   // what the float call will do, known before anything is launched (integer arithmetic): sizes the images
   uint32_t most_in = 0, most_out = 0;
@@ -135,9 +178,10 @@ int Batch::process_fmt_device(int in_fmt, const void *d_in, uint64_t in_stride, 
   if (conv_out && !split) {
     // (out_len: what the float call produced)
     const int crc = convert_streams(false, out_fmt, d_planar_out_, out_pitch * sizeof(float), d_out, out_stride * bout, out_len,
-                                    stream);
+                                    stream, dith && integer_fmt(out_fmt));
     if (crc != SPEEXHIP_ERR_SUCCESS) return crc;
   }
+  if (dith) dither_advance(out_len);
   return rc;
 }
 
@@ -184,10 +228,16 @@ int Batch::process_fmt_host(int in_fmt, const void *in, uint32_t *in_len, int ou
   if (n_streams_ != 1) return SPEEXHIP_ERR_BAD_STATE;
   const size_t bin = fmt_bytes(in_fmt), bout = fmt_bytes(out_fmt);
   if (bin == 0 || bout == 0 || out == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
-  if (same_bytes_pair(in_fmt, out_fmt)) return process_host(in, in_len, out, out_len, in_fmt != SPEEXHIP_FMT_S16);
+  const bool dith = dither_on();
+  const bool split = !uniform(0);
+  if (dith && split) return SPEEXHIP_ERR_BAD_STATE;
+  if (same_bytes_pair(in_fmt, out_fmt) && !(dith && in_fmt == SPEEXHIP_FMT_S16)) {
+    const int rc = process_host(in, in_len, out, out_len, in_fmt != SPEEXHIP_FMT_S16);
+    if (dith && (rc == SPEEXHIP_ERR_SUCCESS || rc == SPEEXHIP_ERR_ALLOC_FAILED)) dither_advance(out_len);
+    return rc;
+  }
   ON_DEVICE();
   const uint32_t frames = *in_len;
-  const bool split = !uniform(0);
   uint32_t will_make = 0;  // only as many output frames as this call can produce need a device buffer
   for (uint32_t c = 0; c < (split ? channels_ : 1u); c++)
     will_make = std::max(will_make, produced_closed_form(filter_.num, filter_.den, frames, *out_len, P(0, c)));

@@ -226,4 +226,24 @@ struct MixPack {            // like ConvertPack: up to 32 streams and the matrix
 hipError_t launch_mix_in(int fmt, const MixPack &pack, uint32_t n, uint32_t max_frames, hipStream_t stream);
 hipError_t launch_mix_out(int fmt, const MixPack &pack, uint32_t n, uint32_t max_frames, hipStream_t stream);
 
+// ---- dither on the way out (dither.h): convert_out_dither<F> / mix_out_dither<F>, the output pass of a formatted or mixed
+// call of a state with dither on, for the integer formats.  The streams' arguments are the undithered pass's; what the
+// dither needs travels beside them in a second kernel argument.
+struct DitherStream {       // one stream's share
+  uint64_t seed;            // the stream's own seed
+  uint64_t first;           // convert_out_dither: idx of the stream's sample 0 of this launch (position * channels);
+                            // mix_out_dither: the stream's position, idx = (first + frame) * dst_channels + channel
+};
+struct DitherPack {         // like ConvertPack: up to 32 streams, in the kernel-argument segment (520 bytes)
+  DitherStream s[kMaxPackedStreams];
+  int32_t kind;             // SPEEXHIP_DITHER_*: one for the launch, wave-uniform
+  uint32_t reserved;
+};
+// As launch_convert_out / launch_mix_out; fmt = U8, S16, S24 or S32.  Every ConvertStream::step must be 1: sample k of a
+// stream has idx first + k.
+hipError_t launch_convert_out_dither(int fmt, const ConvertPack &pack, const DitherPack &dith, uint32_t n, uint64_t max_samples,
+                                     hipStream_t stream);
+hipError_t launch_mix_out_dither(int fmt, const MixPack &pack, const DitherPack &dith, uint32_t n, uint32_t max_frames,
+                                 hipStream_t stream);
+
 }  // namespace speexhip

@@ -20,9 +20,17 @@
 //
 // The formats themselves -- one sample to and from the image, rounding half up, and the loads / stores of one sample --
 // are stated in format_device.h, which the mixing kernels (kernels_mix.hip) share.
+//
+// convert_out_dither<F> (integer formats; a state with dither on): convert_out with the dither of dither.h added before
+// the rounding.  Instances of their own beside convert_out, which stays what it was: the same two paths, the same
+// bytes from both.  Sample k of a stream has idx first + k (DitherPack), so a lane's group on the vector path is a run
+// of G consecutive idx: the inner half of the generator's word, which changes once per 2^32 samples, is taken once per
+// group (twice for the one group that crosses such a boundary), once per sample on the element path.  The kind is one
+// per launch: wave-uniform.
 #include <hip/hip_runtime.h>
 
 #include "../../include/speexhip_resampler.h"
+#include "dither.h"
 #include "format_device.h"
 #include "kernels.h"
 
@@ -136,6 +144,62 @@ __global__ __launch_bounds__(kLanes) void convert_out(const ConvertPack pack) {
   convert_tile<F, true>(pack);
 }
 
+// ---- ... with dither ---------------------------------------------------------------------------------------------------
+template <int F>
+__device__ __forceinline__ void vector_tile_dither(const ConvertStream &s, const DitherStream &d, int kind, uint64_t tile0) {
+  constexpr uint32_t B = bytes_of(F), G = group_of(F), words = G * B / 4;
+  const char *src = static_cast<const char *>(s.src);
+  char *dst = static_cast<char *>(s.dst);
+#pragma unroll
+  for (uint32_t pass = 0; pass < kTile / (kLanes * G); pass++) {
+    const uint64_t first = tile0 + static_cast<uint64_t>(pass * kLanes + threadIdx.x) * G;  // the lane's first sample
+    const dither::Run run = dither::run_of(d.seed, d.first + first, G);
+    uint32_t w[words];
+    float e[G];
+    const float4 *in = reinterpret_cast<const float4 *>(src + first * sizeof(float));
+#pragma unroll
+    for (uint32_t i = 0; i < G / 4; i++) {
+      const float4 v = in[i];
+      e[4 * i] = v.x, e[4 * i + 1] = v.y, e[4 * i + 2] = v.z, e[4 * i + 3] = v.w;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < words; i++) w[i] = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < G; j++) put_raw<F>(w, j, from_internal_dither<F>(e[j], dither::noise_in(kind, run, j)));
+    uint4 *out = reinterpret_cast<uint4 *>(dst + first * B);
+#pragma unroll
+    for (uint32_t i = 0; i < words / 4; i++) out[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+  }
+}
+
+// samples [tile0, tile0 + n) of the stream, one after the other in both buffers
+template <int F>
+__device__ __forceinline__ void element_tile_dither(const ConvertStream &s, const DitherStream &d, int kind, uint64_t tile0,
+                                                    uint32_t n) {
+  constexpr uint32_t B = bytes_of(F);
+  const char *src = static_cast<const char *>(s.src);
+  char *dst = static_cast<char *>(s.dst);
+  for (uint32_t i = threadIdx.x; i < n; i += kLanes) {
+    const uint64_t at = tile0 + i;
+    const float y = *reinterpret_cast<const float *>(src + at * sizeof(float));
+    store_raw<F>(dst + at * B, from_internal_dither<F>(y, dither::noise(kind, d.seed, d.first + at)));
+  }
+}
+
+template <int F>
+__global__ __launch_bounds__(kLanes) void convert_out_dither(const ConvertPack pack, const DitherPack dith) {
+  const ConvertStream &s = pack.s[blockIdx.y];
+  const DitherStream &d = dith.s[blockIdx.y];
+  const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kTile;
+  if (s.src == nullptr || tile0 >= s.n) return;  // (nothing to convert, or a shorter stream of the launch)
+  const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(kTile), s.n - tile0));
+  const bool aligned = ((reinterpret_cast<uintptr_t>(s.src) | reinterpret_cast<uintptr_t>(s.dst)) & 15u) == 0;
+  if (n == kTile && aligned)
+    vector_tile_dither<F>(s, d, dith.kind, tile0);
+  else
+    element_tile_dither<F>(s, d, dith.kind, tile0, n);
+}
+
 #define CONVERT_LAUNCH(F)                                                           \
   if (kOut)                                                                         \
     hipLaunchKernelGGL((convert_out<F>), grid, block, 0, stream, pack);             \
@@ -165,6 +229,21 @@ hipError_t launch_convert_in(int fmt, const ConvertPack &pack, uint32_t n, uint6
 }
 hipError_t launch_convert_out(int fmt, const ConvertPack &pack, uint32_t n, uint64_t max_samples, hipStream_t stream) {
   return launch_convert<true>(fmt, pack, n, max_samples, stream);
+}
+hipError_t launch_convert_out_dither(int fmt, const ConvertPack &pack, const DitherPack &dith, uint32_t n, uint64_t max_samples,
+                                     hipStream_t stream) {
+  if (n == 0 || max_samples == 0) return hipSuccess;
+  for (uint32_t j = 0; j < n; j++)
+    if (pack.s[j].step != 1) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<uint32_t>((max_samples + kTile - 1) / kTile), n), block(kLanes);
+  switch (fmt) {
+    case SPEEXHIP_FMT_U8: hipLaunchKernelGGL((convert_out_dither<SPEEXHIP_FMT_U8>), grid, block, 0, stream, pack, dith); break;
+    case SPEEXHIP_FMT_S16: hipLaunchKernelGGL((convert_out_dither<SPEEXHIP_FMT_S16>), grid, block, 0, stream, pack, dith); break;
+    case SPEEXHIP_FMT_S24: hipLaunchKernelGGL((convert_out_dither<SPEEXHIP_FMT_S24>), grid, block, 0, stream, pack, dith); break;
+    case SPEEXHIP_FMT_S32: hipLaunchKernelGGL((convert_out_dither<SPEEXHIP_FMT_S32>), grid, block, 0, stream, pack, dith); break;
+    default: return hipErrorInvalidValue;  // (the float formats are not dithered)
+  }
+  return hipGetLastError();
 }
 
 }  // namespace speexhip

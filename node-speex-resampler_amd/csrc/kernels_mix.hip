@@ -28,11 +28,17 @@
 // faster than this one ("Mixed calls"), so it is gone: a lane's stores already fall into lines its
 // neighbours fill.
 //
+// mix_out_dither<F> (integer formats; a state with dither on): mix_out with the dither of dither.h added before the
+// rounding, instances of their own beside mix_out.  Output o of frame f of a stream at position p has idx
+// (p + f) * dst_channels + o: a frame is a run of consecutive idx, so the inner half of the generator's word is taken
+// once per frame (twice for the one frame that crosses a 2^32 boundary of idx).
+//
 // The image mix_in writes is read by the very next kernel and mix_out's source was written by the previous one: plain
 // loads and stores throughout, so that the images can stay in L2 / Infinity Cache.
 #include <hip/hip_runtime.h>
 
 #include "../../include/speexhip_resampler.h"
+#include "dither.h"
 #include "format_device.h"
 #include "kernels.h"
 
@@ -155,6 +161,28 @@ __global__ __launch_bounds__(kLanes) void mix_out(const MixPack pack) {
   mix_tile<F, true>(pack, mix_lds);
 }
 
+// mix_out with dither: frames [tile0, tile0 + n) of the stream, frame by frame as element_path
+template <int F>
+__global__ __launch_bounds__(kLanes) void mix_out_dither(const MixPack pack, const DitherPack dith) {
+  constexpr uint32_t B = bytes_of(F);
+  const MixStream &s = pack.s[blockIdx.y];
+  const DitherStream &d = dith.s[blockIdx.y];
+  const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kTileFrames;
+  if (s.src == nullptr || tile0 >= s.frames) return;  // (nothing to mix, or a shorter stream of the launch)
+  const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(kTileFrames), s.frames - tile0));
+  const uint32_t ns = pack.src_channels, nd = pack.dst_channels;
+  const int kind = dith.kind;
+  for (uint32_t f = threadIdx.x; f < n; f += kLanes) {
+    const uint64_t frame = tile0 + f;
+    const float *src = static_cast<const float *>(s.src) + frame * ns;
+    char *dst = static_cast<char *>(s.dst) + frame * nd * B;
+    const dither::Run run = dither::run_of(d.seed, (d.first + frame) * nd, nd);
+    mix_frame(
+        pack, ns, nd, [&](uint32_t i) { return src[i]; },
+        [&](uint32_t o, float y) { store_raw<F>(dst + o * B, from_internal_dither<F>(y, dither::noise_in(kind, run, o))); });
+  }
+}
+
 #define MIX_LAUNCH(F)                                                      \
   if (kOut)                                                                \
     hipLaunchKernelGGL((mix_out<F>), grid, block, lds, stream, pack);      \
@@ -191,6 +219,22 @@ hipError_t launch_mix_in(int fmt, const MixPack &pack, uint32_t n, uint32_t max_
 }
 hipError_t launch_mix_out(int fmt, const MixPack &pack, uint32_t n, uint32_t max_frames, hipStream_t stream) {
   return launch_mix<true>(fmt, pack, n, max_frames, stream);
+}
+hipError_t launch_mix_out_dither(int fmt, const MixPack &pack, const DitherPack &dith, uint32_t n, uint32_t max_frames,
+                                 hipStream_t stream) {
+  if (n == 0 || max_frames == 0) return hipSuccess;
+  if (pack.src_channels == 0 || pack.src_channels > kMixMaxChannels || pack.dst_channels == 0 ||
+      pack.dst_channels > kMixMaxChannels)
+    return hipErrorInvalidValue;
+  const dim3 grid((max_frames + kTileFrames - 1) / kTileFrames, n), block(kLanes);
+  switch (fmt) {
+    case SPEEXHIP_FMT_U8: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_U8>), grid, block, 0, stream, pack, dith); break;
+    case SPEEXHIP_FMT_S16: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_S16>), grid, block, 0, stream, pack, dith); break;
+    case SPEEXHIP_FMT_S24: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_S24>), grid, block, 0, stream, pack, dith); break;
+    case SPEEXHIP_FMT_S32: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_S32>), grid, block, 0, stream, pack, dith); break;
+    default: return hipErrorInvalidValue;  // (the float formats are not dithered)
+  }
+  return hipGetLastError();
 }
 
 }  // namespace speexhip

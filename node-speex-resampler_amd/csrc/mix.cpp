@@ -87,9 +87,13 @@ int Batch::process_mix_device(int in_fmt, uint32_t in_channels, const float *in_
   rc = process_device(image_in, image_in_stride, in_len, image_out, image_out_stride, out_len, true, stream);
   if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
   // (out_len: what the float call produced; the zero fallback's zeros take the same way out)
+  // With dither on (engine.h, set_dither) the integer formats leave through the dithered instances of either pass, at the
+  // streams' positions, and every format counts the frames it produced.
+  const bool dith = dither_on();
+  const bool dith_out = dith && out_fmt != SPEEXHIP_FMT_F32 && out_fmt != SPEEXHIP_FMT_F32N;
   if (pass_out && out_mix == nullptr) {
     const int crc = convert_streams(false, out_fmt, d_planar_out_, out_pitch * sizeof(float), d_out, out_stride * bout, out_len,
-                                    stream);
+                                    stream, dith_out);
     if (crc != SPEEXHIP_ERR_SUCCESS) return crc;
   }
   for (uint32_t s0 = 0; pass_out && out_mix != nullptr && s0 < n_streams_; s0 += kChunk) {
@@ -106,8 +110,11 @@ int Batch::process_mix_device(int in_fmt, uint32_t in_channels, const float *in_
       pack.s[j].frames = out_len[s];
       most = std::max(most, out_len[s]);
     }
-    if (hip_failed(launch_mix_out(out_fmt, pack, n, most, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+    const hipError_t e = dith_out ? launch_mix_out_dither(out_fmt, pack, dither_pack(s0, n, 1), n, most, stream)
+                                  : launch_mix_out(out_fmt, pack, n, most, stream);
+    if (hip_failed(e, "kernel launch")) return SPEEXHIP_ERR_DEVICE;
   }
+  if (dith) dither_advance(out_len);
   return rc;
 }
 

@@ -16,6 +16,8 @@ import { Transform, TransformCallback } from 'stream';
  * processChunkFloat takes), 'f32le-normalized' float32 with +-1.0 full scale (Web Audio)
  */
 export type SampleFormat = 'u8' | 's16le' | 's24le' | 's32le' | 'f32le' | 'f32le-normalized';
+/** dither of the integer results of processChunkFormat / processChunkMix (setDither) */
+export type DitherKind = 'none' | 'rectangular' | 'triangular';
 
 export interface SpeexResamplerTransformOptions {
     /**
@@ -146,6 +148,15 @@ declare class SpeexResampler {
      * (bit-identical to the reference, slower) or 'fast_f32'.  SPEEXHIP_MODE in the environment sets the initial mode.
      */
     setMode(mode: 'fast' | 'exact' | 'fast_f32' | 'fast_fixed'): void;
+    /**
+     * Dither of the integer results of processChunkFormat / processChunkMix: 'none' (default, round half up),
+     * 'rectangular' (+-0.5 LSB) or 'triangular' (TPDF, +-1 LSB).  Counter based: the noise of a sample depends on (seed,
+     * its index in the stream) alone, so the bytes do not depend on the chunking.  position = index of the next output
+     * frame.  While on, 's16le' -> 's16le' runs as processChunkFloat between the two conversions.
+     */
+    setDither(kind: DitherKind, seed?: bigint | number, position?: bigint | number): void;
+    /** position: output frames made by processChunkFormat / processChunkMix since setDither, plus its position */
+    getDither(): { kind: DitherKind, seed: bigint, position: bigint };
     skipZeros(): void;
     resetMem(): void;
     /** filter delay in frames at the input rate / at the output rate */
@@ -196,6 +207,10 @@ export declare class SpeexResamplerBatch {
     processChunks(chunks: Array<Buffer | null>): Array<Buffer | null>;
     processChunksAsync(chunks: Array<Buffer | null>): Promise<Array<Buffer | null>>;
     setMode(mode: 'fast' | 'exact' | 'fast_f32' | 'fast_fixed'): void;
+    /** setDither of every stream; stream k draws from seed + k * 0x9E3779B97F4A7C15 (mod 2^64) */
+    setDither(kind: DitherKind, seed?: bigint | number, position?: bigint | number): void;
+    /** getDither of stream k (default 0) */
+    getDither(stream?: number): { kind: DitherKind, seed: bigint, position: bigint };
     destroy(): void;
 }
 

@@ -21,6 +21,8 @@ const SAMPLE_FORMATS = {
   'f32le': { id: 4, bytes: 4 },
   'f32le-normalized': { id: 5, bytes: 4 },
 };
+// setDither: the names of the dither kinds (SPEEXHIP_DITHER_* = the index)
+const DITHER_KINDS = ['none', 'rectangular', 'triangular'];
 let speexModule;
 const globalModulePromise = new Promise((resolve, reject) => {
   try {
@@ -336,6 +338,30 @@ class SpeexResampler {
     speexModule.setMode(this._ensureNative(), code);
   }
 
+  /**
+   * Dither of the integer results ('u8', 's16le', 's24le', 's32le') of processChunkFormat and processChunkMix: 'none' (the
+   * default: round half up), 'rectangular' (uniform in +-0.5 LSB) or 'triangular' (TPDF, +-1 LSB: the error of a
+   * requantised signal becomes noise instead of harmonics).  The noise of a sample is a pure function of (seed, its index
+   * in the stream), so the bytes do not depend on how the stream is cut into chunks; `position` is the index of the next
+   * output frame (resume a stream in a new instance with the seed and getDither().position of the old one).  While on,
+   * 's16le' -> 's16le' runs as processChunkFloat between the two conversions.  seed and position: bigint or number.
+   */
+  setDither(kind, seed = 0n, position = 0n) {
+    this._refuseWhileAsyncPending('setDither');
+    const code = DITHER_KINDS.indexOf(kind);
+    if (code < 0) throw new Error("dither must be 'none', 'rectangular' or 'triangular'");
+    const s = BigInt.asUintN(64, BigInt(seed));
+    const p = BigInt.asUintN(64, BigInt(position));
+    speexModule.setDither(this._ensureNative(), code, Number(s & 0xffffffffn), Number(s >> 32n), Number(p & 0xffffffffn),
+      Number(p >> 32n));
+  }
+
+  /** { kind, seed, position }: seed and position are bigints; position = output frames made with dither on so far */
+  getDither() {
+    const [code, sLo, sHi, pLo, pHi] = speexModule.getDither(this._ensureNative());
+    return { kind: DITHER_KINDS[code], seed: (BigInt(sHi) << 32n) | BigInt(sLo), position: (BigInt(pHi) << 32n) | BigInt(pLo) };
+  }
+
   /** Start half a filter in, so the stream does not begin with the filter's ramp-up. */
   skipZeros() {
     this._refuseWhileAsyncPending('skipZeros');
@@ -533,6 +559,14 @@ class SpeexResamplerBatch {
   }
 
   setMode(mode) { for (const r of this.streams) r.setMode(mode); }
+
+  /** setDither of every stream: stream k draws from seed + k * 0x9E3779B97F4A7C15 (mod 2^64), as a batch of the C API */
+  setDither(kind, seed = 0n, position = 0n) {
+    this.streams.forEach((r, k) => r.setDither(kind, BigInt.asUintN(64, BigInt(seed) + BigInt(k) * 0x9E3779B97F4A7C15n), position));
+  }
+
+  /** getDither of stream k (its own seed and position) */
+  getDither(stream = 0) { return this.streams[stream].getDither(); }
 
   destroy() { for (const r of this.streams) r.destroy(); }
 }

@@ -839,6 +839,52 @@ static napi_value ResetMem(napi_env env, napi_callback_info info) {
   return control_result(env, rc);
 }
 
+/* setDither(handle, kind, seedLo, seedHi, positionLo, positionHi): the 64-bit values travel as uint32 halves (index.js
+ * splits and joins the BigInts) */
+static napi_value SetDither(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 6) {
+    napi_throw_type_error(env, NULL, "setDither(handle, kind, seedLo, seedHi, positionLo, positionHi)");
+    return NULL;
+  }
+  Handle *h = NULL;
+  SpeexHipResamplerState *st = lock_state(env, argv[0], &h);
+  if (st == NULL) return NULL;
+  int32_t kind = 0;
+  uint32_t v[4] = {0, 0, 0, 0};
+  NAPI_OK_LOCKED(h, napi_get_value_int32(env, argv[1], &kind));
+  for (size_t i = 0; i < 4; i++) NAPI_OK_LOCKED(h, napi_get_value_uint32(env, argv[2 + i], &v[i]));
+  const int rc = speexhip_resampler_set_dither(st, kind, ((uint64_t)v[1] << 32) | v[0], ((uint64_t)v[3] << 32) | v[2]);
+  UNLOCK(h);
+  return control_result(env, rc);
+}
+
+/* getDither(handle) -> [kind, seedLo, seedHi, positionLo, positionHi] */
+static napi_value GetDither(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  Handle *h = NULL;
+  SpeexHipResamplerState *st = lock_state(env, argv[0], &h);
+  if (st == NULL) return NULL;
+  int kind = 0;
+  uint64_t seed = 0, position = 0;
+  const int rc = speexhip_resampler_get_dither(st, &kind, &seed, &position);
+  UNLOCK(h);
+  if (rc != 0) return control_result(env, rc);
+  const uint32_t out[5] = {(uint32_t)kind, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)position,
+                           (uint32_t)(position >> 32)};
+  napi_value arr, v;
+  NAPI_OK(napi_create_array_with_length(env, 5, &arr));
+  for (uint32_t i = 0; i < 5; i++) {
+    NAPI_OK(napi_create_uint32(env, out[i], &v));
+    NAPI_OK(napi_set_element(env, arr, i, v));
+  }
+  return arr;
+}
+
 static napi_value pair_u32(napi_env env, uint32_t a, uint32_t b) {
   napi_value arr, v;
   NAPI_OK(napi_create_array_with_length(env, 2, &arr));
@@ -1354,6 +1400,8 @@ NAPI_MODULE_INIT() {
       {"setQuality", NULL, SetQuality, NULL, NULL, NULL, napi_default, NULL},
       {"skipZeros", NULL, SkipZeros, NULL, NULL, NULL, napi_default, NULL},
       {"resetMem", NULL, ResetMem, NULL, NULL, NULL, napi_default, NULL},
+      {"setDither", NULL, SetDither, NULL, NULL, NULL, napi_default, NULL},
+      {"getDither", NULL, GetDither, NULL, NULL, NULL, napi_default, NULL},
       {"getLatency", NULL, GetLatency, NULL, NULL, NULL, napi_default, NULL},
       {"setMode", NULL, SetMode, NULL, NULL, NULL, napi_default, NULL},
       {"getInfo", NULL, GetInfo, NULL, NULL, NULL, napi_default, NULL},

@@ -24,6 +24,8 @@ ERR_NO_BLOCK = 7  # the ..._take calls: no pinned result block free right now, s
 FMT_U8, FMT_S16, FMT_S24, FMT_S32, FMT_F32, FMT_F32N = range(6)
 FMT_BYTES = (1, 2, 3, 4, 4, 4)
 FMT_DTYPE = (np.uint8, np.int16, np.uint8, np.int32, np.float32, np.float32)  # numpy storage type of each format
+# dither of the integer output formats of the formatted and mixed calls (SPEEXHIP_DITHER_*), a property of the state
+DITHER_NONE, DITHER_RECTANGULAR, DITHER_TRIANGULAR = range(3)
 
 EXPORTS = [
     "speexhip_resampler_init", "speexhip_resampler_destroy",
@@ -71,6 +73,9 @@ EXPORTS = [
     # channel mixing in the formatted calls: a matrix before the FIR and / or after it
     "speexhip_resampler_process_interleaved_mix", "speexhip_resampler_process_interleaved_mix_device",
     "speexhip_batch_process_interleaved_mix_device",
+    # dither of the integer output formats of the formatted and mixed calls
+    "speexhip_resampler_set_dither", "speexhip_resampler_get_dither", "speexhip_batch_set_dither",
+    "speexhip_batch_get_dither", "speexhip_debug_dither",
 ]
 
 
@@ -282,6 +287,18 @@ def lib():
             L.speexhip_batch_process_interleaved_mix_device.restype = i32
             L.speexhip_batch_process_interleaved_mix_device.argtypes = [p, i32, u32, p, p, u64, pu32, i32, u32, p, p, u64,
                                                                         pu32, p]
+        if hasattr(L, "speexhip_resampler_set_dither") or "SPEEXHIP_LIB_PATH" not in os.environ:
+            u64, pu64 = C.c_uint64, C.POINTER(C.c_uint64)
+            L.speexhip_resampler_set_dither.restype = i32
+            L.speexhip_resampler_set_dither.argtypes = [p, i32, u64, u64]
+            L.speexhip_resampler_get_dither.restype = i32
+            L.speexhip_resampler_get_dither.argtypes = [p, C.POINTER(C.c_int), pu64, pu64]
+            L.speexhip_batch_set_dither.restype = i32
+            L.speexhip_batch_set_dither.argtypes = [p, i32, u64, u64]
+            L.speexhip_batch_get_dither.restype = i32
+            L.speexhip_batch_get_dither.argtypes = [p, u32, C.POINTER(C.c_int), pu64, pu64]
+            L.speexhip_debug_dither.restype = i32
+            L.speexhip_debug_dither.argtypes = [i32, u64, u64, u32, C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -334,6 +351,15 @@ def plan_call_ex(num, den, in_len, out_cap, float_entry, block_in, last, frac, m
     if rc != 0:
         raise ValueError(strerror(rc))
     return c.value, p.value, l.value, f.value, m.value
+
+
+def debug_dither(kind, seed, first_index, n):
+    """host-only: the library's dither values d (float64, in LSB) of sample indices first_index .. first_index + n - 1"""
+    d = np.zeros(max(int(n), 1), np.float64)
+    rc = lib().speexhip_debug_dither(kind, seed, first_index, n, d.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc:
+        raise ValueError(strerror(rc))
+    return d[:n]
 
 
 def debug_plan64(ratio_num, ratio_den, quality, channels):
@@ -835,6 +861,20 @@ class Resampler:
             raise RuntimeError(strerror(rc))
         return il.value, ol.value
 
+    def set_dither(self, kind, seed=0, position=0):
+        """Dither of the integer output formats of the formatted and mixed calls: kind = DITHER_NONE / _RECTANGULAR /
+        _TRIANGULAR, position = index of the stream's next output frame.  Returns the C call's code (INVALID_ARG for an
+        unknown kind, the state untouched)."""
+        return lib().speexhip_resampler_set_dither(self._h, int(kind), int(seed), int(position))
+
+    def get_dither(self):
+        """(kind, seed, position)"""
+        k, s, p_ = C.c_int(), C.c_uint64(), C.c_uint64()
+        rc = lib().speexhip_resampler_get_dither(self._h, C.byref(k), C.byref(s), C.byref(p_))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return k.value, s.value, p_.value
+
     def peek(self, in_frames, out_capacity, float_entry=False):
         """(consumed, produced) of the next call, state untouched"""
         c, p_ = C.c_uint32(), C.c_uint32()
@@ -918,6 +958,20 @@ class Batch:
 
     def reset_mem(self):
         return lib().speexhip_batch_reset_mem(self._h)
+
+    def set_dither(self, kind, seed=0, position=0):
+        """Dither of every stream's integer outputs in the formatted and mixed calls (process_tensor through them): stream
+        s draws from seed + s * 0x9E3779B97F4A7C15 (mod 2^64); position = every stream's next output frame.  Returns the C
+        call's code."""
+        return lib().speexhip_batch_set_dither(self._h, int(kind), int(seed), int(position))
+
+    def get_dither(self, stream=0):
+        """(kind, the stream's own seed, the stream's position)"""
+        k, s, p_ = C.c_int(), C.c_uint64(), C.c_uint64()
+        rc = lib().speexhip_batch_get_dither(self._h, stream, C.byref(k), C.byref(s), C.byref(p_))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return k.value, s.value, p_.value
 
     def lines(self, stream):
         """(taps-1+pending, channels) float32 of one stream: history then pending frames"""
