@@ -15,8 +15,20 @@ Output k of a stream sits at pos = k num // den, phase = k num % den, over the l
 stream has consumed):  truth[k, c] = sum_j rows[phase, j] line[pos + j, c],  mag[k, c] = sum_j |rows| |line|.
 The reference and the product differ from this only by the rounding of products and sums.  The model works per STREAM:
 give it the concatenation of what each call consumed and the number of outputs made so far -- multi-call, ragged and
-capacity-bound streams need no history logic.  The control calls (set_rate, set_quality, skip_zeros) change the line
-and are out of scope.
+capacity-bound streams need no history logic.
+
+Segments.  A stream is a sequence of segments: one begins at the stream's start or right after a control call
+(set_rate, set_rate_frac, set_quality, skip_zeros, reset_mem) that returned, and ends at the next control call.  Within
+a segment the definition above holds with
+  line = head ++ (all input consumed in the segment),  head = history ++ pending per channel: the taps - 1 frames of
+         history and the pending ("magic") frames a shortened filter left buffered, both read from the oracle after
+         the control call (Oracle.history(c), Oracle.pending(c): float32, so exact);
+  output k of the segment at pos = last0 + (frac0 + k num) // den, phase = (frac0 + k num) % den, where
+         (last0, frac0) = Oracle.position() at the segment's start;
+  rows:  those of the oracle's filter as it now is (Model.of(o): any set_rate_frac ratio, not only the rates' own).
+Model.of(o).segment_of(o) reads all of it from a live oracle; a segment with head = zeros(taps - 1) and start (0, 0)
+IS the stream of the first paragraph, byte for byte.  A segment has ONE position: channels that per-channel calls
+moved apart stay out of scope.
 
 Input (tests/float_inputs.py).  The model takes any float32 line: a product of two 24-bit numbers is exact in a double
 and the rational arbiter settles the rest, so real float data -- full mantissas, fractions, channels and passages 2^20
@@ -114,18 +126,52 @@ class Model:
     """The exact model of one filter: Model(channels, in_rate, out_rate, quality).truth(consumed_input, outputs_made)."""
 
     def __init__(self, channels, in_rate, out_rate, quality, make=orc.Oracle):
-        o = make(channels, in_rate, out_rate, quality)
+        self._adopt(make(channels, in_rate, out_rate, quality), channels)
+
+    def _adopt(self, o, channels):
         self.channels, self.num, self.den, self.taps, self.kind = channels, o.num, o.den, o.taps, o.kind
         self.double_kind = o.kind.endswith("double")
         self.rows = phase_rows(o)
+        self.head = np.zeros((self.taps - 1, channels))
+        self.last0, self.frac0 = 0, 0
+
+    @classmethod
+    def of(cls, o):
+        """The model of a live oracle's (or reference's) filter as it now is, whatever calls set its ratio and quality;
+        a stream's start: head zeros(taps - 1), position (0, 0)."""
+        m = cls.__new__(cls)
+        m._adopt(o, o.channels)
+        return m
+
+    def segment(self, head, start):
+        """This filter over a segment: head[taps - 1 + pending, ch] (history ++ pending) and start = (last0, frac0)."""
+        m = self.__class__.__new__(self.__class__)
+        m.__dict__.update(self.__dict__)
+        m.head = np.array(head, np.float64).reshape(-1, self.channels)
+        assert m.head.shape[0] >= self.taps - 1, "a head holds taps - 1 frames of history at least"
+        m.last0, m.frac0 = int(start[0]), int(start[1])
+        return m
+
+    def segment_of(self, o):
+        """The segment that begins where the live oracle `o` stands: its history, pending frames and position."""
+        cols = [np.concatenate([o.history(c), o.pending(c)]) for c in range(self.channels)]
+        return self.segment(np.stack(cols, axis=1), o.position())
+
+    @property
+    def pending(self):
+        return self.head.shape[0] - (self.taps - 1)
 
     def line(self, x):
         x = np.asarray(x, np.float64).reshape(-1, self.channels)
-        return np.concatenate([np.zeros((self.taps - 1, self.channels)), x])
+        return np.concatenate([self.head, x])
+
+    def where(self, k):
+        """(pos, phase) of output k (an int or an int64 array) of the segment"""
+        t = self.frac0 + k * self.num
+        return self.last0 + t // self.den, t % self.den
 
     def geometry(self, n_out):
-        k = np.arange(n_out, dtype=np.int64)
-        return k * self.num // self.den, k * self.num % self.den
+        return self.where(np.arange(n_out, dtype=np.int64))
 
     def truth(self, x, n_out, rows=None):
         """-> (truth[n_out, ch], mag[n_out, ch]) in float64.  Outputs of one residue r = k % den share a phase and their
@@ -138,12 +184,13 @@ class Model:
         truth = np.zeros((n_out, ch))
         mag = np.zeros((n_out, ch))
         if n_out:
-            last = (n_out - 1) * num // den + n
+            last = self.where(n_out - 1)[0] + n
             assert last <= line.shape[0], "the stream made output %d before consuming frame %d" % (n_out - 1, last - n)
         fs, cs = line.strides
         for r in range(min(den, n_out)):
             count = (n_out - r + den - 1) // den
-            start, row = r * num // den, rows[r * num % den]
+            start, phase = self.where(r)
+            row = rows[phase]
             for src, dst, taps in ((line, truth, row), (absline, mag, np.abs(row))):
                 win = np.lib.stride_tricks.as_strided(src[start:], (count, n, ch), (num * fs, fs, cs), writeable=False)
                 dst[r::den] = np.einsum("j,njc->nc", taps, win)
@@ -152,7 +199,7 @@ class Model:
     def exact_sample(self, x, k, c):
         """truth[k, c] as a Fraction (no rounding at all): the arbiter for samples a float64 check flags"""
         line = self.line(x)
-        pos, phase = k * self.num // self.den, k * self.num % self.den
+        pos, phase = self.where(k)
         row = self.rows[phase]
         return sum((Fraction(float(row[j])) * Fraction(float(line[pos + j, c])) for j in range(self.taps)), Fraction(0))
 
@@ -210,7 +257,7 @@ def bias_ok(e):
 
 def _describe(model, idx, got, truth, mag, tile=None):
     k, c = (int(v) for v in idx)
-    pos, phase = k * model.num // model.den, k * model.num % model.den
+    pos, phase = model.where(k)
     return "output %d ch %d (phase %d, pos %d%s): got %r, truth %.17g, mag %.6g, e = %.3g" % (
         k, c, phase, pos, "" if not tile else ", pos %% %d = %d" % (tile, pos % tile), got[k, c], truth[k, c], mag[k, c],
         (float(got[k, c]) - truth[k, c]) / (U * mag[k, c]) if mag[k, c] > 0 else float("nan"))
@@ -218,7 +265,7 @@ def _describe(model, idx, got, truth, mag, tile=None):
 
 def _worst_phase(model, bad):
     k = np.nonzero(bad.any(axis=1))[0]
-    phases = (k * model.num % model.den)
+    phases = model.where(k)[1]
     vals, counts = np.unique(phases, return_counts=True)
     return "%d samples fail; worst phase %d (%d of them); first %s" % (
         int(bad.sum()), int(vals[np.argmax(counts)]), int(counts.max()), [int(v) for v in k[:6]])

@@ -411,3 +411,229 @@ def _hard_int16_tail(model, line, got, truth, mag, first, bits):
     masked = got.copy()
     masked[:first] = em.halfup(truth[:first]).astype(np.int16)
     return em.hard_int16(model, line, masked, truth, mag, bits)
+
+
+# ---- segments: streams after mid-stream control calls (tests/control_scripts.py) ----
+import control_scripts as cs
+
+ALL_SCRIPTS = list(cs.SCRIPTS) + list(cs.EXTRA)
+
+
+def _legacy_truth(model, x, n_out):
+    """truth and mag as Model.truth computed them before it knew segments: a stream from its start"""
+    line = np.concatenate([np.zeros((model.taps - 1, model.channels)), np.asarray(x, np.float64)])
+    absline, (fs, cs_) = np.abs(line), line.strides
+    truth, mag = np.zeros((n_out, model.channels)), np.zeros((n_out, model.channels))
+    for r in range(min(model.den, n_out)):
+        count = (n_out - r + model.den - 1) // model.den
+        start, row = r * model.num // model.den, model.rows[r * model.num % model.den]
+        for src, dst, taps in ((line, truth, row), (absline, mag, np.abs(row))):
+            win = np.lib.stride_tricks.as_strided(src[start:], (count, model.taps, model.channels),
+                                                  (model.num * fs, fs, cs_), writeable=False)
+            dst[r::model.den] = np.einsum("j,njc->nc", taps, win)
+    return truth, mag
+
+
+def _legacy_chain32(model, x, n_out):
+    rows32 = model.rows.astype(np.float32).astype(np.float64)
+    line = np.concatenate([np.zeros((model.taps - 1, model.channels)), np.asarray(x, np.float64)])
+    k = np.arange(n_out, dtype=np.int64)
+    pos, phase = k * model.num // model.den, k * model.num % model.den
+    s = np.zeros((n_out, model.channels), np.float32)
+    for j in range(model.taps):
+        s = (rows32[phase, j][:, None] * line[pos + j] + s.astype(np.float64)).astype(np.float32)
+    return s
+
+
+@pytest.mark.parametrize("ch,i,o,q", DEFECT_CASES + [(8, 48000, 44100, 5), (2, 44100, 48000, 10)])
+def test_a_segment_with_a_zero_head_at_the_start_is_the_stream_model_bit_for_bit(ch, i, o, q):
+    xf = _input("lcg", 9000, ch, seed=4).astype(np.float32)
+    model = em.Model(ch, i, o, q)
+    n = (9000 - 1) * model.den // model.num
+    want = _legacy_truth(model, xf, n) + (_legacy_chain32(model, xf, n),)
+    live = orc.Oracle(ch, i, o, q)
+    for m in (model, model.segment(np.zeros((model.taps - 1, ch)), (0, 0)), em.Model.of(live), em.Model.of(live).segment_of(live)):
+        assert (m.last0, m.frac0, m.pending) == (0, 0, 0) and np.array_equal(m.rows, model.rows)
+        truth, mag = m.truth(xf, n)
+        assert truth.tobytes() == want[0].tobytes() and mag.tobytes() == want[1].tobytes()
+        assert em.chain32(m, xf, n).tobytes() == want[2].tobytes()
+        assert m.exact_sample(xf, n - 1, ch - 1) == model.exact_sample(xf, n - 1, ch - 1)
+
+
+def test_a_model_of_a_live_oracle_follows_set_rate_frac_and_set_quality():
+    o = orc.Oracle(2, 44100, 48000, 7)
+    assert o.set_rate_frac(3, 2, 48000, 32000) == 0 and o.set_quality(10) == 0
+    m, fresh = em.Model.of(o), orc.Oracle(2, 48000, 32000, 10, ratio=(3, 2))
+    assert (m.num, m.den, m.taps, m.kind) == (3, 2, fresh.taps, fresh.kind) and np.array_equal(m.rows, em.phase_rows(fresh))
+
+
+def test_the_scripts_use_every_op_and_cover_all_four_kinds():
+    ops = {(op[1] if op[0] == "short" else op[0]) for s in cs.SCRIPTS.values() for op in s[4]}
+    assert ops == {"set_rate", "set_rate_frac", "set_quality", "skip_zeros", "reset_mem"}
+    quals = [(a["quality"], b["quality"]) for n in cs.SCRIPTS for a, b in zip(cs.record(n, cs.streams_of(n)[-1]),
+                                                                               cs.record(n, cs.streams_of(n)[-1])[1:])]
+    assert any(a < b for a, b in quals) and any(a > b for a, b in quals)
+    assert {g["key"][3] for n in cs.SCRIPTS for g in cs.record(n, cs.streams_of(n)[-1])} == set(orc.KIND_NAMES)
+    # a capacity-bound call leaves pending frames partly drained before the next op, which grows or shrinks the filter
+    partly = [(n, g["index"]) for n in cs.SCRIPTS for g in cs.record(n, cs.streams_of(n)[-1])
+              if g["short"] and 0 < g["calls"][-1]["head"].shape[0] - (g["key"][2] - 1) < g["model"].pending]
+    assert len(partly) >= 2, partly
+    # one coalesced call per script, its first chunk shorter than the pending count wherever a script leaves pending frames
+    for n in cs.SCRIPTS:
+        chunked = [g for g in cs.record(n, cs.streams_of(n)[-1]) if g["chunked"]]
+        assert len(chunked) == 1 and [c["group"] for c in chunked[0]["calls"]][:3] == [0, 0, 0]
+        if any(g["model"].pending and not g["short"] for g in cs.record(n, cs.streams_of(n)[-1])):
+            assert 0 < chunked[0]["calls"][0]["x"].shape[0] < chunked[0]["model"].pending, n
+    # the mixed stream: an int16 call right after an op over a head that holds fractions, and the other way round
+    firsts = [(g["calls"][0]["io"], bool((g["head"] != np.rint(g["head"])).any())) for g in cs.record("mixed data", "mixed")[1:]]
+    assert ("int16", True) in firsts and any(io == "float" for io, _ in firsts), firsts
+
+
+def test_every_filter_a_script_visits_has_a_segment_long_enough_for_the_statistics():
+    """what the GPU tests assert of their own runs, on the oracle alone: (b) and (c) are computed on every distinct filter"""
+    for name in cs.SCRIPTS:
+        segs = cs.record(name, cs.streams_of(name)[-1])
+        judged = {g["key"] for g in segs if (cs.judge(g, [c["want"] for c in g["calls"]], 32)[1] or {}).get("judged")}
+        assert judged == {g["key"] for g in segs}, (name, {g["key"] for g in segs} - judged)
+
+
+@pytest.mark.parametrize("name", ALL_SCRIPTS)
+def test_the_oracle_the_reference_and_the_clean_chain_pass_on_every_segment(name):
+    for stream in cs.streams_of(name):
+        segs = cs.record(name, stream)
+        others = [cs.record(name, stream, orc.Reference)] if orc.have_reference() else []
+        for n, seg in enumerate(segs):
+            model, tag = seg["model"], (name, stream, seg["index"], seg["op"])
+            want = [c["want"] for c in seg["calls"]]
+            for other in others:                    # the reference's own C: the same segment, and the same judgement
+                ref = other[n]
+                assert ref["start"] == seg["start"] and np.array_equal(ref["head"], seg["head"]), tag
+                assert np.array_equal(ref["fed"], seg["fed"]) and np.array_equal(ref["model"].rows, model.rows), tag
+                fails, _ = cs.judge(seg, [c["want"] for c in ref["calls"]], 32, want)
+                assert not fails, (tag, "reference", fails)
+            fails, stats = cs.judge(seg, want, 32, [c["want"] for c in others[0][n]["calls"]] if others else None)
+            assert not fails, (tag, "oracle", fails)
+            truth, _ = cs.truth_of(seg)
+            clean = cs.split(seg, em.chain32(model, seg["fed"], truth.shape[0]))
+            fails, cstats = cs.judge(seg, clean, 32, clean if model.double_kind else want)
+            assert not fails, (tag, "chain32", fails)
+            if stats:
+                print("%s: %d float samples, rms(e) oracle %.3f chain32 %.3f, bias %.1f / %.1f sigma%s" % (
+                    tag, stats["n"], stats["rms"], cstats["rms"], stats["z"], cstats["z"], "" if stats["judged"] else " ((a) alone)"))
+
+
+def _segment(name, index, stream="float"):
+    seg = cs.record(name, stream)[index]
+    truth, mag = cs.truth_of(seg)
+    return seg, seg["model"], truth.shape[0] - seg["model"].den - 2     # (room for the defects that read further)
+
+
+def _judge_planted(seg, got, bits=32):
+    """the checks on the first len(got) outputs of the segment's float stream -> failures"""
+    model, (truth, mag) = seg["model"], cs.truth_of(seg)
+    n = got.shape[0]
+    yard = cs.outputs(seg)[:n] if bits == 64 or not model.double_kind else em.chain32(model, seg["fed"], n)
+    fails, _ = em.judge_float(model, seg["fed"], got, truth[:n], mag[:n], bits, yard, margin=em.MARGIN if bits == 32 else 1.0)
+    return fails
+
+
+# (script, segment): what the segment starts with
+START_SEGMENTS = [("period", 3), ("period", 5), ("folded", 2), ("slide", 4), ("wide frames", 2)]
+PENDING_SEGMENTS = [("period", 4), ("folded", 1), ("folded", 2), ("slide", 3), ("slide", 4), ("exact fallback", 2)]
+GROWN_SEGMENTS = [("period", 1), ("slide", 1), ("wide frames", 1)]
+
+
+@pytest.mark.parametrize("defect", ["start phase taken as 0", "frac0 + 1", "frac0 - 1", "last0 + 1", "last0 - 1"])
+@pytest.mark.parametrize("name,index", START_SEGMENTS)
+def test_a_wrong_start_of_a_segment_fails_the_hard_check(name, index, defect):
+    seg, model, n = _segment(name, index)
+    last0, frac0 = seg["start"]
+    assert frac0 >= 1 and last0 >= 1, "the segment must start off the grid for these defects to exist"
+    start = {"start phase taken as 0": (last0, 0), "frac0 + 1": (last0, frac0 + 1), "frac0 - 1": (last0, frac0 - 1),
+             "last0 + 1": (last0 + 1, frac0), "last0 - 1": (last0 - 1, frac0)}[defect]
+    assert not _judge_planted(seg, em.chain32(model, seg["fed"], n))
+    fails = _judge_planted(seg, em.chain32(model.segment(model.head, start), seg["fed"], n))
+    assert any(f.startswith("(a)") for f in fails), (defect, fails)
+
+
+@pytest.mark.parametrize("defect", ["pending frames dropped", "pending frames behind the new input",
+                                    "one pending frame from the neighbouring slot"])
+@pytest.mark.parametrize("name,index", PENDING_SEGMENTS)
+def test_misplaced_pending_frames_fail_the_hard_check(name, index, defect):
+    seg, model, n = _segment(name, index)
+    t, m, fed = model.taps, model.pending, seg["fed"]
+    assert m >= 2
+    if defect == "pending frames dropped":
+        bad = model.segment(model.head[: t - 1], seg["start"])
+        n = min(n, (fed.shape[0] - t - m) * model.den // model.num)
+    elif defect == "pending frames behind the new input":
+        bad, fed = model.segment(model.head[: t - 1], seg["start"]), np.concatenate([fed, model.head[t - 1:]])
+    else:
+        head = model.head.copy()
+        head[t - 1 + m // 2] = head[t + m // 2]
+        bad = model.segment(head, seg["start"])
+    fails = _judge_planted(seg, em.chain32(bad, fed, n))
+    assert any(f.startswith("(a)") for f in fails), (defect, fails)
+
+
+@pytest.mark.parametrize("name,index", GROWN_SEGMENTS)
+def test_a_grown_history_padded_at_the_back_fails_the_hard_check(name, index):
+    seg, model, n = _segment(name, index)
+    before = cs.record(name, "float")[index - 1]["model"]
+    assert model.taps > before.taps and model.pending == 0
+    pad = int(np.argmax(np.abs(model.head).sum(axis=1) > 0))       # the frames of silence the op put in FRONT
+    assert pad > 0 and not model.head[:pad].any() and model.head[-1].any()
+    bad = model.segment(np.concatenate([model.head[pad:], model.head[:pad]]), seg["start"])
+    fails = _judge_planted(seg, em.chain32(bad, seg["fed"], n))
+    assert any(f.startswith("(a)") for f in fails), fails
+
+
+def test_no_two_qualities_share_a_filter_length():
+    """... so the rows of the filter before a set_quality never FIT the segment after it: only a cutoff change at equal
+    length (set_rate_frac between 16:13 and 17:13, 48:47 and 50:47) lets a launch run the previous filter's rows"""
+    for (i, o) in ((48000, 48000), (44100, 48000), (48000, 44100), (48000, 8000)):
+        assert len({orc.Oracle(1, i, o, q).taps for q in range(11)}) == 11
+
+
+@pytest.mark.parametrize("name", list(cs.EXTRA))
+def test_the_previous_filter_s_rows_fail_the_hard_check(name):
+    seg, model, n = _segment(name, 1)
+    before = cs.record(name, "float")[0]["model"]
+    assert before.rows.shape == model.rows.shape and not np.array_equal(before.rows, model.rows)
+    assert not _judge_planted(seg, em.chain32(model, seg["fed"], n))
+    fails = _judge_planted(seg, em.chain32(model, seg["fed"], n, rows=before.rows))
+    assert any(f.startswith("(a)") for f in fails), fails
+
+
+def test_64_bit_accumulation_claimed_after_quality_3_to_10_over_the_fp32_chain_fails():
+    seg, model, n = _segment("period", 3)
+    assert cs.record("period", "float")[2]["quality"] == 3 and seg["quality"] == 10 and model.double_kind
+    chain = em.chain32(model, seg["fed"], n)
+    assert not _judge_planted(seg, chain, 32)
+    fails = _judge_planted(seg, chain, 64)
+    assert any(f.startswith("(a)") for f in fails) and any(f.startswith("(b)") for f in fails), fails
+    # ... while what does accumulate in 64 bits passes as such
+    assert not _judge_planted(seg, cs.truth_of(seg)[0][:n].astype(np.float32), 64)
+
+
+# the segments of "mixed data" on which an int16 image of the HEAD fails (a): the 352- and 224-tap filters whose first calls
+# read the head through many taps.  Not segments 1, 2 and 5: one call that makes 14 samples from pending frames alone; 560
+# taps, whose fp32 bound (0.5 LSB at this loudness) is wider than the image's error (0.2 LSB rms -- see
+# test_an_int16_window_on_float_data_fails_the_hard_check); a skip_zeros that moved the start past most of the head.
+INT16_IMAGE_OF_THE_HEAD_SHOWS = {3, 4}
+
+
+def test_a_head_that_passed_through_an_int16_image_fails_the_hard_check_on_float_data():
+    """float_inputs kinds P and A across a control call: the head of the segment holds fractions"""
+    shown = set()
+    for seg in cs.record("mixed data", "mixed")[1:]:
+        model, (truth, _) = seg["model"], cs.truth_of(seg)
+        assert (seg["head"] != np.rint(seg["head"])).any()
+        clean = cs.split(seg, em.chain32(model, seg["fed"], truth.shape[0]))
+        assert not cs.judge(seg, clean, 32)[0]
+        image = model.segment(np.rint(model.head), seg["start"])
+        fails, _ = cs.judge(seg, cs.split(seg, em.chain32(image, seg["fed"], truth.shape[0])), 32)
+        assert all(f.startswith(("float (a)", "int16 (a)")) for f in fails), fails
+        if any(f.startswith("float (a)") for f in fails):
+            shown.add(seg["index"])
+    assert shown == INT16_IMAGE_OF_THE_HEAD_SHOWS, shown

@@ -60,21 +60,24 @@ def _samples(frames, ch, seed, taps, tone=False):
     return em.with_silence(x, taps) if frames > 2 * taps + 64 else x
 
 
-def _judge(family, name, model, bits, fed, got16, gotf, wantf, fedf=None, underflow=False):
+def _judge(family, name, model, bits, fed, got16, gotf, wantf, fedf=None, underflow=False, statistics=True,
+           truth_mag=None):
     """(a) on the int16 stream, (a) (b) (c) on the float stream.  Both streams consumed the same samples `fed`, unless the
     float stream had a sample maker of its own: `fedf` is what it consumed then (got16 None: there was no int16 stream).
-    underflow: the float stream is judged by (a) alone, with the bounds' underflow term (float_inputs kind D)."""
+    underflow: the float stream is judged by (a) alone, with the bounds' underflow term (float_inputs kind D).
+    statistics False: (a) alone, with no yardstick and no figures noted (a segment of a few samples, whose rms says
+    nothing).  truth_mag: model.truth(fed, outputs) where the caller has it already.  -> the float comparison's stats ("yard" in them: (b) was judged)."""
     fails, differing = [], None
     if got16 is not None:
         assert got16.shape == gotf.shape, (name, got16.shape, gotf.shape)
-        truth, mag = model.truth(fed, got16.shape[0])
+        truth, mag = truth_mag or model.truth(fed, got16.shape[0])
         fails = ["int16 (a) " + m for m in em.hard_int16(model, fed, got16, truth, mag, bits, tile=model.num)]
         differing = float((got16.astype(np.int64) != em.halfup(truth)).mean()) if got16.size else 0.0
     if fedf is None:
         fedf = fed
     else:
         truth, mag = model.truth(fedf, gotf.shape[0])
-    if underflow:
+    if underflow or not statistics:
         yard, margin = None, em.MARGIN
     elif bits == 64:
         yard, margin = wantf, 1.0           # no worse than the reference's double kernels
@@ -83,12 +86,13 @@ def _judge(family, name, model, bits, fed, got16, gotf, wantf, fedf=None, underf
     else:
         yard, margin = wantf, MARGINS.get(family, em.MARGIN)
     ffails, stats = em.judge_float(model, fedf, gotf, truth, mag, bits, yard, margin, tile=model.num, underflow=underflow)
-    _note(family, None if underflow else stats, differing)
+    _note(family, None if underflow or not statistics else stats, differing)
     print("%s %s bits %d: n %d rms(e) %.3f yardstick %.3f max|e| %.2f bias %.1f sigma%s%s" % (
         family, name, bits, stats["n"], stats["rms"], stats.get("yard", 0.0), stats["max"], stats["z"],
         "" if differing is None else ", int16 off halfup(truth) %.2e" % differing,
         " ((a) alone, with the underflow term)" if underflow else ""))
     assert not fails + ffails, (family, name, fails + ffails)
+    return stats
 
 
 def _expect_bits(info, model):

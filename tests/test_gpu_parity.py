@@ -648,14 +648,15 @@ def test_mid_stream_control_scripts_exact_mode(golden):
         r.close()
 
 
-def test_mid_stream_control_scripts_fast_mode(golden):
-    """Same scripts in FAST mode against the oracle running alongside: identical bookkeeping,
-    int16 outputs within +-1 LSB, float outputs within 2e-6 of the window's scale, and the stream lines
+@pytest.mark.parametrize("mode", [speexhip.MODE_FAST, None])
+def test_mid_stream_control_scripts_fast_mode(golden, mode):
+    """Same scripts in FAST mode, and in the default mode (no mode named), against the oracle running alongside: identical
+    bookkeeping, int16 outputs within +-1 LSB, float outputs within 2e-6 of the window's scale, and the stream lines
     (history ++ pending frames) equal after every op."""
     from make_golden import apply_op
     for c in golden["control_cases"]:
         ch = c["channels"]
-        r = speexhip.Resampler(ch, c["in_rate"], c["out_rate"], c["quality"], mode=speexhip.MODE_FAST)
+        r = speexhip.Resampler(ch, c["in_rate"], c["out_rate"], c["quality"], mode=mode)
         ref = orc.Oracle(ch, c["in_rate"], c["out_rate"], c["quality"])
         for k, (op, want) in enumerate(zip(c["ops"], c["results"])):
             # int16 and float calls alternate on one state, so a float call may see int16-scale
@@ -1071,8 +1072,9 @@ def test_one_very_large_call():
     r.close()
 
 
-def test_random_control_soak_against_the_oracle():
-    """Beyond the 40 recorded scripts: 30 fresh random scripts (seeded) of process / process_float /
+@pytest.mark.parametrize("fast_mode", [speexhip.MODE_FAST, None])
+def test_random_control_soak_against_the_oracle(fast_mode):
+    """(fast_mode: what the odd seeds run -- MODE_FAST, or the default mode, no mode named.)  Beyond the 40 recorded scripts: 30 fresh random scripts (seeded) of process / process_float /
     coalesced chunks / set_rate / set_rate_frac / set_quality / skip_zeros / reset_mem over rates that
     reach every kernel (period incl. padded, paired-period and wide-window layouts, slide incl. 6:1,
     exact fallback), EXACT mode bit-for-bit and FAST mode within tolerance against the oracle (which
@@ -1082,7 +1084,7 @@ def test_random_control_soak_against_the_oracle():
         rng = np.random.RandomState(5000 + seed)
         ch = int(rng.choice([1, 2, 2, 3, 4]))
         args = (ch, int(rng.choice(rates)), int(rng.choice(rates)), int(rng.randint(0, 11)))
-        mode = speexhip.MODE_EXACT if seed % 2 == 0 else speexhip.MODE_FAST
+        mode = speexhip.MODE_EXACT if seed % 2 == 0 else fast_mode
         r = speexhip.Resampler(*args, mode=mode)
         ref = orc.Oracle(*args)
         for step in range(14):
