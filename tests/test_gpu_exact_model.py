@@ -358,3 +358,12 @@ def test_exact_model_is_wired_into_the_diagnostics_children():
     src = inspect.getsource(par.test_int16_window_on_small_launches_too)
     assert "exact_model_mixed_entry_points" in src and "EXACT_MODEL_FLOAT_FILE" in src
     assert par.EXACT_MODEL_FLOAT_FILE.endswith("test_gpu_exact_model_float.py") and os.path.exists(par.EXACT_MODEL_FLOAT_FILE)
+    # ... and the period streams in small calls of test_gpu_exact_model_streaming.py: every start phase on the int16
+    # window and on phase pairs, which small launches take in those children alone
+    for fn in (par.test_int16_window_on_small_launches_too, par.test_phase_pair_plans_for_mono_on_every_launch):
+        src = inspect.getsource(fn)
+        assert "exact_model_streaming_period" in src and "EXACT_MODEL_STREAMING_FILE" in src, fn.__name__
+    assert par.EXACT_MODEL_STREAMING_FILE.endswith("test_gpu_exact_model_streaming.py")
+    assert os.path.exists(par.EXACT_MODEL_STREAMING_FILE)
+    import test_gpu_exact_model_streaming as xs
+    assert hasattr(xs, "test_exact_model_streaming_period") and xs.DEFAULT == speexhip.MODE_FAST_FIXED

@@ -31,6 +31,7 @@ DIAG_LIB = os.path.join(ROOT, "node-speex-resampler_amd", "ab", "libspeexhip_dia
 # the exact-model tests of the period kernel run in the diagnostics children below as well (instances only they can force)
 EXACT_MODEL_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_gpu_exact_model.py")
 EXACT_MODEL_FLOAT_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_gpu_exact_model_float.py")
+EXACT_MODEL_STREAMING_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_gpu_exact_model_streaming.py")
 
 
 def diag_env(**switches):
@@ -820,14 +821,15 @@ def test_window_layout_variants_of_the_period_kernel():
 def test_int16_window_on_small_launches_too():
     """The int16-window plan normally serves only launches that fill the chip (a smaller one runs the float
     window in r = 5 shares, which is faster there).  SPEEXHIP_W16_ALWAYS=1 (read once per process) lifts that,
-    so that the small multi-call cases of the layout and mixed int16 / float tests run over it as well."""
+    so that the small multi-call cases of the layout and mixed int16 / float tests run over it as well -- and the
+    period streams in small calls (test_gpu_exact_model_streaming.py), which meet every start phase on it."""
     import subprocess
     import sys
     env = diag_env(SPEEXHIP_MODE="fast", SPEEXHIP_W16_ALWAYS="1")
     res = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.abspath(__file__), EXACT_MODEL_FILE,
-                          EXACT_MODEL_FLOAT_FILE, "-k",
+                          EXACT_MODEL_FLOAT_FILE, EXACT_MODEL_STREAMING_FILE, "-k",
                           "window_layout_variants or int16_window_plan_serves or edge_cases or exact_model_period_layouts "
-                          "or exact_model_mixed_entry_points"],
+                          "or exact_model_mixed_entry_points or exact_model_streaming_period"],
                          env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
 
@@ -1908,10 +1910,11 @@ def test_phase_pair_plans_for_mono_on_every_launch():
     import subprocess
     import sys
     env = diag_env(SPEEXHIP_MODE="fast", SPEEXHIP_PP="1")
-    res = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.abspath(__file__), EXACT_MODEL_FILE, "-k",
+    res = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.abspath(__file__), EXACT_MODEL_FILE,
+                          EXACT_MODEL_STREAMING_FILE, "-k",
                           "(mono or every_golden_case or many_rates or window_layout_variants or edge_cases or tap_range_shares "
                           "or int16_window_plan_serves or history_after or float_entry or control_scripts_fast or many_generation "
-                          "or exact_model_period_layouts) and not phase_pair"],   # (not this test again)
+                          "or exact_model_period_layouts or exact_model_streaming_period) and not phase_pair"],   # (not this test again)
                          env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
     # ... and by the rule: a batch of a wide-window decimator runs over them, one big stream does not; both match
