@@ -415,7 +415,8 @@ SPEEXHIP_API int speexhip_batch_process_planar_float_device(
 
 /* ------------------------------------------------------------------------------------------
  * Sample formats: a formatted call names the format of its input and of its output independently
- * (a decoder's s16le in, Web Audio's float32 in +-1.0 out; 24-bit WAV / FLAC; 8-bit telephony).
+ * (a decoder's s16le in, Web Audio's float32 in +-1.0 out; 24-bit WAV / FLAC; 8-bit telephony -- for
+ * G.711 mu-law / A-law see "Companded formats" below).
  * The library's internal unit is the reference's: one int16 step = 1.0f, what the float entry point
  * takes and gives.  Every format has a full scale FS:
  *
@@ -450,7 +451,10 @@ enum {
   SPEEXHIP_FMT_S24 = 2,
   SPEEXHIP_FMT_S32 = 3,
   SPEEXHIP_FMT_F32 = 4,
-  SPEEXHIP_FMT_F32N = 5
+  SPEEXHIP_FMT_F32N = 5,
+  /* companded formats ("Companded formats" below) start at 16; 6..15 stay invalid */
+  SPEEXHIP_FMT_ULAW = 16,
+  SPEEXHIP_FMT_ALAW = 17
 };
 /* Bytes of one sample of a format (host only); 0 for an unknown format. */
 SPEEXHIP_API uint32_t speexhip_sample_bytes(int fmt);
@@ -563,7 +567,8 @@ SPEEXHIP_API int speexhip_batch_process_interleaved_mix_device(SpeexHipBatch *b,
  * dither nor move the position.  `position` is the index of the stream's next output frame:
  * set_dither sets it (a stream can be resumed in a new state), and while the kind is not NONE every
  * formatted or mixed call advances it by the frames it produced, whatever the output format.  Then
- *   - integer output formats are dithered, the float ones (F32, F32N) written as ever;
+ *   - integer output formats are dithered (and the companded ones, at their int16 stage: "Companded
+ *     formats"), the float ones (F32, F32N) written as ever;
  *   - S16 -> S16 is no longer the int16 call: it runs as the float call between the two conversions,
  *     with the float entry's counter rules (as a mixed call with a matrix does);
  *   - the zero fallback's zeros are dithered like any other value;
@@ -586,6 +591,49 @@ SPEEXHIP_API int speexhip_batch_get_dither(SpeexHipBatch *b, uint32_t stream, in
 /* Host only, no GPU: d[i] = the d above for idx = first_index + i (wrapping), i < n -- the very
  * statement the kernels compile, for the tests to hold against their model. */
 SPEEXHIP_API int speexhip_debug_dither(int kind, uint64_t seed, uint64_t first_index, uint32_t n, double *d);
+
+/* ------------------------------------------------------------------------------------------
+ * Companded formats: G.711 as telephony carries it (RTP PCMU / PCMA, 8 kHz), one byte per sample, no
+ * alignment needed.  SPEEXHIP_FMT_ULAW = 16 and SPEEXHIP_FMT_ALAW = 17: companded formats start at 16,
+ * the values 6..15 stay invalid.  Both are accepted wherever a format is named -- the formatted and the
+ * mixed calls, host, device and batch forms -- and speexhip_sample_bytes gives 1 for them.
+ *
+ * Decode, storage byte b -> the internal float x, an exact integer in int16 units:
+ *   mu-law  u = ~b & 0xFF,  e = (u >> 4) & 7,  m = u & 15
+ *           t = (((m << 3) + 0x84) << e) - 0x84;   x = (u & 0x80) ? -t : t
+ *           range +-32124; byte 0x7F is the negative zero and decodes to 0
+ *   A-law   a = b ^ 0x55,  e = (a >> 4) & 7,  m = a & 15
+ *           t = e == 0 ? (m << 4) + 8 : ((m << 4) + 0x108) << (e - 1);   x = (a & 0x80) ? t : -t
+ *           range +-32256
+ *
+ * Encode, FIR value y -> byte: the S16 output rule, then the G.711 compressor on that int16 -- the
+ * bytes a caller gets from the S16 call followed by its own encoder.
+ *   q = clamp(halfup(y), -32768, 32767) as for S16; NaN -> q = 0, +-inf -> the rails.  With dither on
+ *   q comes from the dithered S16 rule above: d in int16 steps, v = y, t = v + d, floor(t + 0.5).
+ *   mu-law  s = q < 0;  mag = min(|q|, 32635) + 132;  e = floor(log2(mag)) - 7  (0..7)
+ *           m = (mag >> (e + 3)) & 15;   b = ~((s << 7) | (e << 4) | m) & 0xFF
+ *   A-law   pos = q >= 0;  mag = (pos ? q : -q - 1) >> 3  (0..4095)
+ *           e = mag < 32 ? 0 : floor(log2(mag)) - 4;   m = e == 0 ? (mag >> 1) & 15 : (mag >> e) & 15
+ *           b = ((pos << 7) | (e << 4) | m) ^ 0x55
+ * The format's zero (NaN, the zero fallback's silence) is 0xFF for mu-law and 0xD5 for A-law; the rails
+ * are 0x80 / 0x00 for mu-law and 0xAA / 0x2A for A-law.  A-law round-trips all 256 bytes through decode
+ * and encode; mu-law all but the negative zero (0x7F -> 0xFF).
+ *
+ * In the calls: a companded format on either side always runs as the float call between the two
+ * conversions, with the float entry's counter rules (speexhip_resampler_peek with float_entry = 1
+ * sizes it); no companded pair is an identity pair -- ULAW -> ULAW decodes, filters and encodes.
+ * State, history and position are the float call's, so these calls mix freely with all others on one
+ * state.  For dither the companded outputs count as integer formats: the noise joins at the int16
+ * stage, position advances as for any formatted call, and a state whose channels the per-channel
+ * calls moved apart returns BAD_STATE with dither on and goes channel by channel without it.
+ *
+ * ABI note: 0.7 + g711 adds two enum values and two entry points; SpeexHipInfo, the error codes and the
+ * version string are unchanged. */
+/* Host only, no GPU: the very statements the kernels compile, for the tests to hold against their
+ * model.  x[i] = decode(codes[i]); codes[i] = encode(y[i]) with d[i] (int16 steps) added before the
+ * rounding, d == NULL = no dither.  INVALID_ARG for a format that is not companded. */
+SPEEXHIP_API int speexhip_debug_g711_decode(int fmt, const uint8_t *codes, uint32_t n, float *x);
+SPEEXHIP_API int speexhip_debug_g711_encode(int fmt, const float *y, const double *d, uint32_t n, uint8_t *codes);
 
 /* Mid-stream control for every stream of a batch (same semantics as the single-stream calls). */
 SPEEXHIP_API int speexhip_batch_set_rate_frac(SpeexHipBatch *b, uint32_t ratio_num, uint32_t ratio_den,

@@ -9,6 +9,7 @@
 #include "devices.h"
 #include "dither.h"
 #include "engine.h"
+#include "g711.h"
 #include "pool.h"
 
 using speexhip::Batch;
@@ -580,7 +581,9 @@ int speexhip_batch_process_planar_float_device(SpeexHipBatch *b, const float *d_
 
 uint32_t speexhip_sample_bytes(int fmt) {
   switch (fmt) {
-    case SPEEXHIP_FMT_U8: return 1;
+    case SPEEXHIP_FMT_U8:
+    case SPEEXHIP_FMT_ULAW:
+    case SPEEXHIP_FMT_ALAW: return 1;
     case SPEEXHIP_FMT_S16: return 2;
     case SPEEXHIP_FMT_S24: return 3;
     case SPEEXHIP_FMT_S32:
@@ -661,6 +664,23 @@ int speexhip_batch_get_dither(SpeexHipBatch *b, uint32_t stream, int *kind, uint
 int speexhip_debug_dither(int kind, uint64_t seed, uint64_t first_index, uint32_t n, double *d) {
   if (!speexhip::dither::known_kind(kind) || (d == nullptr && n != 0)) return SPEEXHIP_ERR_INVALID_ARG;
   for (uint32_t i = 0; i < n; i++) d[i] = speexhip::dither::noise(kind, seed, first_index + i);
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+int speexhip_debug_g711_decode(int fmt, const uint8_t *codes, uint32_t n, float *x) {
+  if ((fmt != SPEEXHIP_FMT_ULAW && fmt != SPEEXHIP_FMT_ALAW) || ((codes == nullptr || x == nullptr) && n != 0))
+    return SPEEXHIP_ERR_INVALID_ARG;
+  for (uint32_t i = 0; i < n; i++)
+    x[i] = static_cast<float>(fmt == SPEEXHIP_FMT_ULAW ? speexhip::g711::ulaw_decode(codes[i]) : speexhip::g711::alaw_decode(codes[i]));
+  return SPEEXHIP_ERR_SUCCESS;
+}
+int speexhip_debug_g711_encode(int fmt, const float *y, const double *d, uint32_t n, uint8_t *codes) {
+  if ((fmt != SPEEXHIP_FMT_ULAW && fmt != SPEEXHIP_FMT_ALAW) || ((y == nullptr || codes == nullptr) && n != 0))
+    return SPEEXHIP_ERR_INVALID_ARG;
+  for (uint32_t i = 0; i < n; i++) {
+    const int32_t q = d != nullptr ? speexhip::g711::s16_of_dither(y[i], d[i]) : speexhip::g711::s16_of(y[i]);
+    codes[i] = static_cast<uint8_t>(fmt == SPEEXHIP_FMT_ULAW ? speexhip::g711::ulaw_encode(q) : speexhip::g711::alaw_encode(q));
+  }
   return SPEEXHIP_ERR_SUCCESS;
 }
 

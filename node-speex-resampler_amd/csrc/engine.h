@@ -85,7 +85,8 @@ class Batch {
   // Formatted calls (formats.cpp; SPEEXHIP_FMT_*): the float call on the converted input followed by the output
   // conversion -- convert_in / convert_out (kernels_convert.hip) either side of process_device(float) on the state's
   // scratch images (the planar calls' ones: calls on a state are ordered).  S16 -> S16, F32 -> F32 and F32N -> F32N go
-  // straight to process_device.  Strides are in samples of the side's format.  plans_out: the plan of every channel of
+  // straight to process_device; the companded ULAW / ALAW (g711.h) are formats like the others and make no such pair.
+  // Strides are in samples of the side's format.  plans_out: the plan of every channel of
   // a state whose channels stand apart (empty otherwise).
   int process_fmt_device(int in_fmt, const void *d_in, uint64_t in_stride, uint32_t *in_len, int out_fmt, void *d_out,
                          uint64_t out_stride, uint32_t *out_len, hipStream_t stream,

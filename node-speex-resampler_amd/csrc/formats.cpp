@@ -20,7 +20,9 @@ namespace {
 inline size_t line_pitch(size_t elements) { return (elements + 63) & ~static_cast<size_t>(63); }
 inline size_t fmt_bytes(int fmt) {
   switch (fmt) {
-    case SPEEXHIP_FMT_U8: return 1;
+    case SPEEXHIP_FMT_U8:
+    case SPEEXHIP_FMT_ULAW:
+    case SPEEXHIP_FMT_ALAW: return 1;
     case SPEEXHIP_FMT_S16: return 2;
     case SPEEXHIP_FMT_S24: return 3;
     case SPEEXHIP_FMT_S32:
@@ -33,8 +35,10 @@ inline size_t fmt_bytes(int fmt) {
 inline bool same_bytes_pair(int in_fmt, int out_fmt) {
   return in_fmt == out_fmt && (in_fmt == SPEEXHIP_FMT_S16 || in_fmt == SPEEXHIP_FMT_F32 || in_fmt == SPEEXHIP_FMT_F32N);
 }
+// (the companded formats quantise to int16 on their way out: dithered like the integer ones)
 inline bool integer_fmt(int fmt) {
-  return fmt == SPEEXHIP_FMT_U8 || fmt == SPEEXHIP_FMT_S16 || fmt == SPEEXHIP_FMT_S24 || fmt == SPEEXHIP_FMT_S32;
+  return fmt == SPEEXHIP_FMT_U8 || fmt == SPEEXHIP_FMT_S16 || fmt == SPEEXHIP_FMT_S24 || fmt == SPEEXHIP_FMT_S32 ||
+         fmt == SPEEXHIP_FMT_ULAW || fmt == SPEEXHIP_FMT_ALAW;
 }
 }  // namespace
 

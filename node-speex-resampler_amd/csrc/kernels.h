@@ -227,7 +227,7 @@ hipError_t launch_mix_in(int fmt, const MixPack &pack, uint32_t n, uint32_t max_
 hipError_t launch_mix_out(int fmt, const MixPack &pack, uint32_t n, uint32_t max_frames, hipStream_t stream);
 
 // ---- dither on the way out (dither.h): convert_out_dither<F> / mix_out_dither<F>, the output pass of a formatted or mixed
-// call of a state with dither on, for the integer formats.  The streams' arguments are the undithered pass's; what the
+// call of a state with dither on, for the integer formats and the companded ones (g711.h).  The streams' arguments are the undithered pass's; what the
 // dither needs travels beside them in a second kernel argument.
 struct DitherStream {       // one stream's share
   uint64_t seed;            // the stream's own seed

@@ -1,5 +1,6 @@
 // kernels_convert.hip -- sample formats <-> the internal float image: the two passes either side of a formatted call
-// (engine.h, process_fmt_device).  convert_in<F> reads storage of format F (u8, s16, packed s24, s32, float in +-1.0)
+// (engine.h, process_fmt_device).  convert_in<F> reads storage of format F (u8, s16, packed s24, s32, float in +-1.0,
+// G.711 mu-law and A-law)
 // and writes the float image the FIR kernels read, in the library's unit (one int16 step = 1.0f); convert_out<F> reads
 // the image they wrote and stores format F, rounding half up and saturating the integer formats.  Elementwise.
 //
@@ -8,11 +9,11 @@
 //
 // Vector path (whole tiles; storage and image 16-byte aligned; step 1 -- decided per workgroup from the stream's
 // arguments, so it is wave-uniform): every access is 16 bytes per lane.  A lane owns G consecutive samples per pass --
-// G = 16 for u8 (one 16-byte piece of storage, four of the image) and packed s24 (three pieces of storage, unpacked /
+// G = 16 for the 1-byte formats u8, mu-law and A-law (one 16-byte piece of storage, four of the image) and packed s24 (three pieces of storage, unpacked /
 // packed in registers with byte shifts across dword pairs, four of the image), 8 for s16, 4 for the 4-byte formats --
 // and a workgroup makes 16 / G passes, lane t on group pass * 256 + t.
 //
-// Element path (any byte address for u8 / s24, any element-aligned one for the rest; partial tiles; strided samples of
+// Element path (any byte address for the 1-byte formats and s24, any element-aligned one for the rest; partial tiles; strided samples of
 // a state whose channels stand apart): sample by sample, s24 byte by byte, consecutive lanes on consecutive samples.
 //
 // The image convert_in writes is read by the very next kernel and convert_out's source was written by the previous
@@ -21,7 +22,7 @@
 // The formats themselves -- one sample to and from the image, rounding half up, and the loads / stores of one sample --
 // are stated in format_device.h, which the mixing kernels (kernels_mix.hip) share.
 //
-// convert_out_dither<F> (integer formats; a state with dither on): convert_out with the dither of dither.h added before
+// convert_out_dither<F> (integer and companded formats; a state with dither on): convert_out with the dither of dither.h added before
 // the rounding.  Instances of their own beside convert_out, which stays what it was: the same two paths, the same
 // bytes from both.  Sample k of a stream has idx first + k (DitherPack), so a lane's group on the vector path is a run
 // of G consecutive idx: the inner half of the generator's word, which changes once per 2^32 samples, is taken once per
@@ -46,7 +47,7 @@ constexpr uint32_t kLanes = 256;
 constexpr uint32_t kTile = 4096;  // samples per workgroup
 
 // samples a lane owns per pass of the vector path: whole 16-byte pieces on both sides
-constexpr uint32_t group_of(int f) { return f == SPEEXHIP_FMT_U8 || f == SPEEXHIP_FMT_S24 ? 16u : f == SPEEXHIP_FMT_S16 ? 8u : 4u; }
+constexpr uint32_t group_of(int f) { return bytes_of(f) == 1 || f == SPEEXHIP_FMT_S24 ? 16u : f == SPEEXHIP_FMT_S16 ? 8u : 4u; }
 
 // ---- 16 bytes per lane ---------------------------------------------------------------------------------------------
 // sample j (compile-time) of a lane's group, from / into the group's storage words
@@ -216,6 +217,8 @@ hipError_t launch_convert(int fmt, const ConvertPack &pack, uint32_t n, uint64_t
     case SPEEXHIP_FMT_S24: CONVERT_LAUNCH(SPEEXHIP_FMT_S24);
     case SPEEXHIP_FMT_S32: CONVERT_LAUNCH(SPEEXHIP_FMT_S32);
     case SPEEXHIP_FMT_F32N: CONVERT_LAUNCH(SPEEXHIP_FMT_F32N);
+    case SPEEXHIP_FMT_ULAW: CONVERT_LAUNCH(SPEEXHIP_FMT_ULAW);
+    case SPEEXHIP_FMT_ALAW: CONVERT_LAUNCH(SPEEXHIP_FMT_ALAW);
     default: return hipErrorInvalidValue;  // (F32 is the image's own format: nothing to convert)
   }
   return hipGetLastError();
@@ -241,6 +244,8 @@ hipError_t launch_convert_out_dither(int fmt, const ConvertPack &pack, const Dit
     case SPEEXHIP_FMT_S16: hipLaunchKernelGGL((convert_out_dither<SPEEXHIP_FMT_S16>), grid, block, 0, stream, pack, dith); break;
     case SPEEXHIP_FMT_S24: hipLaunchKernelGGL((convert_out_dither<SPEEXHIP_FMT_S24>), grid, block, 0, stream, pack, dith); break;
     case SPEEXHIP_FMT_S32: hipLaunchKernelGGL((convert_out_dither<SPEEXHIP_FMT_S32>), grid, block, 0, stream, pack, dith); break;
+    case SPEEXHIP_FMT_ULAW: hipLaunchKernelGGL((convert_out_dither<SPEEXHIP_FMT_ULAW>), grid, block, 0, stream, pack, dith); break;
+    case SPEEXHIP_FMT_ALAW: hipLaunchKernelGGL((convert_out_dither<SPEEXHIP_FMT_ALAW>), grid, block, 0, stream, pack, dith); break;
     default: return hipErrorInvalidValue;  // (the float formats are not dithered)
   }
   return hipGetLastError();

@@ -22,13 +22,13 @@
 // banks (stride 8: frame 4a + b -> bank 8b + a).  The copies move their 16-byte pieces as four dword accesses, which the
 // padding keeps conflict-free too (piece 8a + b -> bank 4b + a + j).
 //
-// Element path (mix_out always; mix_in on partial tiles and at any byte address for u8 / s24, any element-aligned one for
+// Element path (mix_out always; mix_in on partial tiles and at any byte address for the 1-byte formats and s24, any element-aligned one for
 // the rest): frame by frame from and to global memory, consecutive lanes on consecutive frames.  Both paths run the same
 // mix_frame: the same bytes.  mix_out had a tile path of the same build; measured on whole aligned tiles it was not
 // faster than this one ("Mixed calls"), so it is gone: a lane's stores already fall into lines its
 // neighbours fill.
 //
-// mix_out_dither<F> (integer formats; a state with dither on): mix_out with the dither of dither.h added before the
+// mix_out_dither<F> (integer and companded formats; a state with dither on): mix_out with the dither of dither.h added before the
 // rounding, instances of their own beside mix_out.  Output o of frame f of a stream at position p has idx
 // (p + f) * dst_channels + o: a frame is a run of consecutive idx, so the inner half of the generator's word is taken
 // once per frame (twice for the one frame that crosses a 2^32 boundary of idx).
@@ -206,6 +206,8 @@ hipError_t launch_mix(int fmt, const MixPack &pack, uint32_t n, uint32_t max_fra
     case SPEEXHIP_FMT_S32: MIX_LAUNCH(SPEEXHIP_FMT_S32);
     case SPEEXHIP_FMT_F32: MIX_LAUNCH(SPEEXHIP_FMT_F32);
     case SPEEXHIP_FMT_F32N: MIX_LAUNCH(SPEEXHIP_FMT_F32N);
+    case SPEEXHIP_FMT_ULAW: MIX_LAUNCH(SPEEXHIP_FMT_ULAW);
+    case SPEEXHIP_FMT_ALAW: MIX_LAUNCH(SPEEXHIP_FMT_ALAW);
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -232,6 +234,8 @@ hipError_t launch_mix_out_dither(int fmt, const MixPack &pack, const DitherPack 
     case SPEEXHIP_FMT_S16: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_S16>), grid, block, 0, stream, pack, dith); break;
     case SPEEXHIP_FMT_S24: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_S24>), grid, block, 0, stream, pack, dith); break;
     case SPEEXHIP_FMT_S32: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_S32>), grid, block, 0, stream, pack, dith); break;
+    case SPEEXHIP_FMT_ULAW: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_ULAW>), grid, block, 0, stream, pack, dith); break;
+    case SPEEXHIP_FMT_ALAW: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_ALAW>), grid, block, 0, stream, pack, dith); break;
     default: return hipErrorInvalidValue;  // (the float formats are not dithered)
   }
   return hipGetLastError();

@@ -90,6 +90,7 @@ int Batch::process_mix_device(int in_fmt, uint32_t in_channels, const float *in_
   // With dither on (engine.h, set_dither) the integer formats leave through the dithered instances of either pass, at the
   // streams' positions, and every format counts the frames it produced.
   const bool dith = dither_on();
+  // (every format but the two float ones: the integer formats and the companded ULAW / ALAW)
   const bool dith_out = dith && out_fmt != SPEEXHIP_FMT_F32 && out_fmt != SPEEXHIP_FMT_F32N;
   if (pass_out && out_mix == nullptr) {
     const int crc = convert_streams(false, out_fmt, d_planar_out_, out_pitch * sizeof(float), d_out, out_stride * bout, out_len,

@@ -13,9 +13,10 @@ import { Transform, TransformCallback } from 'stream';
  */
 /**
  * sample formats of processChunkFormat: 's24le' is packed (3 bytes per sample), 'f32le' is float32 in int16 units (what
- * processChunkFloat takes), 'f32le-normalized' float32 with +-1.0 full scale (Web Audio)
+ * processChunkFloat takes), 'f32le-normalized' float32 with +-1.0 full scale (Web Audio), 'mulaw' / 'alaw' G.711 as RTP
+ * carries it (PCMU / PCMA, one byte per sample; a companded result is the 's16le' result through the G.711 compressor)
  */
-export type SampleFormat = 'u8' | 's16le' | 's24le' | 's32le' | 'f32le' | 'f32le-normalized';
+export type SampleFormat = 'u8' | 's16le' | 's24le' | 's32le' | 'f32le' | 'f32le-normalized' | 'mulaw' | 'alaw';
 /** dither of the integer results of processChunkFormat / processChunkMix (setDither) */
 export type DitherKind = 'none' | 'rectangular' | 'triangular';
 
@@ -149,7 +150,8 @@ declare class SpeexResampler {
      */
     setMode(mode: 'fast' | 'exact' | 'fast_f32' | 'fast_fixed'): void;
     /**
-     * Dither of the integer results of processChunkFormat / processChunkMix: 'none' (default, round half up),
+     * Dither of the integer results of processChunkFormat / processChunkMix ('u8', 's16le', 's24le', 's32le', and 'mulaw' /
+     * 'alaw', where the noise joins the int16 value the compressor takes): 'none' (default, round half up),
      * 'rectangular' (+-0.5 LSB) or 'triangular' (TPDF, +-1 LSB).  Counter based: the noise of a sample depends on (seed,
      * its index in the stream) alone, so the bytes do not depend on the chunking.  position = index of the next output
      * frame.  While on, 's16le' -> 's16le' runs as processChunkFloat between the two conversions.

@@ -20,6 +20,9 @@ const SAMPLE_FORMATS = {
   's32le': { id: 3, bytes: 4 },
   'f32le': { id: 4, bytes: 4 },
   'f32le-normalized': { id: 5, bytes: 4 },
+  // companded (G.711, one byte per sample): ids start at 16
+  'mulaw': { id: 16, bytes: 1 },
+  'alaw': { id: 17, bytes: 1 },
 };
 // setDither: the names of the dither kinds (SPEEXHIP_DITHER_* = the index)
 const DITHER_KINDS = ['none', 'rectangular', 'triangular'];
@@ -238,7 +241,10 @@ class SpeexResampler {
 
   /**
    * Sample formats named independently for the input and the result: 'u8' | 's16le' | 's24le' (packed, 3 bytes) |
-   * 's32le' | 'f32le' (float32 in int16 units, as processChunkFloat) | 'f32le-normalized' (float32 in +-1.0, Web Audio).
+   * 's32le' | 'f32le' (float32 in int16 units, as processChunkFloat) | 'f32le-normalized' (float32 in +-1.0, Web Audio) |
+   * 'mulaw' | 'alaw' (G.711 as RTP carries it, PCMU / PCMA: one byte per sample, decoded and encoded on the GPU -- 8 kHz
+   * mu-law to 16 kHz float for a speech model: new SpeexResampler(1, 8000, 16000).processChunkFormat(rtpPayload, 'mulaw',
+   * 'f32le-normalized'); a companded result is the 's16le' result through the G.711 compressor).
    * `chunk` is a Buffer of interleaved frames in inFormat; the result is a Buffer in outFormat.  It is processChunkFloat
    * on the converted samples followed by the output conversion (round half up, saturating), both done on the GPU:
    * a decoder's s16le goes in and Web Audio's float32 comes out with no loop over the samples in JavaScript.  Same
@@ -339,7 +345,8 @@ class SpeexResampler {
   }
 
   /**
-   * Dither of the integer results ('u8', 's16le', 's24le', 's32le') of processChunkFormat and processChunkMix: 'none' (the
+   * Dither of the integer results ('u8', 's16le', 's24le', 's32le', and 'mulaw' / 'alaw', where the noise joins the int16
+   * value the compressor takes) of processChunkFormat and processChunkMix: 'none' (the
    * default: round half up), 'rectangular' (uniform in +-0.5 LSB) or 'triangular' (TPDF, +-1 LSB: the error of a
    * requantised signal becomes noise instead of harmonics).  The noise of a sample is a pure function of (seed, its index
    * in the stream), so the bytes do not depend on how the stream is cut into chunks; `position` is the index of the next

@@ -24,6 +24,28 @@ ERR_NO_BLOCK = 7  # the ..._take calls: no pinned result block free right now, s
 FMT_U8, FMT_S16, FMT_S24, FMT_S32, FMT_F32, FMT_F32N = range(6)
 FMT_BYTES = (1, 2, 3, 4, 4, 4)
 FMT_DTYPE = (np.uint8, np.int16, np.uint8, np.int32, np.float32, np.float32)  # numpy storage type of each format
+# companded formats (G.711 mu-law / A-law, one byte per sample) start at 16; 6..15 stay invalid
+FMT_ULAW, FMT_ALAW = 16, 17
+
+
+def fmt_bytes(fmt):
+    """bytes of one sample of a format (FMT_*), the companded ones included"""
+    if fmt in (FMT_ULAW, FMT_ALAW):
+        return 1
+    if not 0 <= fmt < len(FMT_BYTES):
+        raise ValueError("unknown sample format %r" % (fmt,))
+    return FMT_BYTES[fmt]
+
+
+def fmt_dtype(fmt):
+    """numpy storage type of a format (FMT_*), the companded ones included"""
+    if fmt in (FMT_ULAW, FMT_ALAW):
+        return np.uint8
+    if not 0 <= fmt < len(FMT_DTYPE):
+        raise ValueError("unknown sample format %r" % (fmt,))
+    return FMT_DTYPE[fmt]
+
+
 # dither of the integer output formats of the formatted and mixed calls (SPEEXHIP_DITHER_*), a property of the state
 DITHER_NONE, DITHER_RECTANGULAR, DITHER_TRIANGULAR = range(3)
 
@@ -76,6 +98,8 @@ EXPORTS = [
     # dither of the integer output formats of the formatted and mixed calls
     "speexhip_resampler_set_dither", "speexhip_resampler_get_dither", "speexhip_batch_set_dither",
     "speexhip_batch_get_dither", "speexhip_debug_dither",
+    # companded formats: G.711 mu-law and A-law in the formatted and mixed calls
+    "speexhip_debug_g711_decode", "speexhip_debug_g711_encode",
 ]
 
 
@@ -299,6 +323,11 @@ def lib():
             L.speexhip_batch_get_dither.argtypes = [p, u32, C.POINTER(C.c_int), pu64, pu64]
             L.speexhip_debug_dither.restype = i32
             L.speexhip_debug_dither.argtypes = [i32, u64, u64, u32, C.POINTER(C.c_double)]
+        if hasattr(L, "speexhip_debug_g711_decode") or "SPEEXHIP_LIB_PATH" not in os.environ:
+            L.speexhip_debug_g711_decode.restype = i32
+            L.speexhip_debug_g711_decode.argtypes = [i32, p, u32, p]
+            L.speexhip_debug_g711_encode.restype = i32
+            L.speexhip_debug_g711_encode.argtypes = [i32, p, p, u32, p]
         _lib = L
     return _lib
 
@@ -360,6 +389,31 @@ def debug_dither(kind, seed, first_index, n):
     if rc:
         raise ValueError(strerror(rc))
     return d[:n]
+
+
+def debug_g711_decode(fmt, codes):
+    """host-only: the library's decoding of G.711 bytes (FMT_ULAW / FMT_ALAW) into the internal float (int16 units)"""
+    codes = np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1)
+    x = np.zeros(max(codes.size, 1), np.float32)
+    rc = lib().speexhip_debug_g711_decode(fmt, C.c_void_p(codes.ctypes.data), codes.size, C.c_void_p(x.ctypes.data))
+    if rc:
+        raise ValueError(strerror(rc))
+    return x[: codes.size]
+
+
+def debug_g711_encode(fmt, y, d=None):
+    """host-only: the library's G.711 bytes of FIR values y (float32, int16 units); d: None or the dither of each
+    sample (float64, in int16 steps) added before the rounding"""
+    y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
+    if d is not None:
+        d = np.ascontiguousarray(d, dtype=np.float64).reshape(-1)
+        assert d.size == y.size
+    codes = np.zeros(max(y.size, 1), np.uint8)
+    rc = lib().speexhip_debug_g711_encode(fmt, C.c_void_p(y.ctypes.data), None if d is None else C.c_void_p(d.ctypes.data),
+                                          y.size, C.c_void_p(codes.ctypes.data))
+    if rc:
+        raise ValueError(strerror(rc))
+    return codes[: y.size]
 
 
 def debug_plan64(ratio_num, ratio_den, quality, channels):
@@ -785,15 +839,15 @@ class Resampler:
         if x is None:
             ptr, n = None, int(null_frames)
         else:
-            x = np.ascontiguousarray(x, dtype=FMT_DTYPE[in_fmt]).reshape(-1)
-            n = x.nbytes // (FMT_BYTES[in_fmt] * self.channels)
-            assert n * FMT_BYTES[in_fmt] * self.channels == x.nbytes, "whole frames only"
+            x = np.ascontiguousarray(x, dtype=fmt_dtype(in_fmt)).reshape(-1)
+            n = x.nbytes // (fmt_bytes(in_fmt) * self.channels)
+            assert n * fmt_bytes(in_fmt) * self.channels == x.nbytes, "whole frames only"
             ptr = C.c_void_p(x.ctypes.data)
-        raw = np.full(max(int(cap), 1) * self.channels * FMT_BYTES[out_fmt], self.SENTINEL_BYTE, np.uint8)
+        raw = np.full(max(int(cap), 1) * self.channels * fmt_bytes(out_fmt), self.SENTINEL_BYTE, np.uint8)
         il, ol = C.c_uint32(n), C.c_uint32(int(cap))
         rc = lib().speexhip_resampler_process_interleaved_fmt(self._h, in_fmt, ptr, C.byref(il), out_fmt,
                                                               C.c_void_p(raw.ctypes.data), C.byref(ol))
-        return rc, il.value, ol.value, raw.view(FMT_DTYPE[out_fmt])
+        return rc, il.value, ol.value, raw.view(fmt_dtype(out_fmt))
 
     def process_fmt(self, x, in_fmt, out_fmt, capacity, null_frames=0):
         """Formatted call on host buffers: x in format in_fmt (FMT_*; S24 as a uint8 array of 3 * n bytes; None: silence),
@@ -826,16 +880,16 @@ class Resampler:
         if x is None:
             ptr, n = None, int(null_frames)
         else:
-            x = np.ascontiguousarray(x, dtype=FMT_DTYPE[in_fmt]).reshape(-1)
-            n = x.nbytes // (FMT_BYTES[in_fmt] * n_in)
-            assert n * FMT_BYTES[in_fmt] * n_in == x.nbytes, "whole frames only"
+            x = np.ascontiguousarray(x, dtype=fmt_dtype(in_fmt)).reshape(-1)
+            n = x.nbytes // (fmt_bytes(in_fmt) * n_in)
+            assert n * fmt_bytes(in_fmt) * n_in == x.nbytes, "whole frames only"
             ptr = C.c_void_p(x.ctypes.data)
-        raw = np.full(max(int(cap), 1) * n_out * FMT_BYTES[out_fmt], self.SENTINEL_BYTE, np.uint8)
+        raw = np.full(max(int(cap), 1) * n_out * fmt_bytes(out_fmt), self.SENTINEL_BYTE, np.uint8)
         il, ol = C.c_uint32(n), C.c_uint32(int(cap))
         rc = lib().speexhip_resampler_process_interleaved_mix(
             self._h, in_fmt, n_in, _mix_ptr(mi), ptr, C.byref(il), out_fmt, n_out, _mix_ptr(mo),
             C.c_void_p(raw.ctypes.data), C.byref(ol))
-        return rc, il.value, ol.value, raw.view(FMT_DTYPE[out_fmt])
+        return rc, il.value, ol.value, raw.view(fmt_dtype(out_fmt))
 
     def process_mix(self, x, in_fmt, out_fmt, capacity, in_mix=None, out_mix=None, null_frames=0):
         """Mixed call on host buffers: the formatted call with a channel matrix on either side -- in_mix (channels x
@@ -1045,16 +1099,30 @@ class Batch:
             raise RuntimeError(strerror(rc))
         return list(il), list(ol)
 
-    def _process_tensor_fmt(self, x, out_capacity, in_frames, out_dtype, normalized, in_mix=None, out_mix=None):
+    def _process_tensor_fmt(self, x, out_capacity, in_frames, out_dtype, normalized, in_mix=None, out_mix=None,
+                            in_format=None, out_format=None):
         """process_tensor beyond int16 -> int16 and float32 -> float32: interleaved frames (..., T, C) through the
         formatted call (the mixed call when a matrix is given: x then holds in_channels per frame and the result
-        out_channels).  uint8 = U8, int16 = S16, int32 = S32, float32 = F32 (normalized: +-1.0 full scale)."""
+        out_channels).  uint8 = U8, int16 = S16, int32 = S32, float32 = F32 (normalized: +-1.0 full scale); in_format /
+        out_format (FMT_*) name a side's format instead -- a uint8 tensor as FMT_ULAW or FMT_ALAW."""
         import torch
         fmt_of = {torch.uint8: FMT_U8, torch.int16: FMT_S16, torch.int32: FMT_S32,
                   torch.float32: FMT_F32N if normalized else FMT_F32}
-        out_dtype = x.dtype if out_dtype is None else out_dtype
+        torch_of = {np.uint8: torch.uint8, np.int16: torch.int16, np.int32: torch.int32, np.float32: torch.float32}
+        if in_format is not None and x.dtype != torch_of[fmt_dtype(in_format)]:
+            raise ValueError("in_format %d wants a %s tensor" % (in_format, torch_of[fmt_dtype(in_format)]))
+        if out_format is not None:
+            if out_dtype is not None and out_dtype != torch_of[fmt_dtype(out_format)]:
+                raise ValueError("out_format %d gives a %s tensor" % (out_format, torch_of[fmt_dtype(out_format)]))
+            out_dtype = torch_of[fmt_dtype(out_format)]
+        elif out_dtype is None:
+            out_dtype = x.dtype
         if x.dtype not in fmt_of or out_dtype not in fmt_of:
             raise ValueError("process_tensor converts between uint8, int16, int32 and float32 tensors")
+        in_fmt = fmt_of[x.dtype] if in_format is None else in_format
+        out_fmt = fmt_of[out_dtype] if out_format is None else out_format
+        if FMT_S24 in (in_fmt, out_fmt):
+            raise ValueError("process_tensor does not take packed S24: a sample is not a whole element")
         xb = x if x.dim() == 3 else x.unsqueeze(0)
         B, T, Cn = xb.shape
         n_in = self.channels if in_mix is None else _mix_matrix(in_mix, self.channels, True)[1]
@@ -1070,17 +1138,17 @@ class Batch:
         stream = torch.cuda.current_stream(x.device).cuda_stream
         if in_mix is None and out_mix is None:
             _, made = self.process_fmt_device(
-                fmt_of[x.dtype], xb.data_ptr(), xb.stride(0) if B > 1 else 0, T if in_frames is None else in_frames,
-                fmt_of[out_dtype], out.data_ptr(), out.stride(0), int(out_capacity), stream)
+                in_fmt, xb.data_ptr(), xb.stride(0) if B > 1 else 0, T if in_frames is None else in_frames,
+                out_fmt, out.data_ptr(), out.stride(0), int(out_capacity), stream)
         else:
             _, made = self.process_mix_device(
-                fmt_of[x.dtype], xb.data_ptr(), xb.stride(0) if B > 1 else 0, T if in_frames is None else in_frames,
-                fmt_of[out_dtype], out.data_ptr(), out.stride(0), int(out_capacity), in_mix, out_mix, stream)
+                in_fmt, xb.data_ptr(), xb.stride(0) if B > 1 else 0, T if in_frames is None else in_frames,
+                out_fmt, out.data_ptr(), out.stride(0), int(out_capacity), in_mix, out_mix, stream)
         out = out[:, : max(made)]
         return (out if x.dim() == 3 else out[0]), made
 
     def process_tensor(self, x, out_capacity=None, in_frames=None, out_dtype=None, normalized=False, in_mix=None,
-                       out_mix=None):
+                       out_mix=None, in_format=None, out_format=None):
         """x: a CUDA tensor (B, C, T) or (C, T), int16 or float32, whose last dimension is dense (any other strides).
         Runs on torch's current stream.  in_frames: frames per stream (default T for all); out_capacity: frames the
         result may hold per stream (default: what T frames can produce).  Returns (tensor of the same rank with
@@ -1091,8 +1159,18 @@ class Batch:
         interleaved frames: x is then (B, T, C) or (T, C), dense, and so is the result.
 
         in_mix (channels x in_channels) / out_mix (out_channels x channels): the mixed call, also on interleaved
-        frames -- x is (B, T, in_channels) and the result (B, T', out_channels), of any of the sample types above."""
+        frames -- x is (B, T, in_channels) and the result (B, T', out_channels), of any of the sample types above.
+
+        in_format / out_format (FMT_*): name a side's sample format instead of inferring it from the dtype, also on
+        interleaved frames -- a uint8 tensor with in_format=FMT_ULAW is G.711 mu-law, out_format=FMT_ALAW gives a uint8
+        tensor of A-law bytes.  A side that is not named goes by its dtype as above (the result's being x's unless
+        out_dtype says otherwise)."""
         import torch
+        if in_format is not None or out_format is not None:
+            if not x.is_cuda or x.dim() not in (2, 3):
+                raise ValueError("process_tensor wants a CUDA tensor (B, T, C) or (T, C) for a named format")
+            return self._process_tensor_fmt(x, out_capacity, in_frames, out_dtype, normalized, in_mix, out_mix, in_format,
+                                            out_format)
         if in_mix is not None or out_mix is not None:
             if not x.is_cuda or x.dim() not in (2, 3):
                 raise ValueError("process_tensor wants a CUDA tensor (B, T, C) or (T, C) for a mixed call")
