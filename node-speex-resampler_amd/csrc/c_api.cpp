@@ -579,74 +579,73 @@ int speexhip_batch_process_planar_float_device(SpeexHipBatch *b, const float *d_
                                        static_cast<hipStream_t>(hip_stream)); });
 }
 
-uint32_t speexhip_sample_bytes(int fmt) {
-  switch (fmt) {
-    case SPEEXHIP_FMT_U8:
-    case SPEEXHIP_FMT_ULAW:
-    case SPEEXHIP_FMT_ALAW: return 1;
-    case SPEEXHIP_FMT_S16: return 2;
-    case SPEEXHIP_FMT_S24: return 3;
-    case SPEEXHIP_FMT_S32:
-    case SPEEXHIP_FMT_F32:
-    case SPEEXHIP_FMT_F32N: return 4;
-    default: return 0;
-  }
+uint32_t speexhip_sample_bytes(int fmt) { return speexhip::sample_bytes(fmt); }
+
+namespace {
+// the formatted and mixed calls' sides; a formatted call's sides hold the state's channel count and no matrix
+speexhip::CallSide side(int fmt, uint32_t channels, const float *mix, const void *base, uint64_t stride = 0) {
+  return speexhip::CallSide{fmt, channels, mix, const_cast<void *>(base), stride};
 }
+bool fmt_args_ok(const void *handle, const uint32_t *in_len, const uint32_t *out_len, const void *out, int in_fmt, int out_fmt) {
+  return handle != nullptr && in_len != nullptr && out_len != nullptr && out != nullptr && speexhip::sample_bytes(in_fmt) != 0 &&
+         speexhip::sample_bytes(out_fmt) != 0;
+}
+}  // namespace
+
 int speexhip_resampler_process_interleaved_fmt(SpeexHipResamplerState *st, int in_fmt, const void *in, uint32_t *in_len,
                                                int out_fmt, void *out, uint32_t *out_len) {
-  if (st == nullptr || in_len == nullptr || out_len == nullptr || out == nullptr || speexhip_sample_bytes(in_fmt) == 0 ||
-      speexhip_sample_bytes(out_fmt) == 0)
-    return SPEEXHIP_ERR_INVALID_ARG;
-  return guarded([&] { return st->batch->process_fmt_host(in_fmt, in, in_len, out_fmt, out, out_len); });
+  if (!fmt_args_ok(st, in_len, out_len, out, in_fmt, out_fmt)) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] {
+    const uint32_t ch = st->batch->channels();
+    return st->batch->process_sides_host(side(in_fmt, ch, nullptr, in), in_len, side(out_fmt, ch, nullptr, out), out_len);
+  });
 }
 int speexhip_resampler_process_interleaved_fmt_device(SpeexHipResamplerState *st, int in_fmt, const void *d_in,
                                                       uint32_t *in_len, int out_fmt, void *d_out, uint32_t *out_len,
                                                       void *hip_stream) {
-  if (st == nullptr || in_len == nullptr || out_len == nullptr || d_out == nullptr || speexhip_sample_bytes(in_fmt) == 0 ||
-      speexhip_sample_bytes(out_fmt) == 0)
-    return SPEEXHIP_ERR_INVALID_ARG;
-  return guarded([&] { return st->batch->process_fmt_device(in_fmt, d_in, 0, in_len, out_fmt, d_out, 0, out_len,
-                                     static_cast<hipStream_t>(hip_stream)); });
+  if (!fmt_args_ok(st, in_len, out_len, d_out, in_fmt, out_fmt)) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] {
+    const uint32_t ch = st->batch->channels();
+    return st->batch->process_sides_device(side(in_fmt, ch, nullptr, d_in), in_len, side(out_fmt, ch, nullptr, d_out), out_len,
+                                           static_cast<hipStream_t>(hip_stream));
+  });
 }
 int speexhip_batch_process_interleaved_fmt_device(SpeexHipBatch *b, int in_fmt, const void *d_in, uint64_t in_stream_stride,
                                                   uint32_t *in_len, int out_fmt, void *d_out, uint64_t out_stream_stride,
                                                   uint32_t *out_len, void *hip_stream) {
-  if (b == nullptr || in_len == nullptr || out_len == nullptr || d_out == nullptr || speexhip_sample_bytes(in_fmt) == 0 ||
-      speexhip_sample_bytes(out_fmt) == 0)
-    return SPEEXHIP_ERR_INVALID_ARG;
-  return guarded([&] { return b->batch->process_fmt_device(in_fmt, d_in, in_stream_stride, in_len, out_fmt, d_out,
-                                    out_stream_stride, out_len, static_cast<hipStream_t>(hip_stream)); });
+  if (!fmt_args_ok(b, in_len, out_len, d_out, in_fmt, out_fmt)) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] {
+    const uint32_t ch = b->batch->channels();
+    return b->batch->process_sides_device(side(in_fmt, ch, nullptr, d_in, in_stream_stride), in_len,
+                                          side(out_fmt, ch, nullptr, d_out, out_stream_stride), out_len,
+                                          static_cast<hipStream_t>(hip_stream));
+  });
 }
 
 int speexhip_resampler_process_interleaved_mix(SpeexHipResamplerState *st, int in_fmt, uint32_t in_channels,
                                                const float *in_mix, const void *in, uint32_t *in_len, int out_fmt,
                                                uint32_t out_channels, const float *out_mix, void *out, uint32_t *out_len) {
-  if (st == nullptr || in_len == nullptr || out_len == nullptr || out == nullptr || speexhip_sample_bytes(in_fmt) == 0 ||
-      speexhip_sample_bytes(out_fmt) == 0)
-    return SPEEXHIP_ERR_INVALID_ARG;
-  return guarded([&] { return st->batch->process_mix_host(in_fmt, in_channels, in_mix, in, in_len, out_fmt, out_channels,
-                                                          out_mix, out, out_len); });
+  if (!fmt_args_ok(st, in_len, out_len, out, in_fmt, out_fmt)) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return st->batch->process_sides_host(side(in_fmt, in_channels, in_mix, in), in_len,
+                                                            side(out_fmt, out_channels, out_mix, out), out_len); });
 }
 int speexhip_resampler_process_interleaved_mix_device(SpeexHipResamplerState *st, int in_fmt, uint32_t in_channels,
                                                       const float *in_mix, const void *d_in, uint32_t *in_len, int out_fmt,
                                                       uint32_t out_channels, const float *out_mix, void *d_out,
                                                       uint32_t *out_len, void *hip_stream) {
-  if (st == nullptr || in_len == nullptr || out_len == nullptr || d_out == nullptr || speexhip_sample_bytes(in_fmt) == 0 ||
-      speexhip_sample_bytes(out_fmt) == 0)
-    return SPEEXHIP_ERR_INVALID_ARG;
-  return guarded([&] { return st->batch->process_mix_device(in_fmt, in_channels, in_mix, d_in, 0, in_len, out_fmt,
-                                     out_channels, out_mix, d_out, 0, out_len, static_cast<hipStream_t>(hip_stream)); });
+  if (!fmt_args_ok(st, in_len, out_len, d_out, in_fmt, out_fmt)) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return st->batch->process_sides_device(side(in_fmt, in_channels, in_mix, d_in), in_len,
+                                                              side(out_fmt, out_channels, out_mix, d_out), out_len,
+                                                              static_cast<hipStream_t>(hip_stream)); });
 }
 int speexhip_batch_process_interleaved_mix_device(SpeexHipBatch *b, int in_fmt, uint32_t in_channels, const float *in_mix,
                                                   const void *d_in, uint64_t in_stream_stride, uint32_t *in_len, int out_fmt,
                                                   uint32_t out_channels, const float *out_mix, void *d_out,
                                                   uint64_t out_stream_stride, uint32_t *out_len, void *hip_stream) {
-  if (b == nullptr || in_len == nullptr || out_len == nullptr || d_out == nullptr || speexhip_sample_bytes(in_fmt) == 0 ||
-      speexhip_sample_bytes(out_fmt) == 0)
-    return SPEEXHIP_ERR_INVALID_ARG;
-  return guarded([&] { return b->batch->process_mix_device(in_fmt, in_channels, in_mix, d_in, in_stream_stride, in_len,
-                                    out_fmt, out_channels, out_mix, d_out, out_stream_stride, out_len,
-                                    static_cast<hipStream_t>(hip_stream)); });
+  if (!fmt_args_ok(b, in_len, out_len, d_out, in_fmt, out_fmt)) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return b->batch->process_sides_device(side(in_fmt, in_channels, in_mix, d_in, in_stream_stride), in_len,
+                                                             side(out_fmt, out_channels, out_mix, d_out, out_stream_stride),
+                                                             out_len, static_cast<hipStream_t>(hip_stream)); });
 }
 
 int speexhip_resampler_set_dither(SpeexHipResamplerState *st, int kind, uint64_t seed, uint64_t position) {

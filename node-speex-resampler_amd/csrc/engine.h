@@ -4,7 +4,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -55,6 +54,16 @@ int warmup(int device);
 // Idle cache entries back to the pool (speexhip_release_cached_memory); the bytes they held.
 size_t release_cached_tables();
 
+// One side of a formatted or mixed call (process_sides_*).
+struct CallSide {
+  int fmt;            // SPEEXHIP_FMT_* of the caller's storage
+  uint32_t channels;  // samples of a frame there: the state's count, or with a matrix any of 1..8
+  const float *mix;   // host memory, row-major: input side channels() x channels, applied to every frame before the float
+                      // call; output side channels x channels(), applied to every frame it produced.  NULL: no mix
+  void *base;         // stream 0 (an input side is only read; NULL there: silence)
+  uint64_t stride;    // samples of fmt between two streams
+};
+
 class Batch {
  public:
   // Returns nullptr and sets *err on failure.  device: logical ordinal (devices.h), or < 0 for the process-wide
@@ -82,34 +91,25 @@ class Batch {
   // synchronous.  Each plane moves by the rule of host_transfer.h.
   int process_planar_host(const void *const *in_planes, uint32_t *in_len, void *const *out_planes, uint32_t *out_len,
                           bool float_io);
-  // Formatted calls (formats.cpp; SPEEXHIP_FMT_*): the float call on the converted input followed by the output
-  // conversion -- convert_in / convert_out (kernels_convert.hip) either side of process_device(float) on the state's
-  // scratch images (the planar calls' ones: calls on a state are ordered).  S16 -> S16, F32 -> F32 and F32N -> F32N go
-  // straight to process_device; the companded ULAW / ALAW (g711.h) are formats like the others and make no such pair.
-  // Strides are in samples of the side's format.  plans_out: the plan of every channel of
-  // a state whose channels stand apart (empty otherwise).
-  int process_fmt_device(int in_fmt, const void *d_in, uint64_t in_stride, uint32_t *in_len, int out_fmt, void *d_out,
-                         uint64_t out_stride, uint32_t *out_len, hipStream_t stream,
-                         std::vector<CallPlan> *plans_out = nullptr);
-  // ... on host buffers of a single-stream batch; synchronous.  The raw bytes move by the rule of host_transfer.h.
-  int process_fmt_host(int in_fmt, const void *in, uint32_t *in_len, int out_fmt, void *out, uint32_t *out_len);
-  // Mixed calls (mix.cpp): a formatted call whose sides may carry a channel matrix in host memory -- in_mix, row-major
-  // channels() x in_channels, applied to every input frame before the float call; out_mix, row-major out_channels x
-  // channels(), applied to every frame it produced.  NULL = no mix on that side (its channel count is then channels()).
-  // A side with a matrix runs mix_in / mix_out (kernels_mix.hip) in place of convert_in / convert_out; the float call
-  // between them is process_device(float) on the scratch images of channels() channels.  Both NULL: process_fmt_device.
-  // Strides are in samples of the side's format, a frame of a side holding that side's channel count.
-  int process_mix_device(int in_fmt, uint32_t in_channels, const float *in_mix, const void *d_in, uint64_t in_stride,
-                         uint32_t *in_len, int out_fmt, uint32_t out_channels, const float *out_mix, void *d_out,
-                         uint64_t out_stride, uint32_t *out_len, hipStream_t stream);
-  // ... on host buffers of a single-stream batch; synchronous, routed like process_fmt_host.
-  int process_mix_host(int in_fmt, uint32_t in_channels, const float *in_mix, const void *in, uint32_t *in_len, int out_fmt,
-                       uint32_t out_channels, const float *out_mix, void *out, uint32_t *out_len);
+  // Formatted and mixed calls (formats.cpp): the caller names each side's sample format, and a side may carry a channel
+  // matrix (CallSide).  One pipeline: storage --the input side's pass--> float image of channels() channels
+  // --process_device(float)--> float image --the output side's pass--> storage, on the state's scratch images (the
+  // planar calls' ones: calls on a state are ordered).  A side's pass is convert_* (kernels_convert.hip) or, with a
+  // matrix, mix_* (kernels_mix.hip) in its place; a side without a matrix whose storage is F32 IS its image and has no
+  // pass.  S16 -> S16, F32 -> F32 and F32N -> F32N without a matrix go straight to process_device.  Counters, positions
+  // and the history are the float call's.  A state whose channels stand apart is served channel by channel when it is one
+  // stream, has no matrix and dither is off (plans_out: the plan of every channel then, empty otherwise), else BAD_STATE.
+  int process_sides_device(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len, hipStream_t stream,
+                           std::vector<CallPlan> *plans_out = nullptr);
+  // ... on host buffers of a single-stream batch (strides unused); synchronous.  The raw bytes of both sides move by the
+  // rule of host_transfer.h, the passes run on the device.
+  int process_sides_host(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len);
   // Dither of the integer output formats of the formatted and mixed calls (dither.h; include/speexhip_resampler.h,
   // "Dither"): a property of the state, off by default.  kind = SPEEXHIP_DITHER_*; stream s draws from
   // dither::stream_seed(seed, s); position = index of the next output frame of every stream.  While the kind is not NONE
-  // every formatted or mixed call advances each stream's position by the frames it produced, S16 -> S16 runs as the float
-  // call between convert_in and the dithered convert_out, and a state whose channels stand apart returns BAD_STATE.  No
+  // every formatted or mixed call advances each stream's position by the frames it produced, the formats of dithered_fmt
+  // (kernels.h) leave through the dithered instances of their pass, S16 -> S16 runs as the float call between convert_in
+  // and the dithered convert_out, and a state whose channels stand apart returns BAD_STATE.  No
   // other call reads or moves any of this, and no control call (set_rate, set_quality, reset_mem, skip_zeros) touches it.
   int set_dither(int kind, uint64_t seed, uint64_t position);
   int get_dither(uint32_t stream, int *kind, uint64_t *seed, uint64_t *position) const;  // seed: the stream's own
@@ -201,18 +201,19 @@ class Batch {
   int process_split(const void *d_in, uint32_t *in_len, void *d_out, uint32_t *out_len, bool float_io,
                     hipStream_t stream, std::vector<CallPlan> *plans_out, const SplitLayout *layout = nullptr);
   int ensure_planar_scratch(size_t in_bytes, size_t out_bytes);
-  // formats.cpp, shared by the formatted and the mixed calls: the converting pass of a side without a matrix over every
-  // stream (stream s: lens[s] frames of channels() samples at src + s * src_step, dst + s * dst_step bytes; to_image:
-  // convert_in, otherwise convert_out), and the routing of a single-stream call's host buffers around a device call.
-  // dithered (convert_out only, an integer format): convert_out_dither at the streams' dither positions.
-  int convert_streams(bool to_image, int fmt, const void *src, size_t src_step, void *dst, size_t dst_step, const uint32_t *lens,
-                      hipStream_t stream, bool dithered = false);
+  // mix.cpp: one side's pass over every stream, <= kMaxPackedStreams per launch -- to_image: storage -> image, otherwise
+  // image -> storage, dithered when the state and the format say so.  Stream s is lens[s] frames at side.base + s *
+  // side.stride and image + s * pitch (elements).  apart (an output side without a matrix): the plans of the one
+  // stream's channels, which stand apart -- channel c is plans[c].produced samples, channels() elements from one to the next.
+  int side_pass(const CallSide &side, bool to_image, char *image, size_t pitch, const uint32_t *lens, hipStream_t stream,
+                const CallPlan *apart = nullptr);
   bool dither_on() const { return dither_kind_ != SPEEXHIP_DITHER_NONE; }
   // the DitherPack of streams [s0, s0 + n): first = position * per_frame (per_frame = 1: the position itself)
   DitherPack dither_pack(uint32_t s0, uint32_t n, uint32_t per_frame) const;
   void dither_advance(const uint32_t *produced);  // after a formatted or mixed call with dither on
-  int routed_host_call(const void *in, size_t in_bytes, void *out, size_t out_bytes, size_t out_frame_bytes,
-                       const uint32_t *out_len, const std::function<int(const void *, void *)> &device_call);
+  // process_sides_device on own_stream_ with the host buffers of both sides routed around it (host_transfer.h)
+  int routed_host_call(const CallSide &in, size_t in_bytes, uint32_t *in_len, const CallSide &out, size_t out_bytes,
+                       uint32_t *out_len);
   int fetch_history(std::vector<float> *host);
   int quiesce();  // waits for this batch's own enqueued work (never for the whole device)
   uint32_t block_in() const { return line_ - (filter_.taps - 1); }

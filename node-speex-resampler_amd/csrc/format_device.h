@@ -1,6 +1,8 @@
 // format_device.h -- the one device-side statement of the sample formats (SPEEXHIP_FMT_*): a sample's storage bits <->
-// the internal float (one int16 step = 1.0f), and the raw loads / stores of one sample at any address the format allows.
-// Shared by the converting kernels (kernels_convert.hip) and the mixing ones (kernels_mix.hip).
+// the internal float (one int16 step = 1.0f), and the raw loads / stores of one sample at any address the format allows;
+// and with_format, through which a launcher reaches its kernels' instance of a format.  Shared by the converting kernels
+// (kernels_convert.hip) and the mixing ones (kernels_mix.hip).  Bytes per sample and which formats are dithered:
+// sample_bytes and dithered_fmt of kernels.h, which the host reads too.
 //
 // Rounding (include/speexhip_resampler.h): halfup(v) = floor(v + 0.5) on v = y * 2^k, evaluated in fp64 -- the product is
 // exact there, and v + 0.5 is exact wherever its floor depends on it.  NaN becomes the format's zero, +-inf the rails.
@@ -11,18 +13,32 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/speexhip_resampler.h"
 #include "g711.h"
+#include "kernels.h"
 
 namespace speexhip {
 namespace fmtdev {
 
-constexpr uint32_t bytes_of(int f) {
-  return f == SPEEXHIP_FMT_U8 || f == SPEEXHIP_FMT_ULAW || f == SPEEXHIP_FMT_ALAW ? 1u
-         : f == SPEEXHIP_FMT_S16                                                    ? 2u
-         : f == SPEEXHIP_FMT_S24                                                    ? 3u
-                                                                                    : 4u;
+// Host side: fn(std::integral_constant<int, fmt>()) for a format known at run time -- the one place a launcher turns
+// fmt into the template argument of its kernels.  No such format: hipErrorInvalidValue.
+template <class Fn>
+hipError_t with_format(int fmt, Fn fn) {
+  switch (fmt) {
+#define SPEEXHIP_FORMAT_CASE(F) case F: return fn(std::integral_constant<int, F>())
+    SPEEXHIP_FORMAT_CASE(SPEEXHIP_FMT_U8);
+    SPEEXHIP_FORMAT_CASE(SPEEXHIP_FMT_S16);
+    SPEEXHIP_FORMAT_CASE(SPEEXHIP_FMT_S24);
+    SPEEXHIP_FORMAT_CASE(SPEEXHIP_FMT_S32);
+    SPEEXHIP_FORMAT_CASE(SPEEXHIP_FMT_F32);
+    SPEEXHIP_FORMAT_CASE(SPEEXHIP_FMT_F32N);
+    SPEEXHIP_FORMAT_CASE(SPEEXHIP_FMT_ULAW);
+    SPEEXHIP_FORMAT_CASE(SPEEXHIP_FMT_ALAW);
+#undef SPEEXHIP_FORMAT_CASE
+    default: return hipErrorInvalidValue;
+  }
 }
 
 // ---- one sample --------------------------------------------------------------------------------------------------
@@ -39,19 +55,27 @@ __device__ __forceinline__ float to_internal(uint32_t raw) {
   return __uint_as_float(raw) * 32768.0f;  // F32N
 }
 
+// an integer format (U8, S16, S24, S32) on its way out: round(y * scale) + bias, held to [lo, hi]; NaN becomes bias
+struct IntegerFormat {
+  double scale, bias, lo, hi;
+};
+constexpr IntegerFormat integer_format(int f) {
+  return f == SPEEXHIP_FMT_U8    ? IntegerFormat{1.0 / 256.0, 128.0, 0.0, 255.0}
+         : f == SPEEXHIP_FMT_S16 ? IntegerFormat{1.0, 0.0, -32768.0, 32767.0}
+         : f == SPEEXHIP_FMT_S24 ? IntegerFormat{256.0, 0.0, -8388608.0, 8388607.0}
+                                 : IntegerFormat{65536.0, 0.0, -2147483648.0, 2147483647.0};
+}
+
 template <int F>
 __device__ __forceinline__ uint32_t from_internal(float y) {
   if (F == SPEEXHIP_FMT_F32) return __float_as_uint(y);
   if (F == SPEEXHIP_FMT_F32N) return __float_as_uint(y * (1.0f / 32768.0f));
   if (F == SPEEXHIP_FMT_ULAW) return g711::ulaw_encode(g711::s16_of(y));
   if (F == SPEEXHIP_FMT_ALAW) return g711::alaw_encode(g711::s16_of(y));
-  constexpr double scale = F == SPEEXHIP_FMT_U8 ? 1.0 / 256.0 : F == SPEEXHIP_FMT_S16 ? 1.0 : F == SPEEXHIP_FMT_S24 ? 256.0 : 65536.0;
-  constexpr double bias = F == SPEEXHIP_FMT_U8 ? 128.0 : 0.0;
-  constexpr double lo = F == SPEEXHIP_FMT_U8 ? 0.0 : F == SPEEXHIP_FMT_S16 ? -32768.0 : F == SPEEXHIP_FMT_S24 ? -8388608.0 : -2147483648.0;
-  constexpr double hi = F == SPEEXHIP_FMT_U8 ? 255.0 : F == SPEEXHIP_FMT_S16 ? 32767.0 : F == SPEEXHIP_FMT_S24 ? 8388607.0 : 2147483647.0;
-  if (y != y) return static_cast<uint32_t>(static_cast<int32_t>(bias));
-  const double r = floor(static_cast<double>(y) * scale + 0.5) + bias;
-  return static_cast<uint32_t>(static_cast<int32_t>(fmin(fmax(r, lo), hi)));
+  constexpr IntegerFormat k = integer_format(F);
+  if (y != y) return static_cast<uint32_t>(static_cast<int32_t>(k.bias));
+  const double r = floor(static_cast<double>(y) * k.scale + 0.5) + k.bias;
+  return static_cast<uint32_t>(static_cast<int32_t>(fmin(fmax(r, k.lo), k.hi)));
 }
 
 // ... with dither (dither.h): d, in LSB of the integer format F, joins v before the half-up rounding -- v = y * 2^k (exact),
@@ -59,27 +83,31 @@ __device__ __forceinline__ uint32_t from_internal(float y) {
 // d = 0 these are from_internal's bits.
 template <int F>
 __device__ __forceinline__ uint32_t from_internal_dither(float y, double d) {
-  static_assert(F == SPEEXHIP_FMT_U8 || F == SPEEXHIP_FMT_S16 || F == SPEEXHIP_FMT_S24 || F == SPEEXHIP_FMT_S32 ||
-                    F == SPEEXHIP_FMT_ULAW || F == SPEEXHIP_FMT_ALAW,
-                "the integer formats are dithered, the float ones written as they are");
+  static_assert(dithered_fmt(F), "the integer formats are dithered, the float ones written as they are");
   // (the companded formats: d in int16 steps joins at the S16 stage, the compressor follows)
   if (F == SPEEXHIP_FMT_ULAW) return g711::ulaw_encode(g711::s16_of_dither(y, d));
   if (F == SPEEXHIP_FMT_ALAW) return g711::alaw_encode(g711::s16_of_dither(y, d));
-  constexpr double scale = F == SPEEXHIP_FMT_U8 ? 1.0 / 256.0 : F == SPEEXHIP_FMT_S16 ? 1.0 : F == SPEEXHIP_FMT_S24 ? 256.0 : 65536.0;
-  constexpr double bias = F == SPEEXHIP_FMT_U8 ? 128.0 : 0.0;
-  constexpr double lo = F == SPEEXHIP_FMT_U8 ? 0.0 : F == SPEEXHIP_FMT_S16 ? -32768.0 : F == SPEEXHIP_FMT_S24 ? -8388608.0 : -2147483648.0;
-  constexpr double hi = F == SPEEXHIP_FMT_U8 ? 255.0 : F == SPEEXHIP_FMT_S16 ? 32767.0 : F == SPEEXHIP_FMT_S24 ? 8388607.0 : 2147483647.0;
-  if (y != y) return static_cast<uint32_t>(static_cast<int32_t>(bias));
-  const double v = static_cast<double>(y) * scale;
+  constexpr IntegerFormat k = integer_format(F);
+  if (y != y) return static_cast<uint32_t>(static_cast<int32_t>(k.bias));
+  const double v = static_cast<double>(y) * k.scale;
   const double t = v + d;
-  const double r = floor(t + 0.5) + bias;
-  return static_cast<uint32_t>(static_cast<int32_t>(fmin(fmax(r, lo), hi)));
+  const double r = floor(t + 0.5) + k.bias;
+  return static_cast<uint32_t>(static_cast<int32_t>(fmin(fmax(r, k.lo), k.hi)));
+}
+
+// what an output pass stores for y: kDither = false from_internal, otherwise from_internal_dither with d = noise()
+template <int F, bool kDither, class Noise>
+__device__ __forceinline__ uint32_t encode(float y, Noise noise) {
+  if constexpr (kDither)
+    return from_internal_dither<F>(y, noise());
+  else
+    return from_internal<F>(y);
 }
 
 // ---- one sample at its address (any byte address for the 1-byte formats and s24, an element-aligned one for the rest)
 template <int F>
 __device__ __forceinline__ uint32_t load_raw(const char *p) {
-  if (bytes_of(F) == 1) return *reinterpret_cast<const uint8_t *>(p);
+  if (sample_bytes(F) == 1) return *reinterpret_cast<const uint8_t *>(p);
   if (F == SPEEXHIP_FMT_S16) return *reinterpret_cast<const uint16_t *>(p);
   if (F == SPEEXHIP_FMT_S24) {
     const uint8_t *b = reinterpret_cast<const uint8_t *>(p);
@@ -89,7 +117,7 @@ __device__ __forceinline__ uint32_t load_raw(const char *p) {
 }
 template <int F>
 __device__ __forceinline__ void store_raw(char *p, uint32_t raw) {
-  if (bytes_of(F) == 1) {
+  if (sample_bytes(F) == 1) {
     *reinterpret_cast<uint8_t *>(p) = static_cast<uint8_t>(raw);
   } else if (F == SPEEXHIP_FMT_S16) {
     *reinterpret_cast<uint16_t *>(p) = static_cast<uint16_t>(raw);

@@ -1,11 +1,10 @@
-// formats.cpp -- the formatted calls of engine.h: the caller names the sample format of the input and of the output
-// (SPEEXHIP_FMT_*).  A formatted call is the float call on the converted input followed by the output conversion:
-// storage --convert_in--> float scratch image --the existing float launch--> float scratch image --convert_out-->
-// storage (kernels_convert.hip).  Counters, positions and the history are the float call's, so formatted, interleaved,
-// planar and per-channel calls mix freely on one state.
+// formats.cpp -- the formatted and mixed calls of engine.h: the caller names the sample format of either side
+// (SPEEXHIP_FMT_*), and a side may carry a channel matrix (CallSide).  One pipeline serves them all:
+// storage --the input side's pass--> float scratch image --the existing float launch--> float scratch image --the output
+// side's pass--> storage (side_pass, mix.cpp).  Counters, positions and the history are the float call's, so formatted,
+// mixed, interleaved, planar and per-channel calls mix freely on one state.  The state's dither (set_dither) lives here too.
 #include <algorithm>
 #include <cstring>
-#include <functional>
 #include <vector>
 
 #include "dither.h"
@@ -17,28 +16,22 @@ namespace speexhip {
 using namespace detail;
 
 namespace {
-inline size_t line_pitch(size_t elements) { return (elements + 63) & ~static_cast<size_t>(63); }
-inline size_t fmt_bytes(int fmt) {
-  switch (fmt) {
-    case SPEEXHIP_FMT_U8:
-    case SPEEXHIP_FMT_ULAW:
-    case SPEEXHIP_FMT_ALAW: return 1;
-    case SPEEXHIP_FMT_S16: return 2;
-    case SPEEXHIP_FMT_S24: return 3;
-    case SPEEXHIP_FMT_S32:
-    case SPEEXHIP_FMT_F32:
-    case SPEEXHIP_FMT_F32N: return 4;
-    default: return 0;
-  }
+// with a matrix both channel counts are 1..8, without one the caller's count is the state's
+inline bool side_ok(const CallSide &side, uint32_t state_channels) {
+  if (sample_bytes(side.fmt) == 0) return false;
+  if (side.mix == nullptr) return side.channels == state_channels;
+  return state_channels <= kMixMaxChannels && side.channels >= 1 && side.channels <= kMixMaxChannels;
 }
-// the pairs that are an existing call on the same bytes: nothing is converted, nothing extra launched
-inline bool same_bytes_pair(int in_fmt, int out_fmt) {
-  return in_fmt == out_fmt && (in_fmt == SPEEXHIP_FMT_S16 || in_fmt == SPEEXHIP_FMT_F32 || in_fmt == SPEEXHIP_FMT_F32N);
+// The calls that are an existing call on the same bytes: nothing is converted, nothing extra launched.  (F32N -> F32N: a
+// power-of-two scale commutes exactly with the FIR.)  With dither on S16 -> S16 is no such call -- it runs as the float
+// call between convert_in and the dithered convert_out -- and the float pairs, written as ever, still count their frames.
+inline bool same_bytes(const CallSide &in, const CallSide &out, bool dith) {
+  if (in.mix != nullptr || out.mix != nullptr || in.fmt != out.fmt) return false;
+  return in.fmt == SPEEXHIP_FMT_S16 ? !dith : in.fmt == SPEEXHIP_FMT_F32 || in.fmt == SPEEXHIP_FMT_F32N;
 }
-// (the companded formats quantise to int16 on their way out: dithered like the integer ones)
-inline bool integer_fmt(int fmt) {
-  return fmt == SPEEXHIP_FMT_U8 || fmt == SPEEXHIP_FMT_S16 || fmt == SPEEXHIP_FMT_S24 || fmt == SPEEXHIP_FMT_S32 ||
-         fmt == SPEEXHIP_FMT_ULAW || fmt == SPEEXHIP_FMT_ALAW;
+// the side with its one stream at `base` (a staging buffer of a host call)
+inline CallSide at(const CallSide &side, const void *base) {
+  return CallSide{side.fmt, side.channels, side.mix, const_cast<void *>(base), 0};
 }
 }  // namespace
 
@@ -72,56 +65,26 @@ void Batch::dither_advance(const uint32_t *produced) {
   for (uint32_t s = 0; s < n_streams_; s++) dither_pos_[s] += produced[s];
 }
 
-// The converting pass of a side without a matrix over every stream of the batch, <= 32 streams per launch: stream s is
-// lens[s] frames of channels() samples at src + s * src_step and dst + s * dst_step (bytes).  to_image: convert_in (storage
-// -> float image), otherwise convert_out.  Shared with the mixed calls (mix.cpp).
-int Batch::convert_streams(bool to_image, int fmt, const void *src, size_t src_step, void *dst, size_t dst_step,
-                           const uint32_t *lens, hipStream_t stream, bool dithered) {
-  const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
-  for (uint32_t s0 = 0; s0 < n_streams_; s0 += kChunk) {
-    const uint32_t n = std::min(kChunk, n_streams_ - s0);
-    ConvertPack pack;
-    std::memset(&pack, 0, sizeof(pack));
-    uint64_t most = 0;
-    for (uint32_t j = 0; j < n; j++) {
-      const uint32_t s = s0 + j;
-      pack.s[j].src = static_cast<const char *>(src) + s * src_step;
-      pack.s[j].dst = static_cast<char *>(dst) + s * dst_step;
-      pack.s[j].n = static_cast<uint64_t>(lens[s]) * channels_;
-      pack.s[j].step = 1;
-      most = std::max(most, pack.s[j].n);
-    }
-    const hipError_t e = to_image   ? launch_convert_in(fmt, pack, n, most, stream)
-                         : dithered ? launch_convert_out_dither(fmt, pack, dither_pack(s0, n, channels_), n, most, stream)
-                                    : launch_convert_out(fmt, pack, n, most, stream);
-    if (hip_failed(e, "kernel launch")) return SPEEXHIP_ERR_DEVICE;
-  }
-  return SPEEXHIP_ERR_SUCCESS;
-}
-
-int Batch::process_fmt_device(int in_fmt, const void *d_in, uint64_t in_stride, uint32_t *in_len, int out_fmt, void *d_out,
-                              uint64_t out_stride, uint32_t *out_len, hipStream_t stream, std::vector<CallPlan> *plans_out) {
-  const size_t bin = fmt_bytes(in_fmt), bout = fmt_bytes(out_fmt);
-  if (bin == 0 || bout == 0) return SPEEXHIP_ERR_INVALID_ARG;
+int Batch::process_sides_device(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len,
+                                hipStream_t stream, std::vector<CallPlan> *plans_out) {
+  if (!side_ok(in, channels_) || !side_ok(out, channels_)) return SPEEXHIP_ERR_INVALID_ARG;
   ON_DEVICE();
-  EntryRules rules;
-  rules.block_in = block_in();
+  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on();
   bool split = false;
-  const bool dith = dither_on();
   for (uint32_t s = 0; s < n_streams_; s++)
     if (!uniform(s)) {
-      // (with dither on: channels that stand apart produce different numbers of frames, a position is not defined)
-      if (n_streams_ != 1 || dith) return SPEEXHIP_ERR_BAD_STATE;
+      // (channels that stand apart produce different numbers of frames: neither an output frame of a matrix nor a dither
+      //  position is defined)
+      if (n_streams_ != 1 || dith || mixed) return SPEEXHIP_ERR_BAD_STATE;
       split = true;
     }
-  // (F32N -> F32N: a power-of-two scale commutes exactly with the FIR, so the float call on the same bytes)
-  // With dither on S16 -> S16 is no such pair -- it runs as the float call between convert_in and the dithered
-  // convert_out -- and the float pairs, written as ever, still count their frames.
-  if (same_bytes_pair(in_fmt, out_fmt) && !(dith && in_fmt == SPEEXHIP_FMT_S16)) {
-    const int rc = process_device(d_in, in_stride, in_len, d_out, out_stride, out_len, in_fmt != SPEEXHIP_FMT_S16, stream);
+  if (same_bytes(in, out, dith)) {
+    const int rc = process_device(in.base, in.stride, in_len, out.base, out.stride, out_len, in.fmt != SPEEXHIP_FMT_S16, stream);
     if (dith && (rc == SPEEXHIP_ERR_SUCCESS || rc == SPEEXHIP_ERR_ALLOC_FAILED)) dither_advance(out_len);
     return rc;
   }
+  EntryRules rules;
+  rules.block_in = block_in();
   rules.float_entry = true;
   // what the float call will do, known before anything is launched (integer arithmetic): sizes the images
   uint32_t most_in = 0, most_out = 0;
@@ -130,71 +93,53 @@ int Batch::process_fmt_device(int in_fmt, const void *d_in, uint64_t in_stride, 
     for (uint32_t c = 0; c < (split ? channels_ : 1u); c++)
       most_out = std::max(most_out, plan_call(filter_.num, filter_.den, in_len[s], out_len[s], P(s, c), rules).produced);
   }
-  const bool conv_in = in_fmt != SPEEXHIP_FMT_F32 && d_in != nullptr && most_in != 0;
-  const bool conv_out = out_fmt != SPEEXHIP_FMT_F32;
-  // The float images: one stream after the other, sized from what this call moves.  (The zero fallback goes through them
-  // as well: its history still takes the converted input, and its silence is whatever the float call writes, converted.)
-  const size_t in_pitch = line_pitch(static_cast<size_t>(most_in) * channels_);
-  const size_t out_pitch = line_pitch(static_cast<size_t>(most_out) * channels_);
-  int rc = ensure_planar_scratch(conv_in ? in_pitch * n_streams_ * sizeof(float) : 0,
-                                 conv_out ? out_pitch * n_streams_ * sizeof(float) : 0);
+  // a side passes through an image unless it has no matrix and its storage IS the image (F32); a present but empty input
+  // is not silence: no frame is read, any non-null address serves
+  const bool pass_in = (in.mix != nullptr || in.fmt != SPEEXHIP_FMT_F32) && in.base != nullptr && most_in != 0;
+  const bool pass_out = out.mix != nullptr || out.fmt != SPEEXHIP_FMT_F32;
+  // The float images: one stream after the other, whole 128-byte lines each, sized from what this call moves.  (The zero
+  // fallback goes through them as well: its history still takes the converted input, and its silence is whatever the
+  // float call writes, converted -- and dithered.)
+  const size_t in_pitch = align64(static_cast<size_t>(most_in) * channels_);
+  const size_t out_pitch = align64(static_cast<size_t>(most_out) * channels_);
+  int rc = ensure_planar_scratch(pass_in ? in_pitch * n_streams_ * sizeof(float) : 0,
+                                 pass_out ? out_pitch * n_streams_ * sizeof(float) : 0);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
-  if (conv_in || (conv_out && most_out != 0)) {
+  if (pass_in || (pass_out && most_out != 0)) {
     // (the images belong to the state: a call on another stream than the previous one waits for it first)
     rc = chain_to(stream);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
-  if (conv_in) {
-    rc = convert_streams(true, in_fmt, d_in, in_stride * bin, d_planar_in_, in_pitch * sizeof(float), in_len, stream);
+  if (pass_in) {
+    rc = side_pass(in, true, d_planar_in_, in_pitch, in_len, stream);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
-  // (a present but empty input is not silence: no frame is read, any non-null address serves)
-  const void *image_in = conv_in ? static_cast<const void *>(d_planar_in_) : d_in;
-  const uint64_t image_in_stride = conv_in ? in_pitch : in_stride;
-  void *image_out = conv_out ? static_cast<void *>(d_planar_out_) : d_out;
-  const uint64_t image_out_stride = conv_out ? out_pitch : out_stride;
+  const void *image_in = pass_in ? static_cast<const void *>(d_planar_in_) : in.base;
+  void *image_out = pass_out ? static_cast<void *>(d_planar_out_) : out.base;
   std::vector<CallPlan> plans;  // of the channels of a state whose channels stand apart
   if (split)
     rc = process_split(image_in, in_len, image_out, out_len, true, stream, &plans);
   else
-    rc = process_device(image_in, image_in_stride, in_len, image_out, image_out_stride, out_len, true, stream);
+    rc = process_device(image_in, pass_in ? in_pitch : in.stride, in_len, image_out, pass_out ? out_pitch : out.stride, out_len,
+                        true, stream);
   if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
   if (plans_out != nullptr) *plans_out = plans;
-  if (conv_out && split) {
-    // channel c wrote plans[c].produced frames: each channel is a strided stream of the converting launch
-    for (uint32_t c0 = 0; c0 < channels_; c0 += kChunk) {
-      const uint32_t n = std::min(kChunk, channels_ - c0);
-      ConvertPack pack;
-      std::memset(&pack, 0, sizeof(pack));
-      uint64_t most = 0;
-      for (uint32_t j = 0; j < n; j++) {
-        const uint32_t c = c0 + j;
-        pack.s[j].src = d_planar_out_ + c * sizeof(float);
-        pack.s[j].dst = static_cast<char *>(d_out) + c * bout;
-        pack.s[j].n = plans[c].produced;
-        pack.s[j].step = channels_;
-        most = std::max(most, pack.s[j].n);
-      }
-      if (hip_failed(launch_convert_out(out_fmt, pack, n, most, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
-    }
-  }
-  if (conv_out && !split) {
+  if (pass_out) {
     // (out_len: what the float call produced)
-    const int crc = convert_streams(false, out_fmt, d_planar_out_, out_pitch * sizeof(float), d_out, out_stride * bout, out_len,
-                                    stream, dith && integer_fmt(out_fmt));
-    if (crc != SPEEXHIP_ERR_SUCCESS) return crc;
+    const int prc = side_pass(out, false, d_planar_out_, out_pitch, out_len, stream, split ? plans.data() : nullptr);
+    if (prc != SPEEXHIP_ERR_SUCCESS) return prc;
   }
   if (dith) dither_advance(out_len);
   return rc;
 }
 
-// A single-stream call on host buffers around a device call: the raw bytes of both sides move by the rule of
-// host_transfer.h -- in place when pinned, through the bounce buffers when small, by the runtime's staged copy when large.
-// device_call(src, dst) enqueues the work on own_stream_ and sets *out_len to the frames produced, out_frame_bytes each.
-// Shared by the formatted and the mixed host calls.
-int Batch::routed_host_call(const void *in, size_t in_bytes, void *out, size_t out_bytes, size_t out_frame_bytes,
-                            const uint32_t *out_len, const std::function<int(const void *, void *)> &device_call) {
+// process_sides_device on own_stream_ around a single-stream call's host buffers: the raw bytes of both sides move by the
+// rule of host_transfer.h -- in place when pinned, through the bounce buffers when small, by the runtime's staged copy when
+// large.
+int Batch::routed_host_call(const CallSide &in_side, size_t in_bytes, uint32_t *in_len, const CallSide &out_side,
+                            size_t out_bytes, uint32_t *out_len) {
+  const void *in = in_side.base;
+  void *out = out_side.base;
   int rc = SPEEXHIP_ERR_SUCCESS;
   DrainOnExit drain(&own_stream_);
   const void *pin_in = in != nullptr ? pinned_view_of(in, in_bytes) : nullptr;
@@ -214,9 +159,9 @@ int Batch::routed_host_call(const void *in, size_t in_bytes, void *out, size_t o
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   if (src == nullptr && in != nullptr) src = h_pin_out_;  // (an empty chunk, not silence)
   void *dst = out_via == Via::InPlace ? pin_out : out_via == Via::Bounce ? static_cast<void *>(h_pin_out_) : static_cast<void *>(d_stage_out_);
-  rc = device_call(src, dst);
+  rc = process_sides_device(at(in_side, src), in_len, at(out_side, dst), out_len, own_stream_);
   if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
-  const size_t made = static_cast<size_t>(*out_len) * out_frame_bytes;
+  const size_t made = static_cast<size_t>(*out_len) * out_side.channels * sample_bytes(out_side.fmt);
   if (device_part(out_via, made) != 0)
     HIP_TRY(hipMemcpyAsync(out_via == Via::Copy ? out : h_pin_out_, d_stage_out_, made, hipMemcpyDeviceToHost, own_stream_));
   const int wrc = wait_call(own_stream_, wait, tail_word(h_pin_out_, pin_out_cap_), ++done_seq_);
@@ -226,57 +171,51 @@ int Batch::routed_host_call(const void *in, size_t in_bytes, void *out, size_t o
   return rc;
 }
 
-// Host buffers: the raw bytes of both sides move exactly as process_host moves samples -- in place when pinned, through
-// the bounce buffers when small, by the runtime's staged copy when large -- and the conversions run on the device.
-int Batch::process_fmt_host(int in_fmt, const void *in, uint32_t *in_len, int out_fmt, void *out, uint32_t *out_len) {
+int Batch::process_sides_host(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len) {
   if (n_streams_ != 1) return SPEEXHIP_ERR_BAD_STATE;
-  const size_t bin = fmt_bytes(in_fmt), bout = fmt_bytes(out_fmt);
-  if (bin == 0 || bout == 0 || out == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
-  const bool dith = dither_on();
-  const bool split = !uniform(0);
-  if (dith && split) return SPEEXHIP_ERR_BAD_STATE;
-  if (same_bytes_pair(in_fmt, out_fmt) && !(dith && in_fmt == SPEEXHIP_FMT_S16)) {
-    const int rc = process_host(in, in_len, out, out_len, in_fmt != SPEEXHIP_FMT_S16);
+  if (!side_ok(in, channels_) || !side_ok(out, channels_) || out.base == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), split = !uniform(0);
+  if (split && dith && !mixed) return SPEEXHIP_ERR_BAD_STATE;
+  if (same_bytes(in, out, dith)) {
+    const int rc = process_host(in.base, in_len, out.base, out_len, in.fmt != SPEEXHIP_FMT_S16);
     if (dith && (rc == SPEEXHIP_ERR_SUCCESS || rc == SPEEXHIP_ERR_ALLOC_FAILED)) dither_advance(out_len);
     return rc;
   }
   ON_DEVICE();
+  if (split && mixed) return SPEEXHIP_ERR_BAD_STATE;
   const uint32_t frames = *in_len;
   uint32_t will_make = 0;  // only as many output frames as this call can produce need a device buffer
   for (uint32_t c = 0; c < (split ? channels_ : 1u); c++)
     will_make = std::max(will_make, produced_closed_form(filter_.num, filter_.den, frames, *out_len, P(0, c)));
-  const size_t in_bytes = static_cast<size_t>(frames) * channels_ * bin;
-  const size_t out_bytes = static_cast<size_t>(will_make) * channels_ * bout;
-  if (split) {
-    int rc = SPEEXHIP_ERR_SUCCESS;
-    DrainOnExit drain(&own_stream_);
-    std::vector<CallPlan> plans;
-    // channels at different positions write different numbers of frames: fetch the whole block and hand the caller
-    // only the samples each channel really wrote (as process_host does)
-    const Via in_via = route_side(in_bytes, in != nullptr, false, false);
-    rc = ensure_stage(in_bytes, out_bytes, pinned_part(in_via, in_bytes), out_bytes);
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-    const void *src = nullptr;
-    rc = stage_input(in_via, in, in_bytes, nullptr, &src);
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-    if (src == nullptr && in != nullptr) src = h_pin_out_;
-    rc = process_fmt_device(in_fmt, src, 0, in_len, out_fmt, d_stage_out_, 0, out_len, own_stream_, &plans);
-    if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
-    uint32_t most = 0;
-    for (const CallPlan &pl : plans) most = std::max(most, pl.produced);
-    const size_t bytes = static_cast<size_t>(most) * channels_ * bout;
-    if (bytes != 0) HIP_TRY(hipMemcpyAsync(h_pin_out_, d_stage_out_, bytes, hipMemcpyDeviceToHost, own_stream_));
-    HIP_TRY(hipStreamSynchronize(own_stream_));
-    drain.armed = false;
-    for (uint32_t c = 0; c < channels_; c++)
-      for (uint32_t j = 0; j < plans[c].produced; j++)
-        std::memcpy(static_cast<char *>(out) + (static_cast<size_t>(j) * channels_ + c) * bout,
-                    h_pin_out_ + (static_cast<size_t>(j) * channels_ + c) * bout, bout);
-    return rc;
-  }
-  return routed_host_call(in, in_bytes, out, out_bytes, channels_ * bout, out_len, [&](const void *src, void *dst) {
-    return process_fmt_device(in_fmt, src, 0, in_len, out_fmt, dst, 0, out_len, own_stream_);
-  });
+  const size_t bout = sample_bytes(out.fmt);
+  const size_t in_bytes = static_cast<size_t>(frames) * in.channels * sample_bytes(in.fmt);
+  const size_t out_bytes = static_cast<size_t>(will_make) * out.channels * bout;
+  if (!split) return routed_host_call(in, in_bytes, in_len, out, out_bytes, out_len);
+  int rc = SPEEXHIP_ERR_SUCCESS;
+  DrainOnExit drain(&own_stream_);
+  std::vector<CallPlan> plans;
+  // channels at different positions write different numbers of frames: fetch the whole block and hand the caller
+  // only the samples each channel really wrote (as process_host does)
+  const Via in_via = route_side(in_bytes, in.base != nullptr, false, false);
+  rc = ensure_stage(in_bytes, out_bytes, pinned_part(in_via, in_bytes), out_bytes);
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  const void *src = nullptr;
+  rc = stage_input(in_via, in.base, in_bytes, nullptr, &src);
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  if (src == nullptr && in.base != nullptr) src = h_pin_out_;
+  rc = process_sides_device(at(in, src), in_len, at(out, d_stage_out_), out_len, own_stream_, &plans);
+  if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
+  uint32_t most = 0;
+  for (const CallPlan &pl : plans) most = std::max(most, pl.produced);
+  const size_t bytes = static_cast<size_t>(most) * channels_ * bout;
+  if (bytes != 0) HIP_TRY(hipMemcpyAsync(h_pin_out_, d_stage_out_, bytes, hipMemcpyDeviceToHost, own_stream_));
+  HIP_TRY(hipStreamSynchronize(own_stream_));
+  drain.armed = false;
+  for (uint32_t c = 0; c < channels_; c++)
+    for (uint32_t j = 0; j < plans[c].produced; j++)
+      std::memcpy(static_cast<char *>(out.base) + (static_cast<size_t>(j) * channels_ + c) * bout,
+                  h_pin_out_ + (static_cast<size_t>(j) * channels_ + c) * bout, bout);
+  return rc;
 }
 
 }  // namespace speexhip

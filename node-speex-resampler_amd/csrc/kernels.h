@@ -7,10 +7,33 @@
 #include <cstdint>
 #include <vector>
 
+#include "../../include/speexhip_resampler.h"
 #include "device_types.h"
 #include "filter_design.h"
 
 namespace speexhip {
+
+// ---- the sample formats (SPEEXHIP_FMT_*): what host and device both need to know of them, stated once ----------------
+// bytes of one sample; 0 = no such format
+constexpr uint32_t sample_bytes(int fmt) {
+  switch (fmt) {
+    case SPEEXHIP_FMT_U8:
+    case SPEEXHIP_FMT_ULAW:
+    case SPEEXHIP_FMT_ALAW: return 1;
+    case SPEEXHIP_FMT_S16: return 2;
+    case SPEEXHIP_FMT_S24: return 3;
+    case SPEEXHIP_FMT_S32:
+    case SPEEXHIP_FMT_F32:
+    case SPEEXHIP_FMT_F32N: return 4;
+    default: return 0;
+  }
+}
+// the formats a state with dither on dithers on their way out: the integer ones, and the companded ones (g711.h), which
+// quantise to int16 on theirs; the float formats are written as they are
+constexpr bool dithered_fmt(int fmt) {
+  return fmt == SPEEXHIP_FMT_U8 || fmt == SPEEXHIP_FMT_S16 || fmt == SPEEXHIP_FMT_S24 || fmt == SPEEXHIP_FMT_S32 ||
+         fmt == SPEEXHIP_FMT_ULAW || fmt == SPEEXHIP_FMT_ALAW;
+}
 
 // Kernel attributes (the opt-in for more than 64 KiB of dynamic LDS) are per DEVICE: set them the
 // first time a kernel is launched on each device of the process.  `seen` = one bit per device id;
@@ -200,10 +223,6 @@ struct ConvertStream {      // one stream's share of a converting launch
 struct ConvertPack {        // like DescPack: up to 32 streams, in the kernel-argument segment
   ConvertStream s[kMaxPackedStreams];
 };
-// streams [0, n) of `pack` from / into format fmt (SPEEXHIP_FMT_*, not F32: that IS the image's format); max_samples =
-// the largest ConvertStream::n among them
-hipError_t launch_convert_in(int fmt, const ConvertPack &pack, uint32_t n, uint64_t max_samples, hipStream_t stream);
-hipError_t launch_convert_out(int fmt, const ConvertPack &pack, uint32_t n, uint64_t max_samples, hipStream_t stream);
 
 // ---- channel mix folded into the conversion (kernels_mix.hip): the pass of a mixed call's side that has a matrix ------
 // mix_in: storage of the call's format, src_channels per frame -> the float image, dst_channels per frame;
@@ -221,14 +240,10 @@ struct MixPack {            // like ConvertPack: up to 32 streams and the matrix
   float m[kMixMaxChannels * kMixMaxChannels];  // row-major dst_channels x src_channels
   uint32_t src_channels, dst_channels;
 };
-// streams [0, n) of `pack`; fmt = the storage side's format (any SPEEXHIP_FMT_*, F32 included); max_frames = the largest
-// MixStream::frames among them
-hipError_t launch_mix_in(int fmt, const MixPack &pack, uint32_t n, uint32_t max_frames, hipStream_t stream);
-hipError_t launch_mix_out(int fmt, const MixPack &pack, uint32_t n, uint32_t max_frames, hipStream_t stream);
 
 // ---- dither on the way out (dither.h): convert_out_dither<F> / mix_out_dither<F>, the output pass of a formatted or mixed
-// call of a state with dither on, for the integer formats and the companded ones (g711.h).  The streams' arguments are the undithered pass's; what the
-// dither needs travels beside them in a second kernel argument.
+// call of a state with dither on, for the formats of dithered_fmt.  The streams' arguments are the undithered pass's; what
+// the dither needs travels beside them in a second kernel argument.
 struct DitherStream {       // one stream's share
   uint64_t seed;            // the stream's own seed
   uint64_t first;           // convert_out_dither: idx of the stream's sample 0 of this launch (position * channels);
@@ -239,11 +254,16 @@ struct DitherPack {         // like ConvertPack: up to 32 streams, in the kernel
   int32_t kind;             // SPEEXHIP_DITHER_*: one for the launch, wave-uniform
   uint32_t reserved;
 };
-// As launch_convert_out / launch_mix_out; fmt = U8, S16, S24 or S32.  Every ConvertStream::step must be 1: sample k of a
-// stream has idx first + k.
-hipError_t launch_convert_out_dither(int fmt, const ConvertPack &pack, const DitherPack &dith, uint32_t n, uint64_t max_samples,
-                                     hipStream_t stream);
-hipError_t launch_mix_out_dither(int fmt, const MixPack &pack, const DitherPack &dith, uint32_t n, uint32_t max_frames,
-                                 hipStream_t stream);
+
+// ---- the launchers of a pass over streams [0, n) of `pack` -------------------------------------------------------------
+// fmt = the storage side's format: any SPEEXHIP_FMT_* for a mix, any but F32 for a conversion (that IS the image's
+// format).  out: image -> storage, otherwise storage -> image.  dith = NULL: the plain instances; otherwise the dithered
+// ones (out only, a dithered_fmt, every ConvertStream::step 1: sample k of a stream has idx first + k).  most = the
+// largest ConvertStream::n / MixStream::frames among the streams.  What a launcher refuses (and channel counts of a
+// matrix outside 1..8) it refuses with hipErrorInvalidValue before it launches.
+hipError_t launch_convert(int fmt, bool out, const ConvertPack &pack, const DitherPack *dith, uint32_t n, uint64_t most,
+                          hipStream_t stream);
+hipError_t launch_mix(int fmt, bool out, const MixPack &pack, const DitherPack *dith, uint32_t n, uint32_t most,
+                      hipStream_t stream);
 
 }  // namespace speexhip

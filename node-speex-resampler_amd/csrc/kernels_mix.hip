@@ -1,4 +1,4 @@
-// kernels_mix.hip -- the channel mix of a mixed call (engine.h, process_mix_device), folded into the pass that converts a
+// kernels_mix.hip -- the channel mix of a mixed call (engine.h, process_sides_device), folded into the pass that converts a
 // side anyway: mix_in<F> reads storage of format F with src_channels per frame and writes the float image the FIR
 // kernels read with dst_channels per frame; mix_out<F> reads the image they wrote and stores format F.  Per frame:
 // to_internal, the matrix, from_internal (format_device.h).  A side with a matrix runs this INSTEAD of convert_*.
@@ -28,8 +28,8 @@
 // faster than this one ("Mixed calls"), so it is gone: a lane's stores already fall into lines its
 // neighbours fill.
 //
-// mix_out_dither<F> (integer and companded formats; a state with dither on): mix_out with the dither of dither.h added before the
-// rounding, instances of their own beside mix_out.  Output o of frame f of a stream at position p has idx
+// mix_out_dither<F> (the formats of dithered_fmt; a state with dither on): mix_out with the dither of dither.h added before
+// the rounding, instances of their own beside mix_out -- the same body, kDither = true.  Output o of frame f of a stream at position p has idx
 // (p + f) * dst_channels + o: a frame is a run of consecutive idx, so the inner half of the generator's word is taken
 // once per frame (twice for the one frame that crosses a 2^32 boundary of idx).
 //
@@ -79,7 +79,7 @@ __device__ __forceinline__ void mix_frame(const MixPack &pack, uint32_t ns, uint
 // sample s of format F out of an LDS area that holds storage bytes in order
 template <int F>
 __device__ __forceinline__ uint32_t lds_raw(const uint32_t *area, uint32_t s) {
-  constexpr uint32_t B = bytes_of(F);
+  constexpr uint32_t B = sample_bytes(F);
   if (B == 4) return area[pad_dword(s)];
   if (B == 2) return area[pad_dword(s >> 1)] >> ((s & 1u) * 16);
   if (B == 1) return area[pad_dword(s >> 2)] >> ((s & 3u) * 8);
@@ -113,11 +113,11 @@ __device__ __forceinline__ void tile_path(const MixPack &pack, const MixStream &
 }
 
 // ---- frame by frame --------------------------------------------------------------------------------------------------
-// frames [tile0, tile0 + n) of the stream
-template <int F, bool kOut>
-__device__ __forceinline__ void element_path(const MixPack &pack, const MixStream &s, uint64_t tile0, uint32_t n, uint32_t ns,
-                                             uint32_t nd) {
-  constexpr uint32_t B = bytes_of(F);
+// frames [tile0, tile0 + n) of the stream; kDither (kOut only): the dithered instances; d and kind are theirs alone
+template <int F, bool kOut, bool kDither>
+__device__ __forceinline__ void element_path(const MixPack &pack, const MixStream &s, const DitherStream *d, int kind,
+                                             uint64_t tile0, uint32_t n, uint32_t ns, uint32_t nd) {
+  constexpr uint32_t B = sample_bytes(F);
   for (uint32_t f = threadIdx.x; f < n; f += kLanes) {
     const uint64_t frame = tile0 + f;
     if (!kOut) {
@@ -129,116 +129,73 @@ __device__ __forceinline__ void element_path(const MixPack &pack, const MixStrea
     } else {
       const float *src = static_cast<const float *>(s.src) + frame * ns;
       char *dst = static_cast<char *>(s.dst) + frame * nd * B;
+      const dither::Run run = kDither ? dither::run_of(d->seed, (d->first + frame) * nd, nd) : dither::Run{};
       mix_frame(
           pack, ns, nd, [&](uint32_t i) { return src[i]; },
-          [&](uint32_t o, float y) { store_raw<F>(dst + o * B, from_internal<F>(y)); });
+          [&](uint32_t o, float y) {
+            store_raw<F>(dst + o * B, encode<F, kDither>(y, [&] { return dither::noise_in(kind, run, o); }));
+          });
     }
   }
 }
 
-template <int F, bool kOut>
-__device__ __forceinline__ void mix_tile(const MixPack &pack, uint32_t *lds) {
+template <int F, bool kOut, bool kDither>
+__device__ __forceinline__ void mix_tile(const MixPack &pack, const DitherPack *dith, uint32_t *lds) {
   const MixStream &s = pack.s[blockIdx.y];
   const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kTileFrames;
   if (s.src == nullptr || tile0 >= s.frames) return;  // (nothing to mix, or a shorter stream of the launch)
   const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(kTileFrames), s.frames - tile0));
   const uint32_t ns = pack.src_channels, nd = pack.dst_channels;
+  const DitherStream *d = kDither ? &dith->s[blockIdx.y] : nullptr;
+  const int kind = kDither ? dith->kind : 0;
   const bool aligned = ((reinterpret_cast<uintptr_t>(s.src) | reinterpret_cast<uintptr_t>(s.dst)) & 15u) == 0;
   if (!kOut && n == kTileFrames && aligned)
-    tile_path<F>(pack, s, tile0, ns, nd, ns * bytes_of(F), nd * 4u, lds);
+    tile_path<F>(pack, s, tile0, ns, nd, ns * sample_bytes(F), nd * 4u, lds);
   else
-    element_path<F, kOut>(pack, s, tile0, n, ns, nd);
+    element_path<F, kOut, kDither>(pack, s, d, kind, tile0, n, ns, nd);
 }
 
 template <int F>
 __global__ __launch_bounds__(kLanes) void mix_in(const MixPack pack) {
   extern __shared__ uint32_t mix_lds[];
-  mix_tile<F, false>(pack, mix_lds);
+  mix_tile<F, false, false>(pack, nullptr, mix_lds);
 }
 template <int F>
 __global__ __launch_bounds__(kLanes) void mix_out(const MixPack pack) {
   extern __shared__ uint32_t mix_lds[];
-  mix_tile<F, true>(pack, mix_lds);
+  mix_tile<F, true, false>(pack, nullptr, mix_lds);
 }
-
-// mix_out with dither: frames [tile0, tile0 + n) of the stream, frame by frame as element_path
 template <int F>
 __global__ __launch_bounds__(kLanes) void mix_out_dither(const MixPack pack, const DitherPack dith) {
-  constexpr uint32_t B = bytes_of(F);
-  const MixStream &s = pack.s[blockIdx.y];
-  const DitherStream &d = dith.s[blockIdx.y];
-  const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kTileFrames;
-  if (s.src == nullptr || tile0 >= s.frames) return;  // (nothing to mix, or a shorter stream of the launch)
-  const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(kTileFrames), s.frames - tile0));
-  const uint32_t ns = pack.src_channels, nd = pack.dst_channels;
-  const int kind = dith.kind;
-  for (uint32_t f = threadIdx.x; f < n; f += kLanes) {
-    const uint64_t frame = tile0 + f;
-    const float *src = static_cast<const float *>(s.src) + frame * ns;
-    char *dst = static_cast<char *>(s.dst) + frame * nd * B;
-    const dither::Run run = dither::run_of(d.seed, (d.first + frame) * nd, nd);
-    mix_frame(
-        pack, ns, nd, [&](uint32_t i) { return src[i]; },
-        [&](uint32_t o, float y) { store_raw<F>(dst + o * B, from_internal_dither<F>(y, dither::noise_in(kind, run, o))); });
-  }
+  mix_tile<F, true, true>(pack, &dith, nullptr);
 }
-
-#define MIX_LAUNCH(F)                                                      \
-  if (kOut)                                                                \
-    hipLaunchKernelGGL((mix_out<F>), grid, block, lds, stream, pack);      \
-  else                                                                     \
-    hipLaunchKernelGGL((mix_in<F>), grid, block, lds, stream, pack);       \
-  break
-template <bool kOut>
-hipError_t launch_mix(int fmt, const MixPack &pack, uint32_t n, uint32_t max_frames, hipStream_t stream) {
-  if (n == 0 || max_frames == 0) return hipSuccess;
-  if (pack.src_channels == 0 || pack.src_channels > kMixMaxChannels || pack.dst_channels == 0 ||
-      pack.dst_channels > kMixMaxChannels)
-    return hipErrorInvalidValue;
-  // the two LDS areas of mix_in's tile path (at most 33.8 KB: no opt-in needed)
-  const uint32_t src_fb = pack.src_channels * bytes_of(fmt), dst_fb = pack.dst_channels * 4u;
-  const uint32_t lds = kOut ? 0u : (area_dwords(kTileFrames * src_fb / 4) + area_dwords(kTileFrames * dst_fb / 4)) * 4;
-  const dim3 grid((max_frames + kTileFrames - 1) / kTileFrames, n), block(kLanes);
-  switch (fmt) {
-    case SPEEXHIP_FMT_U8: MIX_LAUNCH(SPEEXHIP_FMT_U8);
-    case SPEEXHIP_FMT_S16: MIX_LAUNCH(SPEEXHIP_FMT_S16);
-    case SPEEXHIP_FMT_S24: MIX_LAUNCH(SPEEXHIP_FMT_S24);
-    case SPEEXHIP_FMT_S32: MIX_LAUNCH(SPEEXHIP_FMT_S32);
-    case SPEEXHIP_FMT_F32: MIX_LAUNCH(SPEEXHIP_FMT_F32);
-    case SPEEXHIP_FMT_F32N: MIX_LAUNCH(SPEEXHIP_FMT_F32N);
-    case SPEEXHIP_FMT_ULAW: MIX_LAUNCH(SPEEXHIP_FMT_ULAW);
-    case SPEEXHIP_FMT_ALAW: MIX_LAUNCH(SPEEXHIP_FMT_ALAW);
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-#undef MIX_LAUNCH
 
 }  // namespace
 
-hipError_t launch_mix_in(int fmt, const MixPack &pack, uint32_t n, uint32_t max_frames, hipStream_t stream) {
-  return launch_mix<false>(fmt, pack, n, max_frames, stream);
-}
-hipError_t launch_mix_out(int fmt, const MixPack &pack, uint32_t n, uint32_t max_frames, hipStream_t stream) {
-  return launch_mix<true>(fmt, pack, n, max_frames, stream);
-}
-hipError_t launch_mix_out_dither(int fmt, const MixPack &pack, const DitherPack &dith, uint32_t n, uint32_t max_frames,
-                                 hipStream_t stream) {
-  if (n == 0 || max_frames == 0) return hipSuccess;
+hipError_t launch_mix(int fmt, bool out, const MixPack &pack, const DitherPack *dith, uint32_t n, uint32_t most,
+                      hipStream_t stream) {
+  if (n == 0 || most == 0) return hipSuccess;
   if (pack.src_channels == 0 || pack.src_channels > kMixMaxChannels || pack.dst_channels == 0 ||
-      pack.dst_channels > kMixMaxChannels)
+      pack.dst_channels > kMixMaxChannels || (dith != nullptr && !out))
     return hipErrorInvalidValue;
-  const dim3 grid((max_frames + kTileFrames - 1) / kTileFrames, n), block(kLanes);
-  switch (fmt) {
-    case SPEEXHIP_FMT_U8: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_U8>), grid, block, 0, stream, pack, dith); break;
-    case SPEEXHIP_FMT_S16: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_S16>), grid, block, 0, stream, pack, dith); break;
-    case SPEEXHIP_FMT_S24: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_S24>), grid, block, 0, stream, pack, dith); break;
-    case SPEEXHIP_FMT_S32: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_S32>), grid, block, 0, stream, pack, dith); break;
-    case SPEEXHIP_FMT_ULAW: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_ULAW>), grid, block, 0, stream, pack, dith); break;
-    case SPEEXHIP_FMT_ALAW: hipLaunchKernelGGL((mix_out_dither<SPEEXHIP_FMT_ALAW>), grid, block, 0, stream, pack, dith); break;
-    default: return hipErrorInvalidValue;  // (the float formats are not dithered)
-  }
-  return hipGetLastError();
+  // the two LDS areas of mix_in's tile path (at most 33.8 KB: no opt-in needed)
+  const uint32_t src_fb = pack.src_channels * sample_bytes(fmt), dst_fb = pack.dst_channels * 4u;
+  const uint32_t lds = out ? 0u : (area_dwords(kTileFrames * src_fb / 4) + area_dwords(kTileFrames * dst_fb / 4)) * 4;
+  const dim3 grid((most + kTileFrames - 1) / kTileFrames, n), block(kLanes);
+  return with_format(fmt, [&](auto format) -> hipError_t {
+    constexpr int F = decltype(format)::value;
+    if (dith == nullptr) {
+      if (out)
+        hipLaunchKernelGGL((mix_out<F>), grid, block, lds, stream, pack);
+      else
+        hipLaunchKernelGGL((mix_in<F>), grid, block, lds, stream, pack);
+    } else if constexpr (dithered_fmt(F)) {
+      hipLaunchKernelGGL((mix_out_dither<F>), grid, block, 0, stream, pack, *dith);
+    } else {
+      return hipErrorInvalidValue;  // (the float formats are not dithered)
+    }
+    return hipGetLastError();
+  });
 }
 
 }  // namespace speexhip

@@ -13,11 +13,6 @@
 namespace speexhip {
 using namespace detail;
 
-namespace {
-// elements between two streams of a scratch image / two planes of a host call's planar image: whole 128-byte lines
-inline size_t line_pitch(size_t elements) { return (elements + 63) & ~static_cast<size_t>(63); }
-}  // namespace
-
 // The interleaved images of a planar call: per state, grow-only, from the pool.  A grow waits for the state's own last
 // call (which may still read the old image) and for nothing else.
 int Batch::ensure_planar_scratch(size_t in_bytes, size_t out_bytes) {
@@ -57,9 +52,10 @@ int Batch::process_planar_device(const void *d_in, uint64_t in_stream_stride, ui
     most_in = std::max(most_in, in_len[s]);
     most_out = std::max(most_out, plans[s].produced);
   }
-  // the scratch images: one stream after the other, sized from what this call moves (never from the capacities)
-  const size_t in_pitch = line_pitch(static_cast<size_t>(most_in) * channels_);
-  const size_t out_pitch = line_pitch(static_cast<size_t>(most_out) * channels_);
+  // the scratch images: one stream after the other, whole 128-byte lines each, sized from what this call moves (never
+  // from the capacities)
+  const size_t in_pitch = align64(static_cast<size_t>(most_in) * channels_);
+  const size_t out_pitch = align64(static_cast<size_t>(most_out) * channels_);
   int rc = ensure_planar_scratch(in_pitch * n_streams_ * es, out_pitch * n_streams_ * es);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   for (uint32_t s = 0; s < n_streams_; s++)
@@ -139,7 +135,7 @@ int Batch::process_planar_host(const void *const *in_planes, uint32_t *in_len, v
   }
   if (channels_ == 1) return process_host(in_planes ? in_planes[0] : nullptr, in_len, out_planes[0], out_len, float_io);
   ON_DEVICE();
-  const size_t in_pitch = line_pitch(frames), out_pitch = line_pitch(will_make);  // elements between two planes
+  const size_t in_pitch = align64(frames), out_pitch = align64(will_make);  // elements between two planes: whole lines
   const size_t plane_in = frames * es, plane_out = will_make * es;
   const size_t in_bytes = in_pitch * channels_ * es, out_bytes = out_pitch * channels_ * es;
   const bool present = in_planes != nullptr;

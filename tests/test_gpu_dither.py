@@ -298,6 +298,92 @@ def test_batch_streams_have_their_own_seeds_and_positions():
     b.close()
 
 
+def _batch_of_33():
+    """one launch's 32 streams plus one: streams 0 and 32 are the long ones (2500 frames: one whole 4096-sample convert
+    tile and a tail, four whole 512-frame mix tiles and a tail -- and 32 rows of any length start 16-byte aligned, so
+    both take the 16-bytes-per-lane paths), the others short and ragged: the second launch's longest stream is not the
+    first's, and each launch has whole tiles and element tails"""
+    S, T = 33, 2500
+    return S, T, [T if s in (0, S - 1) else 300 + 7 * s for s in range(S)]
+
+
+def test_second_launch_of_a_batch_of_33_streams_with_dither():
+    """three calls on one batch, positions continuing: formatted f32 -> s16 (dithered convert_out), mixed s16 stereo -> u8
+    mono (convert_in, dithered mix_out), mixed u8 mono -> s24 on the stereo state (mix_in, dithered convert_out); every
+    stream against its own float twin, the mix model and the dither model at the stream's seed and running position"""
+    import torch
+    S, T, lens = _batch_of_33()
+    ch, fi, fo, q = 2, 44100, 48000, 7
+    kind, seed, start = dm.TRIANGULAR, SEED, 12345
+    cap = wcap(T, fi, fo)
+    b = speexhip.Batch(S, ch, fi, fo, q)
+    assert b.set_dither(kind, seed, start) == 0
+    twins = [speexhip.Resampler(ch, fi, fo, q) for _ in range(S)]
+    pos = [start] * S
+    # (input format, its channels, in_mix, output format, its channels, out_mix)
+    calls = ((sf.F32, 2, None, sf.S16, 2, None),
+             (sf.S16, 2, None, sf.U8, 1, cm.STEREO_TO_MONO),
+             (sf.U8, 1, cm.MONO_TO_STEREO, sf.S24, 2, None))
+    for i, (in_fmt, c_in, in_mix, o, c_out, out_mix) in enumerate(calls):
+        bo = sf.BYTES[o]
+        raws = [storage_of(in_fmt, T * c_in, 1300 + 50 * i + s) for s in range(S)]
+        src = torch.from_numpy(np.stack(raws)).cuda()
+        row = cap * c_out * bo + 2 * bo   # bytes of a stream's row: room for cap frames and two samples of sentinel
+        dst = torch.full((S, row), SENTINEL, dtype=torch.uint8, device="cuda")
+        args = (in_fmt, src.data_ptr(), T * c_in, lens, o, dst.data_ptr(), row // bo, cap)
+        stream = torch.cuda.current_stream().cuda_stream
+        if in_mix is None and out_mix is None:
+            used, made = b.process_fmt_device(*args, stream)
+        else:
+            used, made = b.process_mix_device(*args, in_mix, out_mix, stream)
+        torch.cuda.synchronize()
+        flat = dst.cpu().numpy()
+        assert used == lens, i
+        for s in range(S):
+            x = sf.to_internal(in_fmt, raws[s][: lens[s] * c_in])
+            xin = x if in_mix is None else cm.mix(in_mix, x)
+            y, used_t = twins[s].process_float(xin.reshape(-1, ch), cap)
+            yout = y if out_mix is None else cm.mix(out_mix, y)
+            want = dm.from_internal(o, yout, kind, dm.stream_seed(seed, s), pos[s], c_out).view(np.uint8)
+            assert (used[s], made[s]) == (used_t, y.shape[0]), (i, s)
+            assert want.size == made[s] * c_out * bo and flat[s, : want.size].tobytes() == want.tobytes(), (i, s)
+            assert (flat[s, want.size:] == SENTINEL).all(), (i, s)
+            pos[s] += made[s]
+            assert b.get_dither(s) == (kind, dm.stream_seed(seed, s), pos[s]), (i, s)
+    for s in range(S):
+        assert b.lines(s).tobytes() == twins[s]._lines().tobytes(), s
+        twins[s].close()
+    b.close()
+
+
+def test_second_launch_of_a_batch_of_33_streams_without_dither():
+    """s24 -> u8, formatted, no matrix, on a fresh batch: convert_in and the plain convert_out, every stream against a
+    single state given the same call (as test_formatted_batch_equals_single_states)"""
+    import torch
+    S, T, lens = _batch_of_33()
+    ch, fi, fo, q = 2, 44100, 48000, 7
+    cap = wcap(T, fi, fo)
+    raws = [storage_of(sf.S24, T * ch, 1500 + s) for s in range(S)]
+    src = torch.from_numpy(np.stack(raws)).cuda()
+    row = cap * ch + 2
+    dst = torch.full((S, row), SENTINEL, dtype=torch.uint8, device="cuda")
+    b = speexhip.Batch(S, ch, fi, fo, q)
+    used, made = b.process_fmt_device(sf.S24, src.data_ptr(), T * ch, lens, sf.U8, dst.data_ptr(), row, cap,
+                                      torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    flat = dst.cpu().numpy()
+    for s in range(S):
+        r = speexhip.Resampler(ch, fi, fo, q)
+        want, used_r = r.process_fmt(raws[s][: lens[s] * ch * 3], sf.S24, sf.U8, cap)
+        assert (used[s], made[s] * ch) == (used_r, want.size), s
+        assert flat[s, : want.size].tobytes() == want.tobytes(), s
+        assert (flat[s, want.size:] == SENTINEL).all(), s
+        assert b.lines(s).tobytes() == r._lines().tobytes(), s
+        assert b.get_dither(s) == (dm.NONE, dm.stream_seed(0, s), 0), s
+        r.close()
+    b.close()
+
+
 # ---- 6. off is what it was -------------------------------------------------------------------------------------------
 def test_dither_off_is_the_undithered_call():
     ch, fi, fo, q = 2, 44100, 48000, 7
