@@ -635,6 +635,69 @@ SPEEXHIP_API int speexhip_debug_dither(int kind, uint64_t seed, uint64_t first_i
 SPEEXHIP_API int speexhip_debug_g711_decode(int fmt, const uint8_t *codes, uint32_t n, float *x);
 SPEEXHIP_API int speexhip_debug_g711_encode(int fmt, const float *y, const double *d, uint32_t n, uint8_t *codes);
 
+/* ------------------------------------------------------------------------------------------
+ * Layouts: a side of a call (its input or its output) is interleaved -- frame f, channel c at sample
+ * f * channels + c -- or planar -- at c * plane_stride + f, one plane per channel.  The sides calls
+ * name format, channel count, matrix and layout of each side independently: (B, C, T) float32 in
+ * +-1.0 in and out (speech models, Web Audio's getChannelData planes), a decoder's interleaved s16le
+ * or G.711 in and (C, T') float planes out, ffmpeg's s16p / s32p / u8p / fltp, a planar 5.1 downmix.
+ *
+ * A call with a planar side IS the mixed call (speexhip_resampler_process_interleaved_mix*) on the
+ * same samples arranged as interleaved frames: the same counters, the same history and position left
+ * behind in every mode, the same return codes, the same value of every sample.  The dither index is
+ * unchanged -- idx = (position + f) * C_out + c with c the channel of the output frame -- so a
+ * dithered planar result is the dithered interleaved result, transposed, and position advances as
+ * for any formatted call.  Layout changes where a sample lies and nothing else.
+ *
+ * With a planar side the float entry's rules hold for every format pair, S16 -> S16 included, as with
+ * a matrix; speexhip_resampler_peek with float_entry = 1 sizes the call.  A side with one channel is
+ * the same bytes in either layout.  With both layouts interleaved the call IS the mixed call, its
+ * S16 -> S16 rule without matrix and dither included.  Both sides planar, F32 -> F32 or F32N -> F32N,
+ * no matrix: the bytes of the planar float call.  A state whose channels the per-channel calls moved
+ * apart is served channel by channel when it is one stream, has no matrix and dither is off: plane c
+ * receives what channel c produced and the lengths of the last channel are reported; with a matrix
+ * or dither on it returns BAD_STATE.  The zero fallback goes through the passes, its silence being
+ * the format's zero.  Every argument error leaves the state, *in_len and *out_len untouched.
+ *
+ * Lengths are frames; strides count samples of the side's format (a packed S24 sample is 3 bytes).
+ * Planes need no alignment beyond their element, the 1-byte formats and S24 none; planes whose base
+ * and stride are multiples of 16 bytes take the kernels' 16-bytes-per-lane path.  A planar side is
+ * converted, mixed and dithered by the pass that transposes it: a sides call launches no more kernels
+ * than the mixed call.  INVALID_ARG: struct_size smaller than this version's, an unknown layout or
+ * format, a matrix side beyond 8 channels (or a state beyond 8 with a matrix), a channel count that
+ * is not the state's without a matrix, out->data == NULL without planes, a NULL element of planes.
+ * Sides, mixed, formatted, interleaved, planar and per-channel calls may be mixed on one state.
+ *
+ * ABI note: 0.7 + layouts adds one enum, one struct and three entry points; SpeexHipInfo, the error
+ * codes and the version string are unchanged. */
+enum { SPEEXHIP_LAYOUT_INTERLEAVED = 0, SPEEXHIP_LAYOUT_PLANAR = 1 };
+typedef struct SpeexHipSide {
+  uint32_t struct_size;   /* the caller's sizeof(SpeexHipSide); smaller than this version's: INVALID_ARG */
+  int32_t fmt;            /* SPEEXHIP_FMT_* */
+  uint32_t channels;      /* samples per frame on this side (the state's count unless mix != NULL) */
+  int32_t layout;         /* SPEEXHIP_LAYOUT_* */
+  const float *mix;       /* host memory, as in the mixed call; NULL = none */
+  void *data;             /* interleaved: frame 0; planar: plane 0.  Input side: only read, NULL = silence */
+  uint64_t plane_stride;  /* planar: samples of fmt between two planes (>= the frames moved); else ignored */
+  uint64_t stream_stride; /* batch form: samples of fmt between two streams; else ignored */
+  void *const *planes;    /* host form, planar only: plane c = planes[c] (separate allocations); NULL = data + c * plane_stride */
+} SpeexHipSide;
+/* Host buffers, synchronous.  An interleaved side moves like a buffer of the mixed call (pageable,
+ * speexhip_block_acquire blocks and caller-pinned buffers used in place), a planar side plane by
+ * plane like the host planar calls.  PTR_OVERLAP when the frames the call writes to an output plane
+ * overlap another plane of the call. */
+SPEEXHIP_API int speexhip_resampler_process_sides(SpeexHipResamplerState *st, const SpeexHipSide *in, uint32_t *in_len,
+                                                  const SpeexHipSide *out, uint32_t *out_len);
+/* Device buffers (planes is not read), asynchronous on hip_stream, ordered like the other device calls. */
+SPEEXHIP_API int speexhip_resampler_process_sides_device(SpeexHipResamplerState *st, const SpeexHipSide *in,
+                                                         uint32_t *in_len, const SpeexHipSide *out, uint32_t *out_len,
+                                                         void *hip_stream);
+/* ... of every stream of a batch: stream s of a side starts stream_stride samples after stream s - 1
+ * (a tensor shaped (batch, channels, time) or (batch, time, channels)); one entry of in_len / out_len
+ * per stream, the one pair of matrices serves all streams. */
+SPEEXHIP_API int speexhip_batch_process_sides_device(SpeexHipBatch *b, const SpeexHipSide *in, uint32_t *in_len,
+                                                     const SpeexHipSide *out, uint32_t *out_len, void *hip_stream);
+
 /* Mid-stream control for every stream of a batch (same semantics as the single-stream calls). */
 SPEEXHIP_API int speexhip_batch_set_rate_frac(SpeexHipBatch *b, uint32_t ratio_num, uint32_t ratio_den,
                                               uint32_t in_rate, uint32_t out_rate);

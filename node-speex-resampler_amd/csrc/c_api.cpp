@@ -648,6 +648,47 @@ int speexhip_batch_process_interleaved_mix_device(SpeexHipBatch *b, int in_fmt, 
                                                              out_len, static_cast<hipStream_t>(hip_stream)); });
 }
 
+namespace {
+// a caller's SpeexHipSide as the engine's CallSide; false: not a side this version can read
+bool side_of(const SpeexHipSide *s, bool host, speexhip::CallSide *side) {
+  if (s == nullptr || s->struct_size < sizeof(SpeexHipSide)) return false;
+  if (s->layout != SPEEXHIP_LAYOUT_INTERLEAVED && s->layout != SPEEXHIP_LAYOUT_PLANAR) return false;
+  *side = speexhip::CallSide{s->fmt, s->channels, s->mix, s->data, s->stream_stride};
+  side->layout = s->layout;
+  side->plane_stride = s->plane_stride;
+  side->planes = host && s->layout == SPEEXHIP_LAYOUT_PLANAR ? s->planes : nullptr;
+  for (uint32_t c = 0; side->planes != nullptr && c < s->channels; c++)
+    if (side->planes[c] == nullptr) return false;
+  return true;
+}
+}  // namespace
+
+int speexhip_resampler_process_sides(SpeexHipResamplerState *st, const SpeexHipSide *in, uint32_t *in_len,
+                                     const SpeexHipSide *out, uint32_t *out_len) {
+  speexhip::CallSide a, b;
+  if (st == nullptr || in_len == nullptr || out_len == nullptr || !side_of(in, true, &a) || !side_of(out, true, &b) ||
+      (b.base == nullptr && b.planes == nullptr))
+    return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return st->batch->process_sides_host(a, in_len, b, out_len); });
+}
+int speexhip_resampler_process_sides_device(SpeexHipResamplerState *st, const SpeexHipSide *in, uint32_t *in_len,
+                                            const SpeexHipSide *out, uint32_t *out_len, void *hip_stream) {
+  speexhip::CallSide a, b;
+  if (st == nullptr || in_len == nullptr || out_len == nullptr || !side_of(in, false, &a) || !side_of(out, false, &b) ||
+      b.base == nullptr)
+    return SPEEXHIP_ERR_INVALID_ARG;
+  a.stride = b.stride = 0;
+  return guarded([&] { return st->batch->process_sides_device(a, in_len, b, out_len, static_cast<hipStream_t>(hip_stream)); });
+}
+int speexhip_batch_process_sides_device(SpeexHipBatch *bt, const SpeexHipSide *in, uint32_t *in_len, const SpeexHipSide *out,
+                                        uint32_t *out_len, void *hip_stream) {
+  speexhip::CallSide a, b;
+  if (bt == nullptr || in_len == nullptr || out_len == nullptr || !side_of(in, false, &a) || !side_of(out, false, &b) ||
+      b.base == nullptr)
+    return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return bt->batch->process_sides_device(a, in_len, b, out_len, static_cast<hipStream_t>(hip_stream)); });
+}
+
 int speexhip_resampler_set_dither(SpeexHipResamplerState *st, int kind, uint64_t seed, uint64_t position) {
   return guarded([&] { return st ? st->batch->set_dither(kind, seed, position) : SPEEXHIP_ERR_INVALID_ARG; });
 }

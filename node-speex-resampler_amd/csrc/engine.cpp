@@ -1601,6 +1601,7 @@ int warm_device(int device) {
   warm_unit_planar(s);
   warm_unit_convert(s);
   warm_unit_mix(s);
+  warm_unit_sides(s);
   HIP_TRY(hipStreamSynchronize(s));
   return SPEEXHIP_ERR_SUCCESS;
 }

@@ -62,6 +62,13 @@ struct CallSide {
                       // call; output side channels x channels(), applied to every frame it produced.  NULL: no mix
   void *base;         // stream 0 (an input side is only read; NULL there: silence)
   uint64_t stride;    // samples of fmt between two streams
+  // Layout (SPEEXHIP_LAYOUT_*): interleaved -- frame f, channel c at sample f * channels + c -- or planar -- at
+  // c * plane_stride + f.  Layout changes where a sample lies and nothing else.  A side of one channel is the same bytes
+  // either way and is served as interleaved.
+  int layout;                      // (0 = interleaved: what a side built without the members below gets)
+  uint64_t plane_stride;           // planar: samples of fmt between two planes (>= the frames moved)
+  void *const *planes;             // planar, host calls only: plane c = planes[c] (separate allocations) instead of
+                                   // base + c * plane_stride
 };
 
 class Batch {
@@ -99,10 +106,16 @@ class Batch {
   // pass.  S16 -> S16, F32 -> F32 and F32N -> F32N without a matrix go straight to process_device.  Counters, positions
   // and the history are the float call's.  A state whose channels stand apart is served channel by channel when it is one
   // stream, has no matrix and dither is off (plans_out: the plan of every channel then, empty otherwise), else BAD_STATE.
+  // A planar side (CallSide::layout) is the same call on the same samples: its pass is planes_* (kernels_sides.hip) in
+  // the place of convert_* / mix_*, which converts, mixes and dithers while it transposes -- F32 without a matrix
+  // included, whose planes are not the image.  With a planar side every format pair runs as the float call (S16 -> S16
+  // too); both sides planar, F32 -> F32 or F32N -> F32N, no matrix: process_planar_device on the same bytes.
   int process_sides_device(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len, hipStream_t stream,
                            std::vector<CallPlan> *plans_out = nullptr);
   // ... on host buffers of a single-stream batch (strides unused); synchronous.  The raw bytes of both sides move by the
   // rule of host_transfer.h, the passes run on the device.
+  // With a planar side: an interleaved side still moves by that rule, a planar one plane by plane into a pitched image as
+  // in process_planar_host; PTR_OVERLAP when the frames written to an output plane overlap another plane of the call.
   int process_sides_host(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len);
   // Dither of the integer output formats of the formatted and mixed calls (dither.h; include/speexhip_resampler.h,
   // "Dither"): a property of the state, off by default.  kind = SPEEXHIP_DITHER_*; stream s draws from
@@ -214,6 +227,8 @@ class Batch {
   // process_sides_device on own_stream_ with the host buffers of both sides routed around it (host_transfer.h)
   int routed_host_call(const CallSide &in, size_t in_bytes, uint32_t *in_len, const CallSide &out, size_t out_bytes,
                        uint32_t *out_len);
+  // process_sides_host of a call with a planar side
+  int planes_host_call(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len);
   int fetch_history(std::vector<float> *host);
   int quiesce();  // waits for this batch's own enqueued work (never for the whole device)
   uint32_t block_in() const { return line_ - (filter_.taps - 1); }

@@ -19,19 +19,39 @@ namespace {
 // with a matrix both channel counts are 1..8, without one the caller's count is the state's
 inline bool side_ok(const CallSide &side, uint32_t state_channels) {
   if (sample_bytes(side.fmt) == 0) return false;
+  if (side.layout != SPEEXHIP_LAYOUT_INTERLEAVED && side.layout != SPEEXHIP_LAYOUT_PLANAR) return false;
   if (side.mix == nullptr) return side.channels == state_channels;
   return state_channels <= kMixMaxChannels && side.channels >= 1 && side.channels <= kMixMaxChannels;
 }
 // The calls that are an existing call on the same bytes: nothing is converted, nothing extra launched.  (F32N -> F32N: a
 // power-of-two scale commutes exactly with the FIR.)  With dither on S16 -> S16 is no such call -- it runs as the float
 // call between convert_in and the dithered convert_out -- and the float pairs, written as ever, still count their frames.
+inline bool planar(const CallSide &side) { return side.layout == SPEEXHIP_LAYOUT_PLANAR && side.channels != 1; }
 inline bool same_bytes(const CallSide &in, const CallSide &out, bool dith) {
-  if (in.mix != nullptr || out.mix != nullptr || in.fmt != out.fmt) return false;
+  if (in.mix != nullptr || out.mix != nullptr || in.fmt != out.fmt || planar(in) || planar(out)) return false;
   return in.fmt == SPEEXHIP_FMT_S16 ? !dith : in.fmt == SPEEXHIP_FMT_F32 || in.fmt == SPEEXHIP_FMT_F32N;
 }
 // the side with its one stream at `base` (a staging buffer of a host call)
 inline CallSide at(const CallSide &side, const void *base) {
   return CallSide{side.fmt, side.channels, side.mix, const_cast<void *>(base), 0};
+}
+// ... a planar side with its planes `pitch` samples apart in a staging image at `base`
+inline CallSide planes_at(const CallSide &side, const void *base, uint64_t pitch) {
+  CallSide staged = at(side, base);
+  staged.layout = SPEEXHIP_LAYOUT_PLANAR;
+  staged.plane_stride = pitch;
+  return staged;
+}
+// Both sides planar, the same float format, no matrix: the planar float call on the same bytes (F32N: a power-of-two scale
+// commutes exactly with the FIR).
+inline bool planar_float_call(const CallSide &in, const CallSide &out) {
+  return planar(in) && planar(out) && in.mix == nullptr && out.mix == nullptr && in.fmt == out.fmt &&
+         (in.fmt == SPEEXHIP_FMT_F32 || in.fmt == SPEEXHIP_FMT_F32N);
+}
+// plane c of a host side
+inline char *host_plane(const CallSide &side, uint32_t c) {
+  return side.planes != nullptr ? static_cast<char *>(side.planes[c])
+                                : static_cast<char *>(side.base) + c * side.plane_stride * sample_bytes(side.fmt);
 }
 }  // namespace
 
@@ -65,9 +85,13 @@ void Batch::dither_advance(const uint32_t *produced) {
   for (uint32_t s = 0; s < n_streams_; s++) dither_pos_[s] += produced[s];
 }
 
-int Batch::process_sides_device(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len,
+int Batch::process_sides_device(const CallSide &in_side, uint32_t *in_len, const CallSide &out_side, uint32_t *out_len,
                                 hipStream_t stream, std::vector<CallPlan> *plans_out) {
-  if (!side_ok(in, channels_) || !side_ok(out, channels_)) return SPEEXHIP_ERR_INVALID_ARG;
+  if (!side_ok(in_side, channels_) || !side_ok(out_side, channels_)) return SPEEXHIP_ERR_INVALID_ARG;
+  // (a side of one channel is the same bytes in either layout)
+  CallSide in = in_side, out = out_side;
+  if (!planar(in)) in.layout = SPEEXHIP_LAYOUT_INTERLEAVED;
+  if (!planar(out)) out.layout = SPEEXHIP_LAYOUT_INTERLEAVED;
   ON_DEVICE();
   const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on();
   bool split = false;
@@ -83,6 +107,12 @@ int Batch::process_sides_device(const CallSide &in, uint32_t *in_len, const Call
     if (dith && (rc == SPEEXHIP_ERR_SUCCESS || rc == SPEEXHIP_ERR_ALLOC_FAILED)) dither_advance(out_len);
     return rc;
   }
+  if (planar_float_call(in, out) && !split) {
+    const int rc = process_planar_device(in.base, in.stride, in.plane_stride, in_len, out.base, out.stride, out.plane_stride,
+                                         out_len, true, stream);
+    if (dith && (rc == SPEEXHIP_ERR_SUCCESS || rc == SPEEXHIP_ERR_ALLOC_FAILED)) dither_advance(out_len);
+    return rc;
+  }
   EntryRules rules;
   rules.block_in = block_in();
   rules.float_entry = true;
@@ -93,10 +123,10 @@ int Batch::process_sides_device(const CallSide &in, uint32_t *in_len, const Call
     for (uint32_t c = 0; c < (split ? channels_ : 1u); c++)
       most_out = std::max(most_out, plan_call(filter_.num, filter_.den, in_len[s], out_len[s], P(s, c), rules).produced);
   }
-  // a side passes through an image unless it has no matrix and its storage IS the image (F32); a present but empty input
-  // is not silence: no frame is read, any non-null address serves
-  const bool pass_in = (in.mix != nullptr || in.fmt != SPEEXHIP_FMT_F32) && in.base != nullptr && most_in != 0;
-  const bool pass_out = out.mix != nullptr || out.fmt != SPEEXHIP_FMT_F32;
+  // a side passes through an image unless it has no matrix and its storage IS the image (interleaved F32); a present but
+  // empty input is not silence: no frame is read, any non-null address serves
+  const bool pass_in = (in.mix != nullptr || in.fmt != SPEEXHIP_FMT_F32 || planar(in)) && in.base != nullptr && most_in != 0;
+  const bool pass_out = out.mix != nullptr || out.fmt != SPEEXHIP_FMT_F32 || planar(out);
   // The float images: one stream after the other, whole 128-byte lines each, sized from what this call moves.  (The zero
   // fallback goes through them as well: its history still takes the converted input, and its silence is whatever the
   // float call writes, converted -- and dithered.)
@@ -173,7 +203,18 @@ int Batch::routed_host_call(const CallSide &in_side, size_t in_bytes, uint32_t *
 
 int Batch::process_sides_host(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len) {
   if (n_streams_ != 1) return SPEEXHIP_ERR_BAD_STATE;
-  if (!side_ok(in, channels_) || !side_ok(out, channels_) || out.base == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  if (!side_ok(in, channels_) || !side_ok(out, channels_)) return SPEEXHIP_ERR_INVALID_ARG;
+  if (planar(in) || planar(out)) return planes_host_call(in, in_len, out, out_len);
+  // (a mono side given as its one plane)
+  if (in.planes != nullptr || out.planes != nullptr) {
+    if ((in.planes != nullptr && in.planes[0] == nullptr) || (out.planes != nullptr && out.planes[0] == nullptr))
+      return SPEEXHIP_ERR_INVALID_ARG;
+    CallSide in1 = in, out1 = out;
+    if (in.planes != nullptr) in1.base = in.planes[0], in1.planes = nullptr;
+    if (out.planes != nullptr) out1.base = out.planes[0], out1.planes = nullptr;
+    return process_sides_host(in1, in_len, out1, out_len);
+  }
+  if (out.base == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
   const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), split = !uniform(0);
   if (split && dith && !mixed) return SPEEXHIP_ERR_BAD_STATE;
   if (same_bytes(in, out, dith)) {
@@ -215,6 +256,112 @@ int Batch::process_sides_host(const CallSide &in, uint32_t *in_len, const CallSi
     for (uint32_t j = 0; j < plans[c].produced; j++)
       std::memcpy(static_cast<char *>(out.base) + (static_cast<size_t>(j) * channels_ + c) * bout,
                   h_pin_out_ + (static_cast<size_t>(j) * channels_ + c) * bout, bout);
+  return rc;
+}
+
+// A host call with a planar side.  Each side moves by its own rule (host_transfer.h): an interleaved side as in
+// routed_host_call -- in place when pinned, through the bounce buffer when small, by the runtime's staged copy when large --
+// a planar side plane by plane into an image whose planes lie whole 128-byte lines apart, as in process_planar_host (all
+// planes of a side have one size, so one route serves the side).  process_sides_device then runs on the images.
+int Batch::planes_host_call(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len) {
+  const bool pl_in = planar(in), pl_out = planar(out);
+  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), split = !uniform(0);
+  if (split && (dith || mixed)) return SPEEXHIP_ERR_BAD_STATE;
+  // (a mono side given as its one plane is an interleaved buffer)
+  CallSide in_flat = in, out_flat = out;
+  if ((!pl_in && in.planes != nullptr && in.planes[0] == nullptr) || (!pl_out && out.planes != nullptr && out.planes[0] == nullptr))
+    return SPEEXHIP_ERR_INVALID_ARG;
+  if (!pl_in && in.planes != nullptr) in_flat.base = in.planes[0];
+  if (!pl_out && out.planes != nullptr) out_flat.base = out.planes[0];
+  const bool present = pl_in ? in.planes != nullptr || in.base != nullptr : in_flat.base != nullptr;
+  if (pl_out ? out.planes == nullptr && out.base == nullptr : out_flat.base == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  for (uint32_t c = 0; pl_in && in.planes != nullptr && c < in.channels; c++)
+    if (in.planes[c] == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  for (uint32_t c = 0; pl_out && out.planes != nullptr && c < out.channels; c++)
+    if (out.planes[c] == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  const uint32_t frames = *in_len;
+  uint32_t will_make = 0;  // only as many output frames as this call can produce are written (and need a device buffer)
+  for (uint32_t c = 0; c < (split ? channels_ : 1u); c++)
+    will_make = std::max(will_make, produced_closed_form(filter_.num, filter_.den, frames, *out_len, P(0, c)));
+  const size_t bin = sample_bytes(in.fmt), bout = sample_bytes(out.fmt);
+  const size_t plane_in = frames * bin, plane_out = will_make * bout;
+  for (uint32_t c = 0; pl_out && c < out.channels; c++) {
+    for (uint32_t k = 0; k < c; k++)
+      if (buffers_overlap(host_plane(out, c), plane_out, host_plane(out, k), plane_out)) return SPEEXHIP_ERR_PTR_OVERLAP;
+    for (uint32_t k = 0; pl_in && present && k < in.channels; k++)
+      if (buffers_overlap(host_plane(out, c), plane_out, host_plane(in, k), plane_in)) return SPEEXHIP_ERR_PTR_OVERLAP;
+  }
+  ON_DEVICE();
+  // what each side moves (payload) and the image the device call works on
+  const size_t in_pitch = align64(frames), out_pitch = align64(will_make);
+  const size_t in_payload = plane_in * in.channels, out_payload = plane_out * out.channels;
+  const size_t in_bytes = pl_in ? in_pitch * in.channels * bin : in_payload;
+  const size_t out_bytes = pl_out ? out_pitch * out.channels * bout : out_payload;
+  // (channels that stand apart write different numbers of frames: the block is fetched whole and the caller handed only
+  //  what each channel really wrote, so nothing is used in place there)
+  const void *pin_in = !pl_in && present && !split ? pinned_view_of(in_flat.base, in_payload) : nullptr;
+  void *pin_out = !pl_out && !split ? pinned_view_of(out_flat.base, out_payload) : nullptr;
+  if (pin_in != nullptr && pin_out != nullptr && buffers_overlap(in_flat.base, in_payload, out_flat.base, out_payload)) pin_in = nullptr;
+  const bool small = small_call(present && pin_in == nullptr ? in_payload : 0, pin_out == nullptr ? out_payload : 0);
+  const Via in_via = route_side(pl_in ? plane_in : in_payload, present, pin_in != nullptr, small);
+  Via out_via = route_side(pl_out ? plane_out : out_payload, true, pin_out != nullptr, small);
+  if (split && !pl_out && out_via == Via::Copy) out_via = Via::Staged;  // (handed over sample by sample below)
+  Wait wait;
+  wait.add(in_via, in_bytes);
+  wait.add(out_via, out_bytes);
+  DrainOnExit drain(&own_stream_);
+  int rc = ensure_stage(device_part(in_via, in_bytes), device_part(out_via, out_bytes), pinned_part(in_via, in_bytes),
+                        pinned_part(out_via, out_bytes) + 64);
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  const void *src = nullptr;
+  if (!pl_in) {
+    rc = stage_input(in_via, in_flat.base, in_payload, pin_in, &src);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  } else if (present && frames != 0) {
+    for (uint32_t c = 0; c < in.channels; c++) {
+      if (in_via == Via::Copy)
+        HIP_TRY(hipMemcpyAsync(d_stage_in_ + c * in_pitch * bin, host_plane(in, c), plane_in, hipMemcpyHostToDevice, own_stream_));
+      else
+        std::memcpy(h_pin_in_ + c * in_pitch * bin, host_plane(in, c), plane_in);
+    }
+    if (in_via == Via::Staged) HIP_TRY(hipMemcpyAsync(d_stage_in_, h_pin_in_, in_bytes, hipMemcpyHostToDevice, own_stream_));
+    src = in_via == Via::Bounce ? h_pin_in_ : d_stage_in_;
+  }
+  if (src == nullptr && present) src = h_pin_out_;  // (an empty chunk, not silence)
+  void *dst = out_via == Via::InPlace ? pin_out : out_via == Via::Bounce ? static_cast<void *>(h_pin_out_) : static_cast<void *>(d_stage_out_);
+  std::vector<CallPlan> plans;
+  rc = process_sides_device(pl_in ? planes_at(in, src, in_pitch) : at(in, src), in_len,
+                            pl_out ? planes_at(out, dst, out_pitch) : at(out, dst), out_len, own_stream_, &plans);
+  if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
+  // frames each channel of the result received (channels that stand apart produce different numbers of them)
+  std::vector<uint32_t> made(out.channels, *out_len);
+  for (uint32_t c = 0; split && c < out.channels; c++) made[c] = plans[c].produced;
+  const uint32_t most = *std::max_element(made.begin(), made.end());
+  const size_t moved = pl_out ? out_bytes : static_cast<size_t>(most) * out.channels * bout;  // bytes of the result's image
+  if (out_via == Via::Copy && pl_out) {
+    for (uint32_t c = 0; c < out.channels; c++)
+      if (made[c] != 0)
+        HIP_TRY(hipMemcpyAsync(host_plane(out, c), d_stage_out_ + c * out_pitch * bout, made[c] * bout, hipMemcpyDeviceToHost, own_stream_));
+  } else if (out_via == Via::Copy) {
+    if (moved != 0) HIP_TRY(hipMemcpyAsync(out_flat.base, d_stage_out_, moved, hipMemcpyDeviceToHost, own_stream_));
+  } else if (device_part(out_via, moved) != 0) {
+    HIP_TRY(hipMemcpyAsync(h_pin_out_, d_stage_out_, moved, hipMemcpyDeviceToHost, own_stream_));
+  }
+  const int wrc = wait_call(own_stream_, wait, tail_word(h_pin_out_, pin_out_cap_), ++done_seq_);
+  if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
+  drain.armed = false;
+  const bool from_pinned = out_via == Via::Bounce || out_via == Via::Staged;
+  if (from_pinned && pl_out) {
+    for (uint32_t c = 0; c < out.channels; c++)
+      if (made[c] != 0) std::memcpy(host_plane(out, c), h_pin_out_ + c * out_pitch * bout, made[c] * bout);
+  } else if (from_pinned && !split) {
+    std::memcpy(out_flat.base, h_pin_out_, moved);
+  } else if (from_pinned) {
+    for (uint32_t c = 0; c < out.channels; c++)
+      for (uint32_t j = 0; j < made[c]; j++)
+        std::memcpy(static_cast<char *>(out_flat.base) + (static_cast<size_t>(j) * out.channels + c) * bout,
+                    h_pin_out_ + (static_cast<size_t>(j) * out.channels + c) * bout, bout);
+  }
   return rc;
 }
 

@@ -73,6 +73,7 @@ void warm_unit_period_w16g(hipStream_t s);
 void warm_unit_planar(hipStream_t s);
 void warm_unit_convert(hipStream_t s);
 void warm_unit_mix(hipStream_t s);
+void warm_unit_sides(hipStream_t s);
 
 // compute units of the calling thread's current device (cached per device id)
 inline uint32_t device_compute_units() {
@@ -265,5 +266,31 @@ hipError_t launch_convert(int fmt, bool out, const ConvertPack &pack, const Dith
                           hipStream_t stream);
 hipError_t launch_mix(int fmt, bool out, const MixPack &pack, const DitherPack *dith, uint32_t n, uint32_t most,
                       hipStream_t stream);
+
+// ---- channel planes of any format <-> the float image (kernels_sides.hip): the pass of a side whose layout is planar --
+// planes_in: C planes of the call's format -> the interleaved float image; planes_out: the image -> planes.  Conversion,
+// the channel matrix (when the side has one) and the dither happen in the same pass as the transposition.
+// frames of a workgroup's tile, for every format (whole 16-byte pieces of a plane: 64 pieces of the 1-byte formats and
+// packed s24, 128 of s16, 256 of the 4-byte formats)
+constexpr uint32_t kSidesTileFrames = 1024;
+struct PlaneStream {        // one stream's share of a launch
+  const void *src;          // planes_in: plane 0 of the storage, planes_out: the float image; NULL = nothing
+  void *dst;                // planes_in: the float image, planes_out: plane 0
+  uint64_t plane_stride;    // samples of the format between two planes (>= frames)
+  uint32_t frames;          // frames to move
+  uint32_t reserved;
+};
+struct PlanePack {          // like MixPack: up to 32 streams and the matrix, in the kernel-argument segment
+  PlaneStream s[kMaxPackedStreams];
+  float m[kMixMaxChannels * kMixMaxChannels];  // row-major destination x source channels; read when mixed != 0
+  uint32_t storage_channels;  // planes of a stream
+  uint32_t image_channels;    // samples the pass reads or writes per frame of the image
+  uint32_t image_pitch;       // floats between two frames of the image: image_channels, or more when the pass moves one
+                              // channel of wider frames (a state whose channels stand apart)
+  uint32_t mixed;             // 0: plane c is channel c of the image (any channel count); otherwise m applies, 1..8 a side
+};
+// dith as for launch_mix: DitherStream::first = the stream's position, idx = (first + frame) * storage_channels + plane
+hipError_t launch_planes(int fmt, bool out, const PlanePack &pack, const DitherPack *dith, uint32_t n, uint32_t most,
+                         hipStream_t stream);
 
 }  // namespace speexhip

@@ -2,7 +2,8 @@
 // the caller's storage and the float image the FIR runs on, at most kMaxPackedStreams streams per launch.  A side with a
 // matrix runs the mixing kernel (kernels_mix.hip) INSTEAD of the converting one (kernels_convert.hip), so a call launches
 // the float call's kernels plus at most one pass per side.  The state's channel count C is what the FIR runs on; a frame
-// of a side with a matrix holds side.channels samples in storage and C in the image.
+// of a side with a matrix holds side.channels samples in storage and C in the image.  A planar side (CallSide::layout)
+// runs the plane kernel (kernels_sides.hip) instead of either, with or without a matrix: still one pass.
 #include <algorithm>
 #include <cstring>
 
@@ -35,7 +36,30 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
       return apart != nullptr ? apart[item].produced : lens[item];
     };
     hipError_t e;
-    if (side.mix != nullptr) {
+    if (side.layout == SPEEXHIP_LAYOUT_PLANAR) {
+      // planes_* (kernels_sides.hip): conversion, matrix and dither in the pass that transposes.  A stream's planes lie
+      // plane_stride samples apart; a channel that stands apart is one plane and every channels()-th float of the image
+      PlanePack pack;
+      std::memset(&pack, 0, sizeof(pack));
+      pack.storage_channels = apart != nullptr ? 1 : side.channels;
+      pack.image_channels = apart != nullptr ? 1 : channels_;
+      pack.image_pitch = channels_;
+      pack.mixed = side.mix != nullptr;
+      if (side.mix != nullptr) std::memcpy(pack.m, side.mix, sizeof(float) * side.channels * channels_);
+      const size_t planar_step = (apart != nullptr ? side.plane_stride : side.stride) * sample_bytes(side.fmt);
+      uint32_t most = 0;
+      for (uint32_t j = 0; j < n; j++) {
+        const uint32_t item = first + j;
+        char *storage = static_cast<char *>(side.base) + item * planar_step, *in_image = image + item * image_step;
+        pack.s[j].src = to_image ? storage : in_image;
+        pack.s[j].dst = to_image ? in_image : storage;
+        pack.s[j].plane_stride = side.plane_stride;
+        pack.s[j].frames = apart != nullptr ? apart[item].produced : lens[item];
+        most = std::max(most, pack.s[j].frames);
+      }
+      if (dithered) dith = dither_pack(first, n, 1);
+      e = launch_planes(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream);
+    } else if (side.mix != nullptr) {
       MixPack pack;
       std::memset(&pack, 0, sizeof(pack));
       pack.src_channels = to_image ? side.channels : channels_;

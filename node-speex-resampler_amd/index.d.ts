@@ -139,6 +139,17 @@ declare class SpeexResampler {
     processChunkMix(chunk: Buffer, inFormat: SampleFormat, outFormat: SampleFormat, inMix: number[][] | null,
       outMix: number[][] | null): Buffer;
 
+    /**
+     * processChunkMix with a layout per side.  `input`: a Buffer of interleaved frames, or one typed array per input
+     * channel (planar) holding the plane's bytes in inSide.format.  outSide.planar: the result is one typed array per
+     * channel of the format's element type (Uint8Array for the 1-byte formats and 's24le') instead of a Buffer.  The same
+     * samples and stream state as processChunkMix on the frames interleaved; with a planar side every format pair runs
+     * by processChunkFloat's capacity rule.  outSide.channels, when given, must be the result's channel count.
+     */
+    processChunkSides(input: Buffer | ArrayBufferView[], inSide: { format: SampleFormat, mix?: number[][] | null },
+        outSide: { format: SampleFormat, planar?: boolean, channels?: number, mix?: number[][] | null }):
+        Buffer | Array<Uint8Array | Int16Array | Int32Array | Float32Array>;
+
     /** mid-stream control (speex_resampler_set_rate / set_quality / skip_zeros / reset_mem) */
     setRate(inRate: number, outRate: number): void;
     setQuality(quality: number): void;

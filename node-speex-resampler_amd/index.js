@@ -314,6 +314,72 @@ class SpeexResampler {
     return speexModule.processMix(this._resamplerPtr, chunk, fin.id, fout.id, frames, cap, inChannels, mi, outChannels, mo);
   }
 
+  /**
+   * processChunkMix with a layout per side: either side may be planar (one typed array per channel) instead of interleaved.
+   * `input` is a Buffer of interleaved frames, or an array of typed arrays, one per input channel, each holding the
+   * plane's bytes in inSide.format (Web Audio's getChannelData planes are Float32Array in 'f32le-normalized'; a packed
+   * 's24le' plane is a Uint8Array of 3 bytes per sample).  inSide: { format, mix? }; outSide: { format, planar?, channels?,
+   * mix? } -- planar: true gives an array of typed arrays of the format's element type (Uint8Array for the 1-byte formats
+   * and 's24le', Int16Array, Int32Array, Float32Array), otherwise a Buffer.  It is processChunkMix on the same samples
+   * arranged as interleaved frames: the same values, the same stream state; with a planar side every format pair runs by
+   * processChunkFloat's capacity rule.  A decoder's interleaved s16le to a model's float planes:
+   * r.processChunkSides(chunk, { format: 's16le' }, { format: 'f32le-normalized', planar: true }); Web Audio planes in and
+   * out: r.processChunkSides(planes, { format: 'f32le-normalized' }, { format: 'f32le-normalized', planar: true }).
+   */
+  processChunkSides(input, inSide, outSide) {
+    if (!speexModule) {
+      throw new Error('You need to wait for SpeexResampler.initPromise before calling this method');
+    }
+    this._refuseWhileAsyncPending('processChunkSides');
+    const fin = SAMPLE_FORMATS[inSide && inSide.format];
+    const fout = SAMPLE_FORMATS[outSide && outSide.format];
+    if (!fin || !fout) {
+      throw new Error('Unknown sample format: ' + (fin ? outSide && outSide.format : inSide && inSide.format));
+    }
+    const planarIn = Array.isArray(input);
+    const planarOut = !!outSide.planar;
+    const inMix = inSide.mix == null ? null : inSide.mix;
+    const outMix = outSide.mix == null ? null : outSide.mix;
+    if (!planarIn && !planarOut) return this.processChunkMix(input, inSide.format, outSide.format, inMix, outMix);
+    const flat = (m, rows, cols, name) => {
+      if (m == null) return null;
+      const ok = Array.isArray(m) && m.length >= 1 && m.length <= 8 && (rows === undefined || m.length === rows) &&
+        m.every((r) => Array.isArray(r) && r.length >= 1 && r.length <= 8 && r.length === m[0].length &&
+          (cols === undefined || r.length === cols) && r.every((v) => typeof v === 'number'));
+      if (!ok || this.channels > 8) {
+        throw new Error(name + ' should be ' + (rows === undefined ? 'rows of ' + cols : rows + ' rows of') +
+          ' numbers, at most 8 x 8');
+      }
+      return Float32Array.from(m.flat());
+    };
+    const mi = flat(inMix, this.channels, undefined, 'inSide.mix');
+    const mo = flat(outMix, undefined, this.channels, 'outSide.mix');
+    const inChannels = mi ? inMix[0].length : this.channels;
+    const outChannels = mo ? outMix.length : this.channels;
+    if (outSide.channels !== undefined && outSide.channels !== outChannels) {
+      throw new Error('outSide.channels should be ' + outChannels);
+    }
+    let frames;
+    if (planarIn) {
+      const ok = input.length === inChannels && input.every((p) => ArrayBuffer.isView(p) && p.byteLength === input[0].byteLength);
+      if (!ok || input[0].byteLength % fin.bytes !== 0) {
+        throw new Error('input should be ' + inChannels + ' typed arrays of equal length, whole samples of ' + fin.bytes + ' bytes');
+      }
+      frames = (input[0].byteLength / fin.bytes) | 0;
+    } else {
+      if (input.length % (inChannels * fin.bytes) !== 0) {
+        throw new Error('Chunk length should be a multiple of channels * ' + fin.bytes + ' bytes');
+      }
+      frames = (input.length / inChannels / fin.bytes) | 0;
+    }
+    // the capacity rule of processChunkFloat on these frames of the resampler's channel count
+    const [, cap] = this._prepare({ length: frames * this.channels * Float32Array.BYTES_PER_ELEMENT }, Float32Array.BYTES_PER_ELEMENT);
+    // kind of a result plane: Uint8Array, Int16Array, Int32Array, Float32Array
+    const kind = fout.bytes === 2 ? 1 : fout.bytes === 4 ? (fout.id === 3 ? 2 : 3) : 0;
+    return speexModule.processSides(this._resamplerPtr, input, fin.id, fout.id, frames, cap, inChannels, mi, outChannels, mo,
+      planarOut, kind);
+  }
+
   /** Mid-stream control (SURVEY 8f row N3; speex_resampler_set_rate / set_quality / ...). */
   setRate(inRate, outRate) {
     this._refuseWhileAsyncPending('setRate');

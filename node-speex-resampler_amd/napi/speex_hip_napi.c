@@ -489,6 +489,152 @@ static napi_value ProcessMix(napi_env env, napi_callback_info info) {
   return out;
 }
 
+/* bytes of an element of a typed array kind; 0 for a kind the planes of a sides call do not take */
+static size_t typed_element_bytes(napi_typedarray_type t) {
+  switch (t) {
+    case napi_uint8_array:
+    case napi_int8_array: return 1;
+    case napi_int16_array:
+    case napi_uint16_array: return 2;
+    case napi_int32_array:
+    case napi_uint32_array:
+    case napi_float32_array: return 4;
+    default: return 0;
+  }
+}
+
+/* processSides(handle, input: Buffer | null | TypedArray[], inFormat, outFormat, inFrames, outCapacityFrames, inChannels,
+ * inMix: Float32Array|null, outChannels, outMix: Float32Array|null, outPlanar: boolean, outKind: the kind of a result
+ * plane's typed array) -> Buffer of interleaved frames, or one typed array per output channel: speexhip_resampler_process_sides
+ * on the caller's own memory -- an array of typed arrays is a planar input, plane c being element c -- the result written
+ * straight into fresh memory of exactly the frames the call makes.  index.js names the formats and picks outKind. */
+static napi_value ProcessSides(napi_env env, napi_callback_info info) {
+  size_t argc = 12;
+  napi_value argv[12];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  int32_t in_fmt = -1, out_fmt = -1, out_kind = 0;
+  uint32_t in_len = 0, out_len = 0, in_channels = 0, out_channels = 0;
+  bool out_planar = false, in_planar = false;
+  NAPI_OK(napi_get_value_int32(env, argv[2], &in_fmt));
+  NAPI_OK(napi_get_value_int32(env, argv[3], &out_fmt));
+  NAPI_OK(napi_get_value_uint32(env, argv[4], &in_len));
+  NAPI_OK(napi_get_value_uint32(env, argv[5], &out_len));
+  NAPI_OK(napi_get_value_uint32(env, argv[6], &in_channels));
+  NAPI_OK(napi_get_value_uint32(env, argv[8], &out_channels));
+  NAPI_OK(napi_get_value_bool(env, argv[10], &out_planar));
+  NAPI_OK(napi_get_value_int32(env, argv[11], &out_kind));
+  const float *in_mix = NULL, *out_mix = NULL;
+  size_t in_mix_n = 0, out_mix_n = 0;
+  if (!mix_matrix(env, argv[7], &in_mix, &in_mix_n) || !mix_matrix(env, argv[9], &out_mix, &out_mix_n)) {
+    napi_throw_type_error(env, NULL, "a mix must be a Float32Array or null");
+    return NULL;
+  }
+  const size_t bin = speexhip_sample_bytes(in_fmt), bout = speexhip_sample_bytes(out_fmt);
+  if (bin == 0 || bout == 0 || in_channels == 0 || out_channels == 0 || in_channels > 64 || out_channels > 64) {
+    napi_throw_range_error(env, NULL, "unknown sample format or channel count");
+    return NULL;
+  }
+  /* (index.js names a result plane's kind: 0 Uint8Array, 1 Int16Array, 2 Int32Array, 3 Float32Array) */
+  static const napi_typedarray_type kKinds[4] = {napi_uint8_array, napi_int16_array, napi_int32_array, napi_float32_array};
+  const napi_typedarray_type out_type = kKinds[out_kind & 3];
+  const size_t out_es = typed_element_bytes(out_type);
+  if (out_planar && (out_es == 0 || bout % out_es != 0)) {
+    napi_throw_range_error(env, NULL, "the result's typed array kind does not hold its format");
+    return NULL;
+  }
+  void *in_planes[64], *out_planes[64];
+  void *in_data = NULL;
+  size_t in_bytes = 0;
+  NAPI_OK(napi_is_array(env, argv[1], &in_planar));
+  if (in_planar) {
+    uint32_t n = 0;
+    NAPI_OK(napi_get_array_length(env, argv[1], &n));
+    if (n != in_channels) {
+      napi_throw_range_error(env, NULL, "one typed array per input channel is expected");
+      return NULL;
+    }
+    for (uint32_t c = 0; c < n; c++) {
+      napi_value v;
+      napi_typedarray_type t;
+      size_t len = 0;
+      void *data = NULL;
+      bool typed = false;
+      if (napi_get_element(env, argv[1], c, &v) != napi_ok || napi_is_typedarray(env, v, &typed) != napi_ok || !typed ||
+          napi_get_typedarray_info(env, v, &t, &len, &data, NULL, NULL) != napi_ok || typed_element_bytes(t) == 0) {
+        napi_throw_type_error(env, NULL, "a planar input must be an array of typed arrays");
+        return NULL;
+      }
+      if ((size_t)in_len * bin > len * typed_element_bytes(t)) {
+        napi_throw_range_error(env, NULL, "input frame count exceeds a plane");
+        return NULL;
+      }
+      in_planes[c] = data != NULL ? data : (void *)in_planes; /* (an empty array: nothing is read, but NULL means "no plane") */
+    }
+  } else if (!buffer_or_null(env, argv[1], &in_data, &in_bytes)) {
+    napi_throw_type_error(env, NULL, "input must be a Buffer, null or an array of typed arrays");
+    return NULL;
+  } else if (in_data != NULL && (size_t)in_len * in_channels * bin > in_bytes) {
+    napi_throw_range_error(env, NULL, "input frame count exceeds the chunk");
+    return NULL;
+  }
+  Handle *h = NULL;
+  SpeexHipResamplerState *st = lock_state(env, argv[0], &h);
+  if (st == NULL) return NULL;
+  SpeexHipInfo si;
+  speexhip_resampler_get_info(st, &si);
+  if ((in_mix != NULL && in_mix_n != (size_t)si.nb_channels * in_channels) ||
+      (out_mix != NULL && out_mix_n != (size_t)si.nb_channels * out_channels)) {
+    UNLOCK(h);
+    napi_throw_range_error(env, NULL, "mix size does not match the channel counts");
+    return NULL;
+  }
+  /* (a side of one channel is the same bytes in either layout; with a planar side, as with a matrix, every pair has the
+   *  float call's counters -- otherwise s16 -> s16 is the int16 call) */
+  const int planar_side = (in_planar && in_channels > 1) || (out_planar && out_channels > 1);
+  const int float_entry = planar_side || in_mix != NULL || out_mix != NULL || !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
+  uint32_t will_use = 0, will_make = 0;
+  speexhip_resampler_peek(st, in_len, out_len, float_entry, &will_use, &will_make);
+  napi_value result = NULL;
+  uint64_t nowhere = 0;
+  SpeexHipSide in_side, out_side;
+  memset(&in_side, 0, sizeof(in_side));
+  memset(&out_side, 0, sizeof(out_side));
+  in_side.struct_size = out_side.struct_size = (uint32_t)sizeof(SpeexHipSide);
+  in_side.fmt = in_fmt;
+  in_side.channels = in_channels;
+  in_side.mix = in_mix;
+  in_side.layout = in_planar ? SPEEXHIP_LAYOUT_PLANAR : SPEEXHIP_LAYOUT_INTERLEAVED;
+  in_side.data = in_data;
+  in_side.planes = in_planar ? in_planes : NULL;
+  out_side.fmt = out_fmt;
+  out_side.channels = out_channels;
+  out_side.mix = out_mix;
+  out_side.layout = out_planar ? SPEEXHIP_LAYOUT_PLANAR : SPEEXHIP_LAYOUT_INTERLEAVED;
+  if (out_planar) {
+    NAPI_OK_LOCKED(h, napi_create_array_with_length(env, out_channels, &result));
+    for (uint32_t c = 0; c < out_channels; c++) {
+      napi_value ab, ta;
+      void *dst = NULL;
+      NAPI_OK_LOCKED(h, napi_create_arraybuffer(env, (size_t)will_make * bout, &dst, &ab));
+      NAPI_OK_LOCKED(h, napi_create_typedarray(env, out_type, (size_t)will_make * bout / out_es, ab, 0, &ta));
+      NAPI_OK_LOCKED(h, napi_set_element(env, result, c, ta));
+      out_planes[c] = will_make != 0 && dst != NULL ? dst : (void *)&nowhere;
+    }
+    out_side.planes = out_planes;
+  } else {
+    void *dst = NULL;
+    NAPI_OK_LOCKED(h, napi_create_buffer(env, (size_t)will_make * out_channels * bout, &dst, &result));
+    out_side.data = dst != NULL ? dst : (void *)&nowhere; /* empty Buffer: nothing will be written, but NULL means "no buffer" */
+  }
+  const int rc = speexhip_resampler_process_sides(st, &in_side, &in_len, &out_side, &out_len);
+  UNLOCK(h);
+  if (rc != 0 || out_len != will_make) {
+    napi_throw_error(env, NULL, speexhip_resampler_strerror(rc != 0 ? rc : SPEEXHIP_ERR_BAD_STATE));
+    return NULL;
+  }
+  return result;
+}
+
 /* processChunks(handle, chunks: Buffer[], inFrames: number[], outCapacities: number[]) -> Buffer[]
  * n consecutive process() calls as one transfer + one launch
  * (speexhip_resampler_process_chunks_int); the i-th Buffer is what the i-th call returns. */
@@ -1393,6 +1539,7 @@ NAPI_MODULE_INIT() {
       {"processPlanar", NULL, ProcessPlanar, NULL, NULL, NULL, napi_default, NULL},
       {"processFormat", NULL, ProcessFormat, NULL, NULL, NULL, napi_default, NULL},
       {"processMix", NULL, ProcessMix, NULL, NULL, NULL, napi_default, NULL},
+      {"processSides", NULL, ProcessSides, NULL, NULL, NULL, napi_default, NULL},
       {"processChunks", NULL, ProcessChunks, NULL, NULL, NULL, napi_default, NULL},
       {"processAsync", NULL, ProcessAsync, NULL, NULL, NULL, napi_default, NULL},
       {"processChunksAsync", NULL, ProcessChunksAsync, NULL, NULL, NULL, napi_default, NULL},

@@ -100,7 +100,24 @@ EXPORTS = [
     "speexhip_batch_get_dither", "speexhip_debug_dither",
     # companded formats: G.711 mu-law and A-law in the formatted and mixed calls
     "speexhip_debug_g711_decode", "speexhip_debug_g711_encode",
+    # layouts: planar or interleaved per side of a formatted or mixed call
+    "speexhip_resampler_process_sides", "speexhip_resampler_process_sides_device", "speexhip_batch_process_sides_device",
 ]
+
+# layout of a side of the sides calls (SPEEXHIP_LAYOUT_*)
+LAYOUT_INTERLEAVED, LAYOUT_PLANAR = 0, 1
+
+
+def _layout(name):
+    """'interleaved' / 'planar' (or a LAYOUT_* value, or None = interleaved) as a LAYOUT_* value"""
+    if name is None:
+        return LAYOUT_INTERLEAVED
+    if name in (LAYOUT_INTERLEAVED, LAYOUT_PLANAR) and not isinstance(name, str):
+        return int(name)
+    try:
+        return {"interleaved": LAYOUT_INTERLEAVED, "planar": LAYOUT_PLANAR}[name]
+    except KeyError:
+        raise ValueError("layout must be 'planar' or 'interleaved', not %r" % (name,))
 
 
 def _mix_matrix(m, channels, is_input):
@@ -130,6 +147,27 @@ class Info(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Side(C.Structure):
+    """SpeexHipSide: one side of a sides call"""
+    _fields_ = [("struct_size", C.c_uint32), ("fmt", C.c_int32), ("channels", C.c_uint32), ("layout", C.c_int32),
+                ("mix", C.c_void_p), ("data", C.c_void_p), ("plane_stride", C.c_uint64), ("stream_stride", C.c_uint64),
+                ("planes", C.POINTER(C.c_void_p))]
+
+
+def make_side(fmt, channels, layout=LAYOUT_INTERLEAVED, mix=None, data=None, plane_stride=0, stream_stride=0, planes=None):
+    """A Side: mix = a float32 array (kept alive by the caller) or None; data = an address or None; planes = a ctypes
+    array of addresses (host form) or None."""
+    side = Side()
+    side.struct_size = C.sizeof(Side)
+    side.fmt, side.channels, side.layout = int(fmt), int(channels), int(layout)
+    side.mix = None if mix is None else mix.ctypes.data
+    side.data = data
+    side.plane_stride, side.stream_stride = int(plane_stride), int(stream_stride)
+    if planes is not None:
+        side.planes = C.cast(planes, C.POINTER(C.c_void_p))
+    return side
 
 
 _lib = None
@@ -328,6 +366,14 @@ def lib():
             L.speexhip_debug_g711_decode.argtypes = [i32, p, u32, p]
             L.speexhip_debug_g711_encode.restype = i32
             L.speexhip_debug_g711_encode.argtypes = [i32, p, p, u32, p]
+        if hasattr(L, "speexhip_resampler_process_sides") or "SPEEXHIP_LIB_PATH" not in os.environ:
+            ps = C.POINTER(Side)
+            L.speexhip_resampler_process_sides.restype = i32
+            L.speexhip_resampler_process_sides.argtypes = [p, ps, pu32, ps, pu32]
+            L.speexhip_resampler_process_sides_device.restype = i32
+            L.speexhip_resampler_process_sides_device.argtypes = [p, ps, pu32, ps, pu32, p]
+            L.speexhip_batch_process_sides_device.restype = i32
+            L.speexhip_batch_process_sides_device.argtypes = [p, ps, pu32, ps, pu32, p]
         _lib = L
     return _lib
 
@@ -915,6 +961,86 @@ class Resampler:
             raise RuntimeError(strerror(rc))
         return il.value, ol.value
 
+    def sides_call(self, x, in_fmt, out_fmt, cap, in_layout=None, out_layout=None, in_mix=None, out_mix=None,
+                   null_frames=0, out_plane_stride=None, separate_planes=False):
+        """The host sides C call itself.  in_layout / out_layout: 'planar' | 'interleaved' (None = interleaved).  x: an
+        interleaved input holds whole frames as in mix_call; a planar one is (in_channels, T) of in_fmt's storage type
+        (packed S24: (in_channels, 3 * T) uint8) or a sequence of such 1-D planes; None = silence of null_frames frames.
+        separate_planes: hand the planes over as separate allocations (SpeexHipSide::planes) instead of one block.
+        Returns (rc, consumed, produced, out): `out` is the whole output buffer, every byte pre-filled with SENTINEL_BYTE --
+        flat and `cap` frames long when interleaved, (out_channels, out_plane_stride) when planar (out_plane_stride
+        defaults to cap; S24: three bytes per sample along the last axis)."""
+        mi, n_in = _mix_matrix(in_mix, self.channels, True)
+        mo, n_out = _mix_matrix(out_mix, self.channels, False)
+        li, lo = _layout(in_layout), _layout(out_layout)
+        bi, bo = fmt_bytes(in_fmt), fmt_bytes(out_fmt)
+        keep = []
+        a = make_side(in_fmt, n_in, li, mi)
+        if x is None:
+            n = int(null_frames)
+        elif li == LAYOUT_PLANAR:
+            planes = [np.ascontiguousarray(q, dtype=fmt_dtype(in_fmt)).reshape(-1) for q in x]
+            assert len(planes) == n_in and all(q.nbytes == planes[0].nbytes for q in planes)
+            n = planes[0].nbytes // bi
+            if separate_planes:
+                keep.append(planes)
+                ptrs = (C.c_void_p * n_in)(*[q.ctypes.data for q in planes])
+                a = make_side(in_fmt, n_in, li, mi, planes=ptrs)
+            else:
+                block = np.stack(planes) if n else np.zeros((n_in, 1), fmt_dtype(in_fmt))
+                keep.append(block)
+                a = make_side(in_fmt, n_in, li, mi, data=block.ctypes.data, plane_stride=n)
+        else:
+            xf = np.ascontiguousarray(x, dtype=fmt_dtype(in_fmt)).reshape(-1)
+            n = xf.nbytes // (bi * n_in)
+            assert n * bi * n_in == xf.nbytes, "whole frames only"
+            keep.append(xf)
+            a = make_side(in_fmt, n_in, li, mi, data=xf.ctypes.data)
+        room = max(int(cap), 1)
+        if lo == LAYOUT_PLANAR:
+            ps = room if out_plane_stride is None else int(out_plane_stride)
+            if separate_planes:
+                outs = [np.full(ps * bo, self.SENTINEL_BYTE, np.uint8) for _ in range(n_out)]
+                ptrs_o = (C.c_void_p * n_out)(*[q.ctypes.data for q in outs])
+                b = make_side(out_fmt, n_out, lo, mo, planes=ptrs_o)
+            else:
+                raw = np.full((n_out, ps * bo), self.SENTINEL_BYTE, np.uint8)
+                b = make_side(out_fmt, n_out, lo, mo, data=raw.ctypes.data, plane_stride=ps)
+        else:
+            raw = np.full(room * n_out * bo, self.SENTINEL_BYTE, np.uint8)
+            b = make_side(out_fmt, n_out, lo, mo, data=raw.ctypes.data)
+        il, ol = C.c_uint32(n), C.c_uint32(int(cap))
+        rc = lib().speexhip_resampler_process_sides(self._h, C.byref(a), C.byref(il), C.byref(b), C.byref(ol))
+        if lo == LAYOUT_PLANAR and separate_planes:
+            out = np.stack(outs).view(fmt_dtype(out_fmt))
+        else:
+            out = raw.view(fmt_dtype(out_fmt))
+        return rc, il.value, ol.value, out
+
+    def process_sides(self, x, in_fmt, out_fmt, capacity, in_layout=None, out_layout=None, in_mix=None, out_mix=None,
+                      null_frames=0):
+        """Sides call on host buffers: the mixed call with a layout per side ('planar' | 'interleaved').  A planar x is
+        (in_channels, T); a planar result is (out_channels, produced) (S24: three bytes per sample along the last axis),
+        an interleaved one flat as in process_mix.  Returns (result, consumed)."""
+        rc, used, made, out = self.sides_call(x, in_fmt, out_fmt, capacity, in_layout, out_layout, in_mix, out_mix,
+                                              null_frames)
+        if rc:
+            raise RuntimeError(strerror(rc))
+        per = 3 if out_fmt == FMT_S24 else 1
+        if _layout(out_layout) == LAYOUT_PLANAR:
+            return out[:, : made * per].copy(), used
+        n_out = self.channels if out_mix is None else len(out_mix)
+        return out[: made * n_out * per].copy(), used
+
+    def process_sides_device(self, in_side, in_frames, out_side, out_capacity, stream_ptr=0):
+        """device buffers described by two Side structures (make_side); (consumed, produced)"""
+        il, ol = C.c_uint32(in_frames), C.c_uint32(out_capacity)
+        rc = lib().speexhip_resampler_process_sides_device(self._h, C.byref(in_side), C.byref(il), C.byref(out_side),
+                                                           C.byref(ol), C.c_void_p(stream_ptr))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return il.value, ol.value
+
     def set_dither(self, kind, seed=0, position=0):
         """Dither of the integer output formats of the formatted and mixed calls: kind = DITHER_NONE / _RECTANGULAR /
         _TRIANGULAR, position = index of the stream's next output frame.  Returns the C call's code (INVALID_ARG for an
@@ -1099,8 +1225,21 @@ class Batch:
             raise RuntimeError(strerror(rc))
         return list(il), list(ol)
 
+    def process_sides_device(self, in_side, in_frames, out_side, out_capacity, stream_ptr=0):
+        """Sides call of every stream: the mixed call with a layout per side.  in_side / out_side: Side structures
+        (make_side) naming format, channel count, layout, matrix, stream 0's address and the strides in samples of the
+        side's format."""
+        n = self.n_streams
+        il = (C.c_uint32 * n)(*([in_frames] * n if np.isscalar(in_frames) else in_frames))
+        ol = (C.c_uint32 * n)(*([out_capacity] * n if np.isscalar(out_capacity) else out_capacity))
+        rc = lib().speexhip_batch_process_sides_device(self._h, C.byref(in_side), il, C.byref(out_side), ol,
+                                                       C.c_void_p(stream_ptr))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return list(il), list(ol)
+
     def _process_tensor_fmt(self, x, out_capacity, in_frames, out_dtype, normalized, in_mix=None, out_mix=None,
-                            in_format=None, out_format=None):
+                            in_format=None, out_format=None, in_layout=None, out_layout=None):
         """process_tensor beyond int16 -> int16 and float32 -> float32: interleaved frames (..., T, C) through the
         formatted call (the mixed call when a matrix is given: x then holds in_channels per frame and the result
         out_channels).  uint8 = U8, int16 = S16, int32 = S32, float32 = F32 (normalized: +-1.0 full scale); in_format /
@@ -1124,18 +1263,42 @@ class Batch:
         if FMT_S24 in (in_fmt, out_fmt):
             raise ValueError("process_tensor does not take packed S24: a sample is not a whole element")
         xb = x if x.dim() == 3 else x.unsqueeze(0)
-        B, T, Cn = xb.shape
-        n_in = self.channels if in_mix is None else _mix_matrix(in_mix, self.channels, True)[1]
-        n_out = self.channels if out_mix is None else _mix_matrix(out_mix, self.channels, False)[1]
+        sides = in_layout is not None or out_layout is not None
+        planar_in = _layout(in_layout) == LAYOUT_PLANAR
+        if planar_in:
+            B, Cn, T = xb.shape
+        else:
+            B, T, Cn = xb.shape
+        mi, n_in = _mix_matrix(in_mix, self.channels, True)
+        mo, n_out = _mix_matrix(out_mix, self.channels, False)
         if B != self.n_streams or Cn != n_in:
             raise ValueError("tensor of %d streams x %d channels for a batch of %d x %d" % (B, Cn, self.n_streams, n_in))
-        if not xb[0].is_contiguous():
+        if planar_in:
+            if T > 1 and xb.stride(-1) != 1:
+                raise ValueError("the last dimension of a planar tensor must be dense (stride 1)")
+        elif not xb[0].is_contiguous():
             raise ValueError("the frames of a stream must be dense (T, C)")
         i = self.info()
         if out_capacity is None:
             out_capacity = (T * i["den_rate"] + i["num_rate"] - 1) // i["num_rate"] + 1
-        out = torch.empty((B, max(int(out_capacity), 1), n_out), dtype=out_dtype, device=x.device)
         stream = torch.cuda.current_stream(x.device).cuda_stream
+        if sides:
+            if _layout(out_layout) == LAYOUT_PLANAR:
+                # (rows of whole 128-byte lines: aligned planes take the kernels' 16-bytes-per-lane path; the result is a
+                #  view of the padded buffer)
+                pitch = (max(int(out_capacity), 1) + 127) & ~127
+                out = torch.empty((B, n_out, pitch), dtype=out_dtype, device=x.device)
+                b = make_side(out_fmt, n_out, LAYOUT_PLANAR, mo, out.data_ptr(), out.stride(1), out.stride(0))
+            else:
+                out = torch.empty((B, max(int(out_capacity), 1), n_out), dtype=out_dtype, device=x.device)
+                b = make_side(out_fmt, n_out, LAYOUT_INTERLEAVED, mo, out.data_ptr(), 0, out.stride(0))
+            # (a dimension of size 1 may carry any stride: planes and streams are then never stepped over)
+            a = make_side(in_fmt, n_in, _layout(in_layout), mi, xb.data_ptr(), xb.stride(1) if planar_in else 0,
+                          xb.stride(0) if B > 1 else 0)
+            _, made = self.process_sides_device(a, T if in_frames is None else in_frames, b, int(out_capacity), stream)
+            out = out[:, :, : max(made)] if _layout(out_layout) == LAYOUT_PLANAR else out[:, : max(made)]
+            return (out if x.dim() == 3 else out[0]), made
+        out = torch.empty((B, max(int(out_capacity), 1), n_out), dtype=out_dtype, device=x.device)
         if in_mix is None and out_mix is None:
             _, made = self.process_fmt_device(
                 in_fmt, xb.data_ptr(), xb.stride(0) if B > 1 else 0, T if in_frames is None else in_frames,
@@ -1148,15 +1311,16 @@ class Batch:
         return (out if x.dim() == 3 else out[0]), made
 
     def process_tensor(self, x, out_capacity=None, in_frames=None, out_dtype=None, normalized=False, in_mix=None,
-                       out_mix=None, in_format=None, out_format=None):
+                       out_mix=None, in_format=None, out_format=None, in_layout=None, out_layout=None):
         """x: a CUDA tensor (B, C, T) or (C, T), int16 or float32, whose last dimension is dense (any other strides).
         Runs on torch's current stream.  in_frames: frames per stream (default T for all); out_capacity: frames the
         result may hold per stream (default: what T frames can produce).  Returns (tensor of the same rank with
         T_out = max(produced), list of frames produced per stream).
 
         Other sample types -- a uint8 (offset binary) or int32 tensor, out_dtype= another type than x's, or
-        normalized=True (float32 in +-1.0 instead of int16 units) -- take the formatted call, which works on
-        interleaved frames: x is then (B, T, C) or (T, C), dense, and so is the result.
+        normalized=True (float32 in +-1.0 instead of int16 units) -- take the formatted call: without a named layout
+        (below) x is then interleaved frames (B, T, C) or (T, C), dense, and so is the result; with in_layout='planar' /
+        out_layout='planar' the same conversions work on (B, C, T) directly.
 
         in_mix (channels x in_channels) / out_mix (out_channels x channels): the mixed call, also on interleaved
         frames -- x is (B, T, in_channels) and the result (B, T', out_channels), of any of the sample types above.
@@ -1164,8 +1328,21 @@ class Batch:
         in_format / out_format (FMT_*): name a side's sample format instead of inferring it from the dtype, also on
         interleaved frames -- a uint8 tensor with in_format=FMT_ULAW is G.711 mu-law, out_format=FMT_ALAW gives a uint8
         tensor of A-law bytes.  A side that is not named goes by its dtype as above (the result's being x's unless
-        out_dtype says otherwise)."""
+        out_dtype says otherwise).
+
+        in_layout / out_layout ('planar' | 'interleaved'): the sides call, which takes either layout on either side with
+        every keyword above -- no transpose on the caller's part.  When either is given (the other then defaults to
+        'interleaved'), x is (B, C, T) for a planar input -- any view whose last dimension is dense -- and (B, T, C) for
+        an interleaved one, and the result is (B, C', T') or (B, T', C') by out_layout.  (B, C, T) float32 in +-1.0 both
+        ways: process_tensor(x, normalized=True, in_layout='planar', out_layout='planar'); a decoder's interleaved
+        int16 to a model's planes: process_tensor(x, out_dtype=torch.float32, normalized=True, in_layout='interleaved',
+        out_layout='planar').  With both None the function does what the paragraphs above say."""
         import torch
+        if in_layout is not None or out_layout is not None:
+            if not x.is_cuda or x.dim() not in (2, 3):
+                raise ValueError("process_tensor wants a CUDA tensor of rank 2 or 3 for a named layout")
+            return self._process_tensor_fmt(x, out_capacity, in_frames, out_dtype, normalized, in_mix, out_mix, in_format,
+                                            out_format, in_layout, out_layout)
         if in_format is not None or out_format is not None:
             if not x.is_cuda or x.dim() not in (2, 3):
                 raise ValueError("process_tensor wants a CUDA tensor (B, T, C) or (T, C) for a named format")
