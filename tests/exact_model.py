@@ -111,6 +111,15 @@ def with_silence(x, taps, at=None):
     return x
 
 
+def samples(frames, ch, seed, taps, tone=False):
+    """One call's int16 samples, as the one-state streams of the GPU tests feed them: noise with a stretch of silence
+    longer than the filter wherever one fits, or (tone) a low-amplitude tonal signal."""
+    if tone:
+        return orc.tone_pcm(frames, ch, seed=seed)
+    x = orc.lcg_pcm(frames * ch, seed).reshape(frames, ch)
+    return with_silence(x, taps) if frames > 2 * taps + 64 else x
+
+
 def ulp32(v):
     """the spacing of float32 around the real value v (array): 2^(exponent - 23), subnormal spacing below 2^-126"""
     _, ex = np.frexp(np.abs(v))

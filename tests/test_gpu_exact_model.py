@@ -53,11 +53,7 @@ def _report(family):
               "int16 samples off halfup(truth) <= %.2e" % (family, f["cases"], f["rms"], f["ratio"], f["max"], f["z"], f["int16"]))
 
 
-def _samples(frames, ch, seed, taps, tone=False):
-    if tone:
-        return orc.tone_pcm(frames, ch, seed=seed)
-    x = orc.lcg_pcm(frames * ch, seed).reshape(frames, ch)
-    return em.with_silence(x, taps) if frames > 2 * taps + 64 else x
+_samples = em.samples
 
 
 def _judge(family, name, model, bits, fed, got16, gotf, wantf, fedf=None, underflow=False, statistics=True,
@@ -126,7 +122,9 @@ def _one_state(family, ch, i, o, q, fast_path, sizes=(1, 21011, 0, 9000), mode=N
                 y, u = r.process(x, cap)
                 w, wu = ref.process(x, cap)
             assert u == wu and y.shape == w.shape and r.position() == ref.position(), (name, kind, call)
-            got.append(y), want.append(w), fed.append(x[:u])
+            # (a capacity-bound call may end between two outputs of one input frame: the stream has read that frame
+            #  and not consumed it.  After the last call nothing else takes its place: it belongs to the line.)
+            got.append(y), want.append(w), fed.append(x[: u + 1] if call == len(sizes) - 1 else x[:u])
         outs[kind] = (np.concatenate(got), np.concatenate(want), np.concatenate(fed))
         r.close()
     if float_samples is None:
@@ -240,31 +238,37 @@ def test_exact_model_exact_fallback():
     """192:1: no fast kernel holds the filter.  The exact kernel's output must EQUAL the oracle's, and the oracle (the
     reference's fp32-rounded products) must pass (a) with the fp32 bound."""
     for (ch, i, o, q, frames) in par.EXACT_FALLBACK_CASES:
-        model = em.Model(ch, i, o, q)
-        for kind in ("int16", "float"):
-            r, ref = speexhip.Resampler(ch, i, o, q), orc.Oracle(ch, i, o, q)
-            assert r.info()["fast_path"] == 0 and r.info()["accumulate_bits"] == (64 if model.double_kind else 32)
-            got, fed = [], []
-            for call, n in enumerate((1, frames // 3, 0, frames - frames // 3)):
-                x = _samples(n, ch, 77 + call, model.taps)
-                if kind == "float":
-                    y, u = r.process_float(x.astype(np.float32), BIG)
-                    w, wu = ref.process_float(x.astype(np.float32), BIG)
-                else:
-                    y, u = r.process(x, BIG)
-                    w, wu = ref.process(x, BIG)
-                assert u == wu and np.array_equal(y, w), ((ch, i, o, q), kind, call)
-                got.append(y), fed.append(x[:u])
-            got, fed = np.concatenate(got), np.concatenate(fed)
-            truth, mag = model.truth(fed, got.shape[0])
-            if kind == "float":
-                fails, stats = em.judge_float(model, fed, got, truth, mag, 32, None)
-                _note("exact fallback", stats)
-            else:
-                fails = em.hard_int16(model, fed, got, truth, mag, 32)
-            assert not fails, ((ch, i, o, q), kind, fails)
-            r.close()
+        _exact_kernel("exact fallback", ch, i, o, q, frames)
     _report("exact fallback")
+
+
+def _exact_kernel(family, ch, i, o, q, frames):
+    """One int16 and one float stream of `frames` frames through the exact kernel: bytes equal to the oracle's call by
+    call, and the oracle inside (a)."""
+    model = em.Model(ch, i, o, q)
+    for kind in ("int16", "float"):
+        r, ref = speexhip.Resampler(ch, i, o, q), orc.Oracle(ch, i, o, q)
+        assert r.info()["fast_path"] == 0 and r.info()["accumulate_bits"] == (64 if model.double_kind else 32)
+        got, fed = [], []
+        for call, n in enumerate((1, frames // 3, 0, frames - frames // 3)):
+            x = _samples(n, ch, 77 + call, model.taps)
+            if kind == "float":
+                y, u = r.process_float(x.astype(np.float32), BIG)
+                w, wu = ref.process_float(x.astype(np.float32), BIG)
+            else:
+                y, u = r.process(x, BIG)
+                w, wu = ref.process(x, BIG)
+            assert u == wu and np.array_equal(y, w), ((ch, i, o, q), kind, call)
+            got.append(y), fed.append(x[:u])
+        got, fed = np.concatenate(got), np.concatenate(fed)
+        truth, mag = model.truth(fed, got.shape[0])
+        if kind == "float":
+            fails, stats = em.judge_float(model, fed, got, truth, mag, 32, None)
+            _note(family, stats)
+        else:
+            fails = em.hard_int16(model, fed, got, truth, mag, 32)
+        assert not fails, ((ch, i, o, q), kind, fails)
+        r.close()
 
 
 # (channels, in, out, quality, streams, frames, fast_path, int16 window expected or None = not asserted)
@@ -288,9 +292,13 @@ def test_exact_model_batches_that_fill_the_chip(ch, i, o, q, S, F, fast_path, w1
     _report("batch")
 
 
+# (channels, in, out, quality, streams, frames)
+PHASE_PAIR_BATCHES = [(1, 44100, 8000, 7, 8, 131072), (2, 48000, 22050, 7, 8, 131072), (3, 44100, 16000, 5, 6, 100000)]
+
+
 def test_exact_model_mono_phase_pair_plans_by_the_rule():
     """batches of wide-window decimators that the launch rule runs over phase pairs (period_launch_prefers_pp)"""
-    for (ch, i, o, q, S, F) in ((1, 44100, 8000, 7, 8, 131072), (2, 48000, 22050, 7, 8, 131072), (3, 44100, 16000, 5, 6, 100000)):
+    for (ch, i, o, q, S, F) in PHASE_PAIR_BATCHES:
         g = gcd(i, o)
         assert speexhip.debug_launch_shape(i // g, o // g, q, ch, S, F)["phase_pairs"] or ch == 3, (ch, i, o, q)
         _batch("phase pairs", ch, i, o, q, S, F, 2)

@@ -276,14 +276,14 @@ def test_many_rates_and_qualities_against_the_oracle():
         frames = int(rng.choice([700, 5000, 20000]))
         x = orc.tone_pcm(frames, ch, seed=trial) if trial % 2 else orc.lcg_pcm(frames * ch, trial).reshape(frames, ch)
         want, wu = orc.Oracle(ch, i, o, q).process(x, 1 << 20)
-        for mode in (speexhip.MODE_EXACT, speexhip.MODE_FAST):
+        for mode in (speexhip.MODE_EXACT, speexhip.MODE_FAST, None):      # (None: the default mode, judged like FAST)
             r = speexhip.Resampler(ch, i, o, q, mode=mode)
             got, used = r.process(x, 1 << 20)
             assert used == wu, (ch, i, o, q)
             if mode == speexhip.MODE_EXACT:
                 assert np.array_equal(got, want), "EXACT differs for %s" % ((ch, i, o, q),)
             else:
-                assert_close(got, want, "fast %s" % ((ch, i, o, q),))
+                assert_close(got, want, "%s %s" % ("fast" if mode is not None else "default mode", (ch, i, o, q)))
             r.close()
 
 
