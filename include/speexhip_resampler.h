@@ -431,7 +431,9 @@ SPEEXHIP_API int speexhip_batch_process_planar_float_device(
  * halfup(v) = floor(v + 0.5), evaluated exactly (ties go up, negative ones too: -2.5 -> -2).  The
  * integer formats saturate, +inf / -inf go to their rails and NaN becomes the format's zero (128 for
  * U8); the float formats never saturate.  U8 and packed S24 buffers need no alignment, the others that
- * of their element.
+ * of their element.  Further formats, stated in sections of their own below: G.711 mu-law / A-law
+ * ("Companded formats"), binary16 / bfloat16 in +-1.0 and big-endian S16 / S24 / S32 ("Half-float and
+ * big-endian formats").
  *
  * A formatted call IS the float call (..._process_interleaved_float*) on the converted input,
  * followed by the output conversion: the same counters (speexhip_resampler_peek with float_entry = 1
@@ -454,7 +456,13 @@ enum {
   SPEEXHIP_FMT_F32N = 5,
   /* companded formats ("Companded formats" below) start at 16; 6..15 stay invalid */
   SPEEXHIP_FMT_ULAW = 16,
-  SPEEXHIP_FMT_ALAW = 17
+  SPEEXHIP_FMT_ALAW = 17,
+  /* half-float and big-endian formats ("Half-float and big-endian formats" below); 18, 19, 22, 23 stay invalid */
+  SPEEXHIP_FMT_F16N = 20,
+  SPEEXHIP_FMT_BF16N = 21,
+  SPEEXHIP_FMT_S16BE = 24,
+  SPEEXHIP_FMT_S24BE = 25,
+  SPEEXHIP_FMT_S32BE = 26
 };
 /* Bytes of one sample of a format (host only); 0 for an unknown format. */
 SPEEXHIP_API uint32_t speexhip_sample_bytes(int fmt);
@@ -634,6 +642,55 @@ SPEEXHIP_API int speexhip_debug_dither(int kind, uint64_t seed, uint64_t first_i
  * rounding, d == NULL = no dither.  INVALID_ARG for a format that is not companded. */
 SPEEXHIP_API int speexhip_debug_g711_decode(int fmt, const uint8_t *codes, uint32_t n, float *x);
 SPEEXHIP_API int speexhip_debug_g711_encode(int fmt, const float *y, const double *d, uint32_t n, uint8_t *codes);
+
+/* ------------------------------------------------------------------------------------------
+ * Half-float and big-endian formats: what a model in half precision reads and writes, and linear
+ * PCM in network / file byte order (RTP L16 of RFC 3551 and L24 of RFC 3190, AIFF).  All at most 4
+ * bytes per sample:
+ *
+ *   format  value  storage                                                     FS
+ *   F16N    20     IEEE binary16, little-endian, +-1.0 full scale              1
+ *   BF16N   21     bfloat16 (the upper half of an fp32), little-endian, +-1.0  1
+ *   S16BE   24     the S16 sample, bytes reversed                              2^15
+ *   S24BE   25     the packed S24 sample, bytes reversed (3 bytes)             2^23
+ *   S32BE   26     the S32 sample, bytes reversed                              2^31
+ *
+ * The values 6..15 stay invalid, and so do 18, 19, 22 and 23.  speexhip_sample_bytes gives 2, 2, 2, 3, 4.
+ *
+ * Big-endian PCM: decode is the S16 / S24 / S32 rule on the byte-reversed sample; encode is the S16 /
+ * S24 / S32 rule, then the byte reversal -- half-up rounding, saturation, NaN to 0 and +-inf to the
+ * rails as there.  For dither they are integer formats: the noise joins exactly as for the
+ * little-endian format, and a dithered BE result is the dithered LE result with each sample's bytes
+ * reversed.  S24BE needs no alignment, S16BE and S32BE that of their element.
+ *
+ * F16N: decode x = (float)h * 32768.0f -- both steps exact for every code, subnormals included; +-inf
+ * stay +-inf and NaN stays NaN.  Encode z = y * (1.0f / 32768.0f) in fp32, then z rounded to nearest
+ * even to binary16 with subnormal results kept (not flushed); |z| >= 65520 goes to +-inf.  NaN encodes
+ * to the canonical 0x7E00 | sign: the bytes of a stream stay a function of the stream alone.
+ *
+ * BF16N: decode x = as_float(b << 16) * 32768.0f, one fp32 product, fp32 subnormal inputs honoured.
+ * Encode z = y * (1.0f / 32768.0f), u = bits(z): NaN -> 0x7FC0 | (u >> 16 & 0x8000); otherwise
+ * (u + 0x7FFF + ((u >> 16) & 1)) >> 16 -- round to nearest even, overflow rounds into 0x7F80 by itself.
+ *
+ * Both half formats are float formats: they never saturate and are never dithered (with dither on the
+ * call still advances position, as for F32 / F32N), and the zero fallback's silence is +0.
+ *
+ * In the calls: a format of this section on either side always runs as the float call between the two
+ * passes, with the float entry's counter rules (speexhip_resampler_peek with float_entry = 1 sizes
+ * it); no pair among them is an identity pair -- S16BE -> S16BE decodes, filters and encodes, as the
+ * companded formats do.  Everything else a formatted, mixed or sides call promises holds unchanged:
+ * channels moved apart, the zero fallback, argument errors leaving state and lengths untouched,
+ * struct_size.  The formats are accepted in every host, device and batch form of ..._fmt*, ..._mix*
+ * and ..._sides*, interleaved or planar.
+ *
+ * ABI note: 0.7 + halfbe adds five enum values and two entry points; SpeexHipInfo, the error codes
+ * and the version string are unchanged. */
+/* Host only, no GPU: the very statements the kernels compile, for the tests to hold against their
+ * model.  x[i] = decode(sample i of storage); sample i of storage = encode(y[i]), for the three
+ * big-endian formats with d[i] (LSB of the format) added before the rounding, d == NULL = no dither
+ * (d must be NULL for the half formats).  INVALID_ARG for a format that is not of this section. */
+SPEEXHIP_API int speexhip_debug_format_decode(int fmt, const void *storage, uint32_t n, float *x);
+SPEEXHIP_API int speexhip_debug_format_encode(int fmt, const float *y, const double *d, uint32_t n, void *storage);
 
 /* ------------------------------------------------------------------------------------------
  * Layouts: a side of a call (its input or its output) is interleaved -- frame f, channel c at sample

@@ -10,6 +10,7 @@
 #include "dither.h"
 #include "engine.h"
 #include "g711.h"
+#include "halfbe.h"
 #include "pool.h"
 
 using speexhip::Batch;
@@ -720,6 +721,54 @@ int speexhip_debug_g711_encode(int fmt, const float *y, const double *d, uint32_
   for (uint32_t i = 0; i < n; i++) {
     const int32_t q = d != nullptr ? speexhip::g711::s16_of_dither(y[i], d[i]) : speexhip::g711::s16_of(y[i]);
     codes[i] = static_cast<uint8_t>(fmt == SPEEXHIP_FMT_ULAW ? speexhip::g711::ulaw_encode(q) : speexhip::g711::alaw_encode(q));
+  }
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+namespace {
+// one sample's storage bits at byte i * bytes of a buffer of a format of halfbe.h (any address: byte by byte)
+uint32_t sample_at(const uint8_t *p, uint32_t bytes) {
+  uint32_t raw = 0;
+  for (uint32_t k = 0; k < bytes; k++) raw |= static_cast<uint32_t>(p[k]) << (8 * k);
+  return raw;
+}
+bool halfbe_format(int fmt) {
+  return fmt == SPEEXHIP_FMT_F16N || fmt == SPEEXHIP_FMT_BF16N || fmt == SPEEXHIP_FMT_S16BE || fmt == SPEEXHIP_FMT_S24BE ||
+         fmt == SPEEXHIP_FMT_S32BE;
+}
+}  // namespace
+
+int speexhip_debug_format_decode(int fmt, const void *storage, uint32_t n, float *x) {
+  namespace hb = speexhip::halfbe;
+  if (!halfbe_format(fmt) || ((storage == nullptr || x == nullptr) && n != 0)) return SPEEXHIP_ERR_INVALID_ARG;
+  const uint32_t bytes = speexhip::sample_bytes(fmt);
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t raw = sample_at(static_cast<const uint8_t *>(storage) + static_cast<size_t>(i) * bytes, bytes);
+    x[i] = fmt == SPEEXHIP_FMT_F16N    ? hb::f16n_decode(raw)
+           : fmt == SPEEXHIP_FMT_BF16N ? hb::bf16n_decode(raw)
+           : fmt == SPEEXHIP_FMT_S16BE ? hb::pcm_decode(16, hb::swap16(raw))
+           : fmt == SPEEXHIP_FMT_S24BE ? hb::pcm_decode(24, hb::swap24(raw))
+                                       : hb::pcm_decode(32, hb::swap32(raw));
+  }
+  return SPEEXHIP_ERR_SUCCESS;
+}
+int speexhip_debug_format_encode(int fmt, const float *y, const double *d, uint32_t n, void *storage) {
+  namespace hb = speexhip::halfbe;
+  if (!halfbe_format(fmt) || ((y == nullptr || storage == nullptr) && n != 0)) return SPEEXHIP_ERR_INVALID_ARG;
+  if (d != nullptr && !speexhip::dithered_fmt(fmt)) return SPEEXHIP_ERR_INVALID_ARG;  // (the half formats are not dithered)
+  const uint32_t bytes = speexhip::sample_bytes(fmt), bits = 8 * bytes;
+  for (uint32_t i = 0; i < n; i++) {
+    uint32_t raw;
+    if (fmt == SPEEXHIP_FMT_F16N) {
+      raw = hb::f16n_encode(y[i]);
+    } else if (fmt == SPEEXHIP_FMT_BF16N) {
+      raw = hb::bf16n_encode(y[i]);
+    } else {
+      const uint32_t q = static_cast<uint32_t>(d != nullptr ? hb::pcm_of_dither(bits, y[i], d[i]) : hb::pcm_of(bits, y[i]));
+      raw = bits == 16 ? hb::swap16(q) : bits == 24 ? hb::swap24(q) : hb::swap32(q);
+    }
+    uint8_t *p = static_cast<uint8_t *>(storage) + static_cast<size_t>(i) * bytes;
+    for (uint32_t k = 0; k < bytes; k++) p[k] = static_cast<uint8_t>(raw >> (8 * k));
   }
   return SPEEXHIP_ERR_SUCCESS;
 }

@@ -20,19 +20,25 @@ constexpr uint32_t sample_bytes(int fmt) {
     case SPEEXHIP_FMT_U8:
     case SPEEXHIP_FMT_ULAW:
     case SPEEXHIP_FMT_ALAW: return 1;
-    case SPEEXHIP_FMT_S16: return 2;
-    case SPEEXHIP_FMT_S24: return 3;
+    case SPEEXHIP_FMT_S16:
+    case SPEEXHIP_FMT_S16BE:
+    case SPEEXHIP_FMT_F16N:
+    case SPEEXHIP_FMT_BF16N: return 2;
+    case SPEEXHIP_FMT_S24:
+    case SPEEXHIP_FMT_S24BE: return 3;
     case SPEEXHIP_FMT_S32:
+    case SPEEXHIP_FMT_S32BE:
     case SPEEXHIP_FMT_F32:
     case SPEEXHIP_FMT_F32N: return 4;
     default: return 0;
   }
 }
 // the formats a state with dither on dithers on their way out: the integer ones, and the companded ones (g711.h), which
-// quantise to int16 on theirs; the float formats are written as they are
+// quantise to int16 on theirs, and the big-endian ones; the float formats, the half ones among them, are written as they are
 constexpr bool dithered_fmt(int fmt) {
   return fmt == SPEEXHIP_FMT_U8 || fmt == SPEEXHIP_FMT_S16 || fmt == SPEEXHIP_FMT_S24 || fmt == SPEEXHIP_FMT_S32 ||
-         fmt == SPEEXHIP_FMT_ULAW || fmt == SPEEXHIP_FMT_ALAW;
+         fmt == SPEEXHIP_FMT_ULAW || fmt == SPEEXHIP_FMT_ALAW || fmt == SPEEXHIP_FMT_S16BE || fmt == SPEEXHIP_FMT_S24BE ||
+         fmt == SPEEXHIP_FMT_S32BE;
 }
 
 // Kernel attributes (the opt-in for more than 64 KiB of dynamic LDS) are per DEVICE: set them the

@@ -10,8 +10,10 @@
 // Vector path (whole tiles; storage and image 16-byte aligned; step 1 -- decided per workgroup from the stream's
 // arguments, so it is wave-uniform): every access is 16 bytes per lane.  A lane owns G consecutive samples per pass --
 // G = 16 for the 1-byte formats u8, mu-law and A-law (one 16-byte piece of storage, four of the image) and packed s24 (three pieces of storage, unpacked /
-// packed in registers with byte shifts across dword pairs, four of the image), 8 for s16, 4 for the 4-byte formats --
-// and a workgroup makes 16 / G passes, lane t on group pass * 256 + t.
+// packed in registers with byte shifts across dword pairs, four of the image), 8 for the 2-byte formats, 4 for the
+// 4-byte ones -- and a workgroup makes 16 / G passes, lane t on group pass * 256 + t.  Big-endian s16 and s32 are
+// reversed per dword (format_device.h, swap_words: two s16 samples per v_perm_b32) and then are their little-endian
+// twins; a packed big-endian s24 sample is reversed on its own.
 //
 // Element path (any byte address for the 1-byte formats and s24, any element-aligned one for the rest; partial tiles; strided samples of
 // a state whose channels stand apart): sample by sample, s24 byte by byte, consecutive lanes on consecutive samples.
@@ -47,7 +49,7 @@ constexpr uint32_t kLanes = 256;
 constexpr uint32_t kTile = 4096;  // samples per workgroup
 
 // samples a lane owns per pass of the vector path: whole 16-byte pieces on both sides
-constexpr uint32_t group_of(int f) { return sample_bytes(f) == 1 || f == SPEEXHIP_FMT_S24 ? 16u : f == SPEEXHIP_FMT_S16 ? 8u : 4u; }
+constexpr uint32_t group_of(int f) { return sample_bytes(f) == 1 || sample_bytes(f) == 3 ? 16u : sample_bytes(f) == 2 ? 8u : 4u; }
 
 // ---- 16 bytes per lane ---------------------------------------------------------------------------------------------
 // sample j (compile-time) of a lane's group, from / into the group's storage words
@@ -71,6 +73,7 @@ __device__ __forceinline__ void put_raw(uint32_t *w, uint32_t j, uint32_t raw) {
 template <int F, bool kOut, bool kDither>
 __device__ __forceinline__ void vector_tile(const ConvertStream &s, const DitherStream *d, int kind, uint64_t tile0) {
   constexpr uint32_t B = sample_bytes(F), G = group_of(F), words = G * B / 4;
+  constexpr int W = word_format(F);  // (S16BE / S32BE: the words are reversed as dwords, the samples then the twin's)
   const char *src = static_cast<const char *>(s.src);
   char *dst = static_cast<char *>(s.dst);
 #pragma unroll
@@ -86,8 +89,9 @@ __device__ __forceinline__ void vector_tile(const ConvertStream &s, const Dither
         const uint4 v = in[i];
         w[4 * i] = v.x, w[4 * i + 1] = v.y, w[4 * i + 2] = v.z, w[4 * i + 3] = v.w;
       }
+      swap_words<F, words>(w);
 #pragma unroll
-      for (uint32_t j = 0; j < G; j++) e[j] = to_internal<F>(raw_of<F>(w, j));
+      for (uint32_t j = 0; j < G; j++) e[j] = to_internal<W>(raw_of<W>(w, j));
       float4 *out = reinterpret_cast<float4 *>(dst + first * sizeof(float));
 #pragma unroll
       for (uint32_t i = 0; i < G / 4; i++) out[i] = make_float4(e[4 * i], e[4 * i + 1], e[4 * i + 2], e[4 * i + 3]);
@@ -102,7 +106,8 @@ __device__ __forceinline__ void vector_tile(const ConvertStream &s, const Dither
       for (uint32_t i = 0; i < words; i++) w[i] = 0;
 #pragma unroll
       for (uint32_t j = 0; j < G; j++)
-        put_raw<F>(w, j, encode<F, kDither>(e[j], [&] { return dither::noise_in(kind, run, j); }));
+        put_raw<W>(w, j, encode<W, kDither>(e[j], [&] { return dither::noise_in(kind, run, j); }));
+      swap_words<F, words>(w);
       uint4 *out = reinterpret_cast<uint4 *>(dst + first * B);
 #pragma unroll
       for (uint32_t i = 0; i < words / 4; i++) out[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);

@@ -15,7 +15,8 @@
 // arguments): every global access is 16 bytes per lane.  With runtime channel counts a lane cannot own whole 16-byte
 // pieces of both sides in registers, so the workgroup copies its tile's raw storage bytes into LDS piece by piece, lane t
 // then mixes frames t and t + 256 out of LDS into a second LDS area laid out as the image, and the workgroup copies that
-// out piece by piece.  512 frames are whole pieces on both sides for every shape and format.
+// out piece by piece.  512 frames are whole pieces on both sides for every shape and format.  Big-endian s16 and s32 are
+// reversed per dword on their way into LDS (format_device.h, swap_words) and are their little-endian twins from there.
 // LDS layout: both areas are the global bytes in order, with one spare dword after every 32 (dword d lives at
 // d + d / 32).  A lane's frame starts frame-stride dwords after its neighbour's -- 1, 2, 4 or 8 dwords for the common
 // shapes, which unpadded would put 32 lanes on 32, 16, 8 or 4 banks; with the spare dword a stride of 2^k walks all 32
@@ -91,19 +92,22 @@ __device__ __forceinline__ uint32_t lds_raw(const uint32_t *area, uint32_t s) {
 template <int F>
 __device__ __forceinline__ void tile_path(const MixPack &pack, const MixStream &s, uint64_t tile0, uint32_t ns, uint32_t nd,
                                           uint32_t src_fb, uint32_t dst_fb, uint32_t *lds) {
+  constexpr int W = word_format(F);
   const uint32_t src_dwords = kTileFrames * src_fb / 4, dst_dwords = kTileFrames * dst_fb / 4;
   uint32_t *a_src = lds, *a_dst = lds + area_dwords(src_dwords);
   const uint4 *g_src = reinterpret_cast<const uint4 *>(static_cast<const char *>(s.src) + tile0 * src_fb);
   uint4 *g_dst = reinterpret_cast<uint4 *>(static_cast<char *>(s.dst) + tile0 * dst_fb);
   for (uint32_t p = threadIdx.x; p < src_dwords / 4; p += kLanes) {
     const uint4 v = g_src[p];
+    uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    swap_words<F, 4>(w);  // (S16BE / S32BE: reversed as dwords on their way in, the samples then the twin's)
     uint32_t *at = a_src + pad_dword(4 * p);  // (a piece never straddles a spare dword)
-    at[0] = v.x, at[1] = v.y, at[2] = v.z, at[3] = v.w;
+    at[0] = w[0], at[1] = w[1], at[2] = w[2], at[3] = w[3];
   }
   __syncthreads();
   for (uint32_t f = threadIdx.x; f < kTileFrames; f += kLanes)
     mix_frame(
-        pack, ns, nd, [&](uint32_t i) { return to_internal<F>(lds_raw<F>(a_src, f * ns + i)); },
+        pack, ns, nd, [&](uint32_t i) { return to_internal<W>(lds_raw<W>(a_src, f * ns + i)); },
         [&](uint32_t o, float y) { a_dst[pad_dword(f * nd + o)] = __float_as_uint(y); });
   __syncthreads();
   for (uint32_t p = threadIdx.x; p < dst_dwords / 4; p += kLanes) {

@@ -12,12 +12,13 @@
 // Vector path (whole tiles; plane base, plane stride in bytes and the image 16-byte aligned; at most 8 planes; image
 // frames as wide as the pass's channels -- decided per workgroup from the stream's arguments, so it is wave-uniform):
 // a plane is contiguous along frames, so a work item is one 16-byte piece of one plane (three pieces of packed s24): G
-// consecutive frames of a channel, G = 16 for the 1-byte formats and s24, 8 for s16, 4 for the 4-byte formats.  The items
+// consecutive frames of a channel, G = 16 for the 1-byte formats and both s24, 8 for the 2-byte formats, 4 for the 4-byte ones.  The items
 // of a tile (planes x 1024 / G) go round the 256 lanes, consecutive lanes on consecutive pieces of a plane.  Between
 // the plane side and the image side the tile lives in LDS as floats, frame-major with the storage side's channel count
 // per frame -- without a matrix that IS the tile of the image, which then moves between LDS and global memory linearly,
 // 16 bytes per lane.  With a matrix lane t mixes frames t, t + 256, ... between LDS and the image directly, a frame's
 // samples in one run per lane (kernels_mix.hip's element path, measured there to be no slower than an LDS tile).
+// Big-endian s16 and s32 pieces are reversed per dword (format_device.h, swap_words) next to their load or store.
 // planes_in:  plane pieces -> to_internal -> LDS | LDS -> (matrix) -> image
 // planes_out: image -> (matrix) -> LDS          | LDS -> encode (+ dither) -> plane pieces
 // LDS layout as in kernels_mix.hip: dword d lives at d + d / 32, so the lane stride of the plane side's accesses (G x
@@ -51,7 +52,7 @@ constexpr uint32_t kLanes = 256;
 constexpr uint32_t kTile = kSidesTileFrames;
 
 // frames of a plane in a work item of the vector path: whole 16-byte pieces
-constexpr uint32_t group_of(int f) { return sample_bytes(f) == 1 || f == SPEEXHIP_FMT_S24 ? 16u : f == SPEEXHIP_FMT_S16 ? 8u : 4u; }
+constexpr uint32_t group_of(int f) { return sample_bytes(f) == 1 || sample_bytes(f) == 3 ? 16u : sample_bytes(f) == 2 ? 8u : 4u; }
 
 // where dword d of the LDS tile lives: one spare dword after every 32
 __host__ __device__ constexpr uint32_t pad_dword(uint32_t d) { return d + (d >> 5); }
@@ -96,6 +97,7 @@ __device__ __forceinline__ void mix_frame(const float *m, uint32_t ns, uint32_t 
 template <int F>
 __device__ __forceinline__ void vector_in(const PlanePack &pack, const PlaneStream &s, uint64_t tile0, uint32_t *lds) {
   constexpr uint32_t B = sample_bytes(F), G = group_of(F), words = G * B / 4, pieces = kTile / G;
+  constexpr int W = word_format(F);
   const uint32_t sc = pack.storage_channels, ic = pack.image_channels;
   const char *planes = static_cast<const char *>(s.src);
   for (uint32_t item = threadIdx.x; item < sc * pieces; item += kLanes) {
@@ -107,8 +109,9 @@ __device__ __forceinline__ void vector_in(const PlanePack &pack, const PlaneStre
       const uint4 v = in[i];
       w[4 * i] = v.x, w[4 * i + 1] = v.y, w[4 * i + 2] = v.z, w[4 * i + 3] = v.w;
     }
+    swap_words<F, words>(w);  // (S16BE / S32BE: reversed as dwords, the samples then the little-endian twin's)
 #pragma unroll
-    for (uint32_t j = 0; j < G; j++) lds[pad_dword((f0 + j) * sc + c)] = __float_as_uint(to_internal<F>(raw_of<F>(w, j)));
+    for (uint32_t j = 0; j < G; j++) lds[pad_dword((f0 + j) * sc + c)] = __float_as_uint(to_internal<W>(raw_of<W>(w, j)));
   }
   __syncthreads();
   float *image = static_cast<float *>(s.dst) + tile0 * ic;
@@ -131,6 +134,7 @@ template <int F, bool kDither>
 __device__ __forceinline__ void vector_out(const PlanePack &pack, const PlaneStream &s, const DitherStream *d, int kind,
                                            uint64_t tile0, uint32_t *lds) {
   constexpr uint32_t B = sample_bytes(F), G = group_of(F), words = G * B / 4, pieces = kTile / G;
+  constexpr int W = word_format(F);
   const uint32_t sc = pack.storage_channels, ic = pack.image_channels;
   const float *image = static_cast<const float *>(s.src) + tile0 * ic;
   if (pack.mixed == 0) {
@@ -156,8 +160,9 @@ __device__ __forceinline__ void vector_out(const PlanePack &pack, const PlaneStr
 #pragma unroll
     for (uint32_t j = 0; j < G; j++) {
       const float y = __uint_as_float(lds[pad_dword((f0 + j) * sc + c)]);
-      put_raw<F>(w, j, encode<F, kDither>(y, [&] { return dither::noise(kind, d->seed, (d->first + tile0 + f0 + j) * sc + c); }));
+      put_raw<W>(w, j, encode<W, kDither>(y, [&] { return dither::noise(kind, d->seed, (d->first + tile0 + f0 + j) * sc + c); }));
     }
+    swap_words<F, words>(w);
     uint4 *out = reinterpret_cast<uint4 *>(planes + (c * s.plane_stride + tile0 + f0) * B);
 #pragma unroll
     for (uint32_t i = 0; i < words / 4; i++) out[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);

@@ -14,9 +14,12 @@ import { Transform, TransformCallback } from 'stream';
 /**
  * sample formats of processChunkFormat: 's24le' is packed (3 bytes per sample), 'f32le' is float32 in int16 units (what
  * processChunkFloat takes), 'f32le-normalized' float32 with +-1.0 full scale (Web Audio), 'mulaw' / 'alaw' G.711 as RTP
- * carries it (PCMU / PCMA, one byte per sample; a companded result is the 's16le' result through the G.711 compressor)
+ * carries it (PCMU / PCMA, one byte per sample; a companded result is the 's16le' result through the G.711 compressor),
+ * 's16be' / 's24be' / 's32be' the same samples in network and file byte order (RTP L16 / L24, AIFF), 'f16le-normalized' /
+ * 'bf16le-normalized' IEEE binary16 / bfloat16 with +-1.0 full scale (round to nearest even)
  */
-export type SampleFormat = 'u8' | 's16le' | 's24le' | 's32le' | 'f32le' | 'f32le-normalized' | 'mulaw' | 'alaw';
+export type SampleFormat = 'u8' | 's16le' | 's24le' | 's32le' | 'f32le' | 'f32le-normalized' | 'mulaw' | 'alaw' |
+    's16be' | 's24be' | 's32be' | 'f16le-normalized' | 'bf16le-normalized';
 /** dither of the integer results of processChunkFormat / processChunkMix (setDither) */
 export type DitherKind = 'none' | 'rectangular' | 'triangular';
 
@@ -142,13 +145,14 @@ declare class SpeexResampler {
     /**
      * processChunkMix with a layout per side.  `input`: a Buffer of interleaved frames, or one typed array per input
      * channel (planar) holding the plane's bytes in inSide.format.  outSide.planar: the result is one typed array per
-     * channel of the format's element type (Uint8Array for the 1-byte formats and 's24le') instead of a Buffer.  The same
+     * channel of the format's element type (Uint8Array for the 1-byte formats, 's24le' and the big-endian formats,
+     * Uint16Array of the bits for the half-float ones, for which a Float16Array is accepted on input) instead of a Buffer.  The same
      * samples and stream state as processChunkMix on the frames interleaved; with a planar side every format pair runs
      * by processChunkFloat's capacity rule.  outSide.channels, when given, must be the result's channel count.
      */
     processChunkSides(input: Buffer | ArrayBufferView[], inSide: { format: SampleFormat, mix?: number[][] | null },
         outSide: { format: SampleFormat, planar?: boolean, channels?: number, mix?: number[][] | null }):
-        Buffer | Array<Uint8Array | Int16Array | Int32Array | Float32Array>;
+        Buffer | Array<Uint8Array | Int16Array | Int32Array | Float32Array | Uint16Array>;
 
     /** mid-stream control (speex_resampler_set_rate / set_quality / skip_zeros / reset_mem) */
     setRate(inRate: number, outRate: number): void;
@@ -161,8 +165,8 @@ declare class SpeexResampler {
      */
     setMode(mode: 'fast' | 'exact' | 'fast_f32' | 'fast_fixed'): void;
     /**
-     * Dither of the integer results of processChunkFormat / processChunkMix ('u8', 's16le', 's24le', 's32le', and 'mulaw' /
-     * 'alaw', where the noise joins the int16 value the compressor takes): 'none' (default, round half up),
+     * Dither of the integer results of processChunkFormat / processChunkMix ('u8', 's16le', 's24le', 's32le', 's16be', 's24be',
+     * 's32be', and 'mulaw' / 'alaw', where the noise joins the int16 value the compressor takes): 'none' (default, round half up),
      * 'rectangular' (+-0.5 LSB) or 'triangular' (TPDF, +-1 LSB).  Counter based: the noise of a sample depends on (seed,
      * its index in the stream) alone, so the bytes do not depend on the chunking.  position = index of the next output
      * frame.  While on, 's16le' -> 's16le' runs as processChunkFloat between the two conversions.

@@ -23,7 +23,17 @@ const SAMPLE_FORMATS = {
   // companded (G.711, one byte per sample): ids start at 16
   'mulaw': { id: 16, bytes: 1 },
   'alaw': { id: 17, bytes: 1 },
+  // half-float in +-1.0 (binary16, bfloat16) and big-endian PCM (RTP L16 / L24, AIFF)
+  'f16le-normalized': { id: 20, bytes: 2 },
+  'bf16le-normalized': { id: 21, bytes: 2 },
+  's16be': { id: 24, bytes: 2 },
+  's24be': { id: 25, bytes: 3 },
+  's32be': { id: 26, bytes: 4 },
 };
+// result planes of processChunkSides: typed arrays are host-endian, so the big-endian formats come as bytes
+// (Uint8Array, kind 0) and the half-float ones as their bits (Uint16Array, kind 4)
+const BIG_ENDIAN_IDS = [24, 25, 26];
+const HALF_FLOAT_IDS = [20, 21];
 // setDither: the names of the dither kinds (SPEEXHIP_DITHER_* = the index)
 const DITHER_KINDS = ['none', 'rectangular', 'triangular'];
 let speexModule;
@@ -244,7 +254,10 @@ class SpeexResampler {
    * 's32le' | 'f32le' (float32 in int16 units, as processChunkFloat) | 'f32le-normalized' (float32 in +-1.0, Web Audio) |
    * 'mulaw' | 'alaw' (G.711 as RTP carries it, PCMU / PCMA: one byte per sample, decoded and encoded on the GPU -- 8 kHz
    * mu-law to 16 kHz float for a speech model: new SpeexResampler(1, 8000, 16000).processChunkFormat(rtpPayload, 'mulaw',
-   * 'f32le-normalized'); a companded result is the 's16le' result through the G.711 compressor).
+   * 'f32le-normalized'); a companded result is the 's16le' result through the G.711 compressor) |
+   * 's16be' | 's24be' | 's32be' (network and file byte order: RTP L16 / L24 payloads, AIFF -- no swap16() either side of
+   * the call: r.processChunkFormat(rtpL16Payload, 's16be', 'f32le-normalized')) | 'f16le-normalized' |
+   * 'bf16le-normalized' (IEEE binary16 / bfloat16 in +-1.0, what a model in half precision reads; round to nearest even).
    * `chunk` is a Buffer of interleaved frames in inFormat; the result is a Buffer in outFormat.  It is processChunkFloat
    * on the converted samples followed by the output conversion (round half up, saturating), both done on the GPU:
    * a decoder's s16le goes in and Web Audio's float32 comes out with no loop over the samples in JavaScript.  Same
@@ -320,7 +333,9 @@ class SpeexResampler {
    * plane's bytes in inSide.format (Web Audio's getChannelData planes are Float32Array in 'f32le-normalized'; a packed
    * 's24le' plane is a Uint8Array of 3 bytes per sample).  inSide: { format, mix? }; outSide: { format, planar?, channels?,
    * mix? } -- planar: true gives an array of typed arrays of the format's element type (Uint8Array for the 1-byte formats
-   * and 's24le', Int16Array, Int32Array, Float32Array), otherwise a Buffer.  It is processChunkMix on the same samples
+   * and 's24le', Int16Array, Int32Array, Float32Array; typed arrays are host-endian, so planes of the big-endian formats are
+   * Uint8Array, and half-float planes are Uint16Array of the bits -- a Float16Array is accepted on input where the runtime
+   * defines one), otherwise a Buffer.  It is processChunkMix on the same samples
    * arranged as interleaved frames: the same values, the same stream state; with a planar side every format pair runs by
    * processChunkFloat's capacity rule.  A decoder's interleaved s16le to a model's float planes:
    * r.processChunkSides(chunk, { format: 's16le' }, { format: 'f32le-normalized', planar: true }); Web Audio planes in and
@@ -374,8 +389,13 @@ class SpeexResampler {
     }
     // the capacity rule of processChunkFloat on these frames of the resampler's channel count
     const [, cap] = this._prepare({ length: frames * this.channels * Float32Array.BYTES_PER_ELEMENT }, Float32Array.BYTES_PER_ELEMENT);
-    // kind of a result plane: Uint8Array, Int16Array, Int32Array, Float32Array
-    const kind = fout.bytes === 2 ? 1 : fout.bytes === 4 ? (fout.id === 3 ? 2 : 3) : 0;
+    // kind of a result plane: Uint8Array, Int16Array, Int32Array, Float32Array, Uint16Array
+    const kind = BIG_ENDIAN_IDS.includes(fout.id) ? 0 : HALF_FLOAT_IDS.includes(fout.id) ? 4
+      : fout.bytes === 2 ? 1 : fout.bytes === 4 ? (fout.id === 3 ? 2 : 3) : 0;
+    // (a Float16Array plane, where the runtime defines one, travels as its bits)
+    if (planarIn && typeof Float16Array !== 'undefined') {
+      input = input.map((p) => (p instanceof Float16Array ? new Uint16Array(p.buffer, p.byteOffset, p.length) : p));
+    }
     return speexModule.processSides(this._resamplerPtr, input, fin.id, fout.id, frames, cap, inChannels, mi, outChannels, mo,
       planarOut, kind);
   }
@@ -411,8 +431,8 @@ class SpeexResampler {
   }
 
   /**
-   * Dither of the integer results ('u8', 's16le', 's24le', 's32le', and 'mulaw' / 'alaw', where the noise joins the int16
-   * value the compressor takes) of processChunkFormat and processChunkMix: 'none' (the
+   * Dither of the integer results ('u8', 's16le', 's24le', 's32le', 's16be', 's24be', 's32be', and 'mulaw' / 'alaw', where
+   * the noise joins the int16 value the compressor takes; the half-float results are float results: never dithered) of processChunkFormat and processChunkMix: 'none' (the
    * default: round half up), 'rectangular' (uniform in +-0.5 LSB) or 'triangular' (TPDF, +-1 LSB: the error of a
    * requantised signal becomes noise instead of harmonics).  The noise of a sample is a pure function of (seed, its index
    * in the stream), so the bytes do not depend on how the stream is cut into chunks; `position` is the index of the next

@@ -534,9 +534,14 @@ static napi_value ProcessSides(napi_env env, napi_callback_info info) {
     napi_throw_range_error(env, NULL, "unknown sample format or channel count");
     return NULL;
   }
-  /* (index.js names a result plane's kind: 0 Uint8Array, 1 Int16Array, 2 Int32Array, 3 Float32Array) */
-  static const napi_typedarray_type kKinds[4] = {napi_uint8_array, napi_int16_array, napi_int32_array, napi_float32_array};
-  const napi_typedarray_type out_type = kKinds[out_kind & 3];
+  /* (index.js names a result plane's kind: 0 Uint8Array, 1 Int16Array, 2 Int32Array, 3 Float32Array, 4 Uint16Array) */
+  static const napi_typedarray_type kKinds[5] = {napi_uint8_array, napi_int16_array, napi_int32_array, napi_float32_array,
+                                                 napi_uint16_array};
+  if (out_kind < 0 || out_kind > 4) {
+    napi_throw_range_error(env, NULL, "unknown kind of result plane");
+    return NULL;
+  }
+  const napi_typedarray_type out_type = kKinds[out_kind];
   const size_t out_es = typed_element_bytes(out_type);
   if (out_planar && (out_es == 0 || bout % out_es != 0)) {
     napi_throw_range_error(env, NULL, "the result's typed array kind does not hold its format");

@@ -26,24 +26,35 @@ FMT_BYTES = (1, 2, 3, 4, 4, 4)
 FMT_DTYPE = (np.uint8, np.int16, np.uint8, np.int32, np.float32, np.float32)  # numpy storage type of each format
 # companded formats (G.711 mu-law / A-law, one byte per sample) start at 16; 6..15 stay invalid
 FMT_ULAW, FMT_ALAW = 16, 17
+# half-float formats in +-1.0 (binary16; bfloat16, whose numpy storage is its bits: numpy has no bfloat16) and big-endian
+# PCM (S24BE packed: 3 bytes per sample, a uint8 array here); 18, 19, 22, 23 stay invalid
+FMT_F16N, FMT_BF16N = 20, 21
+FMT_S16BE, FMT_S24BE, FMT_S32BE = 24, 25, 26
+_MORE_FORMATS = {FMT_ULAW: (1, np.uint8), FMT_ALAW: (1, np.uint8), FMT_F16N: (2, np.float16), FMT_BF16N: (2, np.uint16),
+                 FMT_S16BE: (2, np.dtype(">i2")), FMT_S24BE: (3, np.uint8), FMT_S32BE: (4, np.dtype(">i4"))}
 
 
 def fmt_bytes(fmt):
-    """bytes of one sample of a format (FMT_*), the companded ones included"""
-    if fmt in (FMT_ULAW, FMT_ALAW):
-        return 1
+    """bytes of one sample of a format (FMT_*), the companded, half-float and big-endian ones included"""
+    if fmt in _MORE_FORMATS:
+        return _MORE_FORMATS[fmt][0]
     if not 0 <= fmt < len(FMT_BYTES):
         raise ValueError("unknown sample format %r" % (fmt,))
     return FMT_BYTES[fmt]
 
 
 def fmt_dtype(fmt):
-    """numpy storage type of a format (FMT_*), the companded ones included"""
-    if fmt in (FMT_ULAW, FMT_ALAW):
-        return np.uint8
+    """numpy storage type of a format (FMT_*), the companded, half-float and big-endian ones included"""
+    if fmt in _MORE_FORMATS:
+        return _MORE_FORMATS[fmt][1]
     if not 0 <= fmt < len(FMT_DTYPE):
         raise ValueError("unknown sample format %r" % (fmt,))
     return FMT_DTYPE[fmt]
+
+
+def _per_sample(fmt):
+    """elements of a format's numpy storage array per sample (the packed 24-bit formats: 3 bytes)"""
+    return fmt_bytes(fmt) // np.dtype(fmt_dtype(fmt)).itemsize
 
 
 # dither of the integer output formats of the formatted and mixed calls (SPEEXHIP_DITHER_*), a property of the state
@@ -100,6 +111,8 @@ EXPORTS = [
     "speexhip_batch_get_dither", "speexhip_debug_dither",
     # companded formats: G.711 mu-law and A-law in the formatted and mixed calls
     "speexhip_debug_g711_decode", "speexhip_debug_g711_encode",
+    # half-float (binary16, bfloat16 in +-1.0) and big-endian (s16, packed s24, s32) formats
+    "speexhip_debug_format_decode", "speexhip_debug_format_encode",
     # layouts: planar or interleaved per side of a formatted or mixed call
     "speexhip_resampler_process_sides", "speexhip_resampler_process_sides_device", "speexhip_batch_process_sides_device",
 ]
@@ -366,6 +379,11 @@ def lib():
             L.speexhip_debug_g711_decode.argtypes = [i32, p, u32, p]
             L.speexhip_debug_g711_encode.restype = i32
             L.speexhip_debug_g711_encode.argtypes = [i32, p, p, u32, p]
+        if hasattr(L, "speexhip_debug_format_decode") or "SPEEXHIP_LIB_PATH" not in os.environ:
+            L.speexhip_debug_format_decode.restype = i32
+            L.speexhip_debug_format_decode.argtypes = [i32, p, u32, p]
+            L.speexhip_debug_format_encode.restype = i32
+            L.speexhip_debug_format_encode.argtypes = [i32, p, p, u32, p]
         if hasattr(L, "speexhip_resampler_process_sides") or "SPEEXHIP_LIB_PATH" not in os.environ:
             ps = C.POINTER(Side)
             L.speexhip_resampler_process_sides.restype = i32
@@ -460,6 +478,34 @@ def debug_g711_encode(fmt, y, d=None):
     if rc:
         raise ValueError(strerror(rc))
     return codes[: y.size]
+
+
+def debug_format_decode(fmt, storage):
+    """host-only: the library's decoding of storage of a half-float or big-endian format (FMT_F16N, FMT_BF16N, FMT_S16BE,
+    FMT_S24BE, FMT_S32BE; an array of fmt_dtype(fmt), its bytes taken as they are) into the internal float (int16 units)"""
+    storage = np.ascontiguousarray(storage, dtype=fmt_dtype(fmt)).reshape(-1)
+    n = storage.nbytes // fmt_bytes(fmt)
+    x = np.zeros(max(n, 1), np.float32)
+    rc = lib().speexhip_debug_format_decode(fmt, C.c_void_p(storage.ctypes.data), n, C.c_void_p(x.ctypes.data))
+    if rc:
+        raise ValueError(strerror(rc))
+    return x[:n]
+
+
+def debug_format_encode(fmt, y, d=None):
+    """host-only: the library's storage (flat, fmt_dtype(fmt)) of FIR values y (float32, int16 units) in a half-float or
+    big-endian format; d: None or, for the big-endian formats, the dither of each sample (float64, in LSB of the format)
+    added before the rounding"""
+    y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
+    if d is not None:
+        d = np.ascontiguousarray(d, dtype=np.float64).reshape(-1)
+        assert d.size == y.size
+    raw = np.zeros(max(y.size, 1) * fmt_bytes(fmt), np.uint8)
+    rc = lib().speexhip_debug_format_encode(fmt, C.c_void_p(y.ctypes.data), None if d is None else C.c_void_p(d.ctypes.data),
+                                            y.size, C.c_void_p(raw.ctypes.data))
+    if rc:
+        raise ValueError(strerror(rc))
+    return raw[: y.size * fmt_bytes(fmt)].view(fmt_dtype(fmt))
 
 
 def debug_plan64(ratio_num, ratio_den, quality, channels):
@@ -902,7 +948,7 @@ class Resampler:
         rc, used, made, out = self.fmt_call(x, in_fmt, out_fmt, capacity, null_frames)
         if rc:
             raise RuntimeError(strerror(rc))
-        per = self.channels * (3 if out_fmt == FMT_S24 else 1)
+        per = self.channels * _per_sample(out_fmt)
         return out[: made * per].copy(), used
 
     def process_fmt_device(self, in_fmt, d_in_ptr, in_frames, out_fmt, d_out_ptr, out_capacity, stream_ptr=0):
@@ -946,7 +992,7 @@ class Resampler:
         if rc:
             raise RuntimeError(strerror(rc))
         n_out = self.channels if out_mix is None else len(out_mix)
-        return out[: made * n_out * (3 if out_fmt == FMT_S24 else 1)].copy(), used
+        return out[: made * n_out * _per_sample(out_fmt)].copy(), used
 
     def process_mix_device(self, in_fmt, d_in_ptr, in_frames, out_fmt, d_out_ptr, out_capacity, in_mix=None, out_mix=None,
                            stream_ptr=0):
@@ -987,7 +1033,8 @@ class Resampler:
                 ptrs = (C.c_void_p * n_in)(*[q.ctypes.data for q in planes])
                 a = make_side(in_fmt, n_in, li, mi, planes=ptrs)
             else:
-                block = np.stack(planes) if n else np.zeros((n_in, 1), fmt_dtype(in_fmt))
+                # (stacked as bytes: numpy would turn a big-endian storage type into the host's, values kept, bytes swapped)
+                block = np.stack([q.view(np.uint8) for q in planes]) if n else np.zeros((n_in, 1), np.uint8)
                 keep.append(block)
                 a = make_side(in_fmt, n_in, li, mi, data=block.ctypes.data, plane_stride=n)
         else:
@@ -1026,7 +1073,7 @@ class Resampler:
                                               null_frames)
         if rc:
             raise RuntimeError(strerror(rc))
-        per = 3 if out_fmt == FMT_S24 else 1
+        per = _per_sample(out_fmt)
         if _layout(out_layout) == LAYOUT_PLANAR:
             return out[:, : made * per].copy(), used
         n_out = self.channels if out_mix is None else len(out_mix)
@@ -1243,25 +1290,33 @@ class Batch:
         """process_tensor beyond int16 -> int16 and float32 -> float32: interleaved frames (..., T, C) through the
         formatted call (the mixed call when a matrix is given: x then holds in_channels per frame and the result
         out_channels).  uint8 = U8, int16 = S16, int32 = S32, float32 = F32 (normalized: +-1.0 full scale); in_format /
-        out_format (FMT_*) name a side's format instead -- a uint8 tensor as FMT_ULAW or FMT_ALAW."""
+        out_format (FMT_*) name a side's format instead -- a uint8 tensor as FMT_ULAW or FMT_ALAW, an int16 / int32
+        tensor holding the raw bytes as FMT_S16BE / FMT_S32BE.  float16 = F16N and bfloat16 = BF16N, both in +-1.0
+        whatever `normalized` says: the flag speaks of float32 only."""
         import torch
         fmt_of = {torch.uint8: FMT_U8, torch.int16: FMT_S16, torch.int32: FMT_S32,
-                  torch.float32: FMT_F32N if normalized else FMT_F32}
-        torch_of = {np.uint8: torch.uint8, np.int16: torch.int16, np.int32: torch.int32, np.float32: torch.float32}
-        if in_format is not None and x.dtype != torch_of[fmt_dtype(in_format)]:
-            raise ValueError("in_format %d wants a %s tensor" % (in_format, torch_of[fmt_dtype(in_format)]))
+                  torch.float32: FMT_F32N if normalized else FMT_F32, torch.float16: FMT_F16N, torch.bfloat16: FMT_BF16N}
+
+        def torch_of(fmt):  # the tensor type that holds a format's samples, one element each
+            if fmt == FMT_BF16N:
+                return torch.bfloat16
+            return {1: {"u": torch.uint8}, 2: {"i": torch.int16, "f": torch.float16},
+                    4: {"i": torch.int32, "f": torch.float32}}[fmt_bytes(fmt)][np.dtype(fmt_dtype(fmt)).kind]
+
+        if FMT_S24 in (in_format, out_format) or FMT_S24BE in (in_format, out_format):
+            raise ValueError("process_tensor does not take packed S24: a sample is not a whole element")
+        if in_format is not None and x.dtype != torch_of(in_format):
+            raise ValueError("in_format %d wants a %s tensor" % (in_format, torch_of(in_format)))
         if out_format is not None:
-            if out_dtype is not None and out_dtype != torch_of[fmt_dtype(out_format)]:
-                raise ValueError("out_format %d gives a %s tensor" % (out_format, torch_of[fmt_dtype(out_format)]))
-            out_dtype = torch_of[fmt_dtype(out_format)]
+            if out_dtype is not None and out_dtype != torch_of(out_format):
+                raise ValueError("out_format %d gives a %s tensor" % (out_format, torch_of(out_format)))
+            out_dtype = torch_of(out_format)
         elif out_dtype is None:
             out_dtype = x.dtype
         if x.dtype not in fmt_of or out_dtype not in fmt_of:
-            raise ValueError("process_tensor converts between uint8, int16, int32 and float32 tensors")
+            raise ValueError("process_tensor converts between uint8, int16, int32, float16, bfloat16 and float32 tensors")
         in_fmt = fmt_of[x.dtype] if in_format is None else in_format
         out_fmt = fmt_of[out_dtype] if out_format is None else out_format
-        if FMT_S24 in (in_fmt, out_fmt):
-            raise ValueError("process_tensor does not take packed S24: a sample is not a whole element")
         xb = x if x.dim() == 3 else x.unsqueeze(0)
         sides = in_layout is not None or out_layout is not None
         planar_in = _layout(in_layout) == LAYOUT_PLANAR
@@ -1317,7 +1372,8 @@ class Batch:
         result may hold per stream (default: what T frames can produce).  Returns (tensor of the same rank with
         T_out = max(produced), list of frames produced per stream).
 
-        Other sample types -- a uint8 (offset binary) or int32 tensor, out_dtype= another type than x's, or
+        Other sample types -- a uint8 (offset binary), int32, float16 or bfloat16 tensor (the half types in +-1.0,
+        whatever `normalized` says), out_dtype= another type than x's, or
         normalized=True (float32 in +-1.0 instead of int16 units) -- take the formatted call: without a named layout
         (below) x is then interleaved frames (B, T, C) or (T, C), dense, and so is the result; with in_layout='planar' /
         out_layout='planar' the same conversions work on (B, C, T) directly.
@@ -1327,7 +1383,8 @@ class Batch:
 
         in_format / out_format (FMT_*): name a side's sample format instead of inferring it from the dtype, also on
         interleaved frames -- a uint8 tensor with in_format=FMT_ULAW is G.711 mu-law, out_format=FMT_ALAW gives a uint8
-        tensor of A-law bytes.  A side that is not named goes by its dtype as above (the result's being x's unless
+        tensor of A-law bytes; an int16 tensor with in_format=FMT_S16BE holds big-endian samples as they came off the
+        wire (RTP L16), likewise int32 with FMT_S32BE.  A side that is not named goes by its dtype as above (the result's being x's unless
         out_dtype says otherwise).
 
         in_layout / out_layout ('planar' | 'interleaved'): the sides call, which takes either layout on either side with
@@ -1336,7 +1393,7 @@ class Batch:
         an interleaved one, and the result is (B, C', T') or (B, T', C') by out_layout.  (B, C, T) float32 in +-1.0 both
         ways: process_tensor(x, normalized=True, in_layout='planar', out_layout='planar'); a decoder's interleaved
         int16 to a model's planes: process_tensor(x, out_dtype=torch.float32, normalized=True, in_layout='interleaved',
-        out_layout='planar').  With both None the function does what the paragraphs above say."""
+        out_layout='planar'), or out_dtype=torch.bfloat16 for a model that runs in half precision.  With both None the function does what the paragraphs above say."""
         import torch
         if in_layout is not None or out_layout is not None:
             if not x.is_cuda or x.dim() not in (2, 3):
@@ -1353,7 +1410,7 @@ class Batch:
                 raise ValueError("process_tensor wants a CUDA tensor (B, T, C) or (T, C) for a mixed call")
             return self._process_tensor_fmt(x, out_capacity, in_frames, out_dtype, normalized, in_mix, out_mix)
         if x.is_cuda and x.dim() in (2, 3) and (
-                x.dtype in (torch.uint8, torch.int32) or normalized or (out_dtype is not None and out_dtype != x.dtype)):
+                x.dtype in (torch.uint8, torch.int32, torch.float16, torch.bfloat16) or normalized or (out_dtype is not None and out_dtype != x.dtype)):
             return self._process_tensor_fmt(x, out_capacity, in_frames, out_dtype, normalized)
         if not x.is_cuda or x.dtype not in (torch.int16, torch.float32) or x.dim() not in (2, 3):
             raise ValueError("process_tensor wants a CUDA tensor (B, C, T) or (C, T) of int16 or float32")
