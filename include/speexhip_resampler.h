@@ -755,6 +755,53 @@ SPEEXHIP_API int speexhip_resampler_process_sides_device(SpeexHipResamplerState 
 SPEEXHIP_API int speexhip_batch_process_sides_device(SpeexHipBatch *b, const SpeexHipSide *in, uint32_t *in_len,
                                                      const SpeexHipSide *out, uint32_t *out_len, void *hip_stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Many states, formatted: speexhip_resampler_process_many_int / _float with a format per state -- a
+ * gateway's few hundred RTP legs, some PCMU, some PCMA, some L16, in ONE host call per 20 ms tick
+ * instead of one per leg.  in[i] / out[i] are entry i's sides (host buffers; struct_size is checked
+ * per entry, stream_stride is not read), in_len[i] / out_len[i] its frames available / capacity on
+ * entry and consumed / written on return.
+ *
+ * Entry i is exactly speexhip_resampler_process_sides(st[i], &in[i], &in_len[i], &out[i],
+ * &out_len[i]): the same bytes, counters, history, position, dither position and return code, the
+ * zero fallback included -- in the default mode (SPEEXHIP_MODE_FAST_FIXED) and in SPEEXHIP_MODE_EXACT,
+ * whose bytes do not depend on what shares a launch.  In the opt-in modes SPEEXHIP_MODE_FAST and
+ * _FAST_F32 the last bit of a sample may depend on the launch's shape, here as in every call: counters,
+ * positions and codes are still the separate calls', the samples within that mode's bound.  codes[i] (may be NULL) receives entry i's code and the
+ * function returns the first one that is not SUCCESS.  An entry's argument error -- a NULL state, an
+ * unknown format or layout, out->data == NULL without planes, a struct_size smaller than this
+ * version's, a channel count that is not the state's without a matrix -- is INVALID_ARG for that
+ * entry, leaves its state and its lengths untouched, and the other entries run.
+ *
+ * Which entries are fused: those whose state is one uniform stream out of the zero fallback and not
+ * named earlier in the call, whose sides are both interleaved (or have one channel) in one buffer each,
+ * and neither of which has a matrix.  Per device they cost one transfer in, per <= 32 states that share
+ * (rates, quality, channels, mode) at most one input pass, one FIR launch and one output pass --
+ * whatever formats the states name, each dithered at its own state's kind, seed and position -- and
+ * one transfer out.  S16 -> S16 with dither off is the int16 call (no pass), F32 -> F32 and F32N -> F32N
+ * the float call on the same bytes (no pass); an F32 side needs no pass.  Every other entry -- a side
+ * with a matrix, a planar side of several channels, a state whose channels the per-channel calls moved
+ * apart, the zero fallback, a state named twice -- is correct through this call but NOT fused: it takes
+ * its own process_sides call, in the caller's order, after the fused ones.
+ *
+ * ..._fmt is the thin form: every side interleaved with the state's channel count and no matrix.
+ * Synchronous; a state must not be used by another thread meanwhile.
+ *
+ * speexhip_debug_many_counters: process-wide counts since start, over all the many-states calls (the
+ * two above and _int / _float) -- out[0] FIR launches, out[1] input passes, out[2] output passes,
+ * out[3] entries that took their own call.  Host only.
+ *
+ * ABI note: 0.7 + many formats adds these three entry points; SpeexHipInfo, SpeexHipSide, the enums,
+ * the error codes and the version string are unchanged. */
+SPEEXHIP_API int speexhip_resampler_process_many_sides(uint32_t n, SpeexHipResamplerState *const *st,
+                                                       const SpeexHipSide *in, uint32_t *in_len,
+                                                       const SpeexHipSide *out, uint32_t *out_len, int *codes);
+SPEEXHIP_API int speexhip_resampler_process_many_fmt(uint32_t n, SpeexHipResamplerState *const *st,
+                                                     const int *in_fmt, const void *const *in, uint32_t *in_len,
+                                                     const int *out_fmt, void *const *out, uint32_t *out_len,
+                                                     int *codes);
+SPEEXHIP_API void speexhip_debug_many_counters(uint64_t out[4]);
+
 /* Mid-stream control for every stream of a batch (same semantics as the single-stream calls). */
 SPEEXHIP_API int speexhip_batch_set_rate_frac(SpeexHipBatch *b, uint32_t ratio_num, uint32_t ratio_den,
                                               uint32_t in_rate, uint32_t out_rate);

@@ -690,6 +690,46 @@ int speexhip_batch_process_sides_device(SpeexHipBatch *bt, const SpeexHipSide *i
   return guarded([&] { return bt->batch->process_sides_device(a, in_len, b, out_len, static_cast<hipStream_t>(hip_stream)); });
 }
 
+// ---- many states, formatted ---------------------------------------------------------------------------------------------
+int speexhip_resampler_process_many_sides(uint32_t n, SpeexHipResamplerState *const *st, const SpeexHipSide *in,
+                                          uint32_t *in_len, const SpeexHipSide *out, uint32_t *out_len, int *codes) {
+  if (n == 0) return SPEEXHIP_ERR_SUCCESS;
+  if (st == nullptr || in == nullptr || in_len == nullptr || out == nullptr || out_len == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] {
+    std::vector<Batch *> b(n);
+    std::vector<speexhip::CallSide> a(n), o(n);
+    std::vector<uint8_t> bad(n, 0);
+    for (uint32_t i = 0; i < n; i++) {
+      b[i] = st[i] != nullptr ? st[i]->batch : nullptr;
+      // (each entry's struct_size stands at the head of ITS side: an array of this version's structs)
+      if (!side_of(&in[i], true, &a[i]) || !side_of(&out[i], true, &o[i])) bad[i] = 1;
+    }
+    return Batch::process_host_many_sides(n, b.data(), a.data(), in_len, o.data(), out_len, bad.data(), codes);
+  });
+}
+int speexhip_resampler_process_many_fmt(uint32_t n, SpeexHipResamplerState *const *st, const int *in_fmt,
+                                        const void *const *in, uint32_t *in_len, const int *out_fmt, void *const *out,
+                                        uint32_t *out_len, int *codes) {
+  if (n == 0) return SPEEXHIP_ERR_SUCCESS;
+  if (st == nullptr || in_fmt == nullptr || in == nullptr || in_len == nullptr || out_fmt == nullptr || out == nullptr ||
+      out_len == nullptr)
+    return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] {
+    std::vector<Batch *> b(n);
+    std::vector<speexhip::CallSide> a(n), o(n);
+    for (uint32_t i = 0; i < n; i++) {
+      b[i] = st[i] != nullptr ? st[i]->batch : nullptr;
+      const uint32_t ch = b[i] != nullptr ? b[i]->channels() : 0;
+      a[i] = side(in_fmt[i], ch, nullptr, in[i]);
+      o[i] = side(out_fmt[i], ch, nullptr, out[i]);
+    }
+    return Batch::process_host_many_sides(n, b.data(), a.data(), in_len, o.data(), out_len, nullptr, codes);
+  });
+}
+void speexhip_debug_many_counters(uint64_t out[4]) {
+  if (out != nullptr) speexhip::many_counters(out);
+}
+
 int speexhip_resampler_set_dither(SpeexHipResamplerState *st, int kind, uint64_t seed, uint64_t position) {
   return guarded([&] { return st ? st->batch->set_dither(kind, seed, position) : SPEEXHIP_ERR_INVALID_ARG; });
 }

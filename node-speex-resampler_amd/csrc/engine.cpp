@@ -1600,6 +1600,7 @@ int warm_device(int device) {
   warm_unit_slide64_f32(s);
   warm_unit_planar(s);
   warm_unit_convert(s);
+  warm_unit_convert_many(s);
   warm_unit_mix(s);
   warm_unit_sides(s);
   HIP_TRY(hipStreamSynchronize(s));
@@ -1637,8 +1638,16 @@ struct ManyStage {
   std::vector<hipEvent_t> events;
   char *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
   size_t d_in_cap = 0, d_out_cap = 0, h_in_cap = 0, h_out_cap = 0;
+  // the float images of the entries whose storage is not the image (ManyEntry::Image): device scratch either side of the
+  // FIR launch, one range per entry
+  char *d_img_in = nullptr, *d_img_out = nullptr;
+  size_t d_img_in_cap = 0, d_img_out_cap = 0;
   uint32_t seq = 0;
 };
+// speexhip_debug_many_counters: FIR launches, input passes, output passes, entries that took their own call
+std::atomic<uint64_t> g_many_counters[4];
+inline void count_many(int which, uint64_t by = 1) { g_many_counters[which].fetch_add(by, std::memory_order_relaxed); }
+inline size_t align128(size_t v) { return (v + 127) & ~static_cast<size_t>(127); }
 // (device, lane): a large call on one device runs as two halves side by side, each on a stage of its own (below)
 ManyStage &many_stage(int device, int lane) {
   static std::mutex mu;
@@ -1691,18 +1700,23 @@ int prime_copy_stream(int device, ManyStage &ms) {
 }  // namespace
 
 // The fused states of ONE device: idx = their positions in the caller's arrays.
-int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx, Batch *const *st, const void *const *in,
-                          uint32_t *in_len, void *const *out, uint32_t *out_len, bool float_io, int *rcs) {
+int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx, const ManyEntry *entries, uint32_t *in_len,
+                          uint32_t *out_len, int *rcs) {
   ManyStage &ms = many_stage(device, lane);
   std::lock_guard<std::mutex> lock(ms.mu);
   DeviceScope device_scope(device);
   HIP_TRY(device_scope.error());
   if (ms.stream == nullptr) HIP_TRY(pool::stream_get(device, &ms.stream));
   DrainOnExit drain(&ms.stream);
-  const size_t es = float_io ? sizeof(float) : sizeof(int16_t);
   struct Item {
     uint32_t i;
     Batch *b;
+    const ManyEntry *e;
+    const void *in;                               // the caller's buffers (raw bytes of e->in_fmt / e->out_fmt)
+    void *out;
+    bool float_io;                                // the FIR launch's sample type: int16 direct, or float (direct or images)
+    bool pass_in, pass_out;                       // the entry's storage goes through a float image on that side
+    size_t img_in, img_out;                       // ... at this offset of the stage's images
     CallPlan plan;
     size_t in_bytes, out_bytes, in_off, out_off;
     const void *pin_in;                           // round 6: the caller's own buffers where they are pinned memory
@@ -1712,19 +1726,33 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
   };
   std::vector<Item> items(idx.size());
   size_t total_in = 0, total_out = 0;  // pageable bytes, as laid out in the stage
+  size_t images_in = 0, images_out = 0;
   for (size_t k = 0; k < idx.size(); k++) {
     Item &it = items[k];
     it.i = idx[k];
-    it.b = st[it.i];
+    it.e = &entries[it.i];
+    it.b = it.e->b;
+    it.in = it.e->in;
+    it.out = it.e->out;
+    it.float_io = it.e->kind != ManyEntry::Int16;
     EntryRules rules;
     rules.block_in = it.b->block_in();
-    rules.float_entry = float_io;
+    rules.float_entry = it.float_io;
     it.plan = plan_call(it.b->filter_.num, it.b->filter_.den, in_len[it.i], out_len[it.i], it.b->P(0, 0), rules);
-    it.in_bytes = in[it.i] != nullptr ? static_cast<size_t>(in_len[it.i]) * it.b->channels_ * es : 0;
-    it.out_bytes = static_cast<size_t>(it.plan.produced) * it.b->channels_ * es;
-    it.pin_in = pinned_view(in[it.i], it.in_bytes);
-    it.pin_out = pinned_view(out[it.i], it.out_bytes);
-    if (it.pin_in != nullptr && it.pin_out != nullptr && buffers_overlap(in[it.i], it.in_bytes, out[it.i], it.out_bytes)) it.pin_in = nullptr;
+    // the raw bytes of either side, in the side's own format: what every size decision below goes by
+    it.in_bytes = it.in != nullptr ? static_cast<size_t>(in_len[it.i]) * it.b->channels_ * sample_bytes(it.e->in_fmt) : 0;
+    it.out_bytes = static_cast<size_t>(it.plan.produced) * it.b->channels_ * sample_bytes(it.e->out_fmt);
+    // (formats.cpp, process_sides_device: F32 storage IS the image; a present but empty input is not silence, no frame of
+    //  it is read)
+    it.pass_in = it.e->kind == ManyEntry::Image && it.e->in_fmt != SPEEXHIP_FMT_F32 && it.in != nullptr && in_len[it.i] != 0;
+    it.pass_out = it.e->kind == ManyEntry::Image && it.e->out_fmt != SPEEXHIP_FMT_F32;
+    it.img_in = images_in;
+    it.img_out = images_out;
+    if (it.pass_in) images_in += align128(static_cast<size_t>(in_len[it.i]) * it.b->channels_ * sizeof(float));
+    if (it.pass_out) images_out += align128(static_cast<size_t>(it.plan.produced) * it.b->channels_ * sizeof(float));
+    it.pin_in = pinned_view(it.in, it.in_bytes);
+    it.pin_out = pinned_view(it.out, it.out_bytes);
+    if (it.pin_in != nullptr && it.pin_out != nullptr && buffers_overlap(it.in, it.in_bytes, it.out, it.out_bytes)) it.pin_in = nullptr;
     // (a pinned input whose result goes to a LARGE pageable buffer is copied like any other -- from pinned memory the copy
     //  is a plain DMA -- so that the call can take the pipelined path, inputs arriving while results leave: read in place,
     //  all the reads come first and all the pageable copies out after them, 32 x 2^20 stereo frames 5.4 ms against 4.0,
@@ -1743,7 +1771,7 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
   Wait wait;
   bool all_big = true;  // every working state Copy both ways: the pipelined path (below)
   for (Item &it : items) {
-    it.in_via = route_side(it.in_bytes, in[it.i] != nullptr, it.pin_in != nullptr, small);
+    it.in_via = route_side(it.in_bytes, it.in != nullptr, it.pin_in != nullptr, small);
     it.out_via = route_side(it.out_bytes, true, it.pin_out != nullptr, small);
     wait.add(it.in_via, it.in_bytes);
     wait.add(it.out_via, it.out_bytes);
@@ -1769,6 +1797,9 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
   if (rc == SPEEXHIP_ERR_SUCCESS) rc = grow_stage(device, &ms.h_out, &ms.h_out_cap, gathered_out + 128, true);
   if (rc == SPEEXHIP_ERR_SUCCESS && !small) rc = grow_stage(device, &ms.d_in, &ms.d_in_cap, total_in, false);
   if (rc == SPEEXHIP_ERR_SUCCESS && !small) rc = grow_stage(device, &ms.d_out, &ms.d_out_cap, total_out, false);
+  // (a line of slack behind the last image, as the single call's pitched images have behind every stream)
+  if (rc == SPEEXHIP_ERR_SUCCESS && images_in != 0) rc = grow_stage(device, &ms.d_img_in, &ms.d_img_in_cap, images_in + 256, false);
+  if (rc == SPEEXHIP_ERR_SUCCESS && images_out != 0) rc = grow_stage(device, &ms.d_img_out, &ms.d_img_out_cap, images_out + 256, false);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   char *src_base = small ? ms.h_in : ms.d_in, *dst_base = small ? ms.h_out : ms.d_out;
 
@@ -1776,15 +1807,16 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
   // piece and the results of the previous one have something to overlap with.
   static const int env_pipe = diag_int(SPEEXHIP_DIAG_ENV("SPEEXHIP_MANY_PIPELINE"), -1);  // A/B: 0 off
   const bool pipelined = all_big && env_pipe != 0 && total_in >= (static_cast<size_t>(32) << 20);
-  // launches: the states that share (tables, mode, window format) go together, at most 32 per launch
+  // launches: the states that share (tables, mode, window format, sample type of the launch) go together, at most 32 per
+  // launch
   std::vector<std::vector<Item *>> launches;
   {
-    std::map<std::tuple<const void *, int, bool>, std::vector<Item *>> groups;
+    std::map<std::tuple<const void *, int, bool, bool>, std::vector<Item *>> groups;
     for (Item &it : items) {
-      if (float_io) it.b->float_seen_ = true;
+      if (it.float_io) it.b->float_seen_ = true;
       if (in_len[it.i] != 0 && out_len[it.i] != 0) it.b->started_[0] = 1;  // resample.c:886
       if (!it.work) continue;  // nothing to run: the state stays where it is
-      groups[std::make_tuple(static_cast<const void *>(it.b->tables_.get()), it.b->mode_, it.b->float_seen_)].push_back(&it);
+      groups[std::make_tuple(static_cast<const void *>(it.b->tables_.get()), it.b->mode_, it.b->float_seen_, it.float_io)].push_back(&it);
     }
     for (auto &kv : groups) {
       std::vector<Item *> &g = kv.second;
@@ -1801,16 +1833,27 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
   }
   auto commit_item = [&](Item &it) {  // counters and position of one state
     for (uint32_t c = 0; c < it.b->channels_; c++) it.b->P(0, c) = it.plan.end;
-    if (!float_io && it.work) it.b->int16_call_done(&it.plan, 1);
+    if (!it.float_io && it.work) it.b->int16_call_done(&it.plan, 1);
     in_len[it.i] = it.plan.consumed;
     out_len[it.i] = it.plan.produced;
+    // (a formatted call of a state with dither on moves its position by the frames produced, whatever the format)
+    if (it.e->sides && it.b->dither_on()) it.b->dither_advance(&out_len[it.i]);
     rcs[it.i] = SPEEXHIP_ERR_SUCCESS;
   };
   // one launch of `launches[k]` on `stream`
   auto launch = [&](const std::vector<Item *> &g, hipStream_t stream) -> int {
     const uint32_t cnt = static_cast<uint32_t>(g.size());
+    const bool float_io = g[0]->float_io;  // (the group's: part of its key)
     DescPack pack;
     std::memset(&pack, 0, sizeof(pack));
+    // the passes either side of the launch (kernels_convert_many.hip): one each for all the formats the group's entries
+    // name, over the entries whose storage is not their image
+    ConvertPack to_image, from_image;
+    DitherPack dith;
+    uint64_t most_to = 0, most_from = 0;
+    std::memset(&to_image, 0, sizeof(to_image));
+    std::memset(&from_image, 0, sizeof(from_image));
+    std::memset(&dith, 0, sizeof(dith));
     uint32_t max_out = 0;
     for (uint32_t j = 0; j < cnt; j++) {
       Item &it = *g[j];
@@ -1819,17 +1862,46 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
       if (crc != SPEEXHIP_ERR_SUCCESS) return crc;
       StreamDesc &d = pack.d[j];
       const FilterSpec &f = b->filter_;
-      d.in = in[it.i] == nullptr ? nullptr : it.pin_in != nullptr ? it.pin_in : src_base + it.in_off;
+      const void *storage_in = it.in == nullptr ? nullptr : it.pin_in != nullptr ? it.pin_in : src_base + it.in_off;
+      void *storage_out = it.pin_out != nullptr ? it.pin_out : dst_base + it.out_off;
+      d.in = it.pass_in ? ms.d_img_in + it.img_in : storage_in;
       d.hist = b->d_hist_[b->hist_cur_];
-      d.out = it.pin_out != nullptr ? it.pin_out : dst_base + it.out_off;
+      d.out = it.pass_out ? ms.d_img_out + it.img_out : storage_out;
+      if (it.pass_in) {
+        ConvertStream &c = to_image.s[j];
+        c.src = storage_in, c.dst = ms.d_img_in + it.img_in;
+        c.n = static_cast<uint64_t>(in_len[it.i]) * b->channels_;
+        c.step = 1;
+        c.reserved = convert_many_tag(it.e->in_fmt, SPEEXHIP_DITHER_NONE);
+        most_to = std::max(most_to, c.n);
+      }
+      if (it.pass_out && it.plan.produced != 0) {
+        ConvertStream &c = from_image.s[j];
+        c.src = ms.d_img_out + it.img_out, c.dst = storage_out;
+        c.n = static_cast<uint64_t>(it.plan.produced) * b->channels_;
+        c.step = 1;
+        const bool dithered = b->dither_on() && dithered_fmt(it.e->out_fmt);
+        c.reserved = convert_many_tag(it.e->out_fmt, dithered ? b->dither_kind_ : SPEEXHIP_DITHER_NONE);
+        if (dithered) dith.s[j] = b->dither_pack(0, 1, b->channels_).s[0];
+        most_from = std::max(most_from, c.n);
+      }
       d.hist_next = b->d_hist_[b->hist_cur_ ^ 1];
       d.in_frames = in_len[it.i];
       set_position(d, f, it.plan.begin, it.plan.produced, it.plan.magic_used + it.plan.consumed, f.taps - 1 + it.plan.begin.magic,
                    f.taps - 1 + it.plan.end.magic);
       max_out = std::max(max_out, it.plan.produced);
     }
+    if (most_to != 0) {
+      if (hip_failed(launch_convert_many(false, to_image, dith, cnt, most_to, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+      count_many(1);
+    }
     const int lrc = g[0]->b->launch_chunk(pack.d, pack, cnt, max_out, float_io, stream);
     if (lrc != SPEEXHIP_ERR_SUCCESS) return lrc;
+    count_many(0);
+    if (most_from != 0) {
+      if (hip_failed(launch_convert_many(true, from_image, dith, cnt, most_from, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+      count_many(2);
+    }
     // A state moves as ONE step, the moment its launch is queued: the history ping-pong, the position and the counters
     // together.  (Until round 6 the flip happened here and the positions behind the last launch of the call: a later
     // group's failure left the earlier groups' states with a flipped history and their OLD position -- silently corrupt
@@ -1893,7 +1965,7 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
         }
         for (Item *it : launches[k])
           if (it->out_bytes != 0 &&
-              fail(hipMemcpyAsync(out[it->i], ms.d_out + it->out_off, it->out_bytes, hipMemcpyDeviceToHost, ms.stream), "hipMemcpyAsync (results)"))
+              fail(hipMemcpyAsync(it->out, ms.d_out + it->out_off, it->out_bytes, hipMemcpyDeviceToHost, ms.stream), "hipMemcpyAsync (results)"))
             return;
       }
       if (worker_rc == SPEEXHIP_ERR_SUCCESS) {
@@ -1915,7 +1987,7 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
     for (size_t k = 0; k < launches.size() && copy_err == hipSuccess; k++) {
       for (Item *it : launches[k])
         if (it->in_bytes != 0 && copy_err == hipSuccess)
-          copy_err = hipMemcpyAsync(ms.d_in + it->in_off, in[it->i], it->in_bytes, hipMemcpyHostToDevice, ms.copy_stream);
+          copy_err = hipMemcpyAsync(ms.d_in + it->in_off, it->in, it->in_bytes, hipMemcpyHostToDevice, ms.copy_stream);
       if (copy_err == hipSuccess) copy_err = hipEventRecord(ms.events[k], ms.copy_stream);
       {
         std::lock_guard<std::mutex> l(mu);
@@ -1945,9 +2017,9 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
 
   for (const Item &it : items) {
     if (it.in_bytes == 0) continue;
-    if (it.in_via == Via::Bounce || it.in_via == Via::Staged) std::memcpy(ms.h_in + it.in_off, in[it.i], it.in_bytes);
+    if (it.in_via == Via::Bounce || it.in_via == Via::Staged) std::memcpy(ms.h_in + it.in_off, it.in, it.in_bytes);
     if (it.in_via == Via::Copy)
-      HIP_TRY(hipMemcpyAsync(ms.d_in + it.in_off, in[it.i], it.in_bytes, hipMemcpyHostToDevice, ms.stream));
+      HIP_TRY(hipMemcpyAsync(ms.d_in + it.in_off, it.in, it.in_bytes, hipMemcpyHostToDevice, ms.stream));
   }
   // (not small: the gathered range holds the Staged buffers)
   if (!small && gathered_in != 0) HIP_TRY(hipMemcpyAsync(ms.d_in, ms.h_in, gathered_in, hipMemcpyHostToDevice, ms.stream));
@@ -1960,37 +2032,62 @@ int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx
   if (!small && gathered_out != 0) HIP_TRY(hipMemcpyAsync(ms.h_out, ms.d_out, gathered_out, hipMemcpyDeviceToHost, ms.stream));
   for (const Item &it : items)
     if (it.out_via == Via::Copy)
-      HIP_TRY(hipMemcpyAsync(out[it.i], ms.d_out + it.out_off, it.out_bytes, hipMemcpyDeviceToHost, ms.stream));
+      HIP_TRY(hipMemcpyAsync(it.out, ms.d_out + it.out_off, it.out_bytes, hipMemcpyDeviceToHost, ms.stream));
   if (wait.sync || !launches.empty()) {
     const int wrc = wait_call(ms.stream, wait, tail_word(ms.h_out, ms.h_out_cap), ++ms.seq);
     if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
   }
   drain.armed = false;
   for (const Item &it : items)
-    if (pinned_part(it.out_via, it.out_bytes) != 0) std::memcpy(out[it.i], ms.h_out + it.out_off, it.out_bytes);
+    if (pinned_part(it.out_via, it.out_bytes) != 0) std::memcpy(it.out, ms.h_out + it.out_off, it.out_bytes);
   return SPEEXHIP_ERR_SUCCESS;
 }
 
+void many_counters(uint64_t out[4]) {
+  for (int k = 0; k < 4; k++) out[k] = g_many_counters[k].load(std::memory_order_relaxed);
+}
+
+// process_many_int / _float: the all-S16 / all-F32 case of many_run -- every entry the int16 call, or the float call, on
+// its own bytes; the state's dither is neither read nor moved.
 int Batch::process_host_many(uint32_t n, Batch *const *st, const void *const *in, uint32_t *in_len, void *const *out,
                              uint32_t *out_len, bool float_io, int *codes) {
+  std::vector<ManyEntry> entries(n);
+  for (uint32_t i = 0; i < n; i++) {
+    ManyEntry &e = entries[i];
+    e.b = st[i];
+    e.in = in[i];
+    e.out = out[i];
+    e.in_fmt = e.out_fmt = float_io ? SPEEXHIP_FMT_F32 : SPEEXHIP_FMT_S16;
+    e.kind = float_io ? ManyEntry::Float : ManyEntry::Int16;
+    e.fusable = true;
+    if (st[i] == nullptr || (out[i] == nullptr && out_len[i] != 0)) e.rc = SPEEXHIP_ERR_INVALID_ARG;
+  }
+  return many_run(n, entries.data(), in_len, out_len, codes);
+}
+
+int Batch::many_run(uint32_t n, const ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *codes) {
   std::vector<int> rcs(n, SPEEXHIP_ERR_SUCCESS);
   std::map<int, std::vector<uint32_t>> by_device;  // (ordered: two concurrent calls lock their devices in one order)
   std::vector<uint32_t> apart;                     // states that take the single call (in the caller's order)
   for (uint32_t i = 0; i < n; i++) {
-    Batch *b = st[i];
-    if (b == nullptr || (out[i] == nullptr && out_len[i] != 0)) {
-      rcs[i] = SPEEXHIP_ERR_INVALID_ARG;
+    Batch *b = entries[i].b;
+    if (entries[i].rc != SPEEXHIP_ERR_SUCCESS) {  // (an argument error: the state and the lengths stay as they are)
+      rcs[i] = entries[i].rc;
       continue;
     }
     bool earlier = false;  // a state named twice: its second call must see the first one's end state
-    for (uint32_t j = 0; j < i && !earlier; j++) earlier = st[j] == b;
+    for (uint32_t j = 0; j < i && !earlier; j++) earlier = entries[j].b == b;
     // (rare states -- channels moved apart by the per-channel calls, the zero fallback, batches of several streams --
-    //  keep their own call's rules)
-    if (earlier || b->n_streams_ != 1 || !b->uniform(0) || b->zero_mode_)
+    //  and the sides a launch group does not serve -- a matrix, planes of several channels -- keep their own call's rules)
+    if (earlier || !entries[i].fusable || b->n_streams_ != 1 || !b->uniform(0) || b->zero_mode_)
       apart.push_back(i);
     else
       by_device[b->device_].push_back(i);
   }
+  // the raw bytes entry i's sides would move at most: frames x channels x the side's sample size
+  auto raw_in = [&](uint32_t i) {
+    return static_cast<uint64_t>(in_len[i]) * entries[i].b->channels_ * sample_bytes(entries[i].in_fmt);
+  };
   // Units of work: a device's states -- or, for a large call, two halves of them ("lanes"): one thread's pageable copies
   // do not fill a PCIe link (64 x 2^20 stereo frames on one GPU: 11.0 ms through one stage, 7.6 ms as two logical
   // devices of 32 states each, profiles/r05_host_many.txt), two stages side by side nearly do.
@@ -2010,13 +2107,13 @@ int Batch::process_host_many(uint32_t n, Batch *const *st, const void *const *in
     // that was the copy engines' lottery, not the lanes.)
     uint64_t bytes_in = 0, bytes_out = 0;
     for (uint32_t i : kv.second) {
-      const uint64_t es = float_io ? 4 : 2;
-      const uint64_t b = static_cast<uint64_t>(in_len[i]) * st[i]->channels_ * es;
-      if (in[i] != nullptr && !pool::block_owns(in[i], b)) bytes_in += b;
+      const ManyEntry &e = entries[i];
+      const uint64_t b = raw_in(i);
+      if (e.in != nullptr && !pool::block_owns(e.in, b)) bytes_in += b;
       // (results: about den / num of the input's frames, capped by the caller's capacity)
-      const uint64_t frames_out = std::min<uint64_t>(out_len[i], static_cast<uint64_t>(in_len[i]) * st[i]->filter_.den / std::max<uint32_t>(st[i]->filter_.num, 1) + 1);
-      const uint64_t o = frames_out * st[i]->channels_ * es;
-      if (out[i] != nullptr && !pool::block_owns(out[i], o)) bytes_out += o;
+      const uint64_t frames_out = std::min<uint64_t>(out_len[i], static_cast<uint64_t>(in_len[i]) * e.b->filter_.den / std::max<uint32_t>(e.b->filter_.num, 1) + 1);
+      const uint64_t o = frames_out * e.b->channels_ * sample_bytes(e.out_fmt);
+      if (e.out != nullptr && !pool::block_owns(e.out, o)) bytes_out += o;
     }
     const uint64_t bytes = std::max(bytes_in, bytes_out);
     // (from 128 MB: 32 x 2^20 stereo frames 4.11 -> 4.00 ms, 64 states 7.90 -> 7.14; at 67 MB nothing, 2.26 / 2.44)
@@ -2033,7 +2130,7 @@ int Batch::process_host_many(uint32_t n, Batch *const *st, const void *const *in
   //  unit copies anything -- prime_copy_stream)
   for (const Unit &u : units) {
     uint64_t bytes = 0;
-    for (uint32_t i : u.idx) bytes += static_cast<uint64_t>(in_len[i]) * st[i]->channels_ * (float_io ? 4 : 2);
+    for (uint32_t i : u.idx) bytes += raw_in(i);
     if (bytes >= (static_cast<uint64_t>(32) << 20)) {
       ManyStage &ms = many_stage(u.device, u.lane);
       std::lock_guard<std::mutex> lock(ms.mu);  // (the order many_on_device takes them in: the stage, then the priming)
@@ -2045,7 +2142,7 @@ int Batch::process_host_many(uint32_t n, Batch *const *st, const void *const *in
   auto run_device = [&](size_t slot) {
     const Unit &u = units[slot];
     try {
-      dev_rc[slot] = many_on_device(u.device, u.lane, u.idx, st, in, in_len, out, out_len, float_io, rcs.data());
+      dev_rc[slot] = many_on_device(u.device, u.lane, u.idx, entries, in_len, out_len, rcs.data());
     } catch (const std::bad_alloc &) {
       dev_rc[slot] = SPEEXHIP_ERR_ALLOC_FAILED;
     } catch (const std::exception &e) {  // (anything else: a code and its text, never std::terminate in a worker)
@@ -2082,7 +2179,12 @@ int Batch::process_host_many(uint32_t n, Batch *const *st, const void *const *in
         break;
       }
   }
-  for (uint32_t i : apart) rcs[i] = st[i]->process_host(in[i], &in_len[i], out[i], &out_len[i], float_io);
+  for (uint32_t i : apart) {
+    const ManyEntry &e = entries[i];
+    rcs[i] = e.sides ? e.b->process_sides_host(e.in_side, &in_len[i], e.out_side, &out_len[i])
+                     : e.b->process_host(e.in, &in_len[i], e.out, &out_len[i], e.kind != ManyEntry::Int16);
+  }
+  count_many(3, apart.size());
   int first = SPEEXHIP_ERR_SUCCESS;
   for (uint32_t i = 0; i < n; i++) {
     if (codes != nullptr) codes[i] = rcs[i];

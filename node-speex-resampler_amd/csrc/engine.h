@@ -22,6 +22,9 @@ void set_last_device_error(const std::string &text);
 size_t lds_budget();  // LDS the planners may give one workgroup (of the CU's 160 KiB)
 // Test hook: the n-th next device allocation of a filter install fails (resample.c:785-791 path); 0 = off.
 void debug_fail_device_allocs(int n);
+// speexhip_debug_many_counters: process-wide counts since start, of the many-states calls old and new -- FIR launches, input
+// passes, output passes, entries that took their own call.
+void many_counters(uint64_t out[4]);
 
 // Everything on the device that depends only on (filter, channel count): the reference-layout sinc
 // table, the fast kernels' tap rows and the launch geometry.  Immutable once built, so states with
@@ -140,6 +143,17 @@ class Batch {
   // codes[i] (may be null) = that call's return code; returns the first code that is not SUCCESS.
   static int process_host_many(uint32_t n, Batch *const *states, const void *const *in, uint32_t *in_len,
                                void *const *out, uint32_t *out_len, bool float_io, int *codes);
+  // ... with a format per state (formats.cpp): entry i is exactly process_sides_host(in[i], &in_len[i], out[i],
+  // &out_len[i]) on states[i] -- bytes (in the modes whose bytes do not depend on the launch's shape: FAST_FIXED, EXACT),
+  // counters, history, position, dither position and code.  bad (may be null): bad[i]
+  // != 0 = the caller's side could not be read (INVALID_ARG, nothing runs for it).  An entry whose state is one uniform
+  // stream out of the zero fallback and not named earlier in the call, and whose sides are interleaved (or of one channel)
+  // and have no matrix, is fused: S16 -> S16 without dither as the int16 call, F32 -> F32 and F32N -> F32N as the float
+  // call on the same bytes, everything else as the float call between the passes of kernels_convert_many.hip -- per launch
+  // group of <= 32 states one input pass, one FIR launch and one output pass, whatever formats the states name.  Every
+  // other entry takes its own process_sides_host call, in the caller's order, after the fused ones.
+  static int process_host_many_sides(uint32_t n, Batch *const *states, const CallSide *in, uint32_t *in_len,
+                                     const CallSide *out, uint32_t *out_len, const uint8_t *bad, int *codes);
   int device() const { return device_; }
   // n_chunks consecutive host-buffer calls of a single-stream batch as one launch; outputs are
   // written back to back into `out` (room for the sum of the capacities).
@@ -240,8 +254,23 @@ class Batch {
                    hipStream_t stream);
   // a large host call as pieces: input copies on a second stream, one launch per piece behind each (process_host_take)
   int take_in_pieces(const void *in, uint32_t *in_len, uint32_t *out_len, bool float_io, void *blk, uint32_t pieces);
-  static int many_on_device(int device, int lane, const std::vector<uint32_t> &idx, Batch *const *st, const void *const *in,
-                            uint32_t *in_len, void *const *out, uint32_t *out_len, bool float_io, int *rcs);
+  // One entry of a many-states call, as many_run takes it.
+  struct ManyEntry {
+    enum Kind { Int16, Float, Image };  // the int16 call / the float call on the entry's own bytes / the float call on
+                                        // float images, between the passes that convert the entry's formats
+    Batch *b = nullptr;
+    int rc = SPEEXHIP_ERR_SUCCESS;      // not SUCCESS: an argument error found already; nothing runs for the entry
+    const void *in = nullptr;           // the entry's interleaved host buffers, in_fmt / out_fmt samples
+    void *out = nullptr;
+    int in_fmt = SPEEXHIP_FMT_S16, out_fmt = SPEEXHIP_FMT_S16;
+    Kind kind = Int16;
+    bool fusable = false;               // the sides are ones a launch group serves (the state decides the rest)
+    bool sides = false;                 // an entry of process_host_many_sides: its own call is process_sides_host on
+    CallSide in_side = {}, out_side = {};  // these, and its dither position moves
+  };
+  static int many_run(uint32_t n, const ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *codes);
+  static int many_on_device(int device, int lane, const std::vector<uint32_t> &idx, const ManyEntry *entries, uint32_t *in_len,
+                            uint32_t *out_len, int *rcs);
   bool have_copy_stream();  // copy_stream_ = a pool stream other than own_stream_ (false: none -> no piecewise call)
 
   FilterSpec filter_;

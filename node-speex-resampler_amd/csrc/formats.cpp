@@ -163,6 +163,37 @@ int Batch::process_sides_device(const CallSide &in_side, uint32_t *in_len, const
   return rc;
 }
 
+// The formatted many-states call (engine.h): which entries a launch group can serve and as what -- the rules of
+// process_sides_host above, entry by entry -- then many_run (engine.cpp).
+int Batch::process_host_many_sides(uint32_t n, Batch *const *st, const CallSide *in, uint32_t *in_len, const CallSide *out,
+                                   uint32_t *out_len, const uint8_t *bad, int *codes) {
+  std::vector<ManyEntry> entries(n);
+  for (uint32_t i = 0; i < n; i++) {
+    ManyEntry &e = entries[i];
+    Batch *b = e.b = st[i];
+    e.sides = true;
+    if (b == nullptr || (bad != nullptr && bad[i] != 0) || !side_ok(in[i], b->channels_) || !side_ok(out[i], b->channels_) ||
+        (out[i].base == nullptr && out[i].planes == nullptr)) {
+      e.rc = SPEEXHIP_ERR_INVALID_ARG;
+      continue;
+    }
+    e.in_side = in[i];
+    e.out_side = out[i];
+    e.in_fmt = in[i].fmt;
+    e.out_fmt = out[i].fmt;
+    // fused: both sides interleaved (or of one channel) in one buffer each, no matrix
+    e.fusable = !planar(in[i]) && !planar(out[i]) && in[i].mix == nullptr && out[i].mix == nullptr && in[i].planes == nullptr &&
+                out[i].planes == nullptr;
+    if (!e.fusable) continue;
+    e.in = in[i].base;
+    e.out = out[i].base;
+    e.kind = !same_bytes(in[i], out[i], b->dither_on()) ? ManyEntry::Image
+             : in[i].fmt == SPEEXHIP_FMT_S16            ? ManyEntry::Int16
+                                                        : ManyEntry::Float;
+  }
+  return many_run(n, entries.data(), in_len, out_len, codes);
+}
+
 // process_sides_device on own_stream_ around a single-stream call's host buffers: the raw bytes of both sides move by the
 // rule of host_transfer.h -- in place when pinned, through the bounce buffers when small, by the runtime's staged copy when
 // large.

@@ -78,6 +78,7 @@ void warm_unit_period64_w16(hipStream_t s);
 void warm_unit_period_w16g(hipStream_t s);
 void warm_unit_planar(hipStream_t s);
 void warm_unit_convert(hipStream_t s);
+void warm_unit_convert_many(hipStream_t s);
 void warm_unit_mix(hipStream_t s);
 void warm_unit_sides(hipStream_t s);
 
@@ -272,6 +273,16 @@ hipError_t launch_convert(int fmt, bool out, const ConvertPack &pack, const Dith
                           hipStream_t stream);
 hipError_t launch_mix(int fmt, bool out, const MixPack &pack, const DitherPack *dith, uint32_t n, uint32_t most,
                       hipStream_t stream);
+
+// ---- ... with a format per stream (kernels_convert_many.hip): the passes of a launch group of the formatted many-states
+// call.  Stream j's format and dither kind travel in its ConvertStream::reserved (convert_many_tag); every step is 1.  out:
+// a stream whose kind is not NONE (a dithered_fmt then) leaves through the dithered body with dith.s[j].seed and .first
+// (idx of its sample 0: position * channels); dith.kind is not read.  F32 streams have no pass: leave their src NULL.
+constexpr uint32_t convert_many_tag(int fmt, int dither_kind) {
+  return static_cast<uint32_t>(fmt) | (static_cast<uint32_t>(dither_kind) << 8);
+}
+hipError_t launch_convert_many(bool out, const ConvertPack &pack, const DitherPack &dith, uint32_t n, uint64_t most,
+                               hipStream_t stream);
 
 // ---- channel planes of any format <-> the float image (kernels_sides.hip): the pass of a side whose layout is planar --
 // planes_in: C planes of the call's format -> the interleaved float image; planes_out: the image -> planes.  Conversion,

@@ -21,6 +21,10 @@
 // The image convert_in writes is read by the very next kernel and convert_out's source was written by the previous
 // one: plain loads and stores throughout, so that the images can stay in L2 / Infinity Cache.
 //
+// The bodies of both paths -- vector_tile, element_tile and stream_tile, which picks between them -- are stated in
+// kernels_convert_impl.h, shared with kernels_convert_many.hip (a format per stream of one launch); this unit holds the
+// instances of one format per launch and their launcher.
+//
 // The formats themselves -- one sample to and from the image, rounding half up, and the loads / stores of one sample --
 // are stated in format_device.h, which the mixing kernels (kernels_mix.hip) share.
 //
@@ -36,6 +40,7 @@
 #include "dither.h"
 #include "format_device.h"
 #include "kernels.h"
+#include "kernels_convert_impl.h"
 
 namespace speexhip {
 
@@ -43,109 +48,11 @@ SPEEXHIP_WARM_UNIT(convert)
 
 namespace {
 
-using namespace fmtdev;  // to_internal / from_internal, load_raw / store_raw, with_format
-
-constexpr uint32_t kLanes = 256;
-constexpr uint32_t kTile = 4096;  // samples per workgroup
-
-// samples a lane owns per pass of the vector path: whole 16-byte pieces on both sides
-constexpr uint32_t group_of(int f) { return sample_bytes(f) == 1 || sample_bytes(f) == 3 ? 16u : sample_bytes(f) == 2 ? 8u : 4u; }
-
-// ---- 16 bytes per lane ---------------------------------------------------------------------------------------------
-// sample j (compile-time) of a lane's group, from / into the group's storage words
-template <int F>
-__device__ __forceinline__ uint32_t raw_of(const uint32_t *w, uint32_t j) {
-  constexpr uint32_t bits = 8 * sample_bytes(F), words = group_of(F) * sample_bytes(F) / 4;
-  const uint32_t k = j * bits / 32, shift = j * bits % 32;
-  const uint64_t pair = w[k] | (static_cast<uint64_t>(k + 1 < words ? w[k + 1] : 0u) << 32);
-  return static_cast<uint32_t>(pair >> shift);
-}
-template <int F>
-__device__ __forceinline__ void put_raw(uint32_t *w, uint32_t j, uint32_t raw) {
-  constexpr uint32_t bits = 8 * sample_bytes(F), words = group_of(F) * sample_bytes(F) / 4;
-  const uint32_t k = j * bits / 32, shift = j * bits % 32;
-  const uint64_t pair = static_cast<uint64_t>(bits == 32 ? raw : raw & ((1u << (bits & 31)) - 1u)) << shift;
-  w[k] |= static_cast<uint32_t>(pair);
-  if (k + 1 < words) w[k + 1] |= static_cast<uint32_t>(pair >> 32);
-}
-
-// kDither (kOut only): the dithered instances; d and kind are theirs alone
-template <int F, bool kOut, bool kDither>
-__device__ __forceinline__ void vector_tile(const ConvertStream &s, const DitherStream *d, int kind, uint64_t tile0) {
-  constexpr uint32_t B = sample_bytes(F), G = group_of(F), words = G * B / 4;
-  constexpr int W = word_format(F);  // (S16BE / S32BE: the words are reversed as dwords, the samples then the twin's)
-  const char *src = static_cast<const char *>(s.src);
-  char *dst = static_cast<char *>(s.dst);
-#pragma unroll
-  for (uint32_t pass = 0; pass < kTile / (kLanes * G); pass++) {
-    const uint64_t first = tile0 + static_cast<uint64_t>(pass * kLanes + threadIdx.x) * G;  // the lane's first sample
-    const dither::Run run = kDither ? dither::run_of(d->seed, d->first + first, G) : dither::Run{};
-    uint32_t w[words];
-    float e[G];
-    if (!kOut) {
-      const uint4 *in = reinterpret_cast<const uint4 *>(src + first * B);
-#pragma unroll
-      for (uint32_t i = 0; i < words / 4; i++) {
-        const uint4 v = in[i];
-        w[4 * i] = v.x, w[4 * i + 1] = v.y, w[4 * i + 2] = v.z, w[4 * i + 3] = v.w;
-      }
-      swap_words<F, words>(w);
-#pragma unroll
-      for (uint32_t j = 0; j < G; j++) e[j] = to_internal<W>(raw_of<W>(w, j));
-      float4 *out = reinterpret_cast<float4 *>(dst + first * sizeof(float));
-#pragma unroll
-      for (uint32_t i = 0; i < G / 4; i++) out[i] = make_float4(e[4 * i], e[4 * i + 1], e[4 * i + 2], e[4 * i + 3]);
-    } else {
-      const float4 *in = reinterpret_cast<const float4 *>(src + first * sizeof(float));
-#pragma unroll
-      for (uint32_t i = 0; i < G / 4; i++) {
-        const float4 v = in[i];
-        e[4 * i] = v.x, e[4 * i + 1] = v.y, e[4 * i + 2] = v.z, e[4 * i + 3] = v.w;
-      }
-#pragma unroll
-      for (uint32_t i = 0; i < words; i++) w[i] = 0;
-#pragma unroll
-      for (uint32_t j = 0; j < G; j++)
-        put_raw<W>(w, j, encode<W, kDither>(e[j], [&] { return dither::noise_in(kind, run, j); }));
-      swap_words<F, words>(w);
-      uint4 *out = reinterpret_cast<uint4 *>(dst + first * B);
-#pragma unroll
-      for (uint32_t i = 0; i < words / 4; i++) out[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
-    }
-  }
-}
-
-// ---- sample by sample ----------------------------------------------------------------------------------------------
-// samples [tile0, tile0 + n) of the stream; sample k lies k * step elements into both buffers (dithered: step is 1)
-template <int F, bool kOut, bool kDither>
-__device__ __forceinline__ void element_tile(const ConvertStream &s, const DitherStream *d, int kind, uint64_t tile0,
-                                             uint32_t n) {
-  constexpr uint32_t B = sample_bytes(F);
-  const char *src = static_cast<const char *>(s.src);
-  char *dst = static_cast<char *>(s.dst);
-  for (uint32_t i = threadIdx.x; i < n; i += kLanes) {
-    const uint64_t at = kDither ? tile0 + i : (tile0 + i) * s.step;
-    if (!kOut)
-      *reinterpret_cast<float *>(dst + at * sizeof(float)) = to_internal<F>(load_raw<F>(src + at * B));
-    else
-      store_raw<F>(dst + at * B, encode<F, kDither>(*reinterpret_cast<const float *>(src + at * sizeof(float)),
-                                                    [&] { return dither::noise(kind, d->seed, d->first + at); }));
-  }
-}
+using namespace convert_impl;  // kLanes, kTile, stream_tile: the bodies (kernels_convert_impl.h)
 
 template <int F, bool kOut, bool kDither>
 __device__ __forceinline__ void convert_tile(const ConvertPack &pack, const DitherPack *dith) {
-  const ConvertStream &s = pack.s[blockIdx.y];
-  const DitherStream *d = kDither ? &dith->s[blockIdx.y] : nullptr;
-  const int kind = kDither ? dith->kind : 0;
-  const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kTile;
-  if (s.src == nullptr || tile0 >= s.n) return;  // (nothing to convert, or a shorter stream of the launch)
-  const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(kTile), s.n - tile0));
-  const bool aligned = ((reinterpret_cast<uintptr_t>(s.src) | reinterpret_cast<uintptr_t>(s.dst)) & 15u) == 0;
-  if (n == kTile && aligned && (kDither || s.step == 1))
-    vector_tile<F, kOut, kDither>(s, d, kind, tile0);
-  else
-    element_tile<F, kOut, kDither>(s, d, kind, tile0, n);
+  stream_tile<F, kOut, kDither>(pack.s[blockIdx.y], kDither ? &dith->s[blockIdx.y] : nullptr, kDither ? dith->kind : 0);
 }
 
 template <int F>

@@ -223,6 +223,15 @@ export declare class SpeexResamplerBatch {
     /** one chunk per stream (null: the stream sits the step out) -> one fresh Buffer per stream (null likewise) */
     processChunks(chunks: Array<Buffer | null>): Array<Buffer | null>;
     processChunksAsync(chunks: Array<Buffer | null>): Promise<Array<Buffer | null>>;
+    /**
+     * processChunks with sample formats, all streams in one fused call: entry k equals
+     * `streams[k].processChunkFormat(chunks[k], inFormat[k], outFormat[k])`.  A format is one name for all streams or an
+     * array with one name per stream: a gateway's PCMU / PCMA / L16 legs as `['mulaw', 'alaw', 's16be', ...]`.
+     */
+    processChunksFormat(chunks: Array<Buffer | null>, inFormat: SampleFormat | SampleFormat[],
+                        outFormat: SampleFormat | SampleFormat[]): Array<Buffer | null>;
+    processChunksFormatAsync(chunks: Array<Buffer | null>, inFormat: SampleFormat | SampleFormat[],
+                             outFormat: SampleFormat | SampleFormat[]): Promise<Array<Buffer | null>>;
     setMode(mode: 'fast' | 'exact' | 'fast_f32' | 'fast_fixed'): void;
     /** setDither of every stream; stream k draws from seed + k * 0x9E3779B97F4A7C15 (mod 2^64) */
     setDither(kind: DitherKind, seed?: bigint | number, position?: bigint | number): void;

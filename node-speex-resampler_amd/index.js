@@ -628,8 +628,12 @@ class SpeexResamplerBatch {
     } catch (e) {
       return Promise.reject(e);
     }
-    const run = () => (g.handles.length > 0
-      ? speexModule.processManyAsync(g.handles, g.chunks, g.inFrames, g.caps) : Promise.resolve([]))
+    return this._chainStep(g, () => speexModule.processManyAsync(g.handles, g.chunks, g.inFrames, g.caps));
+  }
+
+  // one asynchronous step of the gathered streams `g`: `call` makes the native call once the step's turn has come
+  _chainStep(g, call) {
+    const run = () => (g.handles.length > 0 ? call() : Promise.resolve([]))
       .then((outs) => {
         const result = new Array(this.streams.length).fill(null);
         g.index.forEach((k, i) => { result[k] = outs[i]; });
@@ -649,6 +653,82 @@ class SpeexResamplerBatch {
     this._pending = done;
     for (const k of g.index) this.streams[k]._pending = done;
     return p;
+  }
+
+  // processChunksFormat: a format name for all streams, or an array with one name per stream
+  _formatsOf(format, what) {
+    const names = Array.isArray(format) ? format : new Array(this.streams.length).fill(format);
+    if (names.length !== this.streams.length) {
+      throw new Error(what + ' expects one format name, or one per stream: ' + this.streams.length);
+    }
+    return names.map((name) => {
+      const f = SAMPLE_FORMATS[name];
+      if (!f) throw new Error('Unknown sample format: ' + name);
+      return f;
+    });
+  }
+
+  _gatherFormat(chunks, inFormat, outFormat) {
+    if (!Array.isArray(chunks) || chunks.length !== this.streams.length) {
+      throw new Error('processChunksFormat expects one chunk (or null) per stream: ' + this.streams.length);
+    }
+    if (!speexModule) {
+      throw new Error('You need to wait for SpeexResampler.initPromise before calling this method');
+    }
+    // formats and chunks are all checked before any stream's state is touched: a step is refused whole
+    const fin = this._formatsOf(inFormat, 'processChunksFormat');
+    const fout = this._formatsOf(outFormat, 'processChunksFormat');
+    for (let k = 0; k < chunks.length; k++) {
+      if (chunks[k] === null || chunks[k] === undefined) continue;
+      if (chunks[k].length % (this.channels * fin[k].bytes) !== 0) {
+        throw new Error('Chunk length should be a multiple of channels * ' + fin[k].bytes + ' bytes');
+      }
+    }
+    const picked = { index: [], handles: [], chunks: [], inFrames: [], caps: [], inFmts: [], outFmts: [] };
+    for (let k = 0; k < chunks.length; k++) {
+      if (chunks[k] === null || chunks[k] === undefined) continue; // this stream sits the step out
+      // the capacity rule of streams[k].processChunkFormat on these frames
+      const frames = (chunks[k].length / this.channels / fin[k].bytes) | 0;
+      const asBytes = fin[k].id === 1 && fout[k].id === 1 ? Uint16Array.BYTES_PER_ELEMENT : Float32Array.BYTES_PER_ELEMENT;
+      const [, cap] = this.streams[k]._prepare({ length: frames * this.channels * asBytes }, asBytes);
+      picked.index.push(k);
+      picked.handles.push(this.streams[k]._resamplerPtr);
+      picked.chunks.push(chunks[k]);
+      picked.inFrames.push(frames);
+      picked.caps.push(cap);
+      picked.inFmts.push(fin[k].id);
+      picked.outFmts.push(fout[k].id);
+    }
+    return picked;
+  }
+
+  /**
+   * processChunks with sample formats: one chunk per stream (null / undefined: the stream sits this step out) in the
+   * stream's input format, one fresh Buffer per stream out in its output format -- entry k is what
+   * streams[k].processChunkFormat(chunks[k], inFormat[k], outFormat[k]) returns, all streams in ONE fused library call: a
+   * gateway's PCMU, PCMA and L16 legs of a 20 ms tick as b.processChunksFormat(payloads, ['mulaw', 'alaw', 's16be', ...],
+   * 'f32le-normalized').  inFormat / outFormat: one of processChunkFormat's names for all streams, or an array with one name
+   * per stream.
+   */
+  processChunksFormat(chunks, inFormat, outFormat) {
+    for (const r of this.streams) r._refuseWhileAsyncPending('SpeexResamplerBatch.processChunksFormat');
+    const g = this._gatherFormat(chunks, inFormat, outFormat);
+    const outs = g.handles.length > 0
+      ? speexModule.processManyFormat(g.handles, g.chunks, g.inFrames, g.caps, g.inFmts, g.outFmts) : [];
+    const result = new Array(this.streams.length).fill(null);
+    g.index.forEach((k, i) => { result[k] = outs[i]; });
+    return result;
+  }
+
+  /** processChunksFormat off the event loop, ordered with the streams' other asynchronous calls like processChunksAsync. */
+  processChunksFormatAsync(chunks, inFormat, outFormat) {
+    let g;
+    try {
+      g = this._gatherFormat(chunks, inFormat, outFormat);
+    } catch (e) {
+      return Promise.reject(e);
+    }
+    return this._chainStep(g, () => speexModule.processManyFormatAsync(g.handles, g.chunks, g.inFrames, g.caps, g.inFmts, g.outFmts));
   }
 
   setMode(mode) { for (const r of this.streams) r.setMode(mode); }

@@ -1152,6 +1152,9 @@ typedef struct {
   int16_t **out;
   uint32_t *in_len, *out_len, *will_make, *channels;
   int *codes;
+  /* processManyFormat: a sample format per entry and side (SPEEXHIP_FMT_*), and whether the entry is sized by the float
+   * entry's rules -- every pair but S16 -> S16 without dither; NULL in processMany, whose entries are all S16 -> S16 calls */
+  int *in_fmt, *out_fmt, *float_entry;
   /* asynchronous form */
   napi_async_work work;
   napi_deferred deferred;
@@ -1179,6 +1182,9 @@ static void many_free(napi_env env, ManyJob *j) {
   free(j->will_make);
   free(j->channels);
   free(j->codes);
+  free(j->in_fmt);
+  free(j->out_fmt);
+  free(j->float_entry);
   free(j->refs);
   free(j);
 }
@@ -1209,7 +1215,8 @@ static void many_run(ManyJob *j) {
    * locks, BEFORE anything is written, and refuse the step whole. */
   for (uint32_t i = 0; i < j->n; i++) {
     uint32_t will_use = 0, will_make = 0;
-    speexhip_resampler_peek(j->st[i], j->in_len[i], j->out_len[i], 0, &will_use, &will_make);
+    speexhip_resampler_peek(j->st[i], j->in_len[i], j->out_len[i], j->float_entry != NULL ? j->float_entry[i] : 0, &will_use,
+                            &will_make);
     if (will_make != j->will_make[i]) {
       j->rc = SPEEXHIP_ERR_BAD_STATE;
       snprintf(j->errmsg, sizeof(j->errmsg), "%s (a state of this step was used by another call while the step was pending)",
@@ -1217,7 +1224,11 @@ static void many_run(ManyJob *j) {
       return;
     }
   }
-  j->rc = speexhip_resampler_process_many_int(j->n, j->st, j->in, j->in_len, j->out, j->out_len, j->codes);
+  if (j->in_fmt != NULL)
+    j->rc = speexhip_resampler_process_many_fmt(j->n, j->st, j->in_fmt, (const void *const *)j->in, j->in_len, j->out_fmt,
+                                                (void *const *)j->out, j->out_len, j->codes);
+  else
+    j->rc = speexhip_resampler_process_many_int(j->n, j->st, j->in, j->in_len, j->out, j->out_len, j->codes);
   j->ran = 1;
   for (uint32_t i = 0; i < j->n; i++)
     if (j->codes[i] == 0 && j->out_len[i] != j->will_make[i]) {
@@ -1227,13 +1238,15 @@ static void many_run(ManyJob *j) {
   if (j->rc != 0) snprintf(j->errmsg, sizeof(j->errmsg), "%s", speexhip_resampler_strerror(j->rc));
 }
 
-/* Parses (handles[], chunks[], inFrames[], caps[]), sizes the results from the states' counters and creates the
- * result Buffers; returns the job with *result = the array of Buffers, or NULL with an exception pending. */
-static ManyJob *many_prepare(napi_env env, napi_callback_info info, napi_value *result, int keep_refs) {
-  size_t argc = 4;
-  napi_value argv[4];
-  if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 4) {
-    napi_throw_type_error(env, NULL, "processMany expects (handle[], Buffer[], number[], number[])");
+/* Parses (handles[], chunks[], inFrames[], caps[]) -- formatted: and (inFmts[], outFmts[]), SPEEXHIP_FMT_* ids per entry --
+ * sizes the results from the states' counters and creates the result Buffers; returns the job with *result = the array
+ * of Buffers, or NULL with an exception pending. */
+static ManyJob *many_prepare(napi_env env, napi_callback_info info, napi_value *result, int keep_refs, int formatted) {
+  size_t argc = 6;
+  napi_value argv[6];
+  if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < (formatted ? 6u : 4u)) {
+    napi_throw_type_error(env, NULL, formatted ? "processManyFormat expects (handle[], Buffer[], number[], number[], number[], number[])"
+                                               : "processMany expects (handle[], Buffer[], number[], number[])");
     return NULL;
   }
   uint32_t n = 0;
@@ -1256,9 +1269,14 @@ static ManyJob *many_prepare(napi_env env, napi_callback_info info, napi_value *
     j->channels = (uint32_t *)calloc(m, sizeof(uint32_t));
     j->codes = (int *)calloc(m, sizeof(int));
     if (keep_refs) j->refs = (napi_ref *)calloc(3 * m, sizeof(napi_ref));
+    if (formatted) {
+      j->in_fmt = (int *)calloc(m, sizeof(int));
+      j->out_fmt = (int *)calloc(m, sizeof(int));
+      j->float_entry = (int *)calloc(m, sizeof(int));
+    }
   }
   if (j == NULL || !j->h || !j->locked || !j->st || !j->in || !j->out || !j->in_len || !j->out_len || !j->will_make ||
-      !j->channels || !j->codes || (keep_refs && !j->refs)) {
+      !j->channels || !j->codes || (keep_refs && !j->refs) || (formatted && (!j->in_fmt || !j->out_fmt || !j->float_entry))) {
     many_free(env, j);
     napi_throw_error(env, NULL, speexhip_resampler_strerror(SPEEXHIP_ERR_ALLOC_FAILED));
     return NULL;
@@ -1276,6 +1294,22 @@ static ManyJob *many_prepare(napi_env env, napi_callback_info info, napi_value *
       fail = "processMany expects (handle[], Buffer[], number[], number[])";
       type_error = 1;
       break;
+    }
+    if (formatted) {
+      napi_value fa, fb;
+      int32_t fi = -1, fo = -1;
+      if (napi_get_element(env, argv[4], i, &fa) != napi_ok || napi_get_value_int32(env, fa, &fi) != napi_ok ||
+          napi_get_element(env, argv[5], i, &fb) != napi_ok || napi_get_value_int32(env, fb, &fo) != napi_ok) {
+        fail = "processManyFormat expects (handle[], Buffer[], number[], number[], number[], number[])";
+        type_error = 1;
+        break;
+      }
+      if (speexhip_sample_bytes(fi) == 0 || speexhip_sample_bytes(fo) == 0) {
+        fail = "processManyFormat: unknown sample format";
+        break;
+      }
+      j->in_fmt[i] = fi;
+      j->out_fmt[i] = fo;
     }
     j->h[i] = (Handle *)p;
     j->in[i] = (const int16_t *)data;
@@ -1309,14 +1343,24 @@ static ManyJob *many_prepare(napi_env env, napi_callback_info info, napi_value *
       }
       SpeexHipInfo si;
       speexhip_resampler_get_info(st, &si);
-      const size_t bytes = j->channels[i], frame_bytes = (size_t)si.nb_channels * 2;
+      const size_t bytes = j->channels[i];
+      const size_t in_frame_bytes = (size_t)si.nb_channels * (formatted ? speexhip_sample_bytes(j->in_fmt[i]) : 2);
+      const size_t frame_bytes = (size_t)si.nb_channels * (formatted ? speexhip_sample_bytes(j->out_fmt[i]) : 2);
       j->channels[i] = si.nb_channels;
-      if (j->in[i] != NULL && (size_t)j->in_len[i] * frame_bytes > bytes) {
+      if (j->in[i] != NULL && (size_t)j->in_len[i] * in_frame_bytes > bytes) {
         fail = "input frame count exceeds the chunk";
         break;
       }
+      int float_entry = 0;
+      if (formatted) {
+        /* (the entry's rules: S16 -> S16 is the int16 call unless the state's dither is on; everything else the float call) */
+        int kind = SPEEXHIP_DITHER_NONE;
+        (void)speexhip_resampler_get_dither(st, &kind, NULL, NULL);
+        float_entry = !(j->in_fmt[i] == SPEEXHIP_FMT_S16 && j->out_fmt[i] == SPEEXHIP_FMT_S16 && kind == SPEEXHIP_DITHER_NONE);
+        j->float_entry[i] = float_entry;
+      }
       uint32_t will_use = 0;
-      speexhip_resampler_peek(st, j->in_len[i], j->out_len[i], 0, &will_use, &j->will_make[i]);
+      speexhip_resampler_peek(st, j->in_len[i], j->out_len[i], float_entry, &will_use, &j->will_make[i]);
       napi_value buf;
       void *dst = NULL;
       /* Round 6: like process(), results of a few KB and more are pinned blocks of the library handed to JavaScript
@@ -1366,9 +1410,18 @@ static ManyJob *many_prepare(napi_env env, napi_callback_info info, napi_value *
 
 /* processMany(handles[], chunks[], inFrames[], outCapacities[]) -> Buffer[]: entry i is what
  * process(handles[i], chunks[i], inFrames[i], outCapacities[i]) returns. */
+static napi_value process_many_now(napi_env env, napi_callback_info info, int formatted);
 static napi_value ProcessMany(napi_env env, napi_callback_info info) {
+  return process_many_now(env, info, 0);
+}
+/* processManyFormat(handles[], chunks[], inFrames[], outCapacities[], inFmts[], outFmts[]) -> Buffer[]: entry i is what
+ * processFormat on handles[i] returns for its formats -- one fused library call (speexhip_resampler_process_many_fmt). */
+static napi_value ProcessManyFormat(napi_env env, napi_callback_info info) {
+  return process_many_now(env, info, 1);
+}
+static napi_value process_many_now(napi_env env, napi_callback_info info, int formatted) {
   napi_value result = NULL;
-  ManyJob *j = many_prepare(env, info, &result, 0);
+  ManyJob *j = many_prepare(env, info, &result, 0, formatted);
   if (j == NULL) return NULL;
   many_run(j); /* (locks held since many_prepare) */
   many_unlock(j);
@@ -1419,9 +1472,13 @@ static void many_complete(napi_env env, napi_status status, void *data) {
 /* processManyAsync(...) -> Promise<Buffer[]>: the same call on a libuv pool thread.  The results are sized on the
  * calling thread from the states' counters, so no state of the call may be used until the promise settles (index.js
  * keeps one call per instance in flight). */
-static napi_value ProcessManyAsync(napi_env env, napi_callback_info info) {
+static napi_value process_many_later(napi_env env, napi_callback_info info, int formatted);
+static napi_value ProcessManyAsync(napi_env env, napi_callback_info info) { return process_many_later(env, info, 0); }
+/* processManyFormatAsync(...) -> Promise<Buffer[]>: processManyFormat on a libuv pool thread, under the same rules */
+static napi_value ProcessManyFormatAsync(napi_env env, napi_callback_info info) { return process_many_later(env, info, 1); }
+static napi_value process_many_later(napi_env env, napi_callback_info info, int formatted) {
   napi_value result = NULL, promise, name;
-  ManyJob *j = many_prepare(env, info, &result, 1);
+  ManyJob *j = many_prepare(env, info, &result, 1, formatted);
   if (j == NULL) return NULL;
   if (napi_create_reference(env, result, 1, &j->result_ref) != napi_ok ||
       napi_create_promise(env, &j->deferred, &promise) != napi_ok ||
@@ -1563,6 +1620,8 @@ NAPI_MODULE_INIT() {
       {"releaseCachedMemory", NULL, ReleaseCachedMemory, NULL, NULL, NULL, napi_default, NULL},
       {"processMany", NULL, ProcessMany, NULL, NULL, NULL, napi_default, NULL},
       {"processManyAsync", NULL, ProcessManyAsync, NULL, NULL, NULL, napi_default, NULL},
+      {"processManyFormat", NULL, ProcessManyFormat, NULL, NULL, NULL, napi_default, NULL},
+      {"processManyFormatAsync", NULL, ProcessManyFormatAsync, NULL, NULL, NULL, napi_default, NULL},
       {"deviceCount", NULL, DeviceCount, NULL, NULL, NULL, napi_default, NULL},
       {"warmup", NULL, Warmup, NULL, NULL, NULL, napi_default, NULL},
       {"stats", NULL, Stats, NULL, NULL, NULL, napi_default, NULL},

@@ -115,6 +115,8 @@ EXPORTS = [
     "speexhip_debug_format_decode", "speexhip_debug_format_encode",
     # layouts: planar or interleaved per side of a formatted or mixed call
     "speexhip_resampler_process_sides", "speexhip_resampler_process_sides_device", "speexhip_batch_process_sides_device",
+    # many states, formatted: a format per state in one fused call
+    "speexhip_resampler_process_many_sides", "speexhip_resampler_process_many_fmt", "speexhip_debug_many_counters",
 ]
 
 # layout of a side of the sides calls (SPEEXHIP_LAYOUT_*)
@@ -392,6 +394,14 @@ def lib():
             L.speexhip_resampler_process_sides_device.argtypes = [p, ps, pu32, ps, pu32, p]
             L.speexhip_batch_process_sides_device.restype = i32
             L.speexhip_batch_process_sides_device.argtypes = [p, ps, pu32, ps, pu32, p]
+        if hasattr(L, "speexhip_resampler_process_many_sides") or "SPEEXHIP_LIB_PATH" not in os.environ:
+            ps, pp, pi = C.POINTER(Side), C.POINTER(C.c_void_p), C.POINTER(C.c_int)
+            L.speexhip_resampler_process_many_sides.restype = i32
+            L.speexhip_resampler_process_many_sides.argtypes = [u32, pp, ps, pu32, ps, pu32, pi]
+            L.speexhip_resampler_process_many_fmt.restype = i32
+            L.speexhip_resampler_process_many_fmt.argtypes = [u32, pp, pi, pp, pu32, pi, pp, pu32, pi]
+            L.speexhip_debug_many_counters.restype = None
+            L.speexhip_debug_many_counters.argtypes = [C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -571,6 +581,77 @@ def process_many(states, chunks, capacities, dtype=np.int16):
     if rc not in (0, ERR_ALLOC_FAILED):
         raise RuntimeError(strerror(rc))
     return [bufs[i][: ol[i]].copy() for i in range(n)], list(il), list(codes)
+
+
+def many_counters():
+    """speexhip_debug_many_counters: process-wide counts of the many-states calls since start, as a dict -- fir_launches,
+    in_passes, out_passes, own_calls (entries that took their own call)."""
+    v = (C.c_uint64 * 4)()
+    lib().speexhip_debug_many_counters(v)
+    return dict(zip(("fir_launches", "in_passes", "out_passes", "own_calls"), (int(x) for x in v)))
+
+
+def _per_state(v, n):
+    """one value for all states, or a sequence with one per state"""
+    return [int(v)] * n if isinstance(v, (int, np.integer)) else [int(f) for f in v]
+
+
+def many_fmt_call(states, in_fmts, in_ptrs, in_lens, out_fmts, out_ptrs, capacities):
+    """speexhip_resampler_process_many_fmt itself, on addresses (None = NULL; a state may be None too): returns
+    (rc, consumed, produced, codes)."""
+    n = len(states)
+    hs, ins, outs = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)()
+    fi, fo = (C.c_int * n)(*_per_state(in_fmts, n)), (C.c_int * n)(*_per_state(out_fmts, n))
+    il, ol, codes = (C.c_uint32 * n)(*in_lens), (C.c_uint32 * n)(*capacities), (C.c_int * n)()
+    for i in range(n):
+        hs[i] = None if states[i] is None else states[i]._h
+        ins[i], outs[i] = in_ptrs[i], out_ptrs[i]
+    rc = lib().speexhip_resampler_process_many_fmt(n, hs, fi, ins, il, fo, outs, ol, codes)
+    return rc, list(il), list(ol), list(codes)
+
+
+def process_many_fmt(states, chunks, in_fmts, out_fmts, capacities):
+    """speexhip_resampler_process_many_fmt: chunks[i] -- whole interleaved frames of in_fmts[i]'s storage type, or None
+    (silence) with capacities[i] = (null_frames, capacity) -- through states[i] into out_fmts[i], all in one fused call.
+    in_fmts / out_fmts: one FMT_* for all states or one per state.  Returns (outputs, consumed, codes); outputs[i] is flat,
+    of out_fmts[i]'s storage type (the packed 24-bit formats: three bytes per sample)."""
+    n = len(states)
+    fi, fo = _per_state(in_fmts, n), _per_state(out_fmts, n)
+    keep, bufs, ins, outs, il, ol = [], [], [], [], [], []
+    for i, (st, ch_) in enumerate(zip(states, chunks)):
+        if ch_ is None:
+            ins.append(None), il.append(int(capacities[i][0])), ol.append(int(capacities[i][1]))
+        else:
+            a = np.ascontiguousarray(ch_, dtype=fmt_dtype(fi[i])).reshape(-1)
+            frames = a.nbytes // (fmt_bytes(fi[i]) * st.channels)
+            if frames * fmt_bytes(fi[i]) * st.channels != a.nbytes:
+                raise ValueError("chunk %d: whole frames only" % i)
+            keep.append(a)
+            ins.append(a.ctypes.data), il.append(frames), ol.append(int(capacities[i]))
+        b = np.zeros(max(ol[i], 1) * st.channels * fmt_bytes(fo[i]), np.uint8)
+        bufs.append(b)
+        outs.append(b.ctypes.data)
+    rc, used, made, codes = many_fmt_call(states, fi, ins, il, fo, outs, ol)
+    if rc not in (0, ERR_ALLOC_FAILED):
+        raise RuntimeError(strerror(rc))
+    return ([bufs[i][: made[i] * states[i].channels * fmt_bytes(fo[i])].view(fmt_dtype(fo[i])).copy() for i in range(n)],
+            used, codes)
+
+
+def process_many_sides(states, in_sides, in_lens, out_sides, capacities):
+    """speexhip_resampler_process_many_sides: in_sides[i] / out_sides[i] = the Side structures (make_side, host buffers the
+    caller keeps alive) of states[i]'s entry, in_lens[i] / capacities[i] its frames.  Returns (rc, consumed, produced,
+    codes); the results lie in the callers' buffers."""
+    n = len(states)
+    hs = (C.c_void_p * n)()
+    a, b = (Side * n)(), (Side * n)()
+    for i in range(n):
+        hs[i] = None if states[i] is None else states[i]._h
+        C.memmove(C.byref(a[i]), C.byref(in_sides[i]), C.sizeof(Side))
+        C.memmove(C.byref(b[i]), C.byref(out_sides[i]), C.sizeof(Side))
+    il, ol, codes = (C.c_uint32 * n)(*in_lens), (C.c_uint32 * n)(*capacities), (C.c_int * n)()
+    rc = lib().speexhip_resampler_process_many_sides(n, hs, a, il, b, ol, codes)
+    return rc, list(il), list(ol), list(codes)
 
 
 class PinnedBlock:

@@ -17,7 +17,10 @@ set_rate that returns RESAMPLER_ERR_OVERFLOW in both (the one documented deviati
 With --batch every third trial drives 1-48 ragged streams of one configuration through the batched
 device-pointer call instead.
 
-usage: python tools/fuzz_gpu.py [--seconds 240] [--seed 1] [--max-frames 300000] [--batch]
+With --many-formats every trial drives 2-40 states through the formatted many-states call, formats drawn per state, and
+compares each entry with a twin state's own formatted call, byte for byte.
+
+usage: python tools/fuzz_gpu.py [--seconds 240] [--seed 1] [--max-frames 300000] [--batch | --many | --many-formats]
 Prints one line per failing trial (with the seed that reproduces it) and a summary; exit code 1 on
 any failure.
 """
@@ -409,6 +412,92 @@ def many_trial(seed, max_frames):
     return None, what
 
 
+ALL_FORMATS = (0, 1, 2, 3, 4, 5, 16, 17, 20, 21, 24, 25, 26)   # SPEEXHIP_FMT_*
+FLOAT_FORMATS = (4, 5, 20, 21)
+
+
+def format_bytes(rng, fmt, samples):
+    """`samples` samples of a format as raw bytes: any bytes for the integer and companded formats, finite values for the
+    float ones"""
+    if fmt not in FLOAT_FORMATS:
+        return rng.randint(0, 256, samples * speexhip.fmt_bytes(fmt)).astype(np.uint8)
+    v = (rng.standard_normal(samples) * 8000.0).astype(np.float32)
+    if fmt == 4:
+        return v.view(np.uint8).copy()
+    v = v / np.float32(32768.0)
+    if fmt == 5:
+        return v.view(np.uint8).copy()
+    if fmt == 20:
+        return v.astype(np.float16).view(np.uint8).copy()
+    return (v.view(np.uint32) >> 16).astype(np.uint16).view(np.uint8).copy()
+
+
+def many_formats_trial(seed, max_frames):
+    """2-40 single-stream states of 1-3 configurations through speexhip_resampler_process_many_fmt, a random pair of sample
+    formats per state and step, dither on for some states, 1-4 steps of ragged lengths and capacities, NULL inputs, now and
+    then a state named twice: every entry against a twin state fed the same bytes by its own formatted call -- bytes,
+    counters, codes, positions and dither positions identical (default mode and EXACT, mixed between the states)."""
+    rng = np.random.RandomState(seed)
+    kinds = []
+    for _ in range(int(rng.randint(1, 4))):
+        i, o = pick_rates(rng)
+        kinds.append((int(rng.choice([1, 2, 2, 3, 4, 8])), i, o, int(rng.randint(0, 11))))
+    S = int(rng.choice([2, 3, 7, 16, 33, 40]))
+    cfg = [kinds[int(rng.randint(0, len(kinds)))] for _ in range(S)]
+    # (the default mode and EXACT: the modes whose bytes do not depend on what shares a launch -- the opt-in FAST modes may
+    #  split an output's sum by the launch's shape, so their last bit differs between a fused and a separate call by design)
+    modes = [speexhip.MODE_EXACT if rng.rand() < 0.4 else None for _ in range(S)]
+    what = "seed=%d MANY-FORMATS S=%d kinds=%s" % (seed, S, kinds)
+    try:
+        states = [speexhip.Resampler(*c, mode=m) for c, m in zip(cfg, modes)]
+        twins = [speexhip.Resampler(*c, mode=m) for c, m in zip(cfg, modes)]
+    except ValueError:
+        return None, what + " (the library refuses)"
+    for s_ in range(S):
+        if rng.rand() < 0.3:
+            kind, dseed, pos = int(rng.randint(1, 3)), int(rng.randint(0, 2 ** 31)), int(rng.randint(0, 2 ** 31))
+            states[s_].set_dither(kind, dseed, pos)
+            twins[s_].set_dither(kind, dseed, pos)
+    fmax = max(16, min(max_frames, int(4e6 / (S * 2))))
+    for step in range(int(rng.randint(1, 5))):
+        order = list(range(S))
+        if rng.rand() < 0.2:
+            order.append(int(rng.randint(0, S)))   # a state twice in one call
+        fi = [int(rng.choice(ALL_FORMATS)) for _ in order]
+        fo = [int(rng.choice(ALL_FORMATS)) for _ in order]
+        chunks, caps = [], []
+        for j, s_ in enumerate(order):
+            ch, i, o, q = cfg[s_]
+            F = int(rng.randint(0, fmax + 1)) if rng.rand() < 0.7 else int(rng.choice([0, 1, 160, 480, 4096 // ch + 37]))
+            full = int(F * o / max(i, 1)) + 64
+            cap = full if rng.rand() < 0.8 else int(rng.randint(0, full + 1))
+            if rng.rand() < 0.05:
+                chunks.append(None)
+                caps.append((F, cap))
+            else:
+                chunks.append(format_bytes(rng, fi[j], F * ch).view(speexhip.fmt_dtype(fi[j])))
+                caps.append(cap)
+        outs, used, codes = speexhip.process_many_fmt([states[s_] for s_ in order], chunks, fi, fo, caps)
+        for j, s_ in enumerate(order):
+            tw = twins[s_]
+            if chunks[j] is None:
+                rc, wu, made, raw = tw.fmt_call(None, fi[j], fo[j], caps[j][1], null_frames=caps[j][0])
+            else:
+                rc, wu, made, raw = tw.fmt_call(chunks[j], fi[j], fo[j], caps[j])
+            want = raw[: made * tw.channels * (speexhip.fmt_bytes(fo[j]) // raw.dtype.itemsize)]
+            tag = "step %d entry %d state %d %s formats %d -> %d" % (step, j, s_, cfg[s_], fi[j], fo[j])
+            if codes[j] != rc or used[j] != wu or outs[j].nbytes != want.nbytes:
+                return "%s: code %d consumed %d, %d bytes; its own call %d, %d, %d" % (tag, codes[j], used[j], outs[j].nbytes, rc, wu, want.nbytes), what
+            if outs[j].tobytes() != want.tobytes():
+                return "%s: bytes differ" % tag, what
+        for s_ in range(S):
+            if states[s_].position() != twins[s_].position() or states[s_].get_dither() != twins[s_].get_dither():
+                return "step %d state %d: position or dither position differs from its twin's" % (step, s_), what
+    for st in states + twins:
+        st.close()
+    return None, what
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=240.0)
@@ -419,6 +508,8 @@ def main():
     ap.add_argument("--only-batch", action="store_true", help="with --only: the seed was a batch trial")
     ap.add_argument("--batch", action="store_true", help="every third trial: many streams through Batch.process_device")
     ap.add_argument("--many", action="store_true", help="every trial: many single-stream states through the many-states host call")
+    ap.add_argument("--many-formats", action="store_true",
+                    help="every trial: many states through the formatted many-states call, a format pair per state, against separate calls")
     args = ap.parse_args()
     orc.build()
     t0 = time.time()
@@ -427,7 +518,9 @@ def main():
     while time.time() - t0 < args.seconds:
         s = args.only if args.only is not None else seed + trials
         try:
-            if args.many:
+            if args.many_formats:
+                err, what = many_formats_trial(s, args.max_frames)
+            elif args.many:
                 err, what = many_trial(s, args.max_frames)
             elif (args.batch or args.only is not None) and (s % 3 == 0) and (args.batch or args.only_batch):
                 err, what = batch_trial(s, args.max_frames)
