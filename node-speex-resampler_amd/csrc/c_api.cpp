@@ -9,6 +9,7 @@
 #include "devices.h"
 #include "dither.h"
 #include "engine.h"
+#include "filter_plans.h"
 #include "g711.h"
 #include "halfbe.h"
 #include "pool.h"
@@ -263,32 +264,42 @@ int speexhip_resampler_get_channel_position(SpeexHipResamplerState *st, uint32_t
   return SPEEXHIP_ERR_SUCCESS;
 }
 
+// The three planner hooks: the plans plan_filter (filter_plans.h) gives a state of this ratio, quality and channel count,
+// which are the ones build_tables uploads rows for, and for _launch_shape the choice choose_launch makes among them.
+namespace {
+struct HookPlans {
+  speexhip::FilterSpec f, folded;
+  speexhip::FilterPlans plans;
+  int design(uint32_t ratio_num, uint32_t ratio_den, int quality, uint32_t channels) {
+    const int rc = speexhip::design_filter_frac(ratio_num, ratio_den, ratio_num, ratio_den, quality, &f, false);
+    if (rc == SPEEXHIP_ERR_SUCCESS) (void)speexhip::plan_filter(f, channels, speexhip::lds_budget(), &plans, &folded);
+    return rc;
+  }
+};
+// out[0..5] of a period plan as _plan and _plan64 report it
+void report_period(const speexhip::PeriodPlan &t, uint32_t code, uint32_t out[8]) {
+  out[0] = code;
+  out[1] = t.r;
+  out[2] = t.lane_periods;
+  out[3] = t.row_len;
+  out[4] = static_cast<uint32_t>(t.window_bytes);
+  out[5] = t.pad;
+}
+}  // namespace
+
 int speexhip_debug_plan(uint32_t ratio_num, uint32_t ratio_den, int quality, uint32_t channels, uint32_t out[8]) {
   if (out == nullptr || channels == 0) return SPEEXHIP_ERR_INVALID_ARG;
   return guarded([&] {
-    speexhip::FilterSpec f;
-    const int rc = speexhip::design_filter_frac(ratio_num, ratio_den, ratio_num, ratio_den, quality, &f, false);
+    HookPlans h;
+    const int rc = h.design(ratio_num, ratio_den, quality, channels);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
     std::memset(out, 0, 8 * sizeof(uint32_t));
-    // (round 6: small-denominator ratios outside the slide kernel's shapes plan the period kernel on a folded view)
-    speexhip::FilterSpec view;
-    const speexhip::FilterSpec &real = f;
-    const speexhip::FilterSpec &pf = speexhip::period_view(real, channels, &view) ? view : real;
-    const speexhip::PeriodPlan t = speexhip::plan_period(pf, channels, speexhip::lds_budget());
-    const speexhip::SlidePlan sl = speexhip::plan_slide(real, channels);
-    if (t.usable) {
-      out[0] = 2;
-      out[1] = t.r;
-      out[2] = t.lane_periods;
-      out[3] = t.row_len;
-      out[4] = static_cast<uint32_t>(t.window_bytes);
-      out[5] = t.pad;
-      if (t.r == 10) {
-        const speexhip::PeriodPlan fine = speexhip::plan_period_r(pf, channels, speexhip::lds_budget(), 5);
-        out[6] = fine.usable && fine.float_ok && fine.lane_periods == t.lane_periods;
-      }
-      const speexhip::PeriodPlan w16 = speexhip::plan_period_w16(pf, channels, speexhip::lds_budget(), t);
-      out[7] = w16.usable ? w16.lane_periods : 0;
+    const speexhip::PeriodPlan *p = h.plans.period;
+    const speexhip::SlidePlan &sl = h.plans.slide;
+    if (p[speexhip::kBase].usable) {
+      report_period(p[speexhip::kBase], 2, out);
+      out[6] = p[speexhip::kFine].usable;
+      out[7] = p[speexhip::kW16].usable ? p[speexhip::kW16].lane_periods : 0;
     } else if (sl.usable) {
       out[0] = 3;
       out[1] = sl.p;
@@ -303,96 +314,62 @@ int speexhip_debug_launch_shape(uint32_t ratio_num, uint32_t ratio_den, int qual
                                 uint32_t frames, int float_io, uint32_t out[10]) {
   if (out == nullptr || channels == 0 || streams == 0 || streams > 32) return SPEEXHIP_ERR_INVALID_ARG;
   return guarded([&]() -> int {
-    speexhip::FilterSpec f;
-    const int rc = speexhip::design_filter_frac(ratio_num, ratio_den, ratio_num, ratio_den, quality, &f, false);
+    HookPlans h;
+    const int rc = h.design(ratio_num, ratio_den, quality, channels);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
     std::memset(out, 0, 10 * sizeof(uint32_t));
-    if (f.kind == speexhip::kDirectDouble || f.kind == speexhip::kInterpolateDouble) return SPEEXHIP_ERR_SUCCESS;
-    // the plans a stream state holds (engine.cpp, build_tables) and the choice of launch_chunk among them, for a
-    // first call of `frames` frames on every stream (an r = 5 companion plan, where one exists, is not modelled)
-    const size_t lds = speexhip::lds_budget();
-    speexhip::FilterSpec view;
-    const speexhip::FilterSpec &pf = speexhip::period_view(f, channels, &view) ? view : f;
-    const speexhip::PeriodPlan base = speexhip::plan_period(pf, channels, lds);
+    // The launch of a first call of `frames` frames on every stream of a fresh state in a fast mode.  Where this models
+    // less than the engine it says so, one line each ("The planner hooks"):
+    const speexhip::FilterSpec &f = h.f;
+    if (speexhip::is_double_kind(f)) return SPEEXHIP_ERR_SUCCESS;  // (the double kinds are not modelled: zeros)
+    const speexhip::PeriodPlan &base = h.plans.period[speexhip::kBase];
     if (!base.usable) return SPEEXHIP_ERR_SUCCESS;
-    if (float_io != 0 && !base.float_ok) return SPEEXHIP_ERR_SUCCESS;  // (a plan that stands for its int16 plan alone: float calls run the exact kernel)
-    const speexhip::PeriodPlan w16 = speexhip::plan_period_w16(pf, channels, lds, base);
-    speexhip::PeriodPlan pp, pp_w16;
-    if (speexhip::period_wants_pp_plans(pf, channels)) {
-      pp = speexhip::plan_period(pf, channels, lds, false, false, true);
-      pp_w16 = speexhip::plan_period_w16(pf, channels, lds, pp);
-    }
+    if (float_io != 0 && !base.float_ok) return SPEEXHIP_ERR_SUCCESS;  // (a plan that stands for its int16 plan alone: float calls run the exact kernel; zeros)
+    h.plans.period[speexhip::kFine].usable = false;  // (an r = 5 companion is not modelled: the rule sees has_fine = false and the shape is the chosen plan's alone)
     std::vector<speexhip::StreamDesc> descs(streams);
     for (auto &d : descs) {
       std::memset(&d, 0, sizeof(d));
       d.in_frames = frames;
       d.n_out = static_cast<uint32_t>(static_cast<uint64_t>(frames) * f.den / f.num);
     }
-    const bool i16 = !float_io;
-    const speexhip::PeriodPlan &two = (i16 && w16.usable) ? w16 : base;
-    const speexhip::PeriodPlan &pairs = (i16 && pp_w16.usable) ? pp_w16 : pp;
-    const speexhip::PeriodPlan *t = &base;
-    if (pp.usable && speexhip::period_launch_prefers_pp(f, two, pairs, descs.data(), streams)) {
-      t = &pairs;
-      out[0] = 1;
-    } else if (i16 && w16.usable && speexhip::period_launch_prefers_w16(f, base, false, descs.data(), streams)) {
-      t = &w16;
-    }
-    out[1] = t->r;
-    out[2] = t->w16 ? 1u : 0u;
-    out[3] = t->lane_periods;
-    if (!speexhip::debug_period_shape(f, *t, channels, descs.data(), streams, float_io != 0, out + 4)) return SPEEXHIP_ERR_BAD_STATE;
+    const speexhip::LaunchChoice c =
+        speexhip::choose_launch(h.plans, f, SPEEXHIP_MODE_FAST_FIXED, /*zero_mode=*/false, float_io != 0, /*float_seen=*/false,
+                                /*w16_override=*/-1, descs.data(), streams);  // (no float call before, no W16 override)
+    if (c.family != speexhip::KernelFamily::Period) return SPEEXHIP_ERR_SUCCESS;  // (cannot happen in the product build: a usable base plan serves every launch asked about here)
+    const speexhip::PeriodPlan &t = h.plans.period[c.variant];
+    out[0] = t.pp ? 1u : 0u;
+    out[1] = t.r;
+    out[2] = t.w16 ? 1u : 0u;
+    out[3] = t.lane_periods;
+    if (!speexhip::debug_period_shape(f, t, channels, descs.data(), streams, float_io != 0, out + 4)) return SPEEXHIP_ERR_BAD_STATE;
     return SPEEXHIP_ERR_SUCCESS;
   });
 }
 int speexhip_debug_plan64(uint32_t ratio_num, uint32_t ratio_den, int quality, uint32_t channels, uint32_t out[8]) {
   if (out == nullptr || channels == 0) return SPEEXHIP_ERR_INVALID_ARG;
   return guarded([&] {
-    speexhip::FilterSpec f;
-    const int rc = speexhip::design_filter_frac(ratio_num, ratio_den, ratio_num, ratio_den, quality, &f, false);
+    HookPlans h;
+    const int rc = h.design(ratio_num, ratio_den, quality, channels);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
     std::memset(out, 0, 8 * sizeof(uint32_t));
-    const bool double_kind = f.kind == speexhip::kDirectDouble || f.kind == speexhip::kInterpolateDouble;
-    speexhip::FilterSpec view;
-    const speexhip::FilterSpec &pf = speexhip::period_view(f, channels, &view) ? view : f;
-    const speexhip::PeriodPlan base = speexhip::plan_period(pf, channels, speexhip::lds_budget());
-    if (double_kind && base.usable) {
-      const speexhip::PeriodPlan t = speexhip::plan_period(pf, channels, speexhip::lds_budget(), false, true);
-      if (t.usable) {
-        out[0] = 5;
-        out[1] = t.r;
-        out[2] = t.lane_periods;
-        out[3] = t.row_len;
-        out[4] = static_cast<uint32_t>(t.window_bytes);
-        out[5] = t.pad;
-        out[6] = t.l4;
-        const speexhip::PeriodPlan w16 = speexhip::plan_period_w16(pf, channels, speexhip::lds_budget(), t);  // (round 5)
-        out[7] = w16.usable ? w16.lane_periods : 0;
-      }
-    } else if (double_kind && speexhip::plan_slide(f, channels).usable) {
-      const speexhip::SlidePlan sl = speexhip::plan_slide64(f, channels);
-      if (sl.usable) {
-        out[0] = 4;
-        out[1] = sl.p;
-        out[3] = sl.row_len;
-        out[4] = static_cast<uint32_t>(speexhip::slide_lds_bytes(sl, 2) * (sl.p * f.den >= 4 ? 2 : 1));  // (image in doubles)
-        out[5] = sl.row_stride;
-        out[7] = sl.p * sl.num;
-      }
+    const speexhip::PeriodPlan *p = h.plans.period;
+    const speexhip::SlidePlan &sl = h.plans.slide64;
+    if (p[speexhip::kPeriod64].usable) {
+      report_period(p[speexhip::kPeriod64], 5, out);
+      out[6] = p[speexhip::kPeriod64].l4;
+      out[7] = p[speexhip::kPeriod64W16].usable ? p[speexhip::kPeriod64W16].lane_periods : 0;  // (round 5)
+    } else if (sl.usable) {
+      out[0] = 4;
+      out[1] = sl.p;
+      out[3] = sl.row_len;
+      out[4] = static_cast<uint32_t>(speexhip::slide_lds_bytes(sl, 2) * (sl.p * h.f.den >= 4 ? 2 : 1));  // (image in doubles)
+      out[5] = sl.row_stride;
+      out[7] = sl.p * sl.num;
     }
-    // phase-pair plans of mono filters with wide windows (any quality below 9)
-    if (!double_kind && base.usable && speexhip::period_wants_pp_plans(pf, channels)) {
-      const speexhip::PeriodPlan t = speexhip::plan_period(pf, channels, speexhip::lds_budget(), false, false, true);
-      if (t.usable) {
-        out[0] = 6;
-        out[1] = t.r;
-        out[2] = t.lane_periods;
-        out[3] = t.row_len;
-        out[4] = static_cast<uint32_t>(t.window_bytes);
-        out[5] = t.pad;
-        const speexhip::PeriodPlan w16 = speexhip::plan_period_w16(pf, channels, speexhip::lds_budget(), t);
-        out[7] = w16.usable ? w16.lane_periods : 0;
-      }
+    // phase-pair plans of filters of up to three channels with wide windows (reported for any quality below 9)
+    if (!speexhip::is_double_kind(h.f) && p[speexhip::kPp].usable) {
+      report_period(p[speexhip::kPp], 6, out);
+      out[7] = p[speexhip::kPpW16].usable ? p[speexhip::kPpW16].lane_periods : 0;
     }
     return static_cast<int>(SPEEXHIP_ERR_SUCCESS);
   });

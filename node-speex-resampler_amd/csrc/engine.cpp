@@ -21,11 +21,8 @@
 #include <tuple>
 
 namespace speexhip {
-namespace {
-thread_local std::string g_last_error = "no HIP error recorded";
-}  // namespace
-
 namespace detail {
+thread_local std::string g_last_error = "no HIP error recorded";
 bool hip_failed(hipError_t e, const char *what) {
   if (e == hipSuccess) return false;
   g_last_error = std::string("HIP device error: ") + what + ": " + hipGetErrorString(e);
@@ -109,6 +106,7 @@ static_assert(kStagedLdsBytes <= kLdsBudget, "the period kernel's staged-store i
 // channels (16.8 MB in), four pieces: 0.617 -> 0.517 ms.
 const size_t kPieceBytes = static_cast<size_t>(2) << 20;
 
+}  // namespace
 // Round 6 -- pinned host buffers are used in place.  Where the kernels reach a HOST buffer directly: the address the
 // device sees when all of [p, p + bytes) is pinned memory -- a block of the library's slabs (speexhip_block_acquire, a
 // result block of ..._take: a range check, no runtime call), or, for buffers of kDirectCopyBytes and more, memory the
@@ -116,7 +114,7 @@ const size_t kPieceBytes = static_cast<size_t>(2) << 20;
 // Such a buffer needs no staging: the kernel that reads it through PCIe can write its result block through PCIe at the
 // same time (the link is full duplex), where copy -> launch -> copy takes the two crossings one after the other; for the
 // Node wrapper this replaces the copy into the module's heap, src/index.ts:71-92.
-void *pinned_view(const void *p, size_t bytes) {
+void *detail::pinned_view(const void *p, size_t bytes) {
   if (p == nullptr || bytes == 0) return nullptr;
   if (pool::block_owns(p, bytes)) return const_cast<void *>(p);
   if (bytes < kDirectCopyBytes) return nullptr;
@@ -133,6 +131,7 @@ void *pinned_view(const void *p, size_t bytes) {
   char *last = device_side(static_cast<const char *>(p) + bytes - 1);
   return last != nullptr && static_cast<size_t>(last - first) == bytes - 1 ? first : nullptr;
 }
+namespace {
 
 // The polled wait of a host-buffer call (host_transfer.h, Wait): a 32-bit stream write behind the kernel
 // (hipStreamWriteValue32: performed once everything before it on the stream has completed) into pinned memory, polled by
@@ -156,7 +155,6 @@ int wait_done(hipStream_t stream, volatile uint32_t *word, uint32_t seq, uint32_
   return SPEEXHIP_ERR_SUCCESS;
 }
 }  // namespace
-void *detail::pinned_view_of(const void *p, size_t bytes) { return pinned_view(p, bytes); }
 // The wait `w` chose.  A polled one arms the completion word at `word` -- 64 bytes of pinned memory the call's kernels do
 // not write: the tail of a pinned result buffer (tail_word) or the bytes behind the samples of a take block -- with a
 // value other than `seq` and waits for the stream to write `seq` there.
@@ -206,6 +204,16 @@ void set_position(StreamDesc &d, const FilterSpec &f, const StreamPos &at, uint3
 }
 }  // namespace
 
+void Batch::fill_desc(StreamDesc &d, uint32_t s, uint32_t c, const void *in, void *out, uint32_t in_frames, const CallPlan &plan) const {
+  d.in = in;
+  d.hist = d_hist_[hist_cur_] + s * hist_elems_ + c;
+  d.out = out;
+  d.hist_next = d_hist_[hist_cur_ ^ 1] + s * hist_elems_ + c;
+  d.in_frames = in_frames;
+  set_position(d, filter_, plan.begin, plan.produced, plan.magic_used + plan.consumed, filter_.taps - 1 + plan.begin.magic,
+               filter_.taps - 1 + plan.end.magic);
+}
+
 // SPEEXHIP_INIT_TRACE=1: where a state's creation goes, step by step (stderr; tools/first_call.py)
 struct InitTrace {
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
@@ -234,8 +242,6 @@ static int w16_env() {
   }();
   return v;
 }
-static bool w16_always() { return w16_env() == 1; }
-static bool w16_never() { return w16_env() == 0; }
 void debug_fail_device_allocs(int n) { g_fail_allocs.store(n < 0 ? 0 : n); }
 
 bool Batch::uniform(uint32_t s) const {
@@ -338,16 +344,9 @@ int Batch::setup() {
 DeviceTables::~DeviceTables() {
   // (whoever dropped the last reference has synchronised: ~Batch, install_filter)
   pool::device_put(device, table);
-  pool::device_put(device, period_rows);
-  pool::device_put(device, fine_rows);
-  pool::device_put(device, w16_rows);
+  for (void *rows : period_rows) pool::device_put(device, rows);
   pool::device_put(device, slide_rows);
   pool::device_put(device, slide64_rows);
-  pool::device_put(device, pp_rows);
-  pool::device_put(device, pp_w16_rows);
-  pool::device_put(device, period64_rows);
-  pool::device_put(device, fine64_rows);
-  pool::device_put(device, period64_w16_rows);
 }
 
 namespace {
@@ -400,103 +399,35 @@ int build_tables(int device, const FilterSpec &g, uint32_t channels, hipStream_t
   rc = upload(&t->table, f.table.data(), f.table_len);
   trace.step("    first allocation + upload (sinc table)");
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  t->geo = exact_geometry(f, channels, kLdsBudget);
-  t->geo_ch = exact_geometry(f, 1, kLdsBudget);
-  // (ratios with den <= 6 outside the slide kernel's shapes -- 7:6, 11:1, 16:3 ... -- plan the period kernel on a folded
-  //  view of the filter, 35:30, 110:10, 80:15: kernels.h, period_view; `pf` is what every period plan below is made on)
+  // which plans the filter gets: filter_plans.h.  Their rows go up in the order of PeriodVariant, the slide rows between
+  // the fp32 and the fp64 variants (the allocation-failure hook counts allocations).
+  FilterPlans &plans = t->plans;
   FilterSpec folded;
-  const bool use_fold = period_view(f, channels, &folded);
-  const FilterSpec &pf = use_fold ? folded : f;
-  t->period = plan_period(pf, channels, kLdsBudget);
-  if (t->period.usable && t->period.float_ok) {
-    std::vector<float> rows;
-    build_period_rows(pf, t->period, &rows);
-    rc = upload(&t->period_rows, rows.data(), rows.size());
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  }
-  if (t->period.usable && t->period.float_ok && t->period.r == 10) {
-    static const bool no_fine = SPEEXHIP_DIAG_ENV("SPEEXHIP_NO_FINE") != nullptr;  // diagnostics: A/B
-    t->fine = plan_period_r(pf, channels, kLdsBudget, 5);
-    // (... and a float window of its own: an R = 5 plan that only stands for its int16 plan -- 100 channels of 320:147, one
-    //  period per tile either way -- has nothing to launch; found by the fuzzer the day the layouts without an ISA loop
-    //  got int16 plans, seed 611002591)
-    if (no_fine || !t->fine.float_ok || t->fine.lane_periods != t->period.lane_periods) t->fine.usable = false;
-    if (t->fine.usable) {
+  const FilterSpec &pf = plan_filter(f, channels, kLdsBudget, &plans, &folded);
+  for (int v = 0; v < kPeriodVariants; v++) {
+    if (v == kPeriod64 && plans.slide.usable) {
       std::vector<float> rows;
-      build_period_rows(pf, t->fine, &rows);
-      rc = upload(&t->fine_rows, rows.data(), rows.size());
+      build_slide_rows(f, plans.slide, &rows);
+      rc = upload(&t->slide_rows, rows.data(), rows.size());
       if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
     }
-  }
-  t->w16 = plan_period_w16(pf, channels, kLdsBudget, t->period);
-  if (t->w16.usable) {
-    std::vector<float> rows;
-    build_period_rows(pf, t->w16, &rows);
-    rc = upload(&t->w16_rows, rows.data(), rows.size());
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  }
-  if (t->period.usable && period_wants_pp_plans(pf, channels)) {
-    t->pp = plan_period(pf, channels, kLdsBudget, false, false, true);
-    if (t->pp.usable) {
-      std::vector<float> rows;
-      build_period_rows(pf, t->pp, &rows);
-      rc = upload(&t->pp_rows, rows.data(), rows.size());
-      if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-      t->pp_w16 = plan_period_w16(pf, channels, kLdsBudget, t->pp);
-      if (t->pp_w16.usable) {
-        build_period_rows(pf, t->pp_w16, &rows);
-        rc = upload(&t->pp_w16_rows, rows.data(), rows.size());
-        if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-      }
-    }
-  }
-  t->slide = plan_slide(f, channels);
-  if (t->slide.usable && !t->period.usable) {
-    std::vector<float> rows;
-    build_slide_rows(f, t->slide, &rows);
-    rc = upload(&t->slide_rows, rows.data(), rows.size());
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  } else {
-    t->slide.usable = false;
-  }
-  // the reference's double kinds (quality 9, 10): fp64-accumulate twins of the fast kernels
-  if (f.kind == kDirectDouble || f.kind == kInterpolateDouble) {
-    if (t->period.usable) {
-      t->period64 = plan_period(pf, channels, kLdsBudget, false, true);
-      if (t->period64.usable) {
-        std::vector<double> rows;
-        build_period_rows64(pf, t->period64, &rows);
-        rc = upload_bytes(reinterpret_cast<void **>(&t->period64_rows), rows.data(), rows.size() * sizeof(double));
-        if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-      }
-      if (t->period64.usable && t->period64.r == 10) {
-        static const bool no_fine64 = SPEEXHIP_DIAG_ENV("SPEEXHIP_NO_FINE") != nullptr;  // diagnostics: A/B
-        t->fine64 = plan_period_r(pf, channels, kLdsBudget, 5, false, true);
-        if (no_fine64 || t->fine64.lane_periods != t->period64.lane_periods) t->fine64.usable = false;
-        if (t->fine64.usable) {
-          std::vector<double> rows;
-          build_period_rows64(pf, t->fine64, &rows);
-          rc = upload_bytes(reinterpret_cast<void **>(&t->fine64_rows), rows.data(), rows.size() * sizeof(double));
-          if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-        }
-      }
-    }
-    if (t->period64.usable) {
-      t->period64_w16 = plan_period_w16(pf, channels, kLdsBudget, t->period64);
-      if (t->period64_w16.usable) {
-        std::vector<double> rows;
-        build_period_rows64(pf, t->period64_w16, &rows);
-        rc = upload_bytes(reinterpret_cast<void **>(&t->period64_w16_rows), rows.data(), rows.size() * sizeof(double));
-        if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-      }
-    }
-    if (t->slide.usable) t->slide64 = plan_slide64(f, channels);
-    if (t->slide64.usable) {
+    if (!plans.has_rows(v)) continue;
+    if (plans.period[v].a64) {
       std::vector<double> rows;
-      build_slide64_rows(f, t->slide64, &rows);
-      rc = upload_bytes(reinterpret_cast<void **>(&t->slide64_rows), rows.data(), rows.size() * sizeof(double));
-      if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+      build_period_rows64(pf, plans.period[v], &rows);
+      rc = upload_bytes(&t->period_rows[v], rows.data(), rows.size() * sizeof(double));
+    } else {
+      std::vector<float> rows;
+      build_period_rows(pf, plans.period[v], &rows);
+      rc = upload_bytes(&t->period_rows[v], rows.data(), rows.size() * sizeof(float));
     }
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  }
+  if (plans.slide64.usable) {
+    std::vector<double> rows;
+    build_slide64_rows(f, plans.slide64, &rows);
+    rc = upload_bytes(reinterpret_cast<void **>(&t->slide64_rows), rows.data(), rows.size() * sizeof(double));
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
   trace.step("    plans, tap rows, their uploads");
   *out = t;
@@ -616,35 +547,12 @@ int Batch::install_filter(const FilterSpec &f, const std::vector<float> &hist, u
   std::swap(d_hist_[0], n.hist[0]);
   std::swap(d_hist_[1], n.hist[1]);  // (~Fresh releases the old history buffers)
   tables_ = tables;
-  d_table_ = tables->table;
-  d_period_rows_ = tables->period_rows;
-  d_period_fine_rows_ = tables->fine_rows;
-  d_period_w16_rows_ = tables->w16_rows;
-  d_slide_rows_ = tables->slide_rows;
-  d_slide64_rows_ = tables->slide64_rows;
-  d_period64_rows_ = tables->period64_rows;
-  d_period_pp_rows_ = tables->pp_rows;
-  d_period_pp_w16_rows_ = tables->pp_w16_rows;
-  d_period64_fine_rows_ = tables->fine64_rows;
-  d_period64_w16_rows_ = tables->period64_w16_rows;
   const std::vector<float> no_table;
   filter_ = f;
   filter_.table = no_table;  // the host copy of the sinc table lives only while the tables are built
   line_ = std::max(line_, f.taps - 1 + kBlockIn);  // grow-only, resample.c:709-720
   hist_elems_ = hist_elems;
   hist_cur_ = 0;
-  exact_geo_ = tables->geo;
-  exact_geo_ch_ = tables->geo_ch;
-  period_ = tables->period;
-  period_fine_ = tables->fine;
-  period_w16_ = tables->w16;
-  slide_ = tables->slide;
-  slide64_ = tables->slide64;
-  period64_ = tables->period64;
-  period_pp_ = tables->pp;
-  period_pp_w16_ = tables->pp_w16;
-  period64_fine_ = tables->fine64;
-  period64_w16_ = tables->period64_w16;
   return SPEEXHIP_ERR_SUCCESS;
 }
 
@@ -904,11 +812,12 @@ void Batch::info(uint32_t s, SpeexHipInfo *o) const {
   o->sinc_table_length = filter_.table_len;
   o->kernel = filter_.kind;
   o->mode = mode_;
-  o->fast_path = period_.usable ? 2 : (slide_.usable ? 3 : 0);
-  const bool double_kind = filter_.kind == kDirectDouble || filter_.kind == kInterpolateDouble;
+  const FilterPlans &p = tables_->plans;
+  o->fast_path = p.period[kBase].usable ? 2 : (p.slide.usable ? 3 : 0);
+  const bool double_kind = is_double_kind(filter_);
   // (what FAST would run: in EXACT mode too; FAST_F32 reports its own fp32-chain kernels)
-  if (double_kind && mode_ != SPEEXHIP_MODE_FAST_F32 && !period_.usable && slide64_.usable) o->fast_path = 4;
-  if (double_kind && mode_ != SPEEXHIP_MODE_FAST_F32 && period64_.usable) o->fast_path = 5;
+  if (double_kind && mode_ != SPEEXHIP_MODE_FAST_F32 && !p.period[kBase].usable && p.slide64.usable) o->fast_path = 4;
+  if (double_kind && mode_ != SPEEXHIP_MODE_FAST_F32 && p.period[kPeriod64].usable) o->fast_path = 5;
   o->accumulate_bits = mode_ == SPEEXHIP_MODE_EXACT || o->fast_path == 0 ? (double_kind ? 64 : 32)
                                                                           : (o->fast_path >= 4 ? 64 : 32);
   if (s < n_streams_) {
@@ -977,21 +886,16 @@ int Batch::run_channel(uint32_t c, const void *d_in, uint32_t in_stride, uint32_
   DescPack pack;
   std::memset(&pack, 0, sizeof(pack));
   StreamDesc &d = pack.d[0];
-  d.in = d_in;
-  d.hist = d_hist_[hist_cur_] + c;
-  d.out = d_out;
-  d.hist_next = d_hist_[hist_cur_ ^ 1] + c;
-  d.in_frames = in_frames;
   // (launch_exact and its kernel read none of k_shift, base_shift, tile_begin, m_total)
-  set_position(d, filter_, plan.begin, plan.produced, walked, filter_.taps - 1 + plan.begin.magic, filter_.taps - 1 + plan.end.magic);
+  fill_desc(d, 0, c, d_in, d_out, in_frames, plan);
   const ExactStrides strides = {in_stride, out_stride, channels_};
-  ExactGeometry geo = exact_geo_ch_;
+  ExactGeometry geo = tables_->plans.geo_ch;
   if (zero_mode_) {  // the window geometry belongs to the filter that is no longer in force
     geo.staged = false;
     geo.lds_bytes = 0;
     geo.outs_per_block = 256;
   }
-  const hipError_t e = launch_exact(filter_, geo, d_table_, 1, &pack, 1, plan.produced, float_io, stream, &strides, zero_mode_);
+  const hipError_t e = launch_exact(filter_, geo, tables_->table, 1, &pack, 1, plan.produced, float_io, stream, &strides, zero_mode_);
   if (hip_failed(e, "kernel launch")) return SPEEXHIP_ERR_DEVICE;
   if (d.hist_keep != 0)
     HIP_TRY(hipMemcpy2DAsync(d_hist_[hist_cur_] + c, channels_ * sizeof(float), d_hist_[hist_cur_ ^ 1] + c,
@@ -1028,50 +932,40 @@ int Batch::process_split(const void *d_in, uint32_t *in_len, void *d_out, uint32
   return zero_mode_ ? SPEEXHIP_ERR_ALLOC_FAILED : SPEEXHIP_ERR_SUCCESS;
 }
 
-// The kernel for one launch of up to 32 stream descriptors (`descs` = pack.d): what the mode, the filter's plans and
-// the launch's size select.
+// One launch of up to 32 stream descriptors (`descs` = pack.d): the kernel choose_launch (filter_plans.h) selects for the
+// mode, the filter's plans and the launch's size.
 int Batch::launch_chunk(const StreamDesc *descs, const DescPack &pack, uint32_t n, uint32_t max_out, bool float_io,
                         hipStream_t stream) {
-  hipError_t e;
-  const bool fast = mode_ != SPEEXHIP_MODE_EXACT;
+  const DeviceTables &t = *tables_;
+  const FilterPlans &p = t.plans;
+  const LaunchChoice c = choose_launch(p, filter_, mode_, zero_mode_, float_io, float_seen_, w16_env(), descs, n);
   const bool fixed = mode_ == SPEEXHIP_MODE_FAST_FIXED;  // (kernels.h: no tap-range shares -- an output's bits depend on the stream alone)
-  if (zero_mode_) {
-    ExactGeometry geo = exact_geo_;  // (its window geometry belongs to the filter no longer in force)
-    geo.staged = false;
-    geo.lds_bytes = 0;
-    geo.outs_per_block = 256;
-    e = launch_exact(filter_, geo, d_table_, channels_, &pack, n, max_out, float_io, stream, nullptr, true);
-  } else if (fast && acc64() && period64_.usable && !float_io && !float_seen_ && period64_w16_.usable && !w16_never() &&
-             (w16_always() || period_launch_prefers_w16(filter_, period64_, period64_fine_.usable, descs, n))) {
-    // ... over an int16 LDS window where the float window holds a fraction of a tile (wide windows; round 5)
-    e = launch_period(filter_, period64_w16_, reinterpret_cast<const float *>(d_period64_w16_rows_), nullptr, nullptr, channels_,
-                      descs, &pack, n, false, stream, fixed);
-  } else if (fast && acc64() && period64_.usable) {
-    // the reference sums these filters in fp64 (resample.c:389-435, :501-558): v_fma_f64 kernels
-    e = launch_period(filter_, period64_, reinterpret_cast<const float *>(d_period64_rows_), &period64_fine_,
-                      reinterpret_cast<const float *>(d_period64_fine_rows_), channels_, descs, &pack, n, float_io, stream, fixed);
-  } else if (fast && acc64() && !period_.usable && slide64_.usable) {
-    e = launch_slide64(filter_, slide64_, d_slide64_rows_, channels_, descs, &pack, n, float_io, stream, fixed);
-  } else if (fast && period_pp_.usable &&
-             period_launch_prefers_pp(filter_, (!float_io && !float_seen_ && period_w16_.usable) ? period_w16_ : period_,
-                                      (!float_io && !float_seen_ && period_pp_w16_.usable) ? period_pp_w16_ : period_pp_, descs, n)) {
-    // up to three channels, wide windows: phase pairs (lane = (period, channel), half the window per tile) where this
-    // launch gains
-    const bool w16 = !float_io && !float_seen_ && period_pp_w16_.usable;
-    e = launch_period(filter_, w16 ? period_pp_w16_ : period_pp_, w16 ? d_period_pp_w16_rows_ : d_period_pp_rows_, nullptr,
-                      nullptr, channels_, descs, &pack, n, float_io, stream, fixed);
-  } else if (fast && period_.usable && !float_io && !float_seen_ && period_w16_.usable &&
-             (w16_always() || period_launch_prefers_w16(filter_, period_, period_fine_.usable, descs, n))) {
-    // wide windows: twice the periods per tile over an int16 LDS image (the histories hold PCM values) -- unless
-    // the launch is too small for that to pay (period_launch_prefers_w16)
-    e = launch_period(filter_, period_w16_, d_period_w16_rows_, nullptr, nullptr, channels_, descs, &pack, n, false, stream, fixed);
-  } else if (fast && period_.usable && period_.float_ok) {
-    e = launch_period(filter_, period_, d_period_rows_, &period_fine_, d_period_fine_rows_, channels_, descs, &pack, n,
-                      float_io, stream, fixed);
-  } else if (fast && slide_.usable) {
-    e = launch_slide(filter_, slide_, d_slide_rows_, channels_, descs, &pack, n, float_io, stream, fixed);
-  } else {
-    e = launch_exact(filter_, exact_geo_, d_table_, channels_, &pack, n, max_out, float_io, stream);
+  hipError_t e = hipSuccess;
+  switch (c.family) {
+    case KernelFamily::Zero: {
+      ExactGeometry geo = p.geo;  // (its window geometry belongs to the filter no longer in force)
+      geo.staged = false;
+      geo.lds_bytes = 0;
+      geo.outs_per_block = 256;
+      e = launch_exact(filter_, geo, t.table, channels_, &pack, n, max_out, float_io, stream, nullptr, true);
+      break;
+    }
+    case KernelFamily::Exact:
+      e = launch_exact(filter_, p.geo, t.table, channels_, &pack, n, max_out, float_io, stream);
+      break;
+    case KernelFamily::Period:
+      // (the rows of the fp64 variants are doubles behind the same pointer type)
+      e = launch_period(filter_, p.period[c.variant], static_cast<const float *>(t.period_rows[c.variant]),
+                        c.with_fine ? &p.period[c.fine] : nullptr,
+                        c.with_fine ? static_cast<const float *>(t.period_rows[c.fine]) : nullptr, channels_, descs, &pack, n,
+                        c.float_io, stream, fixed);
+      break;
+    case KernelFamily::Slide:
+      e = launch_slide(filter_, p.slide, t.slide_rows, channels_, descs, &pack, n, float_io, stream, fixed);
+      break;
+    case KernelFamily::Slide64:
+      e = launch_slide64(filter_, p.slide64, t.slide64_rows, channels_, descs, &pack, n, float_io, stream, fixed);
+      break;
   }
   if (hip_failed(e, "kernel launch")) return SPEEXHIP_ERR_DEVICE;
   return SPEEXHIP_ERR_SUCCESS;
@@ -1102,13 +996,8 @@ int Batch::run_plans(const void *d_in, uint64_t in_stride, const uint32_t *in_fr
       const uint32_t s = s0 + j;
       const CallPlan &plan = plans[s];
       StreamDesc &d = descs[j];
-      d.in = d_in ? static_cast<const char *>(d_in) + s * in_stride * es : nullptr;
-      d.hist = d_hist_[hist_cur_] + s * hist_elems_;
-      d.out = static_cast<char *>(d_out) + s * out_stride * es;
-      d.hist_next = d_hist_[hist_cur_ ^ 1] + s * hist_elems_;
-      d.in_frames = in_frames[s];
-      set_position(d, filter_, plan.begin, plan.produced, plan.magic_used + plan.consumed, filter_.taps - 1 + plan.begin.magic,
-                   filter_.taps - 1 + plan.end.magic);
+      fill_desc(d, s, 0, d_in ? static_cast<const char *>(d_in) + s * in_stride * es : nullptr,
+                static_cast<char *>(d_out) + s * out_stride * es, in_frames[s], plan);
       max_out = std::max(max_out, plan.produced);
       any_work = any_work || plan.produced != 0 || d.consumed != 0;
     }
@@ -1233,9 +1122,13 @@ int Batch::take_in_pieces(const void *in, uint32_t *in_len, uint32_t *out_len, b
   // whole ROW lies inside the frames copied so far: the bound moves back by the longest row any plan of this filter
   // may run (+ one loop iteration of prefetch).
   uint32_t guard = 0;
-  for (const PeriodPlan *t : {&period_, &period_fine_, &period_w16_, &period_pp_, &period_pp_w16_, &period64_, &period64_fine_})
-    if (t->usable && t->row_len > filter_.taps) guard = std::max(guard, t->row_len - filter_.taps);
-  for (const SlidePlan *t : {&slide_, &slide64_})
+  // (kPeriod64W16 has never counted here, and need not: its launches read int16 samples, which hold no NaN.  Left out so
+  //  that the pieces of a call end where they always did.)
+  for (int v = 0; v < kPeriodVariants; v++) {
+    const PeriodPlan &t = tables_->plans.period[v];
+    if (v != kPeriod64W16 && t.usable && t.row_len > filter_.taps) guard = std::max(guard, t.row_len - filter_.taps);
+  }
+  for (const SlidePlan *t : {&tables_->plans.slide, &tables_->plans.slide64})
     if (t->usable && t->row_len > filter_.taps) guard = std::max(guard, t->row_len - filter_.taps + t->p * t->num);
   guard += 16;
   uint32_t done_out = 0;
@@ -1626,571 +1519,6 @@ int warmup(int device) {
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
   return SPEEXHIP_ERR_SUCCESS;
-}
-
-// ---- host-buffer calls of many single-stream states at once (engine.h) ---------------------------------------------
-namespace {
-// Staging of the many-states call: one per logical device, grow-only, taken from the pool and kept for the life of the
-// process like the shared streams.  A call holds the lock of every device it touches from its first copy to its last.
-struct ManyStage {
-  std::mutex mu;
-  hipStream_t stream = nullptr, copy_stream = nullptr;  // (copy_stream + events: the pipelined large path)
-  std::vector<hipEvent_t> events;
-  char *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
-  size_t d_in_cap = 0, d_out_cap = 0, h_in_cap = 0, h_out_cap = 0;
-  // the float images of the entries whose storage is not the image (ManyEntry::Image): device scratch either side of the
-  // FIR launch, one range per entry
-  char *d_img_in = nullptr, *d_img_out = nullptr;
-  size_t d_img_in_cap = 0, d_img_out_cap = 0;
-  uint32_t seq = 0;
-};
-// speexhip_debug_many_counters: FIR launches, input passes, output passes, entries that took their own call
-std::atomic<uint64_t> g_many_counters[4];
-inline void count_many(int which, uint64_t by = 1) { g_many_counters[which].fetch_add(by, std::memory_order_relaxed); }
-inline size_t align128(size_t v) { return (v + 127) & ~static_cast<size_t>(127); }
-// (device, lane): a large call on one device runs as two halves side by side, each on a stage of its own (below)
-ManyStage &many_stage(int device, int lane) {
-  static std::mutex mu;
-  static std::map<std::pair<int, int>, ManyStage *> *all = new std::map<std::pair<int, int>, ManyStage *>();  // never destroyed, like the pool
-  std::lock_guard<std::mutex> lock(mu);
-  ManyStage *&m = (*all)[std::make_pair(device, lane)];
-  if (m == nullptr) m = new ManyStage();
-  return *m;
-}
-
-// The stage's copy stream: a stream of its own that carries host -> device copies and NOTHING else, made and primed here.
-// Why (late in round 6; profiles/r06_engine_log.txt, r06_pinned_in_leg.txt): the runtime picks a copy engine per stream --
-// for a copy in, the lowest engine free at the moment it asks; for a copy out, the engine ROCr recommends for that
-// direction (0x2 on this box) -- and then KEEPS it for that stream whatever the direction of the stream's later copies.
-// The pool's streams are shared with every state's own calls, which copy both ways: a copy stream that had last carried
-// a state's results kept engine 0x2 for the inputs of the next many-states call, the 32 queued copies in of a call over
-// pinned chunks went ahead of every copy out on that one engine, and the call took 6.0-6.3 ms instead of 4.0 (pageable
-// chunks: 5.5 instead of 3.8) -- or not, depending on which calls the process had made before.  A stream that only ever
-// copies in asks once, here, one stage at a time and with its copy waited for, so that the lowest engine is free when
-// the next stage asks: every stage's inputs travel on engine 0x1, the results on 0x2 / 0x4.
-int prime_copy_stream(int device, ManyStage &ms) {
-  static std::mutex one_at_a_time;
-  std::lock_guard<std::mutex> lock(one_at_a_time);
-  if (ms.copy_stream != nullptr) return SPEEXHIP_ERR_SUCCESS;
-  DeviceScope scope(device);
-  HIP_TRY(scope.error());
-  hipStream_t s = nullptr;
-  HIP_TRY(pool::stream_own(device, &s));
-  const size_t bytes = 64 * 1024;  // (above the 16 KiB the runtime copies with a kernel: a copy ENGINE must be asked for)
-  void *h = nullptr, *d = nullptr;
-  hipEvent_t e = nullptr;
-  int rc = SPEEXHIP_ERR_SUCCESS;
-  if (hip_failed(pool::pinned_get(&h, bytes), "hipHostMalloc") || hip_failed(pool::device_get(device, &d, bytes), "hipMalloc") ||
-      hip_failed(pool::event_get(device, &e), "hipEventCreate") ||
-      hip_failed(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync (priming)") ||
-      hip_failed(hipEventRecord(e, s), "hipEventRecord") ||
-      // (the EVENT is waited for, not the stream: the stream is never synchronised, the engine it was given stays its own)
-      hip_failed(hipEventSynchronize(e), "hipEventSynchronize"))
-    rc = SPEEXHIP_ERR_DEVICE;
-  if (e != nullptr) pool::event_put(device, e);
-  if (d != nullptr) pool::device_put(device, d);
-  if (h != nullptr) pool::pinned_put(h);
-  if (rc != SPEEXHIP_ERR_SUCCESS) {
-    (void)hipStreamDestroy(s);
-    return rc;
-  }
-  ms.copy_stream = s;
-  return SPEEXHIP_ERR_SUCCESS;
-}
-}  // namespace
-
-// The fused states of ONE device: idx = their positions in the caller's arrays.
-int Batch::many_on_device(int device, int lane, const std::vector<uint32_t> &idx, const ManyEntry *entries, uint32_t *in_len,
-                          uint32_t *out_len, int *rcs) {
-  ManyStage &ms = many_stage(device, lane);
-  std::lock_guard<std::mutex> lock(ms.mu);
-  DeviceScope device_scope(device);
-  HIP_TRY(device_scope.error());
-  if (ms.stream == nullptr) HIP_TRY(pool::stream_get(device, &ms.stream));
-  DrainOnExit drain(&ms.stream);
-  struct Item {
-    uint32_t i;
-    Batch *b;
-    const ManyEntry *e;
-    const void *in;                               // the caller's buffers (raw bytes of e->in_fmt / e->out_fmt)
-    void *out;
-    bool float_io;                                // the FIR launch's sample type: int16 direct, or float (direct or images)
-    bool pass_in, pass_out;                       // the entry's storage goes through a float image on that side
-    size_t img_in, img_out;                       // ... at this offset of the stage's images
-    CallPlan plan;
-    size_t in_bytes, out_bytes, in_off, out_off;
-    const void *pin_in;                           // round 6: the caller's own buffers where they are pinned memory
-    void *pin_out;                                // (pinned_view): the kernels read / write them directly
-    Via in_via, out_via;                          // host_transfer.h
-    bool work;
-  };
-  std::vector<Item> items(idx.size());
-  size_t total_in = 0, total_out = 0;  // pageable bytes, as laid out in the stage
-  size_t images_in = 0, images_out = 0;
-  for (size_t k = 0; k < idx.size(); k++) {
-    Item &it = items[k];
-    it.i = idx[k];
-    it.e = &entries[it.i];
-    it.b = it.e->b;
-    it.in = it.e->in;
-    it.out = it.e->out;
-    it.float_io = it.e->kind != ManyEntry::Int16;
-    EntryRules rules;
-    rules.block_in = it.b->block_in();
-    rules.float_entry = it.float_io;
-    it.plan = plan_call(it.b->filter_.num, it.b->filter_.den, in_len[it.i], out_len[it.i], it.b->P(0, 0), rules);
-    // the raw bytes of either side, in the side's own format: what every size decision below goes by
-    it.in_bytes = it.in != nullptr ? static_cast<size_t>(in_len[it.i]) * it.b->channels_ * sample_bytes(it.e->in_fmt) : 0;
-    it.out_bytes = static_cast<size_t>(it.plan.produced) * it.b->channels_ * sample_bytes(it.e->out_fmt);
-    // (formats.cpp, process_sides_device: F32 storage IS the image; a present but empty input is not silence, no frame of
-    //  it is read)
-    it.pass_in = it.e->kind == ManyEntry::Image && it.e->in_fmt != SPEEXHIP_FMT_F32 && it.in != nullptr && in_len[it.i] != 0;
-    it.pass_out = it.e->kind == ManyEntry::Image && it.e->out_fmt != SPEEXHIP_FMT_F32;
-    it.img_in = images_in;
-    it.img_out = images_out;
-    if (it.pass_in) images_in += align128(static_cast<size_t>(in_len[it.i]) * it.b->channels_ * sizeof(float));
-    if (it.pass_out) images_out += align128(static_cast<size_t>(it.plan.produced) * it.b->channels_ * sizeof(float));
-    it.pin_in = pinned_view(it.in, it.in_bytes);
-    it.pin_out = pinned_view(it.out, it.out_bytes);
-    if (it.pin_in != nullptr && it.pin_out != nullptr && buffers_overlap(it.in, it.in_bytes, it.out, it.out_bytes)) it.pin_in = nullptr;
-    // (a pinned input whose result goes to a LARGE pageable buffer is copied like any other -- from pinned memory the copy
-    //  is a plain DMA -- so that the call can take the pipelined path, inputs arriving while results leave: read in place,
-    //  all the reads come first and all the pageable copies out after them, 32 x 2^20 stereo frames 5.4 ms against 4.0,
-    //  profiles/r06_bench_driver_form_v2.json)
-    if (it.pin_in != nullptr && it.pin_out == nullptr && it.out_bytes >= kDirectCopyBytes &&
-        diag_int(SPEEXHIP_DIAG_ENV("SPEEXHIP_PIN_IN_COPY"), 1) != 0)  // (A/B: 0 = read in place even then)
-      it.pin_in = nullptr;
-    it.work = it.plan.produced != 0 || it.plan.magic_used + it.plan.consumed != 0;
-    total_in += align64(it.pin_in != nullptr ? 0 : it.in_bytes);
-    total_out += align64(it.pin_out != nullptr ? 0 : it.out_bytes);
-  }
-  // Every side by the rule of host_transfer.h, the call's pageable totals deciding whether it is small.  Small calls (a
-  // server's 10-20 ms frames, a Transform's 64 KiB chunks) run on pinned memory alone; larger ones gather their Staged
-  // buffers in the pinned buffer, which travels as ONE copy each way.
-  const bool small = small_call(total_in, total_out);
-  Wait wait;
-  bool all_big = true;  // every working state Copy both ways: the pipelined path (below)
-  for (Item &it : items) {
-    it.in_via = route_side(it.in_bytes, it.in != nullptr, it.pin_in != nullptr, small);
-    it.out_via = route_side(it.out_bytes, true, it.pin_out != nullptr, small);
-    wait.add(it.in_via, it.in_bytes);
-    wait.add(it.out_via, it.out_bytes);
-    if (it.work && (it.in_via != Via::Copy || it.out_via != Via::Copy)) all_big = false;
-  }
-  // layout: the gathered buffers first (one contiguous range = one copy), then the Copy ones
-  auto through_stage = [](Via v, size_t bytes) { return v == Via::InPlace ? 0 : bytes; };
-  size_t gathered_in = 0, gathered_out = 0, off_in = 0, off_out = 0;
-  for (int pass = 0; pass < 2; pass++)
-    for (Item &it : items) {
-      if ((it.in_via == Via::Copy) == (pass == 1)) {
-        it.in_off = off_in;
-        off_in += align64(through_stage(it.in_via, it.in_bytes));
-        if (pass == 0) gathered_in = off_in;
-      }
-      if ((it.out_via == Via::Copy) == (pass == 1)) {
-        it.out_off = off_out;
-        off_out += align64(through_stage(it.out_via, it.out_bytes));
-        if (pass == 0) gathered_out = off_out;
-      }
-    }
-  int rc = grow_stage(device, &ms.h_in, &ms.h_in_cap, gathered_in, true);
-  if (rc == SPEEXHIP_ERR_SUCCESS) rc = grow_stage(device, &ms.h_out, &ms.h_out_cap, gathered_out + 128, true);
-  if (rc == SPEEXHIP_ERR_SUCCESS && !small) rc = grow_stage(device, &ms.d_in, &ms.d_in_cap, total_in, false);
-  if (rc == SPEEXHIP_ERR_SUCCESS && !small) rc = grow_stage(device, &ms.d_out, &ms.d_out_cap, total_out, false);
-  // (a line of slack behind the last image, as the single call's pitched images have behind every stream)
-  if (rc == SPEEXHIP_ERR_SUCCESS && images_in != 0) rc = grow_stage(device, &ms.d_img_in, &ms.d_img_in_cap, images_in + 256, false);
-  if (rc == SPEEXHIP_ERR_SUCCESS && images_out != 0) rc = grow_stage(device, &ms.d_img_out, &ms.d_img_out_cap, images_out + 256, false);
-  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  char *src_base = small ? ms.h_in : ms.d_in, *dst_base = small ? ms.h_out : ms.d_out;
-
-  // Large calls in pieces (below): a launch then carries about 16 MB of input, so that the transfer of the next
-  // piece and the results of the previous one have something to overlap with.
-  static const int env_pipe = diag_int(SPEEXHIP_DIAG_ENV("SPEEXHIP_MANY_PIPELINE"), -1);  // A/B: 0 off
-  const bool pipelined = all_big && env_pipe != 0 && total_in >= (static_cast<size_t>(32) << 20);
-  // launches: the states that share (tables, mode, window format, sample type of the launch) go together, at most 32 per
-  // launch
-  std::vector<std::vector<Item *>> launches;
-  {
-    std::map<std::tuple<const void *, int, bool, bool>, std::vector<Item *>> groups;
-    for (Item &it : items) {
-      if (it.float_io) it.b->float_seen_ = true;
-      if (in_len[it.i] != 0 && out_len[it.i] != 0) it.b->started_[0] = 1;  // resample.c:886
-      if (!it.work) continue;  // nothing to run: the state stays where it is
-      groups[std::make_tuple(static_cast<const void *>(it.b->tables_.get()), it.b->mode_, it.b->float_seen_, it.float_io)].push_back(&it);
-    }
-    for (auto &kv : groups) {
-      std::vector<Item *> &g = kv.second;
-      size_t per = kMaxPackedStreams;
-      if (pipelined) {
-        size_t bytes = 0;
-        for (Item *it : g) bytes += it->in_bytes;
-        const size_t pieces = std::max<size_t>(1, bytes / (static_cast<size_t>(16) << 20));
-        per = std::min<size_t>(kMaxPackedStreams, std::max<size_t>(1, (g.size() + pieces - 1) / pieces));
-      }
-      for (size_t g0 = 0; g0 < g.size(); g0 += per)
-        launches.emplace_back(g.begin() + g0, g.begin() + std::min(g.size(), g0 + per));
-    }
-  }
-  auto commit_item = [&](Item &it) {  // counters and position of one state
-    for (uint32_t c = 0; c < it.b->channels_; c++) it.b->P(0, c) = it.plan.end;
-    if (!it.float_io && it.work) it.b->int16_call_done(&it.plan, 1);
-    in_len[it.i] = it.plan.consumed;
-    out_len[it.i] = it.plan.produced;
-    // (a formatted call of a state with dither on moves its position by the frames produced, whatever the format)
-    if (it.e->sides && it.b->dither_on()) it.b->dither_advance(&out_len[it.i]);
-    rcs[it.i] = SPEEXHIP_ERR_SUCCESS;
-  };
-  // one launch of `launches[k]` on `stream`
-  auto launch = [&](const std::vector<Item *> &g, hipStream_t stream) -> int {
-    const uint32_t cnt = static_cast<uint32_t>(g.size());
-    const bool float_io = g[0]->float_io;  // (the group's: part of its key)
-    DescPack pack;
-    std::memset(&pack, 0, sizeof(pack));
-    // the passes either side of the launch (kernels_convert_many.hip): one each for all the formats the group's entries
-    // name, over the entries whose storage is not their image
-    ConvertPack to_image, from_image;
-    DitherPack dith;
-    uint64_t most_to = 0, most_from = 0;
-    std::memset(&to_image, 0, sizeof(to_image));
-    std::memset(&from_image, 0, sizeof(from_image));
-    std::memset(&dith, 0, sizeof(dith));
-    uint32_t max_out = 0;
-    for (uint32_t j = 0; j < cnt; j++) {
-      Item &it = *g[j];
-      Batch *b = it.b;
-      const int crc = b->chain_to(stream);  // (each state's calls stay ordered, whatever stream its last one ran on)
-      if (crc != SPEEXHIP_ERR_SUCCESS) return crc;
-      StreamDesc &d = pack.d[j];
-      const FilterSpec &f = b->filter_;
-      const void *storage_in = it.in == nullptr ? nullptr : it.pin_in != nullptr ? it.pin_in : src_base + it.in_off;
-      void *storage_out = it.pin_out != nullptr ? it.pin_out : dst_base + it.out_off;
-      d.in = it.pass_in ? ms.d_img_in + it.img_in : storage_in;
-      d.hist = b->d_hist_[b->hist_cur_];
-      d.out = it.pass_out ? ms.d_img_out + it.img_out : storage_out;
-      if (it.pass_in) {
-        ConvertStream &c = to_image.s[j];
-        c.src = storage_in, c.dst = ms.d_img_in + it.img_in;
-        c.n = static_cast<uint64_t>(in_len[it.i]) * b->channels_;
-        c.step = 1;
-        c.reserved = convert_many_tag(it.e->in_fmt, SPEEXHIP_DITHER_NONE);
-        most_to = std::max(most_to, c.n);
-      }
-      if (it.pass_out && it.plan.produced != 0) {
-        ConvertStream &c = from_image.s[j];
-        c.src = ms.d_img_out + it.img_out, c.dst = storage_out;
-        c.n = static_cast<uint64_t>(it.plan.produced) * b->channels_;
-        c.step = 1;
-        const bool dithered = b->dither_on() && dithered_fmt(it.e->out_fmt);
-        c.reserved = convert_many_tag(it.e->out_fmt, dithered ? b->dither_kind_ : SPEEXHIP_DITHER_NONE);
-        if (dithered) dith.s[j] = b->dither_pack(0, 1, b->channels_).s[0];
-        most_from = std::max(most_from, c.n);
-      }
-      d.hist_next = b->d_hist_[b->hist_cur_ ^ 1];
-      d.in_frames = in_len[it.i];
-      set_position(d, f, it.plan.begin, it.plan.produced, it.plan.magic_used + it.plan.consumed, f.taps - 1 + it.plan.begin.magic,
-                   f.taps - 1 + it.plan.end.magic);
-      max_out = std::max(max_out, it.plan.produced);
-    }
-    if (most_to != 0) {
-      if (hip_failed(launch_convert_many(false, to_image, dith, cnt, most_to, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
-      count_many(1);
-    }
-    const int lrc = g[0]->b->launch_chunk(pack.d, pack, cnt, max_out, float_io, stream);
-    if (lrc != SPEEXHIP_ERR_SUCCESS) return lrc;
-    count_many(0);
-    if (most_from != 0) {
-      if (hip_failed(launch_convert_many(true, from_image, dith, cnt, most_from, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
-      count_many(2);
-    }
-    // A state moves as ONE step, the moment its launch is queued: the history ping-pong, the position and the counters
-    // together.  (Until round 6 the flip happened here and the positions behind the last launch of the call: a later
-    // group's failure left the earlier groups' states with a flipped history and their OLD position -- silently corrupt
-    // for every later call, ADVICE r5.  Now a failure further on costs such a state this call's audio -- its code says
-    // so -- and nothing else; states whose launch was never queued have not moved at all.)
-    for (uint32_t j = 0; j < cnt; j++) {
-      g[j]->b->hist_cur_ ^= 1;
-      commit_item(*g[j]);
-    }
-    return SPEEXHIP_ERR_SUCCESS;
-  };
-  auto commit = [&]() {  // ... and the states with nothing to run: counters of an empty call, position unchanged
-    for (Item &it : items)
-      if (!it.work) commit_item(it);
-  };
-
-  if (pipelined && launches.size() >= 2) {
-    // Large calls, pipelined (round 5).  PCIe is full duplex, but the runtime's pageable copies keep the thread that
-    // issues them busy until they are staged, so one thread alone moves inputs, computes, and moves results strictly
-    // one after the other: 32 streams x 2^20 stereo frames 5.8 ms, of which 0.2 are the kernel.  Here the calling
-    // thread copies the inputs of launch after launch on the stage's copy stream (an event behind each launch's
-    // inputs), while a second thread waits for the events, runs the launches on the stage's stream and copies each
-    // launch's results out behind it: results leave while the next inputs arrive.
-    if (ms.copy_stream == nullptr) {
-      const int prc = prime_copy_stream(device, ms);  // (process_host_many has done this for every large unit, one after the other)
-      if (prc != SPEEXHIP_ERR_SUCCESS) return prc;
-    }
-    while (ms.events.size() < launches.size()) {
-      hipEvent_t e = nullptr;
-      HIP_TRY(pool::event_get(device, &e));
-      ms.events.push_back(e);
-    }
-    DrainOnExit drain_copy(&ms.copy_stream);
-    std::mutex mu;
-    std::condition_variable cv;
-    size_t ready = 0;       // launches whose inputs are enqueued with their event recorded
-    bool copy_failed = false;
-    int worker_rc = SPEEXHIP_ERR_SUCCESS;
-    std::string worker_err;
-    auto helper = [&] {
-      DeviceScope scope(device);
-      try {
-      for (size_t k = 0; k < launches.size() && worker_rc == SPEEXHIP_ERR_SUCCESS; k++) {
-        {
-          std::unique_lock<std::mutex> l(mu);
-          cv.wait(l, [&] { return ready > k || copy_failed; });
-          if (copy_failed) return;
-        }
-        auto fail = [&](hipError_t e, const char *what) {
-          if (e == hipSuccess) return false;
-          worker_err = std::string("HIP device error: ") + what + ": " + hipGetErrorString(e);
-          worker_rc = SPEEXHIP_ERR_DEVICE;
-          return true;
-        };
-        if (fail(hipStreamWaitEvent(ms.stream, ms.events[k], 0), "hipStreamWaitEvent")) return;
-        const int lrc = launch(launches[k], ms.stream);
-        if (lrc != SPEEXHIP_ERR_SUCCESS) {
-          worker_rc = lrc;
-          worker_err = g_last_error;
-          return;
-        }
-        for (Item *it : launches[k])
-          if (it->out_bytes != 0 &&
-              fail(hipMemcpyAsync(it->out, ms.d_out + it->out_off, it->out_bytes, hipMemcpyDeviceToHost, ms.stream), "hipMemcpyAsync (results)"))
-            return;
-      }
-      if (worker_rc == SPEEXHIP_ERR_SUCCESS) {
-        const hipError_t e = hipStreamSynchronize(ms.stream);
-        if (e != hipSuccess) {
-          worker_err = std::string("HIP device error: hipStreamSynchronize: ") + hipGetErrorString(e);
-          worker_rc = SPEEXHIP_ERR_DEVICE;
-        }
-      }
-      } catch (...) {  // (a host allocation inside a launcher: no exception leaves a thread)
-        worker_rc = SPEEXHIP_ERR_ALLOC_FAILED;
-      }
-    };
-    // (the launching half runs on this (device, lane)'s persistent helper thread -- unit_workers.h; until round 6 a
-    //  std::thread made and joined inside every such call.  No thread to be had: the call falls back to one thread,
-    //  copies first, launches after -- the helper's loop then finds every event recorded already.)
-    workers::Ticket helper_job = workers::submit(workers::key_of(device, lane, 1), helper);
-    hipError_t copy_err = hipSuccess;
-    for (size_t k = 0; k < launches.size() && copy_err == hipSuccess; k++) {
-      for (Item *it : launches[k])
-        if (it->in_bytes != 0 && copy_err == hipSuccess)
-          copy_err = hipMemcpyAsync(ms.d_in + it->in_off, it->in, it->in_bytes, hipMemcpyHostToDevice, ms.copy_stream);
-      if (copy_err == hipSuccess) copy_err = hipEventRecord(ms.events[k], ms.copy_stream);
-      {
-        std::lock_guard<std::mutex> l(mu);
-        if (copy_err == hipSuccess)
-          ready = k + 1;
-        else
-          copy_failed = true;
-      }
-      cv.notify_all();
-    }
-    if (helper_job != nullptr) {
-      workers::wait(helper_job);
-      if (workers::failed(helper_job)) worker_rc = SPEEXHIP_ERR_ALLOC_FAILED;
-    } else {
-      helper();
-    }
-    if (hip_failed(copy_err, "hipMemcpyAsync (inputs)")) return SPEEXHIP_ERR_DEVICE;
-    if (worker_rc != SPEEXHIP_ERR_SUCCESS) {
-      g_last_error = worker_err;
-      return worker_rc;
-    }
-    drain.armed = false;
-    drain_copy.armed = false;
-    commit();
-    return SPEEXHIP_ERR_SUCCESS;
-  }
-
-  for (const Item &it : items) {
-    if (it.in_bytes == 0) continue;
-    if (it.in_via == Via::Bounce || it.in_via == Via::Staged) std::memcpy(ms.h_in + it.in_off, it.in, it.in_bytes);
-    if (it.in_via == Via::Copy)
-      HIP_TRY(hipMemcpyAsync(ms.d_in + it.in_off, it.in, it.in_bytes, hipMemcpyHostToDevice, ms.stream));
-  }
-  // (not small: the gathered range holds the Staged buffers)
-  if (!small && gathered_in != 0) HIP_TRY(hipMemcpyAsync(ms.d_in, ms.h_in, gathered_in, hipMemcpyHostToDevice, ms.stream));
-  for (const std::vector<Item *> &g : launches) {
-    rc = launch(g, ms.stream);
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  }
-  commit();
-  // results back
-  if (!small && gathered_out != 0) HIP_TRY(hipMemcpyAsync(ms.h_out, ms.d_out, gathered_out, hipMemcpyDeviceToHost, ms.stream));
-  for (const Item &it : items)
-    if (it.out_via == Via::Copy)
-      HIP_TRY(hipMemcpyAsync(it.out, ms.d_out + it.out_off, it.out_bytes, hipMemcpyDeviceToHost, ms.stream));
-  if (wait.sync || !launches.empty()) {
-    const int wrc = wait_call(ms.stream, wait, tail_word(ms.h_out, ms.h_out_cap), ++ms.seq);
-    if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
-  }
-  drain.armed = false;
-  for (const Item &it : items)
-    if (pinned_part(it.out_via, it.out_bytes) != 0) std::memcpy(it.out, ms.h_out + it.out_off, it.out_bytes);
-  return SPEEXHIP_ERR_SUCCESS;
-}
-
-void many_counters(uint64_t out[4]) {
-  for (int k = 0; k < 4; k++) out[k] = g_many_counters[k].load(std::memory_order_relaxed);
-}
-
-// process_many_int / _float: the all-S16 / all-F32 case of many_run -- every entry the int16 call, or the float call, on
-// its own bytes; the state's dither is neither read nor moved.
-int Batch::process_host_many(uint32_t n, Batch *const *st, const void *const *in, uint32_t *in_len, void *const *out,
-                             uint32_t *out_len, bool float_io, int *codes) {
-  std::vector<ManyEntry> entries(n);
-  for (uint32_t i = 0; i < n; i++) {
-    ManyEntry &e = entries[i];
-    e.b = st[i];
-    e.in = in[i];
-    e.out = out[i];
-    e.in_fmt = e.out_fmt = float_io ? SPEEXHIP_FMT_F32 : SPEEXHIP_FMT_S16;
-    e.kind = float_io ? ManyEntry::Float : ManyEntry::Int16;
-    e.fusable = true;
-    if (st[i] == nullptr || (out[i] == nullptr && out_len[i] != 0)) e.rc = SPEEXHIP_ERR_INVALID_ARG;
-  }
-  return many_run(n, entries.data(), in_len, out_len, codes);
-}
-
-int Batch::many_run(uint32_t n, const ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *codes) {
-  std::vector<int> rcs(n, SPEEXHIP_ERR_SUCCESS);
-  std::map<int, std::vector<uint32_t>> by_device;  // (ordered: two concurrent calls lock their devices in one order)
-  std::vector<uint32_t> apart;                     // states that take the single call (in the caller's order)
-  for (uint32_t i = 0; i < n; i++) {
-    Batch *b = entries[i].b;
-    if (entries[i].rc != SPEEXHIP_ERR_SUCCESS) {  // (an argument error: the state and the lengths stay as they are)
-      rcs[i] = entries[i].rc;
-      continue;
-    }
-    bool earlier = false;  // a state named twice: its second call must see the first one's end state
-    for (uint32_t j = 0; j < i && !earlier; j++) earlier = entries[j].b == b;
-    // (rare states -- channels moved apart by the per-channel calls, the zero fallback, batches of several streams --
-    //  and the sides a launch group does not serve -- a matrix, planes of several channels -- keep their own call's rules)
-    if (earlier || !entries[i].fusable || b->n_streams_ != 1 || !b->uniform(0) || b->zero_mode_)
-      apart.push_back(i);
-    else
-      by_device[b->device_].push_back(i);
-  }
-  // the raw bytes entry i's sides would move at most: frames x channels x the side's sample size
-  auto raw_in = [&](uint32_t i) {
-    return static_cast<uint64_t>(in_len[i]) * entries[i].b->channels_ * sample_bytes(entries[i].in_fmt);
-  };
-  // Units of work: a device's states -- or, for a large call, two halves of them ("lanes"): one thread's pageable copies
-  // do not fill a PCIe link (64 x 2^20 stereo frames on one GPU: 11.0 ms through one stage, 7.6 ms as two logical
-  // devices of 32 states each, profiles/r05_host_many.txt), two stages side by side nearly do.
-  struct Unit {
-    int device, lane;
-    std::vector<uint32_t> idx;
-  };
-  std::vector<Unit> units;
-  static const int env_lanes = SPEEXHIP_DIAG_ENV("SPEEXHIP_MANY_LANES") ? std::atoi(SPEEXHIP_DIAG_ENV("SPEEXHIP_MANY_LANES")) : -1;  // A/B: 1 = never split
-  for (auto &kv : by_device) {
-    // What a lane is for: the runtime's PAGEABLE copies keep the thread that issues them busy, so the bytes that count are
-    // the pageable ones of the busier direction.  Buffers in the library's pinned blocks do not count (a range check; read or
-    // written in place -- or, chunks beside large pageable results, copied by a plain DMA that keeps no thread).
-    // 32 x 2^20 stereo frames, one box (profiles/r06_pin_both_copy.txt, r06_pinned_in_leg.txt): pageable both ways one lane
-    // 4.11, two 3.80 ms; pinned chunks + pageable results (146 MB out) 4.04 -> 3.83; both pinned 3.61 / 3.65 (nothing to
-    // split).  (Until the stages had copy streams of their own -- prime_copy_stream -- the second case measured 4.02 / 4.54:
-    // that was the copy engines' lottery, not the lanes.)
-    uint64_t bytes_in = 0, bytes_out = 0;
-    for (uint32_t i : kv.second) {
-      const ManyEntry &e = entries[i];
-      const uint64_t b = raw_in(i);
-      if (e.in != nullptr && !pool::block_owns(e.in, b)) bytes_in += b;
-      // (results: about den / num of the input's frames, capped by the caller's capacity)
-      const uint64_t frames_out = std::min<uint64_t>(out_len[i], static_cast<uint64_t>(in_len[i]) * e.b->filter_.den / std::max<uint32_t>(e.b->filter_.num, 1) + 1);
-      const uint64_t o = frames_out * e.b->channels_ * sample_bytes(e.out_fmt);
-      if (e.out != nullptr && !pool::block_owns(e.out, o)) bytes_out += o;
-    }
-    const uint64_t bytes = std::max(bytes_in, bytes_out);
-    // (from 128 MB: 32 x 2^20 stereo frames 4.11 -> 4.00 ms, 64 states 7.90 -> 7.14; at 67 MB nothing, 2.26 / 2.44)
-    const bool split = env_lanes != 1 && kv.second.size() >= 8 && (env_lanes == 2 || bytes >= (static_cast<uint64_t>(128) << 20));  // (A/B: 2 = always)
-    if (!split) {
-      units.push_back(Unit{kv.first, 0, kv.second});
-    } else {
-      const size_t half = kv.second.size() / 2;
-      units.push_back(Unit{kv.first, 0, std::vector<uint32_t>(kv.second.begin(), kv.second.begin() + half)});
-      units.push_back(Unit{kv.first, 1, std::vector<uint32_t>(kv.second.begin() + half, kv.second.end())});
-    }
-  }
-  // (the copy streams of the units that will take the pipelined path: made and primed one after the other, before any
-  //  unit copies anything -- prime_copy_stream)
-  for (const Unit &u : units) {
-    uint64_t bytes = 0;
-    for (uint32_t i : u.idx) bytes += raw_in(i);
-    if (bytes >= (static_cast<uint64_t>(32) << 20)) {
-      ManyStage &ms = many_stage(u.device, u.lane);
-      std::lock_guard<std::mutex> lock(ms.mu);  // (the order many_on_device takes them in: the stage, then the priming)
-      (void)prime_copy_stream(u.device, ms);   // (a failure shows again, with its code, in the unit's own call)
-    }
-  }
-  std::vector<int> dev_rc(units.size(), SPEEXHIP_ERR_SUCCESS);
-  std::vector<std::string> dev_err(units.size());
-  auto run_device = [&](size_t slot) {
-    const Unit &u = units[slot];
-    try {
-      dev_rc[slot] = many_on_device(u.device, u.lane, u.idx, entries, in_len, out_len, rcs.data());
-    } catch (const std::bad_alloc &) {
-      dev_rc[slot] = SPEEXHIP_ERR_ALLOC_FAILED;
-    } catch (const std::exception &e) {  // (anything else: a code and its text, never std::terminate in a worker)
-      g_last_error = std::string("internal error: ") + e.what();
-      dev_rc[slot] = SPEEXHIP_ERR_DEVICE;
-    } catch (...) {
-      g_last_error = "internal error: unknown exception";
-      dev_rc[slot] = SPEEXHIP_ERR_DEVICE;
-    }
-    if (dev_rc[slot] != SPEEXHIP_ERR_SUCCESS) {
-      dev_err[slot] = g_last_error;  // (the text lives per thread)
-      for (uint32_t i : u.idx) rcs[i] = dev_rc[slot];
-    }
-  };
-  {
-    // GPUs side by side: every further unit of the call runs on the persistent thread of its (device, lane) -- a GPU
-    // is a PCIe link of its own, and the runtime's pageable copies keep the thread that issues them busy -- while the
-    // calling thread runs the first one (unit_workers.h: one thread per (device, lane) for the life of the process;
-    // until round 6 a std::thread per unit per CALL, 7-15 thread creations per step on an 8-GPU node).  A unit whose
-    // job cannot be queued runs here, after the first.
-    std::vector<workers::Ticket> tickets(units.size());
-    for (size_t slot = 1; slot < units.size(); slot++)
-      tickets[slot] = workers::submit(workers::key_of(units[slot].device, units[slot].lane, 0), [&run_device, slot] { run_device(slot); });
-    if (!units.empty()) run_device(0);
-    for (size_t slot = 1; slot < units.size(); slot++) {
-      if (tickets[slot] != nullptr)
-        workers::wait(tickets[slot]);
-      else
-        run_device(slot);
-    }
-    for (size_t k = 0; k < dev_rc.size(); k++)
-      if (dev_rc[k] != SPEEXHIP_ERR_SUCCESS) {
-        g_last_error = dev_err[k];
-        break;
-      }
-  }
-  for (uint32_t i : apart) {
-    const ManyEntry &e = entries[i];
-    rcs[i] = e.sides ? e.b->process_sides_host(e.in_side, &in_len[i], e.out_side, &out_len[i])
-                     : e.b->process_host(e.in, &in_len[i], e.out, &out_len[i], e.kind != ManyEntry::Int16);
-  }
-  count_many(3, apart.size());
-  int first = SPEEXHIP_ERR_SUCCESS;
-  for (uint32_t i = 0; i < n; i++) {
-    if (codes != nullptr) codes[i] = rcs[i];
-    if (first == SPEEXHIP_ERR_SUCCESS && rcs[i] != SPEEXHIP_ERR_SUCCESS) first = rcs[i];
-  }
-  return first;
 }
 
 }  // namespace speexhip

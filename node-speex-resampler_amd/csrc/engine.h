@@ -11,6 +11,7 @@
 #include "../../include/speexhip_resampler.h"
 #include "device_types.h"
 #include "filter_design.h"
+#include "filter_plans.h"
 #include "host_transfer.h"
 #include "kernels.h"
 #include "stream_plan.h"
@@ -33,18 +34,12 @@ void many_counters(uint64_t out[4]);
 // uploads nothing.
 struct DeviceTables {
   int device = 0;
-  float *table = nullptr;        // reference layout (exact kernel)
-  float *period_rows = nullptr;  // kernels_period.hip, R = 10
-  float *fine_rows = nullptr;    // ... R = 5 (launches of one generation)
-  float *w16_rows = nullptr;     // ... with an int16 LDS window (wide windows; int16 calls)
-  float *slide_rows = nullptr;   // kernels_slide.hip
-  double *slide64_rows = nullptr;  // kernels_slide64_impl.h: fp64 taps (filters of the reference's double kinds)
-  double *period64_rows = nullptr, *fine64_rows = nullptr;  // kernels_period64.hip: the same for the period kernel
-  double *period64_w16_rows = nullptr;                      // ... over an int16 LDS window (kernels_period64_w16.hip)
-  float *pp_rows = nullptr, *pp_w16_rows = nullptr;         // kernels_period_pp.hip: phase pairs (mono, wide windows)
-  ExactGeometry geo, geo_ch;     // exact kernel, all channels / one channel per launch
-  PeriodPlan period, fine, w16, period64, fine64, pp, pp_w16, period64_w16;
-  SlidePlan slide, slide64;
+  FilterPlans plans;                         // filter_plans.h: every plan of the filter, held here and nowhere else
+  float *table = nullptr;                    // reference layout (exact kernel)
+  void *period_rows[kPeriodVariants] = {};   // tap rows of plans.period[v]: floats, doubles for the fp64 variants; null
+                                             // where the variant has none (FilterPlans::has_rows)
+  float *slide_rows = nullptr;               // kernels_slide.hip
+  double *slide64_rows = nullptr;            // kernels_slide64_impl.h: fp64 taps (filters of the reference's double kinds)
   size_t bytes = 0;
   DeviceTables() = default;
   DeviceTables(const DeviceTables &) = delete;
@@ -250,6 +245,9 @@ class Batch {
   int stage_input(Via via, const void *in, size_t bytes, const void *pin, const void **src);
   int run_plans(const void *d_in, uint64_t in_stride, const uint32_t *in_frames, void *d_out,
                 uint64_t out_stride, const CallPlan *plans, bool float_io, hipStream_t stream);
+  // The descriptor of stream s (from its channel c on: 0 for a launch of whole frames) for `plan`: the two history
+  // pointers of the ping-pong as it stands and the position fields.  in_frames = frames readable at `in`.
+  void fill_desc(StreamDesc &d, uint32_t s, uint32_t c, const void *in, void *out, uint32_t in_frames, const CallPlan &plan) const;
   int launch_chunk(const StreamDesc *descs, const DescPack &pack, uint32_t n, uint32_t max_out, bool float_io,
                    hipStream_t stream);
   // a large host call as pieces: input copies on a second stream, one launch per piece behind each (process_host_take)
@@ -285,42 +283,22 @@ class Batch {
   uint32_t in_stride_ = 1, out_stride_ = 1;  // resample.c:842-843, 1170-1188 (per-channel entry points)
   RateView shown_ = {0, 0, 0, 0};  // see rates()
   bool shown_valid_ = false;
-  ExactGeometry exact_geo_ch_;    // the exact kernel's geometry for one-channel launches
   std::vector<uint8_t> started_;  // per stream: a block has run (resample.c:886), so a filter
                                   // change must re-align the history instead of clearing it
   uint32_t line_ = 0;             // frames per channel line, grow-only (resample.c
                                   // "mem_alloc_size", :709-720): block size = line_-(taps-1)
 
-  std::shared_ptr<const DeviceTables> tables_;  // owns the four table pointers below
-  float *d_table_ = nullptr;
+  // Everything of the filter on the device and every plan made for it (DeviceTables: shared between states, immutable).
+  // The launches read the plans and the row pointers through it; while zero_mode_ holds it is still the set of the last
+  // filter that could be built, of which only the sinc table's address and the exact geometry's channel split are used.
+  std::shared_ptr<const DeviceTables> tables_;
   float *d_hist_[2] = {nullptr, nullptr};  // float, like the reference's `mem`
   size_t hist_elems_ = 0;  // per stream: (taps-1 + room for pending frames)*channels
   size_t hist_bytes_ = 0;  // allocation of each history buffer (>= the copy-engine minimum, engine.cpp kCtlCopyMin)
   int hist_cur_ = 0;
 
-  ExactGeometry exact_geo_;
-  PeriodPlan period_;      // primary fast path (kernels_period.hip)
-  float *d_period_rows_ = nullptr;
-  PeriodPlan period_fine_;  // the same filter with 5 phases per wave: single-generation launches
-  float *d_period_fine_rows_ = nullptr;
-  PeriodPlan period_w16_;   // the same filter over an int16 LDS window (usable only where it pays)
-  float *d_period_w16_rows_ = nullptr;
   bool float_seen_ = false;  // a float call has put samples into the histories that an int16 window cannot hold
   void int16_call_done(const CallPlan *plans, uint32_t n);  // ... until int16 calls have replaced all of them (round 6)
-  SlidePlan slide_;        // small-ratio fast path (kernels_slide.hip); neither usable -> exact
-  float *d_slide_rows_ = nullptr;
-  SlidePlan slide64_;      // ... with an fp64 accumulator: what FAST runs for the double kinds (quality 9, 10)
-  double *d_slide64_rows_ = nullptr;
-  PeriodPlan period_pp_, period_pp_w16_;  // phase-pair plans (mono, wide windows): chosen per launch
-  float *d_period_pp_rows_ = nullptr, *d_period_pp_w16_rows_ = nullptr;
-  PeriodPlan period64_, period64_fine_;  // the period kernel's plans with an fp64 accumulator (kernels_period64.hip)
-  double *d_period64_rows_ = nullptr, *d_period64_fine_rows_ = nullptr;
-  PeriodPlan period64_w16_;              // ... over an int16 LDS window (wide windows; int16 calls)
-  double *d_period64_w16_rows_ = nullptr;
-  bool acc64() const {     // the fast path sums in fp64 (mode FAST on a filter the reference sums in fp64)
-    return (mode_ == SPEEXHIP_MODE_FAST || mode_ == SPEEXHIP_MODE_FAST_FIXED) &&
-           (filter_.kind == kDirectDouble || filter_.kind == kInterpolateDouble);
-  }
 
   // Calls on one batch are chained: a call on another stream than the previous one waits for it on the device
   // (an event recorded on the previous stream at that moment), control calls and the destructor wait for the

@@ -1,10 +1,11 @@
-// engine_detail.h -- what the engine's translation units (engine.cpp, planar.cpp) share beside engine.h: the HIP error
+// engine_detail.h -- what the engine's translation units (engine.cpp, many.cpp, planar.cpp ...) share beside engine.h: the HIP error
 // macros, the device scope of an entry point and the staging helpers of the host-buffer calls (product code).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
+#include <string>
 
 #include "../../include/speexhip_resampler.h"
 #include "devices.h"
@@ -13,6 +14,8 @@
 namespace speexhip {
 namespace detail {
 
+// engine.cpp: text of the most recent HIP failure on this thread (last_device_error)
+extern thread_local std::string g_last_error;
 // false on hipSuccess; otherwise records the text speexhip_resampler_strerror(SPEEXHIP_ERR_DEVICE) reports
 bool hip_failed(hipError_t e, const char *what);
 #define HIP_TRY(expr)                                                                  \
@@ -75,8 +78,8 @@ inline size_t pinned_part(Via v, size_t bytes) { return v == Via::Bounce || v ==
 // engine.cpp: the wait a host-buffer call's `Wait` chose, and the grow-only staging buffers
 int wait_call(hipStream_t stream, const Wait &w, void *word, uint32_t seq);
 int grow_stage(int device, char **buf, size_t *cap_now, size_t want, bool pinned);
-// engine.cpp, pinned_view: the address the device sees when all of [p, p + bytes) is pinned memory, else nullptr
-void *pinned_view_of(const void *p, size_t bytes);
+// engine.cpp: the address the device sees when all of [p, p + bytes) is pinned memory, else nullptr
+void *pinned_view(const void *p, size_t bytes);
 
 }  // namespace detail
 }  // namespace speexhip

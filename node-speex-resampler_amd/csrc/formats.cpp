@@ -164,7 +164,7 @@ int Batch::process_sides_device(const CallSide &in_side, uint32_t *in_len, const
 }
 
 // The formatted many-states call (engine.h): which entries a launch group can serve and as what -- the rules of
-// process_sides_host above, entry by entry -- then many_run (engine.cpp).
+// process_sides_host above, entry by entry -- then many_run (many.cpp).
 int Batch::process_host_many_sides(uint32_t n, Batch *const *st, const CallSide *in, uint32_t *in_len, const CallSide *out,
                                    uint32_t *out_len, const uint8_t *bad, int *codes) {
   std::vector<ManyEntry> entries(n);
@@ -203,8 +203,8 @@ int Batch::routed_host_call(const CallSide &in_side, size_t in_bytes, uint32_t *
   void *out = out_side.base;
   int rc = SPEEXHIP_ERR_SUCCESS;
   DrainOnExit drain(&own_stream_);
-  const void *pin_in = in != nullptr ? pinned_view_of(in, in_bytes) : nullptr;
-  void *pin_out = pinned_view_of(out, out_bytes);
+  const void *pin_in = in != nullptr ? pinned_view(in, in_bytes) : nullptr;
+  void *pin_out = pinned_view(out, out_bytes);
   if (pin_in != nullptr && pin_out != nullptr && buffers_overlap(in, in_bytes, out, out_bytes)) pin_in = nullptr;
   const bool small = small_call(in != nullptr && pin_in == nullptr ? in_bytes : 0, pin_out == nullptr ? out_bytes : 0);
   const Via in_via = route_side(in_bytes, in != nullptr, pin_in != nullptr, small);
@@ -330,8 +330,8 @@ int Batch::planes_host_call(const CallSide &in, uint32_t *in_len, const CallSide
   const size_t out_bytes = pl_out ? out_pitch * out.channels * bout : out_payload;
   // (channels that stand apart write different numbers of frames: the block is fetched whole and the caller handed only
   //  what each channel really wrote, so nothing is used in place there)
-  const void *pin_in = !pl_in && present && !split ? pinned_view_of(in_flat.base, in_payload) : nullptr;
-  void *pin_out = !pl_out && !split ? pinned_view_of(out_flat.base, out_payload) : nullptr;
+  const void *pin_in = !pl_in && present && !split ? pinned_view(in_flat.base, in_payload) : nullptr;
+  void *pin_out = !pl_out && !split ? pinned_view(out_flat.base, out_payload) : nullptr;
   if (pin_in != nullptr && pin_out != nullptr && buffers_overlap(in_flat.base, in_payload, out_flat.base, out_payload)) pin_in = nullptr;
   const bool small = small_call(present && pin_in == nullptr ? in_payload : 0, pin_out == nullptr ? out_payload : 0);
   const Via in_via = route_side(pl_in ? plane_in : in_payload, present, pin_in != nullptr, small);
