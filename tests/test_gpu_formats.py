@@ -119,7 +119,8 @@ def test_formatted_call_equals_the_float_twin_for_every_pair(mode, in_fmt):
                  (5000, 777, 0, False),                   # a capacity that binds
                  (300000, wcap(300000, fi, fo), 0, False)]
         got, y = run_pairs(cfg, MODES[mode], in_fmt, calls, seed=31 * ch + q)
-        # both rails of every integer output are reached, and the half-up rule meets exact ties
+        # both rails of every integer output are reached, and the half-up rule meets exact ties -- of the S24 and S32
+        # scales, by chance; every encoder's ties, rails and thresholds by construction: test_gpu_decision_points.py
         for o, lo, hi in ((sf.U8, 0, 255), (sf.S16, -32768, 32767), (sf.S24, -(1 << 23), (1 << 23) - 1),
                           (sf.S32, -(1 << 31), (1 << 31) - 1)):
             if in_fmt == o == sf.S16:
