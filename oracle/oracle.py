@@ -197,6 +197,9 @@ class Oracle(_Base, _FloatMixin, _RawMixin):
             L.orc_set_output_stride.argtypes = [C.c_void_p, C.c_uint32]
             L.orc_channel_position.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int32),
                                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+            L.orc_clone.restype = C.c_void_p
+            L.orc_clone.argtypes = [C.c_void_p]
+            L.orc_set_lines.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.c_uint32]
             cls._lib = L
         return cls._lib
 
@@ -305,6 +308,22 @@ class Oracle(_Base, _FloatMixin, _RawMixin):
         buf = np.zeros(self.taps - 1, np.float32)
         self.lib().orc_history(self._h, c, buf.ctypes.data_as(C.POINTER(C.c_float)))
         return buf
+
+    def clone(self):
+        """an independent copy of this state (tests/async_order.py)"""
+        n = object.__new__(type(self))
+        n._h = self.lib().orc_clone(self._h)
+        if not n._h:
+            raise MemoryError("orc_clone")
+        n.err, n.channels = self.err, self.channels
+        n.refresh()
+        return n
+
+    def set_lines(self, c, values):
+        """overwrite the start of channel c's line -- its history, then its pending frames -- leaving positions and
+        counts alone: the state a call meets that reads lines an earlier call left (tests/async_order.py)"""
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        self.lib().orc_set_lines(self._h, c, v.ctypes.data_as(C.POINTER(C.c_float)), v.size)
 
     def __del__(self):
         if getattr(self, "_h", None):

@@ -666,6 +666,34 @@ uint32_t orc_pending(const orc_state *o, uint32_t c, float *dst) {
 }
 uint32_t orc_block_in(const orc_state *o) { return o->line - (o->taps - 1); }
 
+/* ---- hooks of tests/async_order.py: "what if a call had read the lines an earlier call left" ---- */
+/* An independent copy of a state (NULL when memory runs out). */
+orc_state *orc_clone(const orc_state *o) {
+  orc_state *n = (orc_state *)calloc(1, sizeof(*n));
+  if (!n) return NULL;
+  *n = *o;
+  n->table = (float *)calloc(o->table_cap ? o->table_cap : 1, sizeof(float));
+  n->lines = (float *)calloc((size_t)o->channels * o->line + 1, sizeof(float));
+  n->pos = (int32_t *)calloc(o->channels, sizeof(int32_t));
+  n->phase = (uint32_t *)calloc(o->channels, sizeof(uint32_t));
+  n->pending = (uint32_t *)calloc(o->channels, sizeof(uint32_t));
+  if (!n->table || !n->lines || !n->pos || !n->phase || !n->pending) {
+    orc_free(n);
+    return NULL;
+  }
+  if (o->table) memcpy(n->table, o->table, sizeof(float) * o->table_cap);
+  if (o->lines) memcpy(n->lines, o->lines, sizeof(float) * (size_t)o->channels * o->line);
+  memcpy(n->pos, o->pos, sizeof(int32_t) * o->channels);
+  memcpy(n->phase, o->phase, sizeof(uint32_t) * o->channels);
+  memcpy(n->pending, o->pending, sizeof(uint32_t) * o->channels);
+  return n;
+}
+/* The first n floats of channel c's line (history, then pending frames) overwritten; positions and counts stay. */
+void orc_set_lines(orc_state *o, uint32_t c, const float *src, uint32_t n) {
+  if (n > o->line) n = o->line;
+  memcpy(o->lines + (size_t)c * o->line, src, sizeof(float) * n);
+}
+
 /* resample.c:1222-1239 */
 const char *orc_strerror(int err) {
   switch (err) {
