@@ -204,6 +204,14 @@ void set_position(StreamDesc &d, const FilterSpec &f, const StreamPos &at, uint3
 }
 }  // namespace
 
+// The exact kernel's geometry in the zero fallback: the window geometry belongs to the filter that is no longer in force.
+static ExactGeometry zero_geometry(ExactGeometry geo) {
+  geo.staged = false;
+  geo.lds_bytes = 0;
+  geo.outs_per_block = 256;
+  return geo;
+}
+
 void Batch::fill_desc(StreamDesc &d, uint32_t s, uint32_t c, const void *in, void *out, uint32_t in_frames, const CallPlan &plan) const {
   d.in = in;
   d.hist = d_hist_[hist_cur_] + s * hist_elems_ + c;
@@ -670,7 +678,7 @@ void Batch::enter_zero_mode(const FilterSpec &n) {
 int Batch::change_filter(const FilterSpec &next, int design_rc, const std::vector<uint32_t> *fracs) {
   int rc = design_rc;
   if (rc == SPEEXHIP_ERR_SUCCESS) rc = adopt_filter(next);
-  if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;  // nothing was touched
+  if (!ran(rc)) return rc;  // nothing was touched
   if (fracs != nullptr)
     for (size_t i = 0; i < pos_.size(); i++) pos_[i].frac = (*fracs)[i];
   if (rc == SPEEXHIP_ERR_ALLOC_FAILED) {
@@ -693,7 +701,7 @@ int Batch::set_rate_frac(uint32_t ratio_num, uint32_t ratio_den, uint32_t in_rat
   FilterSpec next;
   const int design_rc =
       design_filter_frac(ratio_num, ratio_den, in_rate, out_rate, filter_.quality, &next, /*fill_table=*/false);
-  if (design_rc != SPEEXHIP_ERR_SUCCESS && design_rc != SPEEXHIP_ERR_ALLOC_FAILED) return design_rc;
+  if (!ran(design_rc)) return design_rc;
   // phase numerators move to the new denominator (resample.c:1130-1139; next.num / next.den are set
   // even when the design failed later on).  On overflow the reference returns RESAMPLER_ERR_OVERFLOW from
   // the middle of that loop: it has ALREADY stored the new rates and the reduced ratio (:1119-1127), so
@@ -713,7 +721,7 @@ int Batch::set_rate_frac(uint32_t ratio_num, uint32_t ratio_den, uint32_t in_rat
     }
   }
   const int rc = change_filter(next, design_rc, &frac);
-  if (rc == SPEEXHIP_ERR_SUCCESS || rc == SPEEXHIP_ERR_ALLOC_FAILED) shown_valid_ = false;  // filter_ holds the truth again
+  if (ran(rc)) shown_valid_ = false;  // filter_ holds the truth again
   return rc;
 }
 
@@ -724,7 +732,7 @@ int Batch::set_quality(int quality) {
   // the stored ratio is already reduced, so designing from it reproduces num/den
   const int design_rc =
       design_filter_frac(filter_.num, filter_.den, filter_.in_rate, filter_.out_rate, quality, &next, /*fill_table=*/false);
-  if (design_rc != SPEEXHIP_ERR_SUCCESS && design_rc != SPEEXHIP_ERR_ALLOC_FAILED) return design_rc;
+  if (!ran(design_rc)) return design_rc;
   return change_filter(next, design_rc, nullptr);
 }
 
@@ -784,9 +792,7 @@ Batch::~Batch() {
 }
 
 CallPlan Batch::peek(uint32_t s, uint32_t in_len, uint32_t out_capacity, bool float_io) const {
-  EntryRules rules;
-  rules.block_in = block_in();
-  rules.float_entry = float_io;
+  const EntryRules rules = entry_rules(float_io);
   // (an interleaved call reports the counters of its LAST channel, resample.c:1070-1078)
   return plan_call(filter_.num, filter_.den, in_len, out_capacity, P(s, channels_ - 1), rules);
 }
@@ -846,9 +852,7 @@ int Batch::process_device(const void *d_in, uint64_t in_stride, uint32_t *in_len
   ON_DEVICE();
   // the int16 entry point emits at most 1024 outputs per 160-frame block (its stack buffer,
   // resample.c:982-991); the float entry point has no such cap (resample.c:943)
-  EntryRules rules;
-  rules.block_in = block_in();
-  rules.float_entry = float_io;
+  const EntryRules rules = entry_rules(float_io);
   for (uint32_t s = 0; s < n_streams_; s++)
     if (!uniform(s)) {
       // channels that the per-channel entry points moved apart: one channel at a time, as the
@@ -889,12 +893,7 @@ int Batch::run_channel(uint32_t c, const void *d_in, uint32_t in_stride, uint32_
   // (launch_exact and its kernel read none of k_shift, base_shift, tile_begin, m_total)
   fill_desc(d, 0, c, d_in, d_out, in_frames, plan);
   const ExactStrides strides = {in_stride, out_stride, channels_};
-  ExactGeometry geo = tables_->plans.geo_ch;
-  if (zero_mode_) {  // the window geometry belongs to the filter that is no longer in force
-    geo.staged = false;
-    geo.lds_bytes = 0;
-    geo.outs_per_block = 256;
-  }
+  const ExactGeometry geo = zero_mode_ ? zero_geometry(tables_->plans.geo_ch) : tables_->plans.geo_ch;
   const hipError_t e = launch_exact(filter_, geo, tables_->table, 1, &pack, 1, plan.produced, float_io, stream, &strides, zero_mode_);
   if (hip_failed(e, "kernel launch")) return SPEEXHIP_ERR_DEVICE;
   if (d.hist_keep != 0)
@@ -914,9 +913,7 @@ int Batch::process_split(const void *d_in, uint32_t *in_len, void *d_out, uint32
   const size_t es = float_io ? sizeof(float) : sizeof(int16_t);
   const SplitLayout interleaved = {1, 1, channels_, channels_};
   const SplitLayout &at = layout != nullptr ? *layout : interleaved;
-  EntryRules rules;
-  rules.block_in = block_in();
-  rules.float_entry = float_io;
+  const EntryRules rules = entry_rules(float_io);
   const uint32_t want_in = *in_len, want_out = *out_len;
   if (want_in != 0 && want_out != 0) started_[0] = 1;
   for (uint32_t c = 0; c < channels_; c++) {
@@ -943,11 +940,7 @@ int Batch::launch_chunk(const StreamDesc *descs, const DescPack &pack, uint32_t 
   hipError_t e = hipSuccess;
   switch (c.family) {
     case KernelFamily::Zero: {
-      ExactGeometry geo = p.geo;  // (its window geometry belongs to the filter no longer in force)
-      geo.staged = false;
-      geo.lds_bytes = 0;
-      geo.outs_per_block = 256;
-      e = launch_exact(filter_, geo, t.table, channels_, &pack, n, max_out, float_io, stream, nullptr, true);
+      e = launch_exact(filter_, zero_geometry(p.geo), t.table, channels_, &pack, n, max_out, float_io, stream, nullptr, true);
       break;
     }
     case KernelFamily::Exact:
@@ -1039,30 +1032,6 @@ void Batch::int16_call_done(const CallPlan *plans, uint32_t n) {
   float_seen_ = false;
 }
 
-// Staging buffers of the host-buffer calls (grow_stage), each taken only when a call needs it: small calls run on the
-// pinned pair alone, large ones on the device pair alone (the runtime copies straight from / to the caller's memory).
-int Batch::ensure_stage(size_t dev_in, size_t dev_out, size_t pin_in, size_t pin_out) {
-  if (own_stream_ == nullptr) HIP_TRY(pool::stream_get(device_, &own_stream_));
-  int rc = grow_stage(device_, &d_stage_in_, &stage_in_cap_, dev_in, false);
-  if (rc == SPEEXHIP_ERR_SUCCESS) rc = grow_stage(device_, &d_stage_out_, &stage_out_cap_, dev_out, false);
-  if (rc == SPEEXHIP_ERR_SUCCESS) rc = grow_stage(device_, &h_pin_in_, &pin_in_cap_, pin_in, true);
-  if (rc == SPEEXHIP_ERR_SUCCESS) rc = grow_stage(device_, &h_pin_out_, &pin_out_cap_, pin_out, true);
-  return rc;
-}
-
-// Brings a host input onto the device the way `via` says (host_transfer.h) and sets *src to what the kernels read:
-// nullptr for an absent or empty input.
-int Batch::stage_input(Via via, const void *in, size_t bytes, const void *pin, const void **src) {
-  *src = nullptr;
-  if (via == Via::InPlace) *src = pin;
-  if (via == Via::None || via == Via::InPlace || bytes == 0) return SPEEXHIP_ERR_SUCCESS;
-  if (via == Via::Bounce || via == Via::Staged) std::memcpy(h_pin_in_, in, bytes);
-  if (via == Via::Copy) HIP_TRY(hipMemcpyAsync(d_stage_in_, in, bytes, hipMemcpyHostToDevice, own_stream_));
-  if (via == Via::Staged) HIP_TRY(hipMemcpyAsync(d_stage_in_, h_pin_in_, bytes, hipMemcpyHostToDevice, own_stream_));
-  *src = via == Via::Bounce ? h_pin_in_ : d_stage_in_;
-  return SPEEXHIP_ERR_SUCCESS;
-}
-
 // The second stream of a piecewise call: one of the pool's shared streams that is NOT this state's own one (on the
 // same stream the copies and the launches would simply take turns: correct, but nothing overlaps).
 bool Batch::have_copy_stream() {
@@ -1091,9 +1060,7 @@ bool Batch::have_copy_stream() {
 int Batch::take_in_pieces(const void *in, uint32_t *in_len, uint32_t *out_len, bool float_io, void *blk, uint32_t pieces) {
   const size_t es = float_io ? sizeof(float) : sizeof(int16_t);
   const uint32_t frames = *in_len;
-  EntryRules rules;
-  rules.block_in = block_in();
-  rules.float_entry = float_io;
+  const EntryRules rules = entry_rules(float_io);
   const CallPlan plan = plan_call(filter_.num, filter_.den, frames, *out_len, P(0, 0), rules);
   if (frames != 0 && *out_len != 0) started_[0] = 1;
   const size_t in_bytes = static_cast<size_t>(frames) * channels_ * es;
@@ -1184,11 +1151,8 @@ int Batch::process_host_take(const void *in, uint32_t *in_len, uint32_t *out_len
   const size_t es = float_io ? sizeof(float) : sizeof(int16_t);
   const uint32_t frames = *in_len;
   const bool split = !uniform(0);
-  uint32_t will_make = 0;
-  for (uint32_t c = 0; c < (split ? channels_ : 1u); c++)
-    will_make = std::max(will_make, produced_closed_form(filter_.num, filter_.den, frames, *out_len, P(0, c)));
   const size_t in_bytes = static_cast<size_t>(frames) * channels_ * es;
-  const size_t out_bytes = static_cast<size_t>(will_make) * channels_ * es;
+  const size_t out_bytes = static_cast<size_t>(will_make(frames, *out_len)) * channels_ * es;
   // (+ 64 bytes behind the samples: the completion word)  Nothing has touched the state yet: without a block the
   // caller makes the copying call instead.
   void *blk = nullptr;
@@ -1212,30 +1176,30 @@ int Batch::process_host_take(const void *in, uint32_t *in_len, uint32_t *out_len
   // it lies -- ONE launch whose loads and stores cross PCIe in opposite directions at the same time, no staging copy, no
   // second stream (the pieces above overlap the two directions only partly and pay ~15 us per piece for it).
   // The result is the block (InPlace); the input takes the rule of host_transfer.h.
-  const void *pin_in = (split || zero_mode_ || in == nullptr) ? nullptr : pinned_view(in, in_bytes);
-  const Via in_via = route_side(in_bytes, in != nullptr, pin_in != nullptr,
-                                small_call(in != nullptr && pin_in == nullptr ? in_bytes : 0, 0));
+  HostCallShape shape;
+  shape.take = true;
+  const void *pin_in = nullptr;
+  void *no_out = nullptr;
+  if (!split && !zero_mode_) pinned_sides(in, in_bytes, nullptr, 0, &pin_in, &no_out);
+  shape.in = flat_side(in != nullptr, pin_in != nullptr, in_bytes);
+  shape.out = flat_side(true, true, out_bytes);
+  const HostRoute route = route_host_call(shape);
   if (split || zero_mode_) {
     rc = process_host(in, in_len, blk, out_len, float_io);
-    if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
-  } else if (in_via == Via::Copy && pieces >= 2 && frames < 0x40000000u && have_copy_stream()) {
+    if (!ran(rc)) return rc;
+  } else if (route.in == Via::Copy && pieces >= 2 && frames < 0x40000000u && have_copy_stream()) {
     rc = take_in_pieces(in, in_len, out_len, float_io, blk, pieces);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   } else {
-    DrainOnExit drain(&own_stream_);
-    rc = ensure_stage(device_part(in_via, in_bytes), 0, pinned_part(in_via, in_bytes), 0);
+    HostCall call(this);
+    const HostPiece piece = {in, 0, in_bytes};
+    call.word = static_cast<char *>(blk) + align64(out_bytes);  // (behind the samples, in the block)
+    rc = call.begin(route, &piece, 1, pin_in, blk);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-    const void *src = nullptr;
-    rc = stage_input(in_via, in, in_bytes, pin_in, &src);
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-    Wait wait;
-    wait.add(in_via, in_bytes);
-    wait.add(Via::InPlace, out_bytes);
-    rc = process_device(src, 0, in_len, blk, 0, out_len, float_io, own_stream_);
-    if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
-    const int wrc = wait_call(own_stream_, wait, static_cast<char *>(blk) + align64(out_bytes), 1u);
+    rc = process_device(call.src, 0, in_len, call.dst, 0, out_len, float_io, own_stream_);
+    if (!ran(rc)) return rc;
+    const int wrc = call.finish_whole(blk, static_cast<size_t>(*out_len) * channels_ * es);
     if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
-    drain.armed = false;
   }
   if (*out_len == 0) return rc;  // (the guard returns the block)
   guard.p = nullptr;
@@ -1249,70 +1213,30 @@ int Batch::process_host(const void *in, uint32_t *in_len, void *out, uint32_t *o
   if (n_streams_ != 1) return SPEEXHIP_ERR_BAD_STATE;
   ON_DEVICE();
   const size_t es = float_io ? sizeof(float) : sizeof(int16_t);
-  const uint32_t frames = *in_len;
   const bool split = !uniform(0);
   // only as many output frames as this call can produce need a device buffer
-  uint32_t will_make = 0;
-  for (uint32_t c = 0; c < (split ? channels_ : 1u); c++)
-    will_make = std::max(will_make, produced_closed_form(filter_.num, filter_.den, frames, *out_len, P(0, c)));
-  const size_t in_bytes = static_cast<size_t>(frames) * channels_ * es;
-  const size_t out_bytes = static_cast<size_t>(will_make) * channels_ * es;
-  int rc = SPEEXHIP_ERR_SUCCESS;
-  DrainOnExit drain(&own_stream_);
-  if (split) {
-    // channels at different positions write different numbers of frames: fetch the whole block
-    // and hand the caller only the samples each channel really wrote
-    const Via in_via = route_side(in_bytes, in != nullptr, false, false);
-    rc = ensure_stage(in_bytes, out_bytes, pinned_part(in_via, in_bytes), out_bytes);
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-    const void *src = nullptr;
-    rc = stage_input(in_via, in, in_bytes, nullptr, &src);
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-    std::vector<CallPlan> plans;
-    rc = process_split(src, in_len, d_stage_out_, out_len, float_io, own_stream_, &plans);
-    if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
-    uint32_t most = 0;
-    for (const CallPlan &pl : plans) most = std::max(most, pl.produced);
-    const size_t bytes = static_cast<size_t>(most) * channels_ * es;
-    if (bytes != 0) HIP_TRY(hipMemcpyAsync(h_pin_out_, d_stage_out_, bytes, hipMemcpyDeviceToHost, own_stream_));
-    HIP_TRY(hipStreamSynchronize(own_stream_));
-    drain.armed = false;
-    for (uint32_t c = 0; c < channels_; c++)
-      for (uint32_t j = 0; j < plans[c].produced; j++)
-        std::memcpy(static_cast<char *>(out) + (static_cast<size_t>(j) * channels_ + c) * es,
-                    h_pin_out_ + (static_cast<size_t>(j) * channels_ + c) * es, es);
-    return rc;
-  }
-  // Both sides by the rule of host_transfer.h.  (A pinned result that overlaps its chunk: the chunk is taken in whole
-  // before anything is written, as on pageable buffers.)
-  const void *pin_in = in != nullptr ? pinned_view(in, in_bytes) : nullptr;
-  void *pin_out = pinned_view(out, out_bytes);
-  if (pin_in != nullptr && pin_out != nullptr && buffers_overlap(in, in_bytes, out, out_bytes)) pin_in = nullptr;
-  const bool small = small_call(in != nullptr && pin_in == nullptr ? in_bytes : 0, pin_out == nullptr ? out_bytes : 0);
-  const Via in_via = route_side(in_bytes, in != nullptr, pin_in != nullptr, small);
-  const Via out_via = route_side(out_bytes, true, pin_out != nullptr, small);
-  Wait wait;
-  wait.add(in_via, in_bytes);
-  wait.add(out_via, out_bytes);
-  // (+ 64 bytes for a polled wait: its completion word lives behind the samples, in the pinned result buffer)
-  rc = ensure_stage(device_part(in_via, in_bytes), device_part(out_via, out_bytes), pinned_part(in_via, in_bytes),
-                    pinned_part(out_via, out_bytes) + (wait.sync ? 0 : 64));
+  const size_t in_bytes = static_cast<size_t>(*in_len) * channels_ * es;
+  const size_t out_bytes = static_cast<size_t>(will_make(*in_len, *out_len)) * channels_ * es;
+  // (channels at different positions write different numbers of frames: the block is fetched whole and the caller handed
+  //  only the samples each channel really wrote, so nothing is used in place there)
+  const void *pin_in = nullptr;
+  void *pin_out = nullptr;
+  if (!split) pinned_sides(in, in_bytes, out, out_bytes, &pin_in, &pin_out);
+  HostCallShape shape;
+  shape.split = split;
+  shape.in = flat_side(in != nullptr, pin_in != nullptr, in_bytes);
+  shape.out = flat_side(true, pin_out != nullptr, out_bytes);
+  HostCall call(this);
+  const HostPiece piece = {in, 0, in_bytes};
+  int rc = call.begin(route_host_call(shape), &piece, 1, pin_in, pin_out);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  const void *src = nullptr;
-  rc = stage_input(in_via, in, in_bytes, pin_in, &src);
-  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  if (src == nullptr && in != nullptr) src = h_pin_out_;  // (an empty chunk, not silence: no frame is read, any non-null address serves)
-  void *dst = out_via == Via::InPlace ? pin_out : out_via == Via::Bounce ? static_cast<void *>(h_pin_out_) : static_cast<void *>(d_stage_out_);
-  rc = process_device(src, 0, in_len, dst, 0, out_len, float_io, own_stream_);
-  if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
-  const size_t made = static_cast<size_t>(*out_len) * channels_ * es;
-  if (device_part(out_via, made) != 0)
-    HIP_TRY(hipMemcpyAsync(out_via == Via::Copy ? out : h_pin_out_, d_stage_out_, made, hipMemcpyDeviceToHost, own_stream_));
-  const int wrc = wait_call(own_stream_, wait, tail_word(h_pin_out_, pin_out_cap_), ++done_seq_);
-  if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
-  drain.armed = false;
-  if (pinned_part(out_via, made) != 0) std::memcpy(out, h_pin_out_, made);
-  return rc;
+  std::vector<CallPlan> plans;
+  rc = split ? process_split(call.src, in_len, call.dst, out_len, float_io, own_stream_, &plans)
+             : process_device(call.src, 0, in_len, call.dst, 0, out_len, float_io, own_stream_);
+  if (!ran(rc)) return rc;
+  const int frc = split ? call.finish_samples(out, channels_, channels_, es, made_per_channel(channels_, 0, plans.data()).data())
+                        : call.finish_whole(out, static_cast<size_t>(*out_len) * channels_ * es);
+  return frc != SPEEXHIP_ERR_SUCCESS ? frc : rc;
 }
 
 // speex_resampler_process_int / _process_float (resample.c:927-1036): ONE channel, host buffers
@@ -1324,33 +1248,24 @@ int Batch::process_channel_host(uint32_t c, const void *in, uint32_t *in_len, vo
   if (c >= channels_) return SPEEXHIP_ERR_INVALID_ARG;
   ON_DEVICE();
   const size_t es = float_io ? sizeof(float) : sizeof(int16_t);
-  EntryRules rules;
-  rules.block_in = block_in();
-  rules.float_entry = float_io;
+  const EntryRules rules = entry_rules(float_io);
   const uint32_t frames = *in_len;
   const CallPlan plan = plan_call(filter_.num, filter_.den, frames, *out_len, P(0, c), rules);
   if (frames != 0 && *out_len != 0) started_[0] = 1;
-  const size_t line_in = static_cast<size_t>(frames) * es, line_out = static_cast<size_t>(plan.produced) * es;
-  DrainOnExit drain(&own_stream_);
-  int rc = ensure_stage(line_in, line_out, line_in, line_out);
+  HostCallShape shape;
+  shape.strided = true;
+  shape.in = flat_side(in != nullptr, false, static_cast<size_t>(frames) * es);
+  shape.out = flat_side(true, false, static_cast<size_t>(plan.produced) * es);
+  HostCall call(this);
+  const HostPiece line = {in, 0, shape.in.image};
+  call.line_step = in_stride_;
+  call.line_es = es;
+  int rc = call.begin(route_host_call(shape), &line, 1, nullptr, nullptr);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  if (in != nullptr && frames != 0) {
-    for (uint32_t j = 0; j < frames; j++)
-      std::memcpy(h_pin_in_ + static_cast<size_t>(j) * es,
-                  static_cast<const char *>(in) + static_cast<size_t>(j) * in_stride_ * es, es);
-    HIP_TRY(hipMemcpyAsync(d_stage_in_, h_pin_in_, static_cast<size_t>(frames) * es, hipMemcpyHostToDevice,
-                           own_stream_));
-  }
-  rc = run_channel(c, in != nullptr ? d_stage_in_ : nullptr, 1, frames, d_stage_out_, 1, plan, float_io, own_stream_);
+  rc = run_channel(c, call.src, 1, frames, call.dst, 1, plan, float_io, own_stream_);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  if (plan.produced != 0)
-    HIP_TRY(hipMemcpyAsync(h_pin_out_, d_stage_out_, static_cast<size_t>(plan.produced) * es, hipMemcpyDeviceToHost,
-                           own_stream_));
-  HIP_TRY(hipStreamSynchronize(own_stream_));
-  drain.armed = false;
-  for (uint32_t j = 0; j < plan.produced; j++)
-    std::memcpy(static_cast<char *>(out) + static_cast<size_t>(j) * out_stride_ * es,
-                h_pin_out_ + static_cast<size_t>(j) * es, es);
+  rc = call.finish_samples(out, 1, out_stride_, es, &plan.produced);
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   P(0, c) = plan.end;
   *in_len = plan.consumed;
   *out_len = plan.produced;
@@ -1376,14 +1291,12 @@ int Batch::process_host_chunks(uint32_t n_chunks, const void *const *in, uint32_
     char *o = static_cast<char *>(out);
     for (uint32_t i = 0; i < n_chunks; i++) {
       last = process_host(in != nullptr ? in[i] : nullptr, &in_len[i], o, &out_len[i], float_io);
-      if (last != SPEEXHIP_ERR_SUCCESS && last != SPEEXHIP_ERR_ALLOC_FAILED) return last;
+      if (!ran(last)) return last;
       o += static_cast<size_t>(out_len[i]) * fb;
     }
     return last;
   }
-  EntryRules rules;
-  rules.block_in = block_in();
-  rules.float_entry = float_io;
+  const EntryRules rules = entry_rules(float_io);
   struct Group {
     CallPlan fused;
     uint64_t in_off = 0, out_off = 0;  // frames into the staging buffers
@@ -1421,37 +1334,32 @@ int Batch::process_host_chunks(uint32_t n_chunks, const void *const *in, uint32_
     }
     if (frames > 0x7fffffffull || made > 0x7fffffffull) return SPEEXHIP_ERR_OVERFLOW;
   }
-  const bool direct_out = made * fb >= kDirectCopyBytes;
   // Small runs -- what a Transform holds back, eight 64 KiB chunks say -- are all latency, like small single calls
   // (process_host): the kernels read the pinned bounce buffer and write the pinned result buffer straight through
   // PCIe, one wait, no copy-engine hand-overs.  (Until round 5 every coalesced run went through the device staging
   // buffers: H2D copy, launch, D2H copy -- three in-order steps of ~10 us hand-over each -- and `coalesceChunks: 8` was
   // SLOWER than the plain pipe on four of the reference's seven test tuples, profiles/r04_node_bench.json.)
-  const bool zero_copy = frames * fb < kZeroCopyBelow && made * fb < kZeroCopyBelow;
-  DrainOnExit drain(&own_stream_);
-  int rc = zero_copy ? ensure_stage(0, 0, frames * fb, made * fb + 64)
-                     : ensure_stage(frames * fb, made * fb, frames * fb, direct_out ? 0 : made * fb);
-  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  HostCallShape shape;
+  shape.gathered = true;
+  shape.in = flat_side(true, false, frames * fb);  // (a null chunk is gathered too, as zeros)
+  shape.out = flat_side(true, false, made * fb);
+  std::vector<HostPiece> pieces(n_chunks);
   size_t off = 0;
   for (uint32_t i = 0; i < n_chunks; i++) {  // frames a call drops never reach the GPU
     const size_t bytes = (plans[i].consumed + (plans[i].consumed < in_len[i] ? 1u : 0u)) * fb;
-    if (in != nullptr && in[i] != nullptr)
-      std::memcpy(h_pin_in_ + off, in[i], bytes);
-    else
-      std::memset(h_pin_in_ + off, 0, bytes);
+    pieces[i] = {in != nullptr ? in[i] : nullptr, off, bytes};
     off += bytes;
   }
-  if (off != 0 && !zero_copy) HIP_TRY(hipMemcpyAsync(d_stage_in_, h_pin_in_, off, hipMemcpyHostToDevice, own_stream_));
-  char *src = zero_copy ? h_pin_in_ : d_stage_in_, *dst = zero_copy ? h_pin_out_ : d_stage_out_;
+  HostCall call(this);
+  int rc = call.begin(route_host_call(shape), pieces.data(), n_chunks, nullptr, nullptr);
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   for (const Group &g : groups) {
-    rc = run_plans(src + g.in_off * fb, 0, &g.readable, dst + g.out_off * fb, 0, &g.fused, float_io, own_stream_);
+    rc = run_plans(static_cast<const char *>(call.src) + g.in_off * fb, 0, &g.readable, static_cast<char *>(call.dst) + g.out_off * fb,
+                   0, &g.fused, float_io, own_stream_);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
-  if (made != 0 && !zero_copy)
-    HIP_TRY(hipMemcpyAsync(direct_out ? out : h_pin_out_, d_stage_out_, made * fb, hipMemcpyDeviceToHost, own_stream_));
-  HIP_TRY(hipStreamSynchronize(own_stream_));
-  drain.armed = false;
-  if (made != 0 && (zero_copy || !direct_out)) std::memcpy(out, h_pin_out_, made * fb);
+  rc = call.finish_whole(out, made * fb);
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   for (uint32_t i = 0; i < n_chunks; i++) {
     in_len[i] = plans[i].consumed;
     out_len[i] = plans[i].produced;

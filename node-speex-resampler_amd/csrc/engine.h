@@ -10,6 +10,7 @@
 
 #include "../../include/speexhip_resampler.h"
 #include "device_types.h"
+#include "engine_detail.h"
 #include "filter_design.h"
 #include "filter_plans.h"
 #include "host_transfer.h"
@@ -233,16 +234,63 @@ class Batch {
   // the DitherPack of streams [s0, s0 + n): first = position * per_frame (per_frame = 1: the position itself)
   DitherPack dither_pack(uint32_t s0, uint32_t n, uint32_t per_frame) const;
   void dither_advance(const uint32_t *produced);  // after a formatted or mixed call with dither on
-  // process_sides_device on own_stream_ with the host buffers of both sides routed around it (host_transfer.h)
-  int routed_host_call(const CallSide &in, size_t in_bytes, uint32_t *in_len, const CallSide &out, size_t out_bytes,
-                       uint32_t *out_len);
   // process_sides_host of a call with a planar side
   int planes_host_call(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len);
   int fetch_history(std::vector<float> *host);
   int quiesce();  // waits for this batch's own enqueued work (never for the whole device)
   uint32_t block_in() const { return line_ - (filter_.taps - 1); }
+  EntryRules entry_rules(bool float_io) const {
+    EntryRules rules;
+    rules.block_in = block_in();
+    rules.float_entry = float_io;
+    return rules;
+  }
+  // The most frames any channel of the one stream can produce from `frames` frames into room for `capacity` (integer
+  // arithmetic, nothing launched): only so many need a staging buffer.
+  uint32_t will_make(uint32_t frames, uint32_t capacity) const;
+  // frames each of n channels of a result received: `all`, or -- channels that stand apart -- each channel's own
+  static std::vector<uint32_t> made_per_channel(uint32_t n, uint32_t all, const CallPlan *apart) {
+    std::vector<uint32_t> made(n, all);
+    for (uint32_t c = 0; apart != nullptr && c < n; c++) made[c] = apart[c].produced;
+    return made;
+  }
+  // host_call.cpp -- the mechanics of a single-state host-buffer call around its device call: what route_host_call
+  // (host_transfer.h) decided, carried out on own_stream_ and the state's staging buffers.
+  //   HostCall call(this);  call.begin(route, pieces, ...);  <the device call on call.src / call.dst>;  call.finish_...(...)
+  // The calls are synchronous and their buffers go on to the next call: whichever way the function is left before a
+  // finish_* has waited, `drain` waits for everything enqueued.
+  struct HostPiece {    // a run of host memory and where it lies in the side's staging image
+    const void *host;   // (an input piece at nullptr: zeros)
+    size_t at, bytes;
+  };
+  struct HostCall {
+    explicit HostCall(Batch *batch) : b(batch), drain(&batch->own_stream_) {}
+    // Set before begin by the one entry point each concerns: where a take call's completion word lies (else the tail of
+    // the pinned result buffer); the samples of a strided line (route.strided) -- line_es bytes each, line_step samples
+    // apart in the caller's memory, 0 included: every frame reads the first sample.
+    void *word = nullptr;
+    uint32_t line_step = 0;
+    size_t line_es = 0;
+    // Takes the staging buffers and brings the input -- one region, the planes of an image, gathered chunks, a strided
+    // line -- to where the kernels read it.  pinned_in / pinned_out: the device's view of a side used in place.
+    int begin(const HostRoute &route, const HostPiece *in, uint32_t n_in, const void *pinned_in, void *pinned_out);
+    const void *src = nullptr;  // what the device call reads (nullptr: silence) ...
+    void *dst = nullptr;        // ... and writes
+    // The result back, the wait, the hand-over: the first `bytes` of the image as they are; plane c's first made[c]
+    // samples from `pitch` bytes apart; or sample by sample -- channel c's first made[c] samples of frames of n samples
+    // into frames of host_step samples (channels that stand apart; n = 1: a strided line).
+    int finish_whole(void *out, size_t bytes);
+    int finish_planes(void *const *planes, uint32_t n, size_t pitch, size_t es, const uint32_t *made);
+    int finish_samples(void *out, uint32_t n, uint32_t host_step, size_t es, const uint32_t *made);
+
+   private:
+    int wait();
+    Batch *b;
+    detail::DrainOnExit drain;
+    HostRoute r;
+  };
   int ensure_stage(size_t dev_in, size_t dev_out, size_t pin_in, size_t pin_out);
-  int stage_input(Via via, const void *in, size_t bytes, const void *pin, const void **src);
+  static void pinned_sides(const void *in, size_t in_bytes, void *out, size_t out_bytes, const void **pin_in, void **pin_out);
   int run_plans(const void *d_in, uint64_t in_stride, const uint32_t *in_frames, void *d_out,
                 uint64_t out_stride, const CallPlan *plans, bool float_io, hipStream_t stream);
   // The descriptor of stream s (from its channel c on: 0 for a launch of whole frames) for `plan`: the two history

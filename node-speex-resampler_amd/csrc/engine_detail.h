@@ -71,9 +71,8 @@ inline bool buffers_overlap(const void *a, size_t na, const void *b, size_t nb) 
   return x < y + nb && y < x + na;
 }
 inline char *tail_word(char *buf, size_t cap) { return buf == nullptr ? nullptr : buf + ((cap - 64) & ~static_cast<size_t>(63)); }
-// bytes of a side that pass through a device / a pinned staging buffer
-inline size_t device_part(Via v, size_t bytes) { return v == Via::Copy || v == Via::Staged ? bytes : 0; }
-inline size_t pinned_part(Via v, size_t bytes) { return v == Via::Bounce || v == Via::Staged ? bytes : 0; }
+// A call that ran: ALLOC_FAILED is what the zero fallback answers after writing its silence, counters and state moved.
+inline bool ran(int rc) { return rc == SPEEXHIP_ERR_SUCCESS || rc == SPEEXHIP_ERR_ALLOC_FAILED; }
 
 // engine.cpp: the wait a host-buffer call's `Wait` chose, and the grow-only staging buffers
 int wait_call(hipStream_t stream, const Wait &w, void *word, uint32_t seq);

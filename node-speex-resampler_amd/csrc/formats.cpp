@@ -104,18 +104,16 @@ int Batch::process_sides_device(const CallSide &in_side, uint32_t *in_len, const
     }
   if (same_bytes(in, out, dith)) {
     const int rc = process_device(in.base, in.stride, in_len, out.base, out.stride, out_len, in.fmt != SPEEXHIP_FMT_S16, stream);
-    if (dith && (rc == SPEEXHIP_ERR_SUCCESS || rc == SPEEXHIP_ERR_ALLOC_FAILED)) dither_advance(out_len);
+    if (dith && ran(rc)) dither_advance(out_len);
     return rc;
   }
   if (planar_float_call(in, out) && !split) {
     const int rc = process_planar_device(in.base, in.stride, in.plane_stride, in_len, out.base, out.stride, out.plane_stride,
                                          out_len, true, stream);
-    if (dith && (rc == SPEEXHIP_ERR_SUCCESS || rc == SPEEXHIP_ERR_ALLOC_FAILED)) dither_advance(out_len);
+    if (dith && ran(rc)) dither_advance(out_len);
     return rc;
   }
-  EntryRules rules;
-  rules.block_in = block_in();
-  rules.float_entry = true;
+  const EntryRules rules = entry_rules(true);
   // what the float call will do, known before anything is launched (integer arithmetic): sizes the images
   uint32_t most_in = 0, most_out = 0;
   for (uint32_t s = 0; s < n_streams_; s++) {
@@ -152,7 +150,7 @@ int Batch::process_sides_device(const CallSide &in_side, uint32_t *in_len, const
   else
     rc = process_device(image_in, pass_in ? in_pitch : in.stride, in_len, image_out, pass_out ? out_pitch : out.stride, out_len,
                         true, stream);
-  if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
+  if (!ran(rc)) return rc;
   if (plans_out != nullptr) *plans_out = plans;
   if (pass_out) {
     // (out_len: what the float call produced)
@@ -196,42 +194,7 @@ int Batch::process_host_many_sides(uint32_t n, Batch *const *st, const CallSide 
 
 // process_sides_device on own_stream_ around a single-stream call's host buffers: the raw bytes of both sides move by the
 // rule of host_transfer.h -- in place when pinned, through the bounce buffers when small, by the runtime's staged copy when
-// large.
-int Batch::routed_host_call(const CallSide &in_side, size_t in_bytes, uint32_t *in_len, const CallSide &out_side,
-                            size_t out_bytes, uint32_t *out_len) {
-  const void *in = in_side.base;
-  void *out = out_side.base;
-  int rc = SPEEXHIP_ERR_SUCCESS;
-  DrainOnExit drain(&own_stream_);
-  const void *pin_in = in != nullptr ? pinned_view(in, in_bytes) : nullptr;
-  void *pin_out = pinned_view(out, out_bytes);
-  if (pin_in != nullptr && pin_out != nullptr && buffers_overlap(in, in_bytes, out, out_bytes)) pin_in = nullptr;
-  const bool small = small_call(in != nullptr && pin_in == nullptr ? in_bytes : 0, pin_out == nullptr ? out_bytes : 0);
-  const Via in_via = route_side(in_bytes, in != nullptr, pin_in != nullptr, small);
-  const Via out_via = route_side(out_bytes, true, pin_out != nullptr, small);
-  Wait wait;
-  wait.add(in_via, in_bytes);
-  wait.add(out_via, out_bytes);
-  rc = ensure_stage(device_part(in_via, in_bytes), device_part(out_via, out_bytes), pinned_part(in_via, in_bytes),
-                    pinned_part(out_via, out_bytes) + (wait.sync ? 0 : 64));
-  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  const void *src = nullptr;
-  rc = stage_input(in_via, in, in_bytes, pin_in, &src);
-  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  if (src == nullptr && in != nullptr) src = h_pin_out_;  // (an empty chunk, not silence)
-  void *dst = out_via == Via::InPlace ? pin_out : out_via == Via::Bounce ? static_cast<void *>(h_pin_out_) : static_cast<void *>(d_stage_out_);
-  rc = process_sides_device(at(in_side, src), in_len, at(out_side, dst), out_len, own_stream_);
-  if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
-  const size_t made = static_cast<size_t>(*out_len) * out_side.channels * sample_bytes(out_side.fmt);
-  if (device_part(out_via, made) != 0)
-    HIP_TRY(hipMemcpyAsync(out_via == Via::Copy ? out : h_pin_out_, d_stage_out_, made, hipMemcpyDeviceToHost, own_stream_));
-  const int wrc = wait_call(own_stream_, wait, tail_word(h_pin_out_, pin_out_cap_), ++done_seq_);
-  if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
-  drain.armed = false;
-  if (pinned_part(out_via, made) != 0) std::memcpy(out, h_pin_out_, made);
-  return rc;
-}
-
+// large; channels that stand apart as in process_host.
 int Batch::process_sides_host(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len) {
   if (n_streams_ != 1) return SPEEXHIP_ERR_BAD_STATE;
   if (!side_ok(in, channels_) || !side_ok(out, channels_)) return SPEEXHIP_ERR_INVALID_ARG;
@@ -250,48 +213,36 @@ int Batch::process_sides_host(const CallSide &in, uint32_t *in_len, const CallSi
   if (split && dith && !mixed) return SPEEXHIP_ERR_BAD_STATE;
   if (same_bytes(in, out, dith)) {
     const int rc = process_host(in.base, in_len, out.base, out_len, in.fmt != SPEEXHIP_FMT_S16);
-    if (dith && (rc == SPEEXHIP_ERR_SUCCESS || rc == SPEEXHIP_ERR_ALLOC_FAILED)) dither_advance(out_len);
+    if (dith && ran(rc)) dither_advance(out_len);
     return rc;
   }
   ON_DEVICE();
   if (split && mixed) return SPEEXHIP_ERR_BAD_STATE;
-  const uint32_t frames = *in_len;
-  uint32_t will_make = 0;  // only as many output frames as this call can produce need a device buffer
-  for (uint32_t c = 0; c < (split ? channels_ : 1u); c++)
-    will_make = std::max(will_make, produced_closed_form(filter_.num, filter_.den, frames, *out_len, P(0, c)));
   const size_t bout = sample_bytes(out.fmt);
-  const size_t in_bytes = static_cast<size_t>(frames) * in.channels * sample_bytes(in.fmt);
-  const size_t out_bytes = static_cast<size_t>(will_make) * out.channels * bout;
-  if (!split) return routed_host_call(in, in_bytes, in_len, out, out_bytes, out_len);
-  int rc = SPEEXHIP_ERR_SUCCESS;
-  DrainOnExit drain(&own_stream_);
-  std::vector<CallPlan> plans;
-  // channels at different positions write different numbers of frames: fetch the whole block and hand the caller
-  // only the samples each channel really wrote (as process_host does)
-  const Via in_via = route_side(in_bytes, in.base != nullptr, false, false);
-  rc = ensure_stage(in_bytes, out_bytes, pinned_part(in_via, in_bytes), out_bytes);
+  // (only as many output frames as this call can produce need a device buffer)
+  const size_t in_bytes = static_cast<size_t>(*in_len) * in.channels * sample_bytes(in.fmt);
+  const size_t out_bytes = static_cast<size_t>(will_make(*in_len, *out_len)) * out.channels * bout;
+  const void *pin_in = nullptr;
+  void *pin_out = nullptr;
+  if (!split) pinned_sides(in.base, in_bytes, out.base, out_bytes, &pin_in, &pin_out);
+  HostCallShape shape;
+  shape.split = split;
+  shape.in = flat_side(in.base != nullptr, pin_in != nullptr, in_bytes);
+  shape.out = flat_side(true, pin_out != nullptr, out_bytes);
+  HostCall call(this);
+  const HostPiece piece = {in.base, 0, in_bytes};
+  int rc = call.begin(route_host_call(shape), &piece, 1, pin_in, pin_out);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  const void *src = nullptr;
-  rc = stage_input(in_via, in.base, in_bytes, nullptr, &src);
-  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  if (src == nullptr && in.base != nullptr) src = h_pin_out_;
-  rc = process_sides_device(at(in, src), in_len, at(out, d_stage_out_), out_len, own_stream_, &plans);
-  if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
-  uint32_t most = 0;
-  for (const CallPlan &pl : plans) most = std::max(most, pl.produced);
-  const size_t bytes = static_cast<size_t>(most) * channels_ * bout;
-  if (bytes != 0) HIP_TRY(hipMemcpyAsync(h_pin_out_, d_stage_out_, bytes, hipMemcpyDeviceToHost, own_stream_));
-  HIP_TRY(hipStreamSynchronize(own_stream_));
-  drain.armed = false;
-  for (uint32_t c = 0; c < channels_; c++)
-    for (uint32_t j = 0; j < plans[c].produced; j++)
-      std::memcpy(static_cast<char *>(out.base) + (static_cast<size_t>(j) * channels_ + c) * bout,
-                  h_pin_out_ + (static_cast<size_t>(j) * channels_ + c) * bout, bout);
-  return rc;
+  std::vector<CallPlan> plans;  // (of the channels that stand apart)
+  rc = process_sides_device(at(in, call.src), in_len, at(out, call.dst), out_len, own_stream_, split ? &plans : nullptr);
+  if (!ran(rc)) return rc;
+  const int frc = split ? call.finish_samples(out.base, channels_, channels_, bout, made_per_channel(channels_, 0, plans.data()).data())
+                        : call.finish_whole(out.base, static_cast<size_t>(*out_len) * out.channels * bout);
+  return frc != SPEEXHIP_ERR_SUCCESS ? frc : rc;
 }
 
 // A host call with a planar side.  Each side moves by its own rule (host_transfer.h): an interleaved side as in
-// routed_host_call -- in place when pinned, through the bounce buffer when small, by the runtime's staged copy when large --
+// process_sides_host above -- in place when pinned, through the bounce buffer when small, by the runtime's staged copy when large --
 // a planar side plane by plane into an image whose planes lie whole 128-byte lines apart, as in process_planar_host (all
 // planes of a side have one size, so one route serves the side).  process_sides_device then runs on the images.
 int Batch::planes_host_call(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len) {
@@ -311,11 +262,9 @@ int Batch::planes_host_call(const CallSide &in, uint32_t *in_len, const CallSide
   for (uint32_t c = 0; pl_out && out.planes != nullptr && c < out.channels; c++)
     if (out.planes[c] == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
   const uint32_t frames = *in_len;
-  uint32_t will_make = 0;  // only as many output frames as this call can produce are written (and need a device buffer)
-  for (uint32_t c = 0; c < (split ? channels_ : 1u); c++)
-    will_make = std::max(will_make, produced_closed_form(filter_.num, filter_.den, frames, *out_len, P(0, c)));
+  const uint32_t most = will_make(frames, *out_len);  // only so many output frames are written (and need a device buffer)
   const size_t bin = sample_bytes(in.fmt), bout = sample_bytes(out.fmt);
-  const size_t plane_in = frames * bin, plane_out = will_make * bout;
+  const size_t plane_in = frames * bin, plane_out = most * bout;
   for (uint32_t c = 0; pl_out && c < out.channels; c++) {
     for (uint32_t k = 0; k < c; k++)
       if (buffers_overlap(host_plane(out, c), plane_out, host_plane(out, k), plane_out)) return SPEEXHIP_ERR_PTR_OVERLAP;
@@ -324,76 +273,41 @@ int Batch::planes_host_call(const CallSide &in, uint32_t *in_len, const CallSide
   }
   ON_DEVICE();
   // what each side moves (payload) and the image the device call works on
-  const size_t in_pitch = align64(frames), out_pitch = align64(will_make);
+  const size_t in_pitch = align64(frames), out_pitch = align64(most);
   const size_t in_payload = plane_in * in.channels, out_payload = plane_out * out.channels;
-  const size_t in_bytes = pl_in ? in_pitch * in.channels * bin : in_payload;
-  const size_t out_bytes = pl_out ? out_pitch * out.channels * bout : out_payload;
   // (channels that stand apart write different numbers of frames: the block is fetched whole and the caller handed only
   //  what each channel really wrote, so nothing is used in place there)
-  const void *pin_in = !pl_in && present && !split ? pinned_view(in_flat.base, in_payload) : nullptr;
-  void *pin_out = !pl_out && !split ? pinned_view(out_flat.base, out_payload) : nullptr;
-  if (pin_in != nullptr && pin_out != nullptr && buffers_overlap(in_flat.base, in_payload, out_flat.base, out_payload)) pin_in = nullptr;
-  const bool small = small_call(present && pin_in == nullptr ? in_payload : 0, pin_out == nullptr ? out_payload : 0);
-  const Via in_via = route_side(pl_in ? plane_in : in_payload, present, pin_in != nullptr, small);
-  Via out_via = route_side(pl_out ? plane_out : out_payload, true, pin_out != nullptr, small);
-  if (split && !pl_out && out_via == Via::Copy) out_via = Via::Staged;  // (handed over sample by sample below)
-  Wait wait;
-  wait.add(in_via, in_bytes);
-  wait.add(out_via, out_bytes);
-  DrainOnExit drain(&own_stream_);
-  int rc = ensure_stage(device_part(in_via, in_bytes), device_part(out_via, out_bytes), pinned_part(in_via, in_bytes),
-                        pinned_part(out_via, out_bytes) + 64);
+  const void *pin_in = nullptr;
+  void *pin_out = nullptr;
+  if (!split)
+    pinned_sides(pl_in ? nullptr : in_flat.base, in_payload, pl_out ? nullptr : out_flat.base, out_payload, &pin_in, &pin_out);
+  HostCallShape shape;
+  shape.split = split;
+  shape.in = pl_in ? planar_side(present, plane_in, in_pitch * bin, in.channels) : flat_side(present, pin_in != nullptr, in_payload);
+  shape.out = pl_out ? planar_side(true, plane_out, out_pitch * bout, out.channels) : flat_side(true, pin_out != nullptr, out_payload);
+  std::vector<HostPiece> pieces(1, HostPiece{in_flat.base, 0, in_payload});
+  if (pl_in) pieces.resize(in.channels);
+  for (uint32_t c = 0; pl_in && c < in.channels; c++) pieces[c] = {present ? host_plane(in, c) : nullptr, c * in_pitch * bin, plane_in};
+  HostCall call(this);
+  int rc = call.begin(route_host_call(shape), pieces.data(), static_cast<uint32_t>(pieces.size()), pin_in, pin_out);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  const void *src = nullptr;
-  if (!pl_in) {
-    rc = stage_input(in_via, in_flat.base, in_payload, pin_in, &src);
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  } else if (present && frames != 0) {
-    for (uint32_t c = 0; c < in.channels; c++) {
-      if (in_via == Via::Copy)
-        HIP_TRY(hipMemcpyAsync(d_stage_in_ + c * in_pitch * bin, host_plane(in, c), plane_in, hipMemcpyHostToDevice, own_stream_));
-      else
-        std::memcpy(h_pin_in_ + c * in_pitch * bin, host_plane(in, c), plane_in);
-    }
-    if (in_via == Via::Staged) HIP_TRY(hipMemcpyAsync(d_stage_in_, h_pin_in_, in_bytes, hipMemcpyHostToDevice, own_stream_));
-    src = in_via == Via::Bounce ? h_pin_in_ : d_stage_in_;
-  }
-  if (src == nullptr && present) src = h_pin_out_;  // (an empty chunk, not silence)
-  void *dst = out_via == Via::InPlace ? pin_out : out_via == Via::Bounce ? static_cast<void *>(h_pin_out_) : static_cast<void *>(d_stage_out_);
   std::vector<CallPlan> plans;
-  rc = process_sides_device(pl_in ? planes_at(in, src, in_pitch) : at(in, src), in_len,
-                            pl_out ? planes_at(out, dst, out_pitch) : at(out, dst), out_len, own_stream_, &plans);
-  if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
+  rc = process_sides_device(pl_in ? planes_at(in, call.src, in_pitch) : at(in, call.src), in_len,
+                            pl_out ? planes_at(out, call.dst, out_pitch) : at(out, call.dst), out_len, own_stream_, &plans);
+  if (!ran(rc)) return rc;
   // frames each channel of the result received (channels that stand apart produce different numbers of them)
-  std::vector<uint32_t> made(out.channels, *out_len);
-  for (uint32_t c = 0; split && c < out.channels; c++) made[c] = plans[c].produced;
-  const uint32_t most = *std::max_element(made.begin(), made.end());
-  const size_t moved = pl_out ? out_bytes : static_cast<size_t>(most) * out.channels * bout;  // bytes of the result's image
-  if (out_via == Via::Copy && pl_out) {
-    for (uint32_t c = 0; c < out.channels; c++)
-      if (made[c] != 0)
-        HIP_TRY(hipMemcpyAsync(host_plane(out, c), d_stage_out_ + c * out_pitch * bout, made[c] * bout, hipMemcpyDeviceToHost, own_stream_));
-  } else if (out_via == Via::Copy) {
-    if (moved != 0) HIP_TRY(hipMemcpyAsync(out_flat.base, d_stage_out_, moved, hipMemcpyDeviceToHost, own_stream_));
-  } else if (device_part(out_via, moved) != 0) {
-    HIP_TRY(hipMemcpyAsync(h_pin_out_, d_stage_out_, moved, hipMemcpyDeviceToHost, own_stream_));
+  const std::vector<uint32_t> made = made_per_channel(out.channels, *out_len, split ? plans.data() : nullptr);
+  int frc;
+  if (pl_out) {
+    std::vector<void *> planes(out.channels);
+    for (uint32_t c = 0; c < out.channels; c++) planes[c] = host_plane(out, c);
+    frc = call.finish_planes(planes.data(), out.channels, out_pitch * bout, bout, made.data());
+  } else if (split) {
+    frc = call.finish_samples(out_flat.base, out.channels, out.channels, bout, made.data());
+  } else {
+    frc = call.finish_whole(out_flat.base, static_cast<size_t>(*out_len) * out.channels * bout);
   }
-  const int wrc = wait_call(own_stream_, wait, tail_word(h_pin_out_, pin_out_cap_), ++done_seq_);
-  if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
-  drain.armed = false;
-  const bool from_pinned = out_via == Via::Bounce || out_via == Via::Staged;
-  if (from_pinned && pl_out) {
-    for (uint32_t c = 0; c < out.channels; c++)
-      if (made[c] != 0) std::memcpy(host_plane(out, c), h_pin_out_ + c * out_pitch * bout, made[c] * bout);
-  } else if (from_pinned && !split) {
-    std::memcpy(out_flat.base, h_pin_out_, moved);
-  } else if (from_pinned) {
-    for (uint32_t c = 0; c < out.channels; c++)
-      for (uint32_t j = 0; j < made[c]; j++)
-        std::memcpy(static_cast<char *>(out_flat.base) + (static_cast<size_t>(j) * out.channels + c) * bout,
-                    h_pin_out_ + (static_cast<size_t>(j) * out.channels + c) * bout, bout);
-  }
-  return rc;
+  return frc != SPEEXHIP_ERR_SUCCESS ? frc : rc;
 }
 
 }  // namespace speexhip

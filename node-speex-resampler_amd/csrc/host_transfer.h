@@ -1,4 +1,7 @@
 // host_transfer.h -- how a host-buffer call moves its buffers and how it waits (host only; tools/san_host.cpp checks it).
+// route_host_call() at the end is the whole decision for a single-state call: every entry point describes its two sides
+// (HostCallShape) and gets the way of each, the wait and the sizes of the staging buffers (HostRoute); host_call.cpp
+// carries it out.  The many-states call (many.cpp) gathers many states into one range and uses the rule's parts itself.
 //
 // Each side of a call (its input, its result) reaches the GPU one of four ways:
 //   InPlace  the buffer is pinned memory (engine.cpp, pinned_view): the kernels read / write it through PCIe;
@@ -79,5 +82,77 @@ struct Wait {
   }
   uint32_t spin_us() const { return spin_budget_us(in_place); }
 };
+
+// ---- the decision of a single-state host-buffer call ----------------------------------------------------------------------
+// One side as the decision sees it.  A planar side (one buffer per channel) is judged plane by plane -- all planes of a side
+// have one size, so one way serves the side -- and staged as an image whose planes lie whole 128-byte lines apart.
+struct HostSide {
+  bool present = false;  // (an absent input is silence; a result is always present)
+  bool pinned = false;   // the kernels reach the buffer where it lies.  The caller's pinned lookup decides, and it is where a
+                         // pinned result overlapping its pinned chunk makes the chunk count as not pinned
+  bool planar = false;
+  size_t judged = 0;     // bytes route_side judges: one plane, or the whole interleaved buffer
+  size_t payload = 0;    // bytes of the caller's that move; they count toward small_call while pageable
+  size_t image = 0;      // bytes of the staging image: planes on whole lines, else the payload
+};
+// an interleaved buffer (or one line) of `bytes`; the planes of a side, `plane` bytes each, `pitch` bytes apart in the image
+inline HostSide flat_side(bool present, bool pinned, size_t bytes) { return HostSide{present, pinned, false, bytes, bytes, bytes}; }
+inline HostSide planar_side(bool present, size_t plane, size_t pitch, size_t n) {
+  return HostSide{present, false, true, plane, plane * n, pitch * n};
+}
+struct HostCallShape {
+  HostSide in, out;
+  bool split = false;     // the channels of the state stand apart: each writes its own number of frames
+  bool gathered = false;  // the input is gathered from several chunks (the chunks call)
+  bool strided = false;   // one channel's line with strides on both sides (the per-channel call)
+  bool take = false;      // the result is a block the caller owns afterwards (the take call; its out side is pinned)
+};
+struct HostRoute {
+  Via in = Via::None, out = Via::None;
+  Wait wait;
+  size_t dev_in = 0, dev_out = 0, pin_in = 0, pin_out = 0;  // what the four staging buffers must hold
+  size_t in_image = 0, out_image = 0;                       // (the shape's, for the one DMA of a staged image)
+  bool strided = false;                                     // (the shape's: the input is gathered sample by sample)
+};
+// bytes of a side that pass through a device / a pinned staging buffer
+inline size_t device_part(Via v, size_t bytes) { return v == Via::Copy || v == Via::Staged ? bytes : 0; }
+inline size_t pinned_part(Via v, size_t bytes) { return v == Via::Bounce || v == Via::Staged ? bytes : 0; }
+
+// The entry points differ in small ways that their histories chose; each is one line here and is kept as it is.
+inline HostRoute route_host_call(const HostCallShape &s) {
+  HostRoute r;
+  r.in_image = s.in.image;
+  r.out_image = s.out.image;
+  r.strided = s.strided;
+  const bool planes = s.in.planar || s.out.planar;
+  if (s.strided || (s.split && !planes)) {
+    // A strided line, and interleaved buffers of a split state (the result is handed over sample by sample): never the
+    // bounce way, never in place -- the input by the size rule alone, the result device -> pinned -> the caller.
+    r.in = s.strided ? (s.in.present ? Via::Staged : Via::None)  // (a line is gathered sample by sample: pinned, one DMA)
+                     : route_side(s.in.judged, s.in.present, false, false);
+    r.out = Via::Staged;
+    r.wait.sync = true;
+    r.dev_in = s.in.image;  // (reserved whatever the input's way, absent included)
+    r.pin_in = s.strided ? s.in.image : pinned_part(r.in, s.in.image);  // (a line's: reserved even when absent)
+    r.dev_out = r.pin_out = s.out.image;
+    return r;
+  }
+  const bool small = small_call(s.in.present && !s.in.pinned ? s.in.payload : 0, s.out.pinned ? 0 : s.out.payload);
+  r.in = route_side(s.in.judged, s.in.present, s.in.pinned, small);
+  r.out = route_side(s.out.judged, true, s.out.pinned, small);
+  if (s.gathered && r.in == Via::Copy) r.in = Via::Staged;  // chunks are gathered in pinned memory: one DMA from there
+  if (s.split && !s.out.planar && r.out == Via::Copy) r.out = Via::Staged;  // handed over sample by sample, from pinned memory
+  r.wait.add(r.in, s.in.image);
+  r.wait.add(r.out, s.out.image);
+  if (s.gathered) r.wait.sync = true;  // the chunks call has always synchronised its stream
+  r.dev_in = device_part(r.in, s.in.image);
+  r.dev_out = device_part(r.out, s.out.image);
+  r.pin_in = pinned_part(r.in, s.in.image);
+  r.pin_out = pinned_part(r.out, s.out.image);
+  // The completion word of a polled wait: 64 bytes behind the samples in the pinned result buffer.  A call with a planar
+  // side reserves it whatever its wait, the chunks call whenever its result bounces; a take call's word lies in its block.
+  if (s.take ? false : planes ? true : s.gathered ? r.out == Via::Bounce : !r.wait.sync) r.pin_out += 64;
+  return r;
+}
 
 }  // namespace speexhip

@@ -30,9 +30,7 @@ int Batch::process_planar_device(const void *d_in, uint64_t in_stream_stride, ui
   if (channels_ == 1) return process_device(d_in, in_stream_stride, in_len, d_out, out_stream_stride, out_len, float_io, stream);
   ON_DEVICE();
   const size_t es = float_io ? sizeof(float) : sizeof(int16_t);
-  EntryRules rules;
-  rules.block_in = block_in();
-  rules.float_entry = float_io;
+  const EntryRules rules = entry_rules(float_io);
   // channels that the per-channel calls moved apart: process_split with plane c as a stride-1 buffer
   const SplitLayout planes = {in_plane_stride, out_plane_stride, 1, 1};
   for (uint32_t s = 0; s < n_streams_; s++)
@@ -46,9 +44,11 @@ int Batch::process_planar_device(const void *d_in, uint64_t in_stream_stride, ui
   if (zero_mode_ && n_streams_ == 1) return process_split(d_in, in_len, d_out, out_len, float_io, stream, nullptr, &planes);
   // planned exactly as process_device plans: `produced` is integer arithmetic, known before anything is launched
   std::vector<CallPlan> plans(n_streams_);
+  std::vector<uint32_t> produced(n_streams_);
   uint32_t most_in = 0, most_out = 0;
   for (uint32_t s = 0; s < n_streams_; s++) {
     plans[s] = plan_call(filter_.num, filter_.den, in_len[s], out_len[s], P(s, 0), rules);
+    produced[s] = plans[s].produced;
     most_in = std::max(most_in, in_len[s]);
     most_out = std::max(most_out, plans[s].produced);
   }
@@ -69,39 +69,39 @@ int Batch::process_planar_device(const void *d_in, uint64_t in_stream_stride, ui
     rc = chain_to(stream);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
-  for (uint32_t s0 = 0; gathers && s0 < n_streams_; s0 += kChunk) {
-    const uint32_t n = std::min(kChunk, n_streams_ - s0);
-    PlanarPack pack;
-    std::memset(&pack, 0, sizeof(pack));
-    uint32_t most = 0;
-    for (uint32_t j = 0; j < n; j++) {
-      const uint32_t s = s0 + j;
-      pack.s[j].planes = static_cast<const char *>(d_in) + s * in_stream_stride * es;
-      pack.s[j].plane_stride = in_plane_stride;
-      pack.s[j].inter = d_planar_in_ + s * in_pitch * es;
-      pack.s[j].frames = in_len[s];
-      most = std::max(most, in_len[s]);
+  // the transposing launches, <= kMaxPackedStreams streams each: planes -> image (gather) or image -> planes
+  auto transpose = [&](bool gather, const void *planes, uint64_t stream_stride, uint64_t plane_stride, char *image, size_t pitch,
+                       const uint32_t *frames) -> int {
+    for (uint32_t s0 = 0; s0 < n_streams_; s0 += kChunk) {
+      const uint32_t n = std::min(kChunk, n_streams_ - s0);
+      PlanarPack pack;
+      std::memset(&pack, 0, sizeof(pack));
+      uint32_t most = 0;
+      for (uint32_t j = 0; j < n; j++) {
+        const uint32_t s = s0 + j;
+        pack.s[j].planes = static_cast<const char *>(planes) + s * stream_stride * es;
+        pack.s[j].plane_stride = plane_stride;
+        pack.s[j].inter = image + s * pitch * es;
+        pack.s[j].frames = frames[s];
+        most = std::max(most, pack.s[j].frames);
+      }
+      const hipError_t e = gather ? launch_planar_gather(pack, n, channels_, most, float_io, stream)
+                                  : launch_planar_scatter(pack, n, channels_, most, float_io, stream);
+      if (hip_failed(e, "kernel launch")) return SPEEXHIP_ERR_DEVICE;
     }
-    if (hip_failed(launch_planar_gather(pack, n, channels_, most, float_io, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+    return SPEEXHIP_ERR_SUCCESS;
+  };
+  if (gathers) {
+    rc = transpose(true, d_in, in_stream_stride, in_plane_stride, d_planar_in_, in_pitch, in_len);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
   // (a present but empty input is not silence: no frame is read, any non-null address serves)
   const void *image_in = d_in == nullptr ? nullptr : d_planar_in_ != nullptr ? static_cast<const void *>(d_planar_in_) : d_in;
   rc = run_plans(image_in, in_pitch, in_len, d_planar_out_, out_pitch, plans.data(), float_io, stream);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  for (uint32_t s0 = 0; scatters && s0 < n_streams_; s0 += kChunk) {
-    const uint32_t n = std::min(kChunk, n_streams_ - s0);
-    PlanarPack pack;
-    std::memset(&pack, 0, sizeof(pack));
-    uint32_t most = 0;
-    for (uint32_t j = 0; j < n; j++) {
-      const uint32_t s = s0 + j;
-      pack.s[j].planes = static_cast<char *>(d_out) + s * out_stream_stride * es;
-      pack.s[j].plane_stride = out_plane_stride;
-      pack.s[j].inter = d_planar_out_ + s * out_pitch * es;
-      pack.s[j].frames = plans[s].produced;
-      most = std::max(most, plans[s].produced);
-    }
-    if (hip_failed(launch_planar_scatter(pack, n, channels_, most, float_io, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+  if (scatters) {
+    rc = transpose(false, d_out, out_stream_stride, out_plane_stride, d_planar_out_, out_pitch, produced.data());
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
   for (uint32_t s = 0; s < n_streams_; s++) {
     in_len[s] = plans[s].consumed;
@@ -124,65 +124,38 @@ int Batch::process_planar_host(const void *const *in_planes, uint32_t *in_len, v
     if (out_planes[c] == nullptr || (in_planes != nullptr && in_planes[c] == nullptr)) return SPEEXHIP_ERR_INVALID_ARG;
   // only as many output frames as this call can produce are written (and need a device buffer)
   const bool split = !uniform(0);
-  uint32_t will_make = 0;
-  for (uint32_t c = 0; c < (split ? channels_ : 1u); c++)
-    will_make = std::max(will_make, produced_closed_form(filter_.num, filter_.den, frames, capacity, P(0, c)));
+  const uint32_t most = will_make(frames, capacity);
   for (uint32_t c = 0; c < channels_; c++) {
     for (uint32_t k = 0; k < c; k++)
-      if (buffers_overlap(out_planes[c], will_make * es, out_planes[k], will_make * es)) return SPEEXHIP_ERR_PTR_OVERLAP;
+      if (buffers_overlap(out_planes[c], most * es, out_planes[k], most * es)) return SPEEXHIP_ERR_PTR_OVERLAP;
     for (uint32_t k = 0; in_planes != nullptr && k < channels_; k++)
-      if (buffers_overlap(out_planes[c], will_make * es, in_planes[k], frames * es)) return SPEEXHIP_ERR_PTR_OVERLAP;
+      if (buffers_overlap(out_planes[c], most * es, in_planes[k], frames * es)) return SPEEXHIP_ERR_PTR_OVERLAP;
   }
   if (channels_ == 1) return process_host(in_planes ? in_planes[0] : nullptr, in_len, out_planes[0], out_len, float_io);
   ON_DEVICE();
-  const size_t in_pitch = align64(frames), out_pitch = align64(will_make);  // elements between two planes: whole lines
-  const size_t plane_in = frames * es, plane_out = will_make * es;
-  const size_t in_bytes = in_pitch * channels_ * es, out_bytes = out_pitch * channels_ * es;
+  const size_t in_pitch = align64(frames), out_pitch = align64(most);  // elements between two planes: whole lines
+  const size_t plane_in = frames * es, plane_out = most * es;
   const bool present = in_planes != nullptr;
-  const bool small = small_call(present ? plane_in * channels_ : 0, plane_out * channels_);
-  const Via in_via = route_side(plane_in, present, false, small);
-  const Via out_via = route_side(plane_out, true, false, small);
-  Wait wait;
-  wait.add(in_via, in_bytes);
-  wait.add(out_via, out_bytes);
-  DrainOnExit drain(&own_stream_);
-  int rc = ensure_stage(device_part(in_via, in_bytes), device_part(out_via, out_bytes), pinned_part(in_via, in_bytes),
-                        pinned_part(out_via, out_bytes) + 64);
+  HostCallShape shape;
+  shape.split = split;
+  shape.in = planar_side(present, plane_in, in_pitch * es, channels_);
+  shape.out = planar_side(true, plane_out, out_pitch * es, channels_);
+  std::vector<HostPiece> pieces(channels_);
+  for (uint32_t c = 0; c < channels_; c++) pieces[c] = {present ? in_planes[c] : nullptr, c * in_pitch * es, plane_in};
+  HostCall call(this);
+  int rc = call.begin(route_host_call(shape), pieces.data(), channels_, nullptr, nullptr);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  if (present && frames != 0) {
-    for (uint32_t c = 0; c < channels_; c++) {
-      if (in_via == Via::Copy)
-        HIP_TRY(hipMemcpyAsync(d_stage_in_ + c * in_pitch * es, in_planes[c], plane_in, hipMemcpyHostToDevice, own_stream_));
-      else
-        std::memcpy(h_pin_in_ + c * in_pitch * es, in_planes[c], plane_in);
-    }
-    if (in_via == Via::Staged) HIP_TRY(hipMemcpyAsync(d_stage_in_, h_pin_in_, in_bytes, hipMemcpyHostToDevice, own_stream_));
-  }
-  char *dst = out_via == Via::Bounce ? h_pin_out_ : d_stage_out_;
-  const void *src = !present ? nullptr : frames == 0 ? h_pin_out_ : in_via == Via::Bounce ? h_pin_in_ : d_stage_in_;
   std::vector<CallPlan> plans;
   const SplitLayout image_planes = {in_pitch, out_pitch, 1, 1};
   if (split)
-    rc = process_split(src, in_len, dst, out_len, float_io, own_stream_, &plans, &image_planes);
+    rc = process_split(call.src, in_len, call.dst, out_len, float_io, own_stream_, &plans, &image_planes);
   else
-    rc = process_planar_device(src, 0, in_pitch, in_len, dst, 0, out_pitch, out_len, float_io, own_stream_);
-  if (rc != SPEEXHIP_ERR_SUCCESS && rc != SPEEXHIP_ERR_ALLOC_FAILED) return rc;
+    rc = process_planar_device(call.src, 0, in_pitch, in_len, call.dst, 0, out_pitch, out_len, float_io, own_stream_);
+  if (!ran(rc)) return rc;
   // frames each plane received (channels that stand apart produce different numbers of them)
-  std::vector<uint32_t> made(channels_, *out_len);
-  for (uint32_t c = 0; split && c < channels_; c++) made[c] = plans[c].produced;
-  if (out_via == Via::Copy)
-    for (uint32_t c = 0; c < channels_; c++)
-      if (made[c] != 0)
-        HIP_TRY(hipMemcpyAsync(out_planes[c], d_stage_out_ + c * out_pitch * es, made[c] * es, hipMemcpyDeviceToHost, own_stream_));
-  if (out_via == Via::Staged && will_make != 0)
-    HIP_TRY(hipMemcpyAsync(h_pin_out_, d_stage_out_, out_bytes, hipMemcpyDeviceToHost, own_stream_));
-  const int wrc = wait_call(own_stream_, wait, tail_word(h_pin_out_, pin_out_cap_), ++done_seq_);
-  if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
-  drain.armed = false;
-  if (out_via != Via::Copy)
-    for (uint32_t c = 0; c < channels_; c++)
-      if (made[c] != 0) std::memcpy(out_planes[c], h_pin_out_ + c * out_pitch * es, made[c] * es);
-  return rc;
+  const std::vector<uint32_t> made = made_per_channel(channels_, *out_len, split ? plans.data() : nullptr);
+  const int frc = call.finish_planes(out_planes, channels_, out_pitch * es, es, made.data());
+  return frc != SPEEXHIP_ERR_SUCCESS ? frc : rc;
 }
 
 }  // namespace speexhip
