@@ -802,6 +802,56 @@ SPEEXHIP_API int speexhip_resampler_process_many_fmt(uint32_t n, SpeexHipResampl
                                                      int *codes);
 SPEEXHIP_API void speexhip_debug_many_counters(uint64_t out[4]);
 
+/* ------------------------------------------------------------------------------------------
+ * Chunk coalescing, formatted: speexhip_resampler_process_chunks_int / _float with a side per
+ * direction -- a microphone's float32 stream, a G.711 RTP payload stream, a 24-bit WAV read in
+ * whatever pieces the file system hands out -- n consecutive calls of one stream as one transfer in,
+ * one transfer out and one wait.
+ *
+ * `in` describes every chunk's input: format, channels, layout, matrix (its data and planes fields
+ * are not read).  Where chunk i lies is in_data's to say: an interleaved side, or a side of one
+ * channel, has n_chunks entries; a planar side n_chunks * in->channels, plane c of chunk i being
+ * entry i * channels + c (separate allocations).  in_data == NULL, or a NULL (first) entry of a chunk:
+ * a chunk of silence; a NULL entry among a present chunk's further planes is INVALID_ARG.  `out` is an
+ * ordinary host output side (data, or planes).  The chunks' results lie back to back in it -- chunk i
+ * starts at the frame where chunk i - 1 ended, in the buffer or in every plane -- so it needs room for
+ * the sum of the capacities.  in_len[i] / out_len[i]: chunk i's frames available / capacity on entry,
+ * consumed / written on return.
+ *
+ * Chunk i is exactly speexhip_resampler_process_sides on the state chunk i - 1 left, with chunk i's
+ * data, in_len[i] and out_len[i] and an output side that begins at the frames already written: the
+ * same bytes, per-chunk counters, history, position and dither position (the dither index runs on
+ * across chunk boundaries) in the default mode and in SPEEXHIP_MODE_EXACT; in SPEEXHIP_MODE_FAST and
+ * _FAST_F32 the launch's shape may move a sample's last bit, as in every call.  The counter rules are
+ * the int16 entry's for S16 -> S16 without matrix, planar side and dither, the float entry's
+ * otherwise.  S16 -> S16, F32 -> F32 and F32N -> F32N without matrix, planar side or dither IS
+ * process_chunks_int / _float.  Frames a capacity-bound chunk leaves unconsumed never travel.  A
+ * state whose channels the per-channel calls moved apart runs the separate calls when it has no
+ * matrix and dither is off, else BAD_STATE, untouched; a state in the zero fallback runs the separate
+ * calls.  Argument errors -- an unknown format or layout, a short struct_size, the channel-count
+ * rules, an output without data or planes, PTR_OVERLAP between the frames written to two output
+ * planes -- leave the state and both length arrays untouched.  The return code follows
+ * process_chunks_int's rule.
+ *
+ * On the GPU a call is one transfer in, at most one input pass, one FIR launch per run of chunks
+ * without dropped input, at most one output pass, one transfer out and one wait, where the n
+ * separate calls take up to 3n launches and n waits.  ..._fmt is the thin form: both sides
+ * interleaved with the state's channel count and no matrix.
+ *
+ * speexhip_debug_chunk_counters: process-wide counts since start over these two calls -- out[0] FIR
+ * launches, out[1] input passes, out[2] output passes, out[3] chunks that took a call of their own.
+ * Host only.
+ *
+ * ABI note: 0.7 + chunk sides adds these three entry points; SpeexHipInfo, SpeexHipSide, the enums,
+ * the error codes and the version string are unchanged. */
+SPEEXHIP_API int speexhip_resampler_process_chunks_sides(SpeexHipResamplerState *st, uint32_t n_chunks,
+                                                         const SpeexHipSide *in, const void *const *in_data,
+                                                         uint32_t *in_len, const SpeexHipSide *out, uint32_t *out_len);
+SPEEXHIP_API int speexhip_resampler_process_chunks_fmt(SpeexHipResamplerState *st, uint32_t n_chunks, int in_fmt,
+                                                       const void *const *in, uint32_t *in_len, int out_fmt, void *out,
+                                                       uint32_t *out_len);
+SPEEXHIP_API void speexhip_debug_chunk_counters(uint64_t out[4]);
+
 /* Mid-stream control for every stream of a batch (same semantics as the single-stream calls). */
 SPEEXHIP_API int speexhip_batch_set_rate_frac(SpeexHipBatch *b, uint32_t ratio_num, uint32_t ratio_den,
                                               uint32_t in_rate, uint32_t out_rate);

@@ -667,6 +667,33 @@ int speexhip_batch_process_sides_device(SpeexHipBatch *bt, const SpeexHipSide *i
   return guarded([&] { return bt->batch->process_sides_device(a, in_len, b, out_len, static_cast<hipStream_t>(hip_stream)); });
 }
 
+// ---- chunk coalescing, formatted ------------------------------------------------------------------------------------------
+int speexhip_resampler_process_chunks_sides(SpeexHipResamplerState *st, uint32_t n_chunks, const SpeexHipSide *in,
+                                            const void *const *in_data, uint32_t *in_len, const SpeexHipSide *out,
+                                            uint32_t *out_len) {
+  speexhip::CallSide a, b;
+  if (st == nullptr || in_len == nullptr || out_len == nullptr || in == nullptr || in->struct_size < sizeof(SpeexHipSide))
+    return SPEEXHIP_ERR_INVALID_ARG;
+  SpeexHipSide every = *in;  // (where a chunk lies is in_data's to say)
+  every.data = nullptr;
+  every.planes = nullptr;
+  if (!side_of(&every, true, &a) || !side_of(out, true, &b) || (b.base == nullptr && b.planes == nullptr))
+    return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return st->batch->process_sides_host_chunks(n_chunks, a, in_data, in_len, b, out_len); });
+}
+int speexhip_resampler_process_chunks_fmt(SpeexHipResamplerState *st, uint32_t n_chunks, int in_fmt, const void *const *in,
+                                          uint32_t *in_len, int out_fmt, void *out, uint32_t *out_len) {
+  if (!fmt_args_ok(st, in_len, out_len, out, in_fmt, out_fmt)) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] {
+    const uint32_t ch = st->batch->channels();
+    return st->batch->process_sides_host_chunks(n_chunks, side(in_fmt, ch, nullptr, nullptr), in, in_len,
+                                                side(out_fmt, ch, nullptr, out), out_len);
+  });
+}
+void speexhip_debug_chunk_counters(uint64_t out[4]) {
+  if (out != nullptr) speexhip::chunk_counters(out);
+}
+
 // ---- many states, formatted ---------------------------------------------------------------------------------------------
 int speexhip_resampler_process_many_sides(uint32_t n, SpeexHipResamplerState *const *st, const SpeexHipSide *in,
                                           uint32_t *in_len, const SpeexHipSide *out, uint32_t *out_len, int *codes) {

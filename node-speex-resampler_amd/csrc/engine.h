@@ -27,6 +27,9 @@ void debug_fail_device_allocs(int n);
 // speexhip_debug_many_counters: process-wide counts since start, of the many-states calls old and new -- FIR launches, input
 // passes, output passes, entries that took their own call.
 void many_counters(uint64_t out[4]);
+// speexhip_debug_chunk_counters: the same four counts over the formatted chunks call (process_sides_host_chunks); chunks
+// that took a call of their own in the place of entries.
+void chunk_counters(uint64_t out[4]);
 
 // Everything on the device that depends only on (filter, channel count): the reference-layout sinc
 // table, the fast kernels' tap rows and the launch geometry.  Immutable once built, so states with
@@ -116,6 +119,18 @@ class Batch {
   // With a planar side: an interleaved side still moves by that rule, a planar one plane by plane into a pitched image as
   // in process_planar_host; PTR_OVERLAP when the frames written to an output plane overlap another plane of the call.
   int process_sides_host(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len);
+  // n_chunks consecutive process_sides_host calls of a single-stream batch as one transfer each way and one wait
+  // (formats.cpp): chunk i is exactly process_sides_host on the state chunk i - 1 left -- its data, in_len[i] and
+  // out_len[i], and an output side that begins at the frames already written -- bytes (in the modes whose bytes do not
+  // depend on the launch's shape), counters, history, position and dither position.  `in` describes every chunk's input
+  // (its base and planes are not read); chunk i lies at in_data[i], a planar chunk's plane c at in_data[i * channels + c];
+  // in_data == nullptr or a null (first) entry: a chunk of silence.  `out` is an ordinary host output side with room for
+  // the sum of the capacities: the results lie back to back in its buffer, or in every plane.  Only the frames a chunk
+  // consumes travel (process_host_chunks); the passes run once over all chunks, the FIR once per run of chunks without
+  // dropped input.  S16 -> S16, F32 -> F32 and F32N -> F32N without matrix, planar side or dither IS process_host_chunks.
+  // A state whose channels stand apart (no matrix, dither off; else BAD_STATE) or in the zero fallback: the separate calls.
+  int process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, const void *const *in_data, uint32_t *in_len,
+                                const CallSide &out, uint32_t *out_len);
   // Dither of the integer output formats of the formatted and mixed calls (dither.h; include/speexhip_resampler.h,
   // "Dither"): a property of the state, off by default.  kind = SPEEXHIP_DITHER_*; stream s draws from
   // dither::stream_seed(seed, s); position = index of the next output frame of every stream.  While the kind is not NONE

@@ -4,6 +4,7 @@
 // side's pass--> storage (side_pass, mix.cpp).  Counters, positions and the history are the float call's, so formatted,
 // mixed, interleaved, planar and per-channel calls mix freely on one state.  The state's dither (set_dither) lives here too.
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <vector>
 
@@ -239,6 +240,198 @@ int Batch::process_sides_host(const CallSide &in, uint32_t *in_len, const CallSi
   const int frc = split ? call.finish_samples(out.base, channels_, channels_, bout, made_per_channel(channels_, 0, plans.data()).data())
                         : call.finish_whole(out.base, static_cast<size_t>(*out_len) * out.channels * bout);
   return frc != SPEEXHIP_ERR_SUCCESS ? frc : rc;
+}
+
+// ---- the formatted chunks call (engine.h) -----------------------------------------------------------------------------------
+namespace {
+// speexhip_debug_chunk_counters: FIR launches, input passes, output passes, chunks that took a call of their own
+std::atomic<uint64_t> g_chunk_counters[4];
+inline void count_chunks(int which, uint64_t by = 1) { g_chunk_counters[which].fetch_add(by, std::memory_order_relaxed); }
+
+// The chunks of a call planned one after the other in integer arithmetic, and the launch groups they form -- the rule of
+// process_host_chunks (engine.cpp): a capacity-bound chunk that leaves input unconsumed keeps one more frame readable and
+// closes its group.
+struct ChunkGroup {
+  CallPlan fused;
+  uint64_t in_off = 0, out_off = 0;  // frames into the staged images
+  uint32_t readable = 0;             // frames at in_off the launch may read
+};
+struct ChunkPlans {
+  std::vector<CallPlan> plans;
+  std::vector<uint32_t> staged;  // frames of chunk i that travel: what it consumes, one more where it drops input
+  std::vector<ChunkGroup> groups;
+  uint64_t frames = 0, made = 0;  // frames staged / produced by the whole call
+  uint32_t launches = 0;          // groups with anything to run
+};
+ChunkPlans plan_chunks(uint32_t num, uint32_t den, uint32_t n, const uint32_t *in_len, const uint32_t *out_len, StreamPos pos,
+                       const EntryRules &rules) {
+  ChunkPlans p;
+  p.plans.resize(n);
+  p.staged.resize(n);
+  bool open = false;
+  for (uint32_t i = 0; i < n; i++) {
+    const CallPlan &plan = p.plans[i] = plan_call(num, den, in_len[i], out_len[i], pos, rules);
+    pos = plan.end;
+    if (!open) {
+      ChunkGroup g;
+      g.fused.begin = plan.begin;
+      g.in_off = p.frames;
+      g.out_off = p.made;
+      p.groups.push_back(g);
+      open = true;
+    }
+    const bool drops = plan.consumed < in_len[i];
+    ChunkGroup &g = p.groups.back();
+    g.fused.end = plan.end;
+    g.fused.magic_used += plan.magic_used;
+    g.fused.consumed += plan.consumed;
+    g.fused.produced += plan.produced;
+    p.staged[i] = plan.consumed + (drops ? 1u : 0u);
+    g.readable += p.staged[i];
+    p.frames += p.staged[i];
+    p.made += plan.produced;
+    if (drops) open = false;
+  }
+  for (const ChunkGroup &g : p.groups)
+    if (g.fused.produced != 0 || g.fused.magic_used + g.fused.consumed != 0) p.launches++;
+  return p;
+}
+}  // namespace
+
+void chunk_counters(uint64_t out[4]) {
+  for (int k = 0; k < 4; k++) out[k] = g_chunk_counters[k].load(std::memory_order_relaxed);
+}
+
+int Batch::process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, const void *const *in_data, uint32_t *in_len,
+                                     const CallSide &out_side, uint32_t *out_len) {
+  if (n_streams_ != 1) return SPEEXHIP_ERR_BAD_STATE;
+  if (!side_ok(in, channels_) || !side_ok(out_side, channels_)) return SPEEXHIP_ERR_INVALID_ARG;
+  const bool pl_in = planar(in), pl_out = planar(out_side);
+  // (a mono side given as its one plane is an interleaved buffer)
+  CallSide out = out_side;
+  if (!pl_out && out.planes != nullptr) out.base = out.planes[0], out.planes = nullptr;
+  if (out.base == nullptr && out.planes == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  for (uint32_t c = 0; out.planes != nullptr && c < out.channels; c++)
+    if (out.planes[c] == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  // entries of in_data per chunk; a present chunk has all its planes
+  const uint32_t per = pl_in ? in.channels : 1u;
+  const auto entry = [&](uint32_t i, uint32_t c) { return in_data != nullptr ? in_data[static_cast<size_t>(i) * per + c] : nullptr; };
+  for (uint32_t i = 0; i < n_chunks; i++)
+    for (uint32_t c = 1; entry(i, 0) != nullptr && c < per; c++)
+      if (entry(i, c) == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), split = !uniform(0);
+  if (split && (dith || mixed)) return SPEEXHIP_ERR_BAD_STATE;
+  const bool same = same_bytes(in, out, dith), own_calls = split || zero_mode_;
+  const size_t bin = sample_bytes(in.fmt), bout = sample_bytes(out.fmt);
+  if (own_calls && !same) {  // rare states: the separate calls, one after the other, each output side behind the frames written
+    int last = SPEEXHIP_ERR_SUCCESS;
+    uint64_t written = 0;
+    std::vector<void *> planes(out.channels);
+    for (uint32_t i = 0; i < n_chunks; i++) {
+      CallSide a = in, b = out;
+      a.base = const_cast<void *>(entry(i, 0));
+      a.planes = nullptr;
+      if (pl_in && a.base != nullptr) a.planes = const_cast<void *const *>(in_data + static_cast<size_t>(i) * per), a.base = nullptr;
+      if (pl_out) {
+        for (uint32_t c = 0; c < out.channels; c++) planes[c] = host_plane(out, c) + written * bout;
+        if (out.planes != nullptr) b.planes = planes.data();
+        else b.base = planes[0];
+      } else {
+        b.base = static_cast<char *>(out.base) + written * out.channels * bout;
+      }
+      last = process_sides_host(a, &in_len[i], b, &out_len[i]);
+      if (!ran(last)) return last;
+      written += out_len[i];
+      count_chunks(3);
+    }
+    return last;
+  }
+  const ChunkPlans p = plan_chunks(filter_.num, filter_.den, n_chunks, in_len, out_len, P(0, 0), entry_rules(!same || in.fmt != SPEEXHIP_FMT_S16));
+  if (same) {  // process_host_chunks on the same bytes (which serves the rare states itself)
+    const int rc = process_host_chunks(n_chunks, in_data, in_len, out.base, out_len, in.fmt != SPEEXHIP_FMT_S16);
+    if (!ran(rc)) return rc;
+    uint32_t made = 0;
+    for (uint32_t i = 0; i < n_chunks; i++) made += out_len[i];
+    if (dith) dither_advance(&made);
+    if (own_calls) count_chunks(3, n_chunks);
+    else count_chunks(0, p.launches);
+    return rc;
+  }
+  if (p.frames > 0x7fffffffull || p.made > 0x7fffffffull) return SPEEXHIP_ERR_OVERFLOW;
+  // (only so many frames are written to a plane: the sum of what the chunks will make)
+  for (uint32_t c = 0; pl_out && c < out.channels; c++)
+    for (uint32_t k = 0; k < c; k++)
+      if (buffers_overlap(host_plane(out, c), p.made * bout, host_plane(out, k), p.made * bout)) return SPEEXHIP_ERR_PTR_OVERLAP;
+  ON_DEVICE();
+  for (uint32_t i = 0; i < n_chunks; i++)
+    if (in_len[i] != 0 && out_len[i] != 0) started_[0] = 1;
+  // The staged images: the chunks' frames back to back, in the buffer or in every plane (planes whole 128-byte lines apart).
+  const uint32_t frames = static_cast<uint32_t>(p.frames), made = static_cast<uint32_t>(p.made);
+  const size_t in_pitch = align64(frames), out_pitch = align64(made);  // samples between two staged planes
+  const size_t fb_in = pl_in ? bin : bin * in.channels;                // bytes of a frame in a piece
+  HostCallShape shape;
+  shape.gathered = true;  // (a silent chunk is gathered too, as zeros)
+  shape.in = pl_in ? planar_side(true, frames * bin, in_pitch * bin, in.channels) : flat_side(true, false, frames * fb_in);
+  shape.out = pl_out ? planar_side(true, made * bout, out_pitch * bout, out.channels) : flat_side(true, false, made * out.channels * bout);
+  std::vector<HostPiece> pieces;
+  pieces.reserve(static_cast<size_t>(n_chunks) * per);
+  uint64_t off = 0;
+  for (uint32_t i = 0; i < n_chunks; i++) {  // frames a chunk drops never reach the GPU
+    for (uint32_t c = 0; c < per; c++) pieces.push_back({entry(i, c), (c * in_pitch + off) * fb_in, p.staged[i] * fb_in});
+    off += p.staged[i];
+  }
+  HostCall call(this);
+  int rc = call.begin(route_host_call(shape), pieces.data(), static_cast<uint32_t>(pieces.size()), nullptr, nullptr);
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  // The passes of process_sides_device, once over all chunks: conversion, matrix and dither are per sample or per frame,
+  // and the dither index runs on over the chunks' output frames as the position does.
+  const bool pass_in = (in.mix != nullptr || in.fmt != SPEEXHIP_FMT_F32 || pl_in) && frames != 0;
+  const bool pass_out = out.mix != nullptr || out.fmt != SPEEXHIP_FMT_F32 || pl_out;
+  const size_t fi = channels_ * sizeof(float);  // bytes of a frame of the float images
+  rc = ensure_planar_scratch(pass_in ? align64(static_cast<size_t>(frames) * channels_) * sizeof(float) : 0,
+                             pass_out ? align64(static_cast<size_t>(made) * channels_) * sizeof(float) : 0);
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  if (pass_in || (pass_out && made != 0)) {
+    rc = chain_to(own_stream_);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  }
+  if (pass_in) {
+    rc = side_pass(pl_in ? planes_at(in, call.src, in_pitch) : at(in, call.src), true, d_planar_in_, 0, &frames, own_stream_);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+    // (a silent chunk is zeros in the float image, as the FIR reads an absent input -- not what the format's zero bytes or
+    //  a matrix's negative coefficient make of them)
+    off = 0;
+    for (uint32_t i = 0; i < n_chunks; off += p.staged[i], i++)
+      if (entry(i, 0) == nullptr && p.staged[i] != 0) HIP_TRY(hipMemsetAsync(d_planar_in_ + off * fi, 0, p.staged[i] * fi, own_stream_));
+  }
+  const char *image_in = pass_in ? d_planar_in_ : static_cast<const char *>(call.src);
+  char *image_out = pass_out ? d_planar_out_ : static_cast<char *>(call.dst);
+  for (const ChunkGroup &g : p.groups) {
+    rc = run_plans(image_in != nullptr ? image_in + g.in_off * fi : nullptr, 0, &g.readable, image_out + g.out_off * fi, 0, &g.fused,
+                   true, own_stream_);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  }
+  if (pass_out) {
+    rc = side_pass(pl_out ? planes_at(out, call.dst, out_pitch) : at(out, call.dst), false, d_planar_out_, 0, &made, own_stream_);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  }
+  if (dith) dither_advance(&made);
+  if (pl_out) {
+    std::vector<void *> planes(out.channels);
+    for (uint32_t c = 0; c < out.channels; c++) planes[c] = host_plane(out, c);
+    rc = call.finish_planes(planes.data(), out.channels, out_pitch * bout, bout, std::vector<uint32_t>(out.channels, made).data());
+  } else {
+    rc = call.finish_whole(out.base, static_cast<size_t>(made) * out.channels * bout);
+  }
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  for (uint32_t i = 0; i < n_chunks; i++) {
+    in_len[i] = p.plans[i].consumed;
+    out_len[i] = p.plans[i].produced;
+  }
+  count_chunks(0, p.launches);
+  count_chunks(1, pass_in ? 1 : 0);
+  count_chunks(2, pass_out && made != 0 ? 1 : 0);
+  return SPEEXHIP_ERR_SUCCESS;
 }
 
 // A host call with a planar side.  Each side moves by its own rule (host_transfer.h): an interleaved side as in

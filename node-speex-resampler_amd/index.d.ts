@@ -55,6 +55,14 @@ export interface SpeexResamplerTransformOptions {
      * buffer.  Same bytes out.  A producer that fills chunks from `allocChunk` itself needs no option.
      */
     pinned?: boolean;
+    /**
+     * The stream's sample formats (default 's16le' each): bytes of inFormat are written, bytes of outFormat are read, in
+     * every mode -- plain, `coalesceChunks`, `async`, `pipeline`, `pinned`, `flushTail`.  Chunks may be cut anywhere: the
+     * bytes that do not complete a frame of channels x bytes(inFormat) are carried to the next chunk.  Without either
+     * option the Transform is the reference's and calls what it always called.
+     */
+    inFormat?: SampleFormat;
+    outFormat?: SampleFormat;
 }
 
 /**
@@ -132,6 +140,20 @@ declare class SpeexResampler {
     processChunkFormat(chunk: Buffer, inFormat: SampleFormat, outFormat: SampleFormat): Buffer;
 
     /**
+     * consecutive chunks of inFormat as one transfer each way, one conversion pass per side and (normally) one
+     * resampling launch; result[i] equals processChunkFormat(chunks[i], inFormat, outFormat), dither running on across
+     * the chunks
+     */
+    processChunksFormat(chunks: Buffer[], inFormat: SampleFormat, outFormat: SampleFormat): Buffer[];
+    /** the same off the event loop */
+    processChunksFormatAsync(chunks: Buffer[], inFormat: SampleFormat, outFormat: SampleFormat): Promise<Buffer[]>;
+    /**
+     * processChunkFormat off the event loop; calls on one instance stay in order, and calls of DIFFERENT instances that
+     * become ready in the same tick leave as one fused native call whatever formats they name, as processChunkAsync's do
+     */
+    processChunkFormatAsync(chunk: Buffer, inFormat: SampleFormat, outFormat: SampleFormat): Promise<Buffer>;
+
+    /**
      * processChunkFormat with a channel mix on either side, done on the GPU in the passes that convert the samples.  The
      * instance's `channels` is the count the resampler runs on.  inMix: `channels` rows, one column per channel of the
      * chunk, applied to every input frame before the filter; outMix: one row per channel of the result, `channels`
@@ -182,6 +204,8 @@ declare class SpeexResampler {
 
     /** the filter's tail: the response to the last inputLatency frames */
     flush(): Buffer;
+    /** the tail in outFormat, as processChunkFormat writes it */
+    flushFormat(outFormat: SampleFormat): Buffer;
     /** release the GPU state now instead of at garbage collection */
     destroy(): void;
     /**

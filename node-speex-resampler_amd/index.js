@@ -283,6 +283,89 @@ class SpeexResampler {
     return speexModule.processFormat(this._resamplerPtr, chunk, fin.id, fout.id, frames, cap);
   }
 
+  // format names, frame counts and capacities of a list of chunks for the formatted chunks calls: the checks and the
+  // grow-only capacity rule of processChunkFormat, chunk by chunk
+  _prepareFormat(chunks, inFormat, outFormat) {
+    if (!speexModule) {
+      throw new Error('You need to wait for SpeexResampler.initPromise before calling this method');
+    }
+    const fin = SAMPLE_FORMATS[inFormat];
+    const fout = SAMPLE_FORMATS[outFormat];
+    if (!fin || !fout) {
+      throw new Error('Unknown sample format: ' + (fin ? outFormat : inFormat));
+    }
+    for (const chunk of chunks) {
+      if (chunk.length % (this.channels * fin.bytes) !== 0) {
+        throw new Error('Chunk length should be a multiple of channels * ' + fin.bytes + ' bytes');
+      }
+    }
+    const asBytes = fin.id === 1 && fout.id === 1 ? Uint16Array.BYTES_PER_ELEMENT : Float32Array.BYTES_PER_ELEMENT;
+    const inFrames = [], caps = [];
+    for (const chunk of chunks) {
+      const frames = (chunk.length / this.channels / fin.bytes) | 0;
+      const [, cap] = this._prepare({ length: frames * this.channels * asBytes }, asBytes);
+      inFrames.push(frames);
+      caps.push(cap);
+    }
+    return { fin, fout, inFrames, caps };
+  }
+
+  /**
+   * processChunkFormat for a list of consecutive chunks as ONE transfer each way, one conversion pass per side and
+   * (normally) one resampling launch -- a microphone's float32 stream, a G.711 RTP payload stream, a 24-bit WAV as the
+   * file system hands it out.  Returns one Buffer per chunk, byte-identical to calling processChunkFormat on each in
+   * turn (the capacity rule is applied per original chunk; dither runs on across the chunks).
+   */
+  processChunksFormat(chunks, inFormat, outFormat) {
+    this._refuseWhileAsyncPending('processChunksFormat');
+    const a = this._prepareFormat(chunks, inFormat, outFormat);
+    return speexModule.processChunksFormat(this._resamplerPtr, chunks, a.fin.id, a.fout.id, a.inFrames, a.caps);
+  }
+
+  /** processChunksFormat off the event loop (one pool-thread call for the whole list); chained with the instance's other async calls. */
+  processChunksFormatAsync(chunks, inFormat, outFormat) {
+    let a;
+    try {
+      a = this._prepareFormat(chunks, inFormat, outFormat);
+    } catch (e) {
+      return Promise.reject(e);
+    }
+    const run = () => speexModule.processChunksFormatAsync(this._resamplerPtr, chunks, a.fin.id, a.fout.id, a.inFrames, a.caps);
+    this._inFlight++;
+    const settle = () => { this._inFlight--; };
+    const p = (this._pending || Promise.resolve()).then(run, run);
+    this._pending = p.then(settle, settle);
+    return p;
+  }
+
+  /**
+   * processChunkFormat that does not block the event loop.  Calls on one instance are chained; calls of DIFFERENT
+   * instances that become ready in the same tick leave as ONE fused native call, whatever formats they name
+   * (speexhip_resampler_process_many_fmt), exactly as processChunkAsync's do.  A lone call takes the single-state path.
+   * Resolves to the same bytes processChunkFormat returns.
+   */
+  processChunkFormatAsync(chunk, inFormat, outFormat) {
+    let a;
+    try {
+      a = this._prepareFormat([chunk], inFormat, outFormat);
+    } catch (e) {
+      return Promise.reject(e);
+    }
+    const run = () => new Promise((resolve, reject) => {
+      formatTickQueue.push({ handle: this._resamplerPtr, chunk, inFrames: a.inFrames[0], cap: a.caps[0], inFmt: a.fin.id,
+        outFmt: a.fout.id, resolve, reject });
+      if (!formatTickScheduled) {
+        formatTickScheduled = true;
+        process.nextTick(flushFormatTick);
+      }
+    });
+    this._inFlight++;
+    const settle = () => { this._inFlight--; };
+    const p = (this._pending || Promise.resolve()).then(run, run);
+    this._pending = p.then(settle, settle);
+    return p;
+  }
+
   /**
    * processChunkFormat with a channel mix on either side, done on the GPU in the same two passes that convert the samples.
    * This instance's `channels` is the count the resampler runs on; inMix (rows = channels, columns = the chunk's channel
@@ -483,6 +566,18 @@ class SpeexResampler {
     return speexModule.process(ptr, null, frames, cap);
   }
 
+  /** flush() with the tail in outFormat: inputLatency frames of silence in, what comes out as processChunkFormat writes it. */
+  flushFormat(outFormat) {
+    this._refuseWhileAsyncPending('flushFormat');
+    const fout = SAMPLE_FORMATS[outFormat];
+    if (!fout) throw new Error('Unknown sample format: ' + outFormat);
+    const ptr = this._ensureNative();
+    const frames = speexModule.getLatency(ptr)[0];
+    const cap = Math.ceil(frames * this.outRate / this.inRate) + 1;
+    // (silence has no format: 's16le' keeps flush()'s own call for an 's16le' tail, every other tail is the float call's)
+    return speexModule.processFormat(ptr, null, fout.id === 1 ? 1 : 4, fout.id, frames, cap);
+  }
+
   /** Release the GPU state now (otherwise it goes with garbage collection). */
   destroy() {
     this._refuseWhileAsyncPending('destroy');
@@ -543,6 +638,42 @@ function flushTick() {
       // The instances of a tick are independent (the reference's model: one failing instance does not touch the
       // others): when the native call ran, its error carries every entry's own code and result -- entries that
       // succeeded have advanced and get their audio, only the offending ones reject.
+      if (e && Array.isArray(e.codes) && Array.isArray(e.results) && e.codes.length === jobs.length) {
+        const first = e.codes.find((c) => c !== 0);
+        jobs.forEach((j, i) => {
+          if (e.codes[i] === 0) j.resolve(e.results[i]);
+          else j.reject(e.codes[i] === first ? e : new Error(speexModule.strerror(e.codes[i])));
+        });
+      } else {
+        for (const j of jobs) j.reject(e);
+      }
+    });
+}
+
+// processChunkFormatAsync calls that became ready in this tick: one fused call of all of them, as flushTick above
+const formatTickQueue = [];
+let formatTickScheduled = false;
+function flushFormatTick() {
+  formatTickScheduled = false;
+  const jobs = formatTickQueue.splice(0, formatTickQueue.length);
+  if (jobs.length === 0) return;
+  if (jobs.length === 1) {
+    const j = jobs[0];
+    speexModule.processChunksFormatAsync(j.handle, [j.chunk], j.inFmt, j.outFmt, [j.inFrames], [j.cap])
+      .then((outs) => j.resolve(outs[0]), j.reject);
+    return;
+  }
+  let promise;
+  try {
+    promise = speexModule.processManyFormatAsync(jobs.map((j) => j.handle), jobs.map((j) => j.chunk),
+      jobs.map((j) => j.inFrames), jobs.map((j) => j.cap), jobs.map((j) => j.inFmt), jobs.map((j) => j.outFmt));
+  } catch (e) {
+    for (const j of jobs) j.reject(e);
+    return;
+  }
+  promise.then((outs) => { jobs.forEach((j, i) => j.resolve(outs[i])); },
+    (e) => {
+      // (the instances of a tick are independent: entries that succeeded get their audio, only the offending ones reject)
       if (e && Array.isArray(e.codes) && Array.isArray(e.results) && e.codes.length === jobs.length) {
         const first = e.codes.find((c) => c !== 0);
         jobs.forEach((j, i) => {
@@ -773,6 +904,10 @@ class SpeexResamplerTransform extends Transform {
    *                         async, pipeline) that is the copy they make anyway, landing in pinned memory instead of an
    *                         ordinary Buffer.  Same bytes out.  (A producer that can fill chunks from allocChunk itself needs
    *                         no option: pinned chunks are recognised wherever they arrive.)
+   *   inFormat, outFormat -- the stream's sample formats, processChunkFormat's names (default 's16le' each): bytes in
+   *                         inFormat are written, bytes in outFormat are read, in every mode above -- a G.711 RTP payload
+   *                         stream to a model's floats: { inFormat: 'mulaw', outFormat: 'f32le-normalized' }.  Without
+   *                         either the Transform is the reference's and calls what it always called.
    */
   constructor(channels, inRate, outRate, quality = 7, options = undefined) {
     super();
@@ -784,6 +919,13 @@ class SpeexResamplerTransform extends Transform {
     this._alignementBuffer = EMPTY_BUFFER;
     this._options = options || {};
     this._held = [];
+    // the stream's formats, or null: the reference's s16le through the calls it has always made
+    this._formats = null;
+    if (this._options.inFormat !== undefined || this._options.outFormat !== undefined) {
+      const names = [this._options.inFormat || 's16le', this._options.outFormat || 's16le'];
+      for (const name of names) if (!SAMPLE_FORMATS[name]) throw new Error('Unknown sample format: ' + name);
+      this._formats = names;
+    }
     if (this._options.pipeline) {
       this._busy = false;       // a processChunksAsync call is in flight
       this._waiting = null;     // the end of the stream, parked until the pipeline has drained
@@ -791,7 +933,7 @@ class SpeexResamplerTransform extends Transform {
       this._flush = (callback) => {
         const finish = () => {
           try {
-            if (this._options.flushTail) this.push(this.resampler.flush());
+            if (this._options.flushTail) this.push(this._tail());
             callback();
           } catch (e) {
             callback(e);
@@ -806,7 +948,7 @@ class SpeexResamplerTransform extends Transform {
       this._flush = (callback) => {
         try {
           this._emitHeld();
-          if (this._options.flushTail) this.push(this.resampler.flush());
+          if (this._options.flushTail) this.push(this._tail());
           callback();
         } catch (e) {
           callback(e);
@@ -826,7 +968,7 @@ class SpeexResamplerTransform extends Transform {
       this._parked = null;
       cb();
     }
-    this.resampler.processChunksAsync(batch).then((outs) => {
+    this._manyAsync(batch).then((outs) => {
       for (const out of outs) this.push(out);
       for (const h of batch) this._recycle(h);
       this._busy = false;
@@ -844,6 +986,28 @@ class SpeexResamplerTransform extends Transform {
       this.destroy(e);
     });
   }
+
+  // The calls of every mode: the stream's formats where it names them, else the reference's s16le calls as ever.
+  _one(chunk) {
+    return this._formats ? this.resampler.processChunkFormat(chunk, this._formats[0], this._formats[1]) : this.resampler.processChunk(chunk);
+  }
+
+  _oneAsync(chunk) {
+    return this._formats ? this.resampler.processChunkFormatAsync(chunk, this._formats[0], this._formats[1])
+      : this.resampler.processChunkAsync(chunk);
+  }
+
+  _many(chunks) {
+    return this._formats ? this.resampler.processChunksFormat(chunks, this._formats[0], this._formats[1])
+      : this.resampler.processChunks(chunks);
+  }
+
+  _manyAsync(chunks) {
+    return this._formats ? this.resampler.processChunksFormatAsync(chunks, this._formats[0], this._formats[1])
+      : this.resampler.processChunksAsync(chunks);
+  }
+
+  _tail() { return this._formats ? this.resampler.flushFormat(this._formats[1]) : this.resampler.flush(); }
 
   // pinned: a copy of `chunk` in a pinned chunk of the library (a plain copy when none is to be had).  Chunks come from a
   // small free list by size class; one is free again once the call that read it has returned -- _recycle().
@@ -875,7 +1039,7 @@ class SpeexResamplerTransform extends Transform {
     if (this._held.length === 0) return;
     const held = this._held;
     this._held = [];
-    for (const out of this.resampler.processChunks(held)) this.push(out);
+    for (const out of this._many(held)) this.push(out);
     for (const h of held) this._recycle(h);
   }
 
@@ -901,7 +1065,7 @@ class SpeexResamplerTransform extends Transform {
       let out;
       try {
         const own = this._pinnedCopy(this._align(chunk));
-        out = this.resampler.processChunk(own);
+        out = this._one(own);
         this._recycle(own);
       } catch (err) {
         callback(err);
@@ -914,12 +1078,12 @@ class SpeexResamplerTransform extends Transform {
   }
 
   /**
-   * Whole frames of (carry ++ chunk); the 0 .. channels*2-1 bytes that do not complete a frame
+   * Whole frames of (carry ++ chunk); the 0 .. channels*2-1 bytes (channels x bytes(inFormat) - 1 with formats) that do not complete a frame
    * are carried to the next chunk in `_alignementBuffer` (the field name, typo included, is the
    * reference's: src/index.ts:148-154 keeps it on the instance).
    */
   _align(chunk) {
-    const frameBytes = this.channels * Uint16Array.BYTES_PER_ELEMENT;
+    const frameBytes = this.channels * (this._formats ? SAMPLE_FORMATS[this._formats[0]].bytes : Uint16Array.BYTES_PER_ELEMENT);
     const carry = this._alignementBuffer;
     const joined = carry.length > 0 ? Buffer.concat([carry, chunk]) : chunk;
     const whole = joined.length - (joined.length % frameBytes);
@@ -937,7 +1101,7 @@ class SpeexResamplerTransform extends Transform {
         if (this._held.length >= this._options.coalesceChunks) this._emitHeld();
         callback();
       } else {
-        this.resampler.processChunkAsync(aligned).then((res) => {
+        this._oneAsync(aligned).then((res) => {
           this._recycle(aligned);
           callback(null, res);
         }, callback);
@@ -951,7 +1115,7 @@ class SpeexResamplerTransform extends Transform {
   _transformReference(chunk, encoding, callback) {
     let out;
     try {
-      out = this.resampler.processChunk(this._align(chunk));
+      out = this._one(this._align(chunk));
     } catch (err) {
       callback(err);
       return;

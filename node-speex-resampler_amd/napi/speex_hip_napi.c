@@ -833,6 +833,173 @@ static napi_value ProcessChunksAsync(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+/* processChunksFormat(handle, chunks: (Buffer|null)[], inFormat, outFormat, inFrames: number[], outCapacities: number[])
+ * -> Buffer[]: n consecutive processFormat() calls as one transfer each way and one wait
+ * (speexhip_resampler_process_chunks_fmt); the i-th Buffer is what the i-th call returns, in outFormat.
+ * processChunksFormatAsync: the same on a libuv pool thread -> Promise<Buffer[]>.  One job serves both. */
+typedef struct {
+  napi_async_work work;
+  napi_deferred deferred;
+  napi_ref handle_ref;
+  napi_ref *chunk_refs; /* (the asynchronous form keeps the chunks' bytes alive) */
+  Handle *h;
+  uint32_t n;
+  int32_t in_fmt, out_fmt;
+  size_t out_frame_bytes;
+  const void **ptrs;
+  uint32_t *in_len, *out_len;
+  char *tmp;
+  int rc;
+  char errmsg[256];
+} FmtChunksJob;
+
+static void fmt_chunks_free(napi_env env, FmtChunksJob *j) {
+  if (j == NULL) return;
+  if (j->chunk_refs != NULL)
+    for (uint32_t i = 0; i < j->n; i++)
+      if (j->chunk_refs[i] != NULL) napi_delete_reference(env, j->chunk_refs[i]);
+  if (j->handle_ref != NULL) napi_delete_reference(env, j->handle_ref);
+  free(j->chunk_refs);
+  free(j->ptrs);
+  free(j->in_len);
+  free(j->out_len);
+  free(j->tmp);
+  free(j);
+}
+/* the arguments as a job; NULL with an exception pending */
+static FmtChunksJob *fmt_chunks_prepare(napi_env env, napi_callback_info info, int keep_refs, napi_value *handle) {
+  size_t argc = 6;
+  napi_value argv[6];
+  if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 6) {
+    napi_throw_type_error(env, NULL, "processChunksFormat expects (handle, Buffer[], inFormat, outFormat, number[], number[])");
+    return NULL;
+  }
+  uint32_t n = 0;
+  int32_t in_fmt = -1, out_fmt = -1;
+  if (napi_get_array_length(env, argv[1], &n) != napi_ok || napi_get_value_int32(env, argv[2], &in_fmt) != napi_ok ||
+      napi_get_value_int32(env, argv[3], &out_fmt) != napi_ok) {
+    napi_throw_type_error(env, NULL, "processChunksFormat expects (handle, Buffer[], inFormat, outFormat, number[], number[])");
+    return NULL;
+  }
+  const size_t bin = speexhip_sample_bytes(in_fmt), bout = speexhip_sample_bytes(out_fmt);
+  if (bin == 0 || bout == 0) {
+    napi_throw_range_error(env, NULL, "unknown sample format");
+    return NULL;
+  }
+  Handle *h = NULL;
+  SpeexHipResamplerState *st = lock_state(env, argv[0], &h);
+  if (st == NULL) return NULL;
+  SpeexHipInfo si;
+  speexhip_resampler_get_info(st, &si); /* only the channel count is used: it never changes */
+  UNLOCK(h);
+  const size_t in_frame_bytes = (size_t)si.nb_channels * bin, m = n ? n : 1;
+  FmtChunksJob *j = (FmtChunksJob *)calloc(1, sizeof(FmtChunksJob));
+  const char *fail = NULL;
+  if (j != NULL) {
+    j->n = n;
+    j->h = h;
+    j->in_fmt = in_fmt;
+    j->out_fmt = out_fmt;
+    j->out_frame_bytes = (size_t)si.nb_channels * bout;
+    j->chunk_refs = (napi_ref *)calloc(m, sizeof(napi_ref));
+    j->ptrs = (const void **)calloc(m, sizeof(*j->ptrs));
+    j->in_len = (uint32_t *)calloc(m, sizeof(uint32_t));
+    j->out_len = (uint32_t *)calloc(m, sizeof(uint32_t));
+  }
+  if (j == NULL || !j->chunk_refs || !j->ptrs || !j->in_len || !j->out_len) fail = speexhip_resampler_strerror(SPEEXHIP_ERR_ALLOC_FAILED);
+  size_t total_cap = 0;
+  for (uint32_t i = 0; fail == NULL && i < n; i++) {
+    napi_value c, a, b;
+    void *data = NULL;
+    size_t bytes = 0;
+    if (napi_get_element(env, argv[1], i, &c) != napi_ok || napi_get_element(env, argv[4], i, &a) != napi_ok ||
+        napi_get_element(env, argv[5], i, &b) != napi_ok || !buffer_or_null(env, c, &data, &bytes) ||
+        napi_get_value_uint32(env, a, &j->in_len[i]) != napi_ok || napi_get_value_uint32(env, b, &j->out_len[i]) != napi_ok) {
+      fail = "processChunksFormat expects (handle, Buffer[], inFormat, outFormat, number[], number[])";
+    } else if (data != NULL && (size_t)j->in_len[i] * in_frame_bytes > bytes) {
+      fail = "input frame count exceeds the chunk";
+    } else if (keep_refs && data != NULL && napi_create_reference(env, c, 1, &j->chunk_refs[i]) != napi_ok) {
+      fail = "speexhip N-API failure: napi_create_reference";
+    }
+    j->ptrs[i] = data;
+    total_cap += j->out_len[i];
+  }
+  if (fail == NULL && (j->tmp = (char *)malloc(total_cap * j->out_frame_bytes + 8)) == NULL)
+    fail = speexhip_resampler_strerror(SPEEXHIP_ERR_ALLOC_FAILED);
+  if (fail != NULL) {
+    fmt_chunks_free(env, j);
+    napi_throw_error(env, NULL, fail);
+    return NULL;
+  }
+  *handle = argv[0];
+  return j;
+}
+static void fmt_chunks_run(FmtChunksJob *j) {
+  pthread_mutex_lock(&j->h->lock);
+  j->rc = j->h->st == NULL ? SPEEXHIP_ERR_BAD_STATE
+                           : speexhip_resampler_process_chunks_fmt(j->h->st, j->n, j->in_fmt, j->ptrs, j->in_len, j->out_fmt,
+                                                                   j->tmp, j->out_len);
+  if (j->rc != 0) snprintf(j->errmsg, sizeof(j->errmsg), "%s", speexhip_resampler_strerror(j->rc));
+  pthread_mutex_unlock(&j->h->lock);
+}
+/* the per-chunk Buffers of a job that ran; 0: N-API failure */
+static int fmt_chunks_result(napi_env env, const FmtChunksJob *j, napi_value *result) {
+  if (napi_create_array_with_length(env, j->n, result) != napi_ok) return 0;
+  size_t off = 0;
+  for (uint32_t i = 0; i < j->n; i++) {
+    napi_value buf;
+    void *copied = NULL;
+    const size_t bytes = (size_t)j->out_len[i] * j->out_frame_bytes;
+    if (napi_create_buffer_copy(env, bytes, j->tmp + off, &copied, &buf) != napi_ok ||
+        napi_set_element(env, *result, i, buf) != napi_ok)
+      return 0;
+    off += bytes;
+  }
+  return 1;
+}
+static napi_value ProcessChunksFormat(napi_env env, napi_callback_info info) {
+  napi_value handle, result = NULL;
+  FmtChunksJob *j = fmt_chunks_prepare(env, info, 0, &handle);
+  if (j == NULL) return NULL;
+  fmt_chunks_run(j);
+  const char *fail = j->rc != 0 ? j->errmsg : fmt_chunks_result(env, j, &result) ? NULL : "speexhip N-API failure: building the result array";
+  if (fail != NULL) napi_throw_error(env, NULL, fail);
+  fmt_chunks_free(env, j);
+  return fail != NULL ? NULL : result;
+}
+static void fmt_chunks_execute(napi_env env, void *data) {
+  (void)env;
+  fmt_chunks_run((FmtChunksJob *)data);
+}
+static void fmt_chunks_complete(napi_env env, napi_status status, void *data) {
+  FmtChunksJob *j = (FmtChunksJob *)data;
+  napi_value v, result;
+  if (status == napi_ok && j->rc == 0 && fmt_chunks_result(env, j, &result)) {
+    napi_resolve_deferred(env, j->deferred, result);
+  } else {
+    napi_value msg;
+    napi_create_string_utf8(env, j->rc != 0 ? j->errmsg : "speexhip: asynchronous call failed", NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &v);
+    napi_reject_deferred(env, j->deferred, v);
+  }
+  napi_delete_async_work(env, j->work);
+  fmt_chunks_free(env, j);
+}
+static napi_value ProcessChunksFormatAsync(napi_env env, napi_callback_info info) {
+  napi_value handle, promise = NULL, name;
+  FmtChunksJob *j = fmt_chunks_prepare(env, info, 1, &handle);
+  if (j == NULL) return NULL;
+  if (napi_create_reference(env, handle, 1, &j->handle_ref) != napi_ok || napi_create_promise(env, &j->deferred, &promise) != napi_ok ||
+      napi_create_string_utf8(env, "speexhip.processChunksFormatAsync", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, NULL, name, fmt_chunks_execute, fmt_chunks_complete, j, &j->work) != napi_ok ||
+      napi_queue_async_work(env, j->work) != napi_ok) {
+    fmt_chunks_free(env, j);
+    napi_throw_error(env, NULL, "speexhip N-API failure: queueing processChunksFormatAsync");
+    return NULL;
+  }
+  return promise;
+}
+
 /* processAsync(handle, chunk, inFrames, outCapacityFrames) -> Promise<Buffer>: the same call on
  * a libuv pool thread, so H2D + kernels + D2H do not block the event loop.  The caller
  * (index.js) chains the promises of one instance, so calls on one state stay in order. */
@@ -1605,6 +1772,8 @@ NAPI_MODULE_INIT() {
       {"processChunks", NULL, ProcessChunks, NULL, NULL, NULL, napi_default, NULL},
       {"processAsync", NULL, ProcessAsync, NULL, NULL, NULL, napi_default, NULL},
       {"processChunksAsync", NULL, ProcessChunksAsync, NULL, NULL, NULL, napi_default, NULL},
+      {"processChunksFormat", NULL, ProcessChunksFormat, NULL, NULL, NULL, napi_default, NULL},
+      {"processChunksFormatAsync", NULL, ProcessChunksFormatAsync, NULL, NULL, NULL, napi_default, NULL},
       {"setRate", NULL, SetRate, NULL, NULL, NULL, napi_default, NULL},
       {"setQuality", NULL, SetQuality, NULL, NULL, NULL, napi_default, NULL},
       {"skipZeros", NULL, SkipZeros, NULL, NULL, NULL, napi_default, NULL},

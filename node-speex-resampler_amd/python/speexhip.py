@@ -117,6 +117,8 @@ EXPORTS = [
     "speexhip_resampler_process_sides", "speexhip_resampler_process_sides_device", "speexhip_batch_process_sides_device",
     # many states, formatted: a format per state in one fused call
     "speexhip_resampler_process_many_sides", "speexhip_resampler_process_many_fmt", "speexhip_debug_many_counters",
+    # chunk coalescing, formatted: a side per direction
+    "speexhip_resampler_process_chunks_sides", "speexhip_resampler_process_chunks_fmt", "speexhip_debug_chunk_counters",
 ]
 
 # layout of a side of the sides calls (SPEEXHIP_LAYOUT_*)
@@ -402,6 +404,14 @@ def lib():
             L.speexhip_resampler_process_many_fmt.argtypes = [u32, pp, pi, pp, pu32, pi, pp, pu32, pi]
             L.speexhip_debug_many_counters.restype = None
             L.speexhip_debug_many_counters.argtypes = [C.POINTER(C.c_uint64)]
+        if hasattr(L, "speexhip_resampler_process_chunks_sides") or "SPEEXHIP_LIB_PATH" not in os.environ:
+            ps, pp = C.POINTER(Side), C.POINTER(C.c_void_p)
+            L.speexhip_resampler_process_chunks_sides.restype = i32
+            L.speexhip_resampler_process_chunks_sides.argtypes = [p, u32, ps, pp, pu32, ps, pu32]
+            L.speexhip_resampler_process_chunks_fmt.restype = i32
+            L.speexhip_resampler_process_chunks_fmt.argtypes = [p, u32, i32, pp, pu32, i32, p, pu32]
+            L.speexhip_debug_chunk_counters.restype = None
+            L.speexhip_debug_chunk_counters.argtypes = [C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -588,6 +598,14 @@ def many_counters():
     in_passes, out_passes, own_calls (entries that took their own call)."""
     v = (C.c_uint64 * 4)()
     lib().speexhip_debug_many_counters(v)
+    return dict(zip(("fir_launches", "in_passes", "out_passes", "own_calls"), (int(x) for x in v)))
+
+
+def chunk_counters():
+    """speexhip_debug_chunk_counters: process-wide counts of the formatted chunks calls since start, as a dict --
+    fir_launches, in_passes, out_passes, own_calls (chunks that took a call of their own)."""
+    v = (C.c_uint64 * 4)()
+    lib().speexhip_debug_chunk_counters(v)
     return dict(zip(("fir_launches", "in_passes", "out_passes", "own_calls"), (int(x) for x in v)))
 
 
@@ -1215,6 +1233,49 @@ class Resampler:
             outs.append(out[off: off + caps[i]].copy())
             off += caps[i]
         return outs, list(lens)
+
+    def process_chunks_sides(self, in_side, in_ptrs, in_lens, out_side, capacities):
+        """speexhip_resampler_process_chunks_sides itself: in_side describes every chunk's input (make_side; its data and
+        planes are not read), in_ptrs the addresses of the chunks -- one per chunk, or in_side.channels per chunk (plane
+        c of chunk i at i * channels + c) for a planar side of several channels; None = NULL, and in_ptrs itself may be
+        None (every chunk silence).  out_side (make_side, host buffers the caller keeps alive) receives the results back
+        to back.  Returns (rc, consumed, produced), one entry per chunk."""
+        n = len(in_lens)
+        ptrs = None
+        if in_ptrs is not None:
+            ptrs = (C.c_void_p * max(len(in_ptrs), 1))()
+            for k, a in enumerate(in_ptrs):
+                ptrs[k] = a
+        il, ol = (C.c_uint32 * max(n, 1))(*in_lens), (C.c_uint32 * max(n, 1))(*capacities)
+        rc = lib().speexhip_resampler_process_chunks_sides(self._h, n, C.byref(in_side), ptrs, il, C.byref(out_side), ol)
+        return rc, list(il)[:n], list(ol)[:n]
+
+    def process_chunks_fmt(self, chunks, in_fmt, out_fmt, capacities):
+        """n consecutive formatted calls as one transfer each way (speexhip_resampler_process_chunks_fmt).  chunks: whole
+        interleaved frames of in_fmt's storage type each (or None with capacities[i] = (null_frames, capacity)).
+        Returns (list of per-call outputs, flat, of out_fmt's storage type; list of frames consumed)."""
+        n = len(chunks)
+        bi, bo = fmt_bytes(in_fmt) * self.channels, fmt_bytes(out_fmt) * self.channels
+        keep, ptrs, lens, caps = [], (C.c_void_p * max(n, 1))(), (C.c_uint32 * max(n, 1))(), (C.c_uint32 * max(n, 1))()
+        for i, ch_ in enumerate(chunks):
+            if ch_ is None:
+                ptrs[i], lens[i], caps[i] = None, capacities[i][0], capacities[i][1]
+            else:
+                a = np.ascontiguousarray(ch_, dtype=fmt_dtype(in_fmt)).reshape(-1)
+                if a.nbytes % bi:
+                    raise ValueError("chunk %d: whole frames only" % i)
+                keep.append(a)
+                ptrs[i], lens[i], caps[i] = a.ctypes.data, a.nbytes // bi, capacities[i]
+        out = np.zeros(max(sum(caps[:n]), 1) * bo, np.uint8)
+        rc = lib().speexhip_resampler_process_chunks_fmt(self._h, n, int(in_fmt), ptrs, lens, int(out_fmt),
+                                                         C.c_void_p(out.ctypes.data), caps)
+        if rc not in (0, ERR_ALLOC_FAILED):
+            raise RuntimeError(strerror(rc))
+        outs, off = [], 0
+        for i in range(n):
+            outs.append(out[off * bo: (off + caps[i]) * bo].view(fmt_dtype(out_fmt)).copy())
+            off += caps[i]
+        return outs, list(lens)[:n]
 
     def process_device(self, d_in_ptr, in_frames, d_out_ptr, out_capacity, stream_ptr=0, float_io=False):
         il, ol = C.c_uint32(in_frames), C.c_uint32(out_capacity)
