@@ -330,8 +330,7 @@ class Batch {
     CallSide in_side = {}, out_side = {};  // these, and its dither position moves
   };
   static int many_run(uint32_t n, const ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *codes);
-  static int many_on_device(int device, int lane, const std::vector<uint32_t> &idx, const ManyEntry *entries, uint32_t *in_len,
-                            uint32_t *out_len, int *rcs);
+  struct ManyUnit;  // many.cpp: the fused entries of one (device, lane), planned by many_plan.h and carried out
   bool have_copy_stream();  // copy_stream_ = a pool stream other than own_stream_ (false: none -> no piecewise call)
 
   FilterSpec filter_;

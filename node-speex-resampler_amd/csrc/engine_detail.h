@@ -65,7 +65,6 @@ struct DrainOnExit {
   }
 };
 
-inline size_t align64(size_t v) { return (v + 63) & ~static_cast<size_t>(63); }
 inline bool buffers_overlap(const void *a, size_t na, const void *b, size_t nb) {
   const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
   return x < y + nb && y < x + na;

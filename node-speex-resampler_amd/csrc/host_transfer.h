@@ -1,7 +1,8 @@
 // host_transfer.h -- how a host-buffer call moves its buffers and how it waits (host only; tools/san_host.cpp checks it).
 // route_host_call() at the end is the whole decision for a single-state call: every entry point describes its two sides
 // (HostCallShape) and gets the way of each, the wait and the sizes of the staging buffers (HostRoute); host_call.cpp
-// carries it out.  The many-states call (many.cpp) gathers many states into one range and uses the rule's parts itself.
+// carries it out.  The many-states call gathers many states into one range: its decision is plan_many_unit (many_plan.h,
+// host only as well and checked by the same program), built from the parts below; many.cpp carries that out.
 //
 // Each side of a call (its input, its result) reaches the GPU one of four ways:
 //   InPlace  the buffer is pinned memory (engine.cpp, pinned_view): the kernels read / write it through PCIe;
@@ -45,6 +46,7 @@ const size_t kDirectCopyBytes = 256 * 1024;  // host buffers at least this big s
 const size_t kZeroCopyBelow = 720 * 1024;    // ... and calls whose buffers are smaller than this run on pinned memory alone
 
 enum class Via { None, InPlace, Bounce, Copy, Staged };
+inline size_t align64(size_t v) { return (v + 63) & ~static_cast<size_t>(63); }
 
 // A call runs on pinned memory alone when its pageable bytes -- pinned sides and an absent input count 0; the
 // many-states call sums its states' -- stay below kZeroCopyBelow in both directions.

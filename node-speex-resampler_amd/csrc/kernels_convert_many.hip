@@ -1,5 +1,5 @@
 // kernels_convert_many.hip -- the converting passes of a launch whose streams name different sample formats: the two
-// passes either side of a launch group of the formatted many-states call (many.cpp, many_on_device).  convert_many_in
+// passes either side of a launch group of the formatted many-states call (many.cpp, launch_group).  convert_many_in
 // reads each stream's storage in the stream's own format and writes its float image; convert_many_out reads the image
 // and stores the stream's format, dithered at the stream's own kind, seed and position where its state says so.
 //
