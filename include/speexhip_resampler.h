@@ -109,6 +109,22 @@ SPEEXHIP_API SpeexHipResamplerState *speexhip_resampler_init_on(int device, uint
 /* Replaces speex_resampler_destroy (speex_resampler.h:157, resample.c:868). */
 SPEEXHIP_API void speexhip_resampler_destroy(SpeexHipResamplerState *st);
 
+/* Extents -- of this call and of every process call below, host or device pointers, one state or a batch.
+ * A length is a uint32 count of frames and a stride a uint64 count of samples.  A single call serves
+ *   *in_len <= 2^32 - 1 - 2^16 - den_rate   and as many output frames, counted as what the input can make within
+ *   *out_len (an *out_len beyond that which the input cannot fill is no reason to refuse),
+ * lengths from 2^31 frames included, and any sample index, byte offset or distance between streams and planes that
+ * follows from them -- beyond 2^31 and 2^32 in one call.  Up to there every quantity of a call is held in a type that
+ * takes it ("Extents", lists them with the test that reaches each): the planner counts in 64 bits,
+ * the position a call leaves is smaller than one input block, the kernels form every address in 64 bits from 32-bit
+ * frame counts, and the one place that narrows frames to int32 -- the pieces of a large ..._take call -- is entered
+ * below 2^30 frames only.  Beyond, two kinds of 32-bit sums wrap -- the launchers round a count of frames or periods up
+ * to whole tiles, and the slide kernels end a call's outputs at k_shift + n_out (k_shift < den_rate) -- so a call that
+ * asks for more returns SPEEXHIP_ERR_OVERFLOW: the first thing every entry point does after checking its arguments,
+ * with the stream's positions, history and dither position, the lengths and the output as they were (in a
+ * many-states call: that entry's code).  The chunk calls, which add lengths up, refuse more than 0x7fffffff frames in
+ * or out in all (OVERFLOW, before anything runs). */
+
 /* Replaces speex_resampler_process_interleaved_int (speex_resampler.h:217-221,
  * resample.c:1061).  `in`/`out` are HOST pointers to interleaved s16 frames; *in_len /
  * *out_len are frames per channel: in = available / capacity, out = consumed / written.

@@ -849,6 +849,7 @@ int Batch::history(uint32_t s, float *dst) {
 
 int Batch::process_device(const void *d_in, uint64_t in_stride, uint32_t *in_len, void *d_out,
                           uint64_t out_stride, uint32_t *out_len, bool float_io, hipStream_t stream) {
+  if (!lengths_fit(in_len, out_len, n_streams_)) return SPEEXHIP_ERR_OVERFLOW;  // (engine.h; nothing touched)
   ON_DEVICE();
   // the int16 entry point emits at most 1024 outputs per 160-frame block (its stack buffer,
   // resample.c:982-991); the float entry point has no such cap (resample.c:943)
@@ -1147,6 +1148,7 @@ int Batch::take_in_pieces(const void *in, uint32_t *in_len, uint32_t *out_len, b
 int Batch::process_host_take(const void *in, uint32_t *in_len, uint32_t *out_len, bool float_io, void **block) {
   *block = nullptr;
   if (n_streams_ != 1) return SPEEXHIP_ERR_BAD_STATE;
+  if (!lengths_fit(in_len, out_len, 1)) return SPEEXHIP_ERR_OVERFLOW;
   ON_DEVICE();
   const size_t es = float_io ? sizeof(float) : sizeof(int16_t);
   const uint32_t frames = *in_len;
@@ -1211,6 +1213,7 @@ void Batch::release_block(void *block) { (void)pool::block_put(block); }
 
 int Batch::process_host(const void *in, uint32_t *in_len, void *out, uint32_t *out_len, bool float_io) {
   if (n_streams_ != 1) return SPEEXHIP_ERR_BAD_STATE;
+  if (!lengths_fit(in_len, out_len, 1)) return SPEEXHIP_ERR_OVERFLOW;
   ON_DEVICE();
   const size_t es = float_io ? sizeof(float) : sizeof(int16_t);
   const bool split = !uniform(0);
@@ -1246,6 +1249,7 @@ int Batch::process_channel_host(uint32_t c, const void *in, uint32_t *in_len, vo
                                 bool float_io) {
   if (n_streams_ != 1) return SPEEXHIP_ERR_BAD_STATE;
   if (c >= channels_) return SPEEXHIP_ERR_INVALID_ARG;
+  if (!lengths_fit(in_len, out_len, 1)) return SPEEXHIP_ERR_OVERFLOW;
   ON_DEVICE();
   const size_t es = float_io ? sizeof(float) : sizeof(int16_t);
   const EntryRules rules = entry_rules(float_io);

@@ -263,6 +263,14 @@ class Batch {
   // The most frames any channel of the one stream can produce from `frames` frames into room for `capacity` (integer
   // arithmetic, nothing launched): only so many need a staging buffer.
   uint32_t will_make(uint32_t frames, uint32_t capacity) const;
+  // Extents: the one host rule for what a single call may ask of the 32-bit counts below it.  The
+  // launchers round a frame or period count up to whole tiles in 32 bits (count + tile - 1, tiles of at most a few
+  // thousand), and the slide kernels end a call's outputs at k_shift + n_out (k_shift < den) in 32 bits.  A call fits
+  // when its in_len and the outputs it can make (the closed form: capacity and input both bound it) leave
+  // kExtentSlack + den below 2^32; every entry point asks before it touches anything and returns
+  // SPEEXHIP_ERR_OVERFLOW otherwise.  in_len / out_len: one pair of lengths for each of the first n streams.
+  static constexpr uint32_t kExtentSlack = 1u << 16;
+  bool lengths_fit(const uint32_t *in_len, const uint32_t *out_len, uint32_t n) const;
   // frames each of n channels of a result received: `all`, or -- channels that stand apart -- each channel's own
   static std::vector<uint32_t> made_per_channel(uint32_t n, uint32_t all, const CallPlan *apart) {
     std::vector<uint32_t> made(n, all);

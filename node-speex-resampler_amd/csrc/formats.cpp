@@ -89,6 +89,7 @@ void Batch::dither_advance(const uint32_t *produced) {
 int Batch::process_sides_device(const CallSide &in_side, uint32_t *in_len, const CallSide &out_side, uint32_t *out_len,
                                 hipStream_t stream, std::vector<CallPlan> *plans_out) {
   if (!side_ok(in_side, channels_) || !side_ok(out_side, channels_)) return SPEEXHIP_ERR_INVALID_ARG;
+  if (!lengths_fit(in_len, out_len, n_streams_)) return SPEEXHIP_ERR_OVERFLOW;  // (engine.h; nothing touched)
   // (a side of one channel is the same bytes in either layout)
   CallSide in = in_side, out = out_side;
   if (!planar(in)) in.layout = SPEEXHIP_LAYOUT_INTERLEAVED;
@@ -199,6 +200,7 @@ int Batch::process_host_many_sides(uint32_t n, Batch *const *st, const CallSide 
 int Batch::process_sides_host(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len) {
   if (n_streams_ != 1) return SPEEXHIP_ERR_BAD_STATE;
   if (!side_ok(in, channels_) || !side_ok(out, channels_)) return SPEEXHIP_ERR_INVALID_ARG;
+  if (!lengths_fit(in_len, out_len, 1)) return SPEEXHIP_ERR_OVERFLOW;
   if (planar(in) || planar(out)) return planes_host_call(in, in_len, out, out_len);
   // (a mono side given as its one plane)
   if (in.planes != nullptr || out.planes != nullptr) {

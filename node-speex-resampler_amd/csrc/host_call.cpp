@@ -43,6 +43,18 @@ uint32_t Batch::will_make(uint32_t frames, uint32_t capacity) const {
   return most;
 }
 
+bool Batch::lengths_fit(const uint32_t *in_len, const uint32_t *out_len, uint32_t n) const {
+  const uint64_t room = 0xffffffffull - kExtentSlack;
+  const uint32_t most = filter_.den < room ? static_cast<uint32_t>(room - filter_.den) : 0u;
+  for (uint32_t s = 0; s < n; s++) {
+    if (in_len[s] > most) return false;
+    if (out_len[s] <= most) continue;  // (every call but those that name a capacity at the very limit)
+    for (uint32_t c = 0; c < channels_; c++)
+      if (produced_closed_form(filter_.num, filter_.den, in_len[s], out_len[s], P(s, c)) > most) return false;
+  }
+  return true;
+}
+
 // The pinned lookup of both sides: the address the device sees where a side is pinned memory (pinned_view), else nullptr
 // (a null side too).  A pinned result that overlaps its pinned chunk: the chunk is taken in whole before anything is
 // written, as on pageable buffers -- it counts as not pinned.

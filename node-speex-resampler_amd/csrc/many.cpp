@@ -477,6 +477,10 @@ int Batch::many_run(uint32_t n, const ManyEntry *entries, uint32_t *in_len, uint
       rcs[i] = entries[i].rc;
       continue;
     }
+    if (b->n_streams_ == 1 && !b->lengths_fit(&in_len[i], &out_len[i], 1)) {  // (engine.h: likewise)
+      rcs[i] = SPEEXHIP_ERR_OVERFLOW;
+      continue;
+    }
     bool earlier = false;  // a state named twice: its second call must see the first one's end state
     for (uint32_t j = 0; j < i && !earlier; j++) earlier = entries[j].b == b;
     // (rare states -- channels moved apart by the per-channel calls, the zero fallback, batches of several streams --

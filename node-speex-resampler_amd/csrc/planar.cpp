@@ -26,6 +26,7 @@ int Batch::ensure_planar_scratch(size_t in_bytes, size_t out_bytes) {
 int Batch::process_planar_device(const void *d_in, uint64_t in_stream_stride, uint64_t in_plane_stride, uint32_t *in_len,
                                  void *d_out, uint64_t out_stream_stride, uint64_t out_plane_stride, uint32_t *out_len,
                                  bool float_io, hipStream_t stream) {
+  if (!lengths_fit(in_len, out_len, n_streams_)) return SPEEXHIP_ERR_OVERFLOW;  // (engine.h; nothing touched)
   // a mono plane is an interleaved buffer
   if (channels_ == 1) return process_device(d_in, in_stream_stride, in_len, d_out, out_stream_stride, out_len, float_io, stream);
   ON_DEVICE();
@@ -122,6 +123,7 @@ int Batch::process_planar_host(const void *const *in_planes, uint32_t *in_len, v
   const uint32_t frames = *in_len, capacity = *out_len;
   for (uint32_t c = 0; c < channels_; c++)
     if (out_planes[c] == nullptr || (in_planes != nullptr && in_planes[c] == nullptr)) return SPEEXHIP_ERR_INVALID_ARG;
+  if (!lengths_fit(in_len, out_len, 1)) return SPEEXHIP_ERR_OVERFLOW;
   // only as many output frames as this call can produce are written (and need a device buffer)
   const bool split = !uniform(0);
   const uint32_t most = will_make(frames, capacity);

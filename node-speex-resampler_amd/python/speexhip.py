@@ -609,6 +609,11 @@ def chunk_counters():
     return dict(zip(("fir_launches", "in_passes", "out_passes", "own_calls"), (int(x) for x in v)))
 
 
+def release_cached_memory():
+    """speexhip_release_cached_memory: hands every idle pooled buffer and cached table back to the device; bytes freed"""
+    return int(lib().speexhip_release_cached_memory())
+
+
 def _per_state(v, n):
     """one value for all states, or a sequence with one per state"""
     return [int(v)] * n if isinstance(v, (int, np.integer)) else [int(f) for f in v]
