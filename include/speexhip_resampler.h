@@ -617,6 +617,72 @@ SPEEXHIP_API int speexhip_batch_get_dither(SpeexHipBatch *b, uint32_t stream, in
 SPEEXHIP_API int speexhip_debug_dither(int kind, uint64_t seed, uint64_t first_index, uint32_t n, double *d);
 
 /* ------------------------------------------------------------------------------------------
+ * Metering: the output passes saturate -- they clamp the integer and companded formats, send +-inf
+ * to the rails and turn NaN into the format's zero -- and without the meter the caller never learns
+ * that they did.  A band-limiting filter overshoots on full-scale material, so a stream that did not
+ * clip at one rate may clip at another; a conversion from float adds whatever gain the producer
+ * applied.  With the meter on, a state counts what its formatted, mixed and sides calls had to throw
+ * away and keeps the peak level, per stream.  (The remedy is in the library already: a diagonal
+ * out_mix is a gain.)  Off by default; while it is off every call is exactly what it is without this
+ * section, shortcuts and kernels included.
+ *
+ * For one value y that an output pass is about to encode to format F, with d the dither of that sample
+ * ("Dither"; 0 when dither is off):
+ *
+ *   nan           y != y.  Nothing else is counted for that sample.
+ *   peak          |y| in int16 units: the value the format's "from a FIR value" rule takes -- behind the
+ *                 output matrix, before the dither.  +inf is a legal peak.  0 when nothing was metered.
+ *   clipped_high  r > hi,   clipped_low  r < lo,   in fp64 and evaluated as written:
+ *                   v = (double)y * 2^k  (exact);   t = v + d  (one rounding);   r = floor(t + 0.5)  (one rounding)
+ *                 that is the dither section's q before the U8 offset and the clamp; lo and hi are the format's
+ *                 rails (U8: 0 and 255 behind the offset, that is -128 and 127 before it; S16: -32768 and 32767;
+ *                 S24: -2^23 and 2^23 - 1; S32: -2^31 and 2^31 - 1).  The companded formats are judged at their
+ *                 int16 stage -- the mu-law compressor's own limit at 32635 is no clip -- and a big-endian format
+ *                 as its little-endian twin.  +-inf count as clips at their rail.
+ *
+ * The float formats (F32, F32N, F16N, BF16N) never count a clip: their callers read the peak, and a
+ * peak above 32768.0 means beyond +-1.0.  `samples` counts every sample metered: frames produced
+ * times samples of an output frame.  The totals are integers and a maximum, so like a stream's bytes
+ * they depend on the stream alone: not on how it is cut into calls, on what shares its launch, or on
+ * the GPU.
+ *
+ * The meter is a property of the state and applies to the formatted, mixed and sides calls only --
+ * host, device, batch, many-states and chunks forms.  The int16, float, planar, per-channel,
+ * chunks_int / _float, many_int / _float and take calls are never metered, exactly as they are never
+ * dithered.  While it is on
+ *   - every output format is metered on its way out; where a call has no output pass (F32 -> F32,
+ *     F32N -> F32N without matrix or planar side) the result is read once more, an F32N result as
+ *     stored * 32768, and its bytes stay the float call's;
+ *   - S16 -> S16 is no longer the int16 call: it runs as the float call between the two conversions,
+ *     with the float entry's counter rules (as with dither on);
+ *   - the zero fallback's zeros are metered like any other value: they count as samples and clip nothing;
+ *   - a state whose channels the per-channel calls moved apart returns BAD_STATE, untouched.
+ * set_meter takes 0 or 1 (anything else: INVALID_ARG) and keeps the totals.  get_meter waits for this
+ * state's own last call -- never for the device -- and reports the totals since the last reset; with
+ * reset != 0 they are zero from there on (m may then be NULL), in a batch for that stream only.
+ * set_rate, set_quality, reset_mem, skip_zeros and set_dither touch neither the switch nor the totals.
+ *
+ * ABI note: 0.7 + metering adds one struct and these five entry points; SpeexHipInfo, SpeexHipSide, the
+ * enums, the error codes and the version string are unchanged. */
+typedef struct SpeexHipMeter {
+  uint32_t struct_size;      /* the caller's sizeof(SpeexHipMeter); at most that many bytes are written; too small for
+                                the fields of this version: INVALID_ARG */
+  uint32_t on;               /* out: whether the meter is on */
+  uint64_t samples;          /* samples metered since the last reset */
+  uint64_t clipped_high, clipped_low, nan;
+  float peak;                /* int16 units; 0 when nothing was metered */
+  uint32_t reserved;
+} SpeexHipMeter;
+SPEEXHIP_API int speexhip_resampler_set_meter(SpeexHipResamplerState *st, int on);
+SPEEXHIP_API int speexhip_resampler_get_meter(SpeexHipResamplerState *st, SpeexHipMeter *m, int reset);
+SPEEXHIP_API int speexhip_batch_set_meter(SpeexHipBatch *b, int on);
+SPEEXHIP_API int speexhip_batch_get_meter(SpeexHipBatch *b, uint32_t stream, SpeexHipMeter *m, int reset);
+/* Host only, no GPU: the very statement the kernels compile, accumulated over y[0..n) into *m (samples = n; `on` is
+ * not written).  d = NULL: no dither; d != NULL for a float format: INVALID_ARG, like an unknown format or a short
+ * struct_size. */
+SPEEXHIP_API int speexhip_debug_meter(int fmt, const float *y, const double *d, uint32_t n, SpeexHipMeter *m);
+
+/* ------------------------------------------------------------------------------------------
  * Companded formats: G.711 as telephony carries it (RTP PCMU / PCMA, 8 kHz), one byte per sample, no
  * alignment needed.  SPEEXHIP_FMT_ULAW = 16 and SPEEXHIP_FMT_ALAW = 17: companded formats start at 16,
  * the values 6..15 stay invalid.  Both are accepted wherever a format is named -- the formatted and the

@@ -8,6 +8,7 @@
 #include "../../include/speexhip_resampler.h"
 #include "devices.h"
 #include "dither.h"
+#include "meter.h"
 #include "engine.h"
 #include "filter_plans.h"
 #include "g711.h"
@@ -749,6 +750,45 @@ int speexhip_batch_get_dither(SpeexHipBatch *b, uint32_t stream, int *kind, uint
 int speexhip_debug_dither(int kind, uint64_t seed, uint64_t first_index, uint32_t n, double *d) {
   if (!speexhip::dither::known_kind(kind) || (d == nullptr && n != 0)) return SPEEXHIP_ERR_INVALID_ARG;
   for (uint32_t i = 0; i < n; i++) d[i] = speexhip::dither::noise(kind, seed, first_index + i);
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+int speexhip_resampler_set_meter(SpeexHipResamplerState *st, int on) {
+  return guarded([&] { return st ? st->batch->set_meter(on) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_resampler_get_meter(SpeexHipResamplerState *st, SpeexHipMeter *m, int reset) {
+  return guarded([&] { return st ? st->batch->get_meter(0, m, reset != 0) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_batch_set_meter(SpeexHipBatch *b, int on) {
+  return guarded([&] { return b ? b->batch->set_meter(on) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_batch_get_meter(SpeexHipBatch *b, uint32_t stream, SpeexHipMeter *m, int reset) {
+  return guarded([&] { return b ? b->batch->get_meter(stream, m, reset != 0) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_debug_meter(int fmt, const float *y, const double *d, uint32_t n, SpeexHipMeter *m) {
+  namespace mt = speexhip::meter;
+  if (m == nullptr || m->struct_size < sizeof(SpeexHipMeter) || speexhip::sample_bytes(fmt) == 0 || (y == nullptr && n != 0))
+    return SPEEXHIP_ERR_INVALID_ARG;
+  if (d != nullptr && !speexhip::dithered_fmt(fmt)) return SPEEXHIP_ERR_INVALID_ARG;  // (the float formats are not dithered)
+  uint64_t hi = 0, lo = 0, nan = 0;
+  uint32_t peak = 0;
+  (void)speexhip::fmtdev::with_format(fmt, [&](auto format) -> hipError_t {
+    for (uint32_t i = 0; i < n; i++) {
+      mt::Lane one;  // (a lane's counts are 32 bits: folded sample by sample here)
+      mt::judge<decltype(format)::value>(one, y[i], d != nullptr ? d[i] : 0.0);
+      hi += one.hi, lo += one.lo, nan += one.nan;
+      peak = one.peak > peak ? one.peak : peak;
+    }
+    return hipSuccess;
+  });
+  SpeexHipMeter now;
+  std::memset(&now, 0, sizeof(now));
+  now.struct_size = m->struct_size;
+  now.on = m->on;
+  now.samples = n;
+  now.clipped_high = hi, now.clipped_low = lo, now.nan = nan;
+  std::memcpy(&now.peak, &peak, sizeof(peak));
+  std::memcpy(m, &now, sizeof(now));
   return SPEEXHIP_ERR_SUCCESS;
 }
 

@@ -784,11 +784,99 @@ Batch::~Batch() {
   pool::device_put(device_, d_stage_out_);
   pool::device_put(device_, d_planar_in_);
   pool::device_put(device_, d_planar_out_);
+  pool::device_put(device_, d_meter_);
   pool::pinned_put(h_pin_in_);
   pool::pinned_put(h_pin_out_);
   for (int i = 0; i < kMaxPieces; i++) pool::event_put(device_, piece_ev_[i]);
   pool::stream_put(device_, copy_stream_);
   pool::stream_put(device_, own_stream_);
+}
+
+// ---- the output meter (engine.h) ---------------------------------------------------------------------------------------
+// The cells are control-plane data: zeroed and fetched through the copy engines (kCtlCopyMin), whole, on own_stream_.
+int Batch::set_meter(int on) {
+  if (on != 0 && on != 1) return SPEEXHIP_ERR_INVALID_ARG;
+  if (on != 0 && d_meter_ == nullptr) {
+    ON_DEVICE();
+    void *cells = nullptr;
+    const size_t bytes = std::max(sizeof(MeterCell) * n_streams_, kCtlCopyMin);
+    int rc = dev_alloc(device_, &cells, bytes);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+    const std::vector<char> zeros(bytes, 0);
+    rc = ctl_upload(cells, zeros.data(), bytes, own_stream_);  // (in place before any launch on any stream)
+    if (rc != SPEEXHIP_ERR_SUCCESS) {
+      pool::device_put(device_, cells);
+      return rc;
+    }
+    d_meter_ = static_cast<MeterCell *>(cells);
+    meter_bytes_ = bytes;
+    meter_samples_.assign(n_streams_, 0);
+  }
+  meter_on_ = on != 0;
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+int Batch::get_meter(uint32_t stream, SpeexHipMeter *m, bool reset) {
+  if (stream >= n_streams_ || (m == nullptr && !reset)) return SPEEXHIP_ERR_INVALID_ARG;
+  if (m != nullptr && m->struct_size < sizeof(SpeexHipMeter)) return SPEEXHIP_ERR_INVALID_ARG;
+  SpeexHipMeter now;
+  std::memset(&now, 0, sizeof(now));
+  now.on = meter_on_ ? 1u : 0u;
+  if (d_meter_ != nullptr) {
+    ON_DEVICE();
+    int rc = quiesce();  // this state's own last call; its totals are in the cells behind it
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+    std::vector<MeterCell> cells(n_streams_);
+    rc = ctl_download(cells.data(), reinterpret_cast<const char *>(d_meter_), meter_bytes_, 0, sizeof(MeterCell) * n_streams_,
+                      own_stream_);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+    const MeterCell &c = cells[stream];
+    now.samples = meter_samples_[stream];
+    now.clipped_high = c.hi;
+    now.clipped_low = c.lo;
+    now.nan = c.nan;
+    std::memcpy(&now.peak, &c.peak_bits, sizeof(now.peak));
+    if (reset) {  // (nothing of this state is in flight: the cells go back whole, this stream's zeroed)
+      std::memset(&cells[stream], 0, sizeof(MeterCell));
+      rc = ctl_upload(d_meter_, cells.data(), sizeof(MeterCell) * n_streams_, own_stream_);
+      if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+      meter_samples_[stream] = 0;
+    }
+  }
+  if (m != nullptr) {
+    now.struct_size = m->struct_size;
+    std::memcpy(m, &now, sizeof(now));
+  }
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+MeterPack Batch::meter_pack(uint32_t s0, uint32_t n) const {
+  MeterPack p;
+  std::memset(&p, 0, sizeof(p));
+  for (uint32_t j = 0; j < n; j++) p.cell[j] = d_meter_ + s0 + j;
+  return p;
+}
+
+void Batch::meter_count(const uint32_t *produced, uint32_t per_frame) {
+  for (uint32_t s = 0; s < n_streams_; s++) meter_samples_[s] += static_cast<uint64_t>(produced[s]) * per_frame;
+}
+
+int Batch::meter_result(const void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream) {
+  const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
+  for (uint32_t first = 0; first < n_streams_; first += kChunk) {
+    const uint32_t n = std::min(kChunk, n_streams_ - first);
+    ConvertPack pack;
+    std::memset(&pack, 0, sizeof(pack));
+    uint64_t most = 0;
+    for (uint32_t j = 0; j < n; j++) {
+      pack.s[j].src = static_cast<const float *>(result) + (first + j) * stride;
+      pack.s[j].n = static_cast<uint64_t>(lens[first + j]) * channels_;
+      pack.s[j].step = 1;
+      most = std::max(most, pack.s[j].n);
+    }
+    if (hip_failed(launch_meter_image(pack, meter_pack(first, n), scale, n, most, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+  }
+  return SPEEXHIP_ERR_SUCCESS;
 }
 
 CallPlan Batch::peek(uint32_t s, uint32_t in_len, uint32_t out_capacity, bool float_io) const {

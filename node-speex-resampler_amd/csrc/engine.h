@@ -112,6 +112,9 @@ class Batch {
   // the place of convert_* / mix_*, which converts, mixes and dithers while it transposes -- F32 without a matrix
   // included, whose planes are not the image.  With a planar side every format pair runs as the float call (S16 -> S16
   // too); both sides planar, F32 -> F32 or F32N -> F32N, no matrix: process_planar_device on the same bytes.
+  // With the meter on (set_meter) the output side's pass is its metered instance, a result that no pass writes is read by
+  // meter_image behind the float call, the planar float pairs run between planes_in and the metered planes_out, S16 -> S16
+  // runs as the float call, and a state whose channels stand apart returns BAD_STATE.
   int process_sides_device(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len, hipStream_t stream,
                            std::vector<CallPlan> *plans_out = nullptr);
   // ... on host buffers of a single-stream batch (strides unused); synchronous.  The raw bytes of both sides move by the
@@ -140,6 +143,19 @@ class Batch {
   // other call reads or moves any of this, and no control call (set_rate, set_quality, reset_mem, skip_zeros) touches it.
   int set_dither(int kind, uint64_t seed, uint64_t position);
   int get_dither(uint32_t stream, int *kind, uint64_t *seed, uint64_t *position) const;  // seed: the stream's own
+  // The output meter of the formatted, mixed and sides calls (meter.h; include/speexhip_resampler.h, "Metering"): a
+  // property of the state, off by default.  While it is on every such call -- host, device, batch, many-states, chunks --
+  // is judged on its output side, sample by sample as it is encoded, into the stream's MeterCell in device memory: by the
+  // metered instances of its output pass, or, where the call has none (a float result written by the FIR itself), by
+  // meter_image over the result.  S16 -> S16 then runs as the float call between convert_in and the metered convert_out,
+  // and a state whose channels stand apart returns BAD_STATE, as with dither on.  The int16, float, planar, per-channel,
+  // chunks_int / _float, many_int / _float and take calls are never metered.  `samples` is kept here on the host: frames
+  // produced x samples of an output frame, added when a call commits.  set_meter keeps the totals; no control call
+  // (set_rate, set_quality, reset_mem, skip_zeros, set_dither) touches the switch or the totals.
+  int set_meter(int on);
+  // The totals of `stream` (m may be null): waits on the host for this state's own last call, as the control calls do --
+  // never for the device -- and fetches the cells in one small copy.  reset: that stream's totals are zero from here on.
+  int get_meter(uint32_t stream, SpeexHipMeter *m, bool reset);
   // Host-buffer call for a single-stream batch; synchronous (H2D, kernels, D2H).
   int process_host(const void *in, uint32_t *in_len, void *out, uint32_t *out_len, bool float_io);
   // The same call with the result left in a pinned block of the pool that the caller then OWNS (release_block):
@@ -249,6 +265,12 @@ class Batch {
   // the DitherPack of streams [s0, s0 + n): first = position * per_frame (per_frame = 1: the position itself)
   DitherPack dither_pack(uint32_t s0, uint32_t n, uint32_t per_frame) const;
   void dither_advance(const uint32_t *produced);  // after a formatted or mixed call with dither on
+  // the cells of streams [s0, s0 + n), as a metered launch takes them
+  MeterPack meter_pack(uint32_t s0, uint32_t n) const;
+  void meter_count(const uint32_t *produced, uint32_t per_frame);  // after a formatted or mixed call with the meter on
+  // meter_image over what a call without an output pass wrote: stream s is lens[s] frames of channels() floats at
+  // result + s * stride (floats), judged as stored * scale
+  int meter_result(const void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream);
   // process_sides_host of a call with a planar side
   int planes_host_call(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len);
   int fetch_history(std::vector<float> *host);
@@ -398,6 +420,10 @@ class Batch {
   int dither_kind_ = SPEEXHIP_DITHER_NONE;  // set_dither
   uint64_t dither_seed_ = 0;
   std::vector<uint64_t> dither_pos_;        // per stream: index of its next output frame (empty until set_dither: 0)
+  bool meter_on_ = false;                   // set_meter
+  MeterCell *d_meter_ = nullptr;            // one cell per stream (null until the meter is first turned on), meter_bytes_ in all
+  size_t meter_bytes_ = 0;
+  std::vector<uint64_t> meter_samples_;     // per stream: samples metered since the last reset
   uint32_t done_seq_ = 0;  // completion word of the small host-buffer calls (engine.cpp, process_host)
   size_t stage_in_cap_ = 0, stage_out_cap_ = 0, pin_in_cap_ = 0, pin_out_cap_ = 0;  // bytes
 };

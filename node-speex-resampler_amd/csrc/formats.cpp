@@ -2,7 +2,8 @@
 // (SPEEXHIP_FMT_*), and a side may carry a channel matrix (CallSide).  One pipeline serves them all:
 // storage --the input side's pass--> float scratch image --the existing float launch--> float scratch image --the output
 // side's pass--> storage (side_pass, mix.cpp).  Counters, positions and the history are the float call's, so formatted,
-// mixed, interleaved, planar and per-channel calls mix freely on one state.  The state's dither (set_dither) lives here too.
+// mixed, interleaved, planar and per-channel calls mix freely on one state.  The state's dither (set_dither) lives here too;
+// its meter (set_meter / get_meter) in engine.cpp, beside the control copies it uses.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -95,21 +96,28 @@ int Batch::process_sides_device(const CallSide &in_side, uint32_t *in_len, const
   if (!planar(in)) in.layout = SPEEXHIP_LAYOUT_INTERLEAVED;
   if (!planar(out)) out.layout = SPEEXHIP_LAYOUT_INTERLEAVED;
   ON_DEVICE();
-  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on();
+  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), meter = meter_on_;
   bool split = false;
   for (uint32_t s = 0; s < n_streams_; s++)
     if (!uniform(s)) {
       // (channels that stand apart produce different numbers of frames: neither an output frame of a matrix nor a dither
-      //  position is defined)
-      if (n_streams_ != 1 || dith || mixed) return SPEEXHIP_ERR_BAD_STATE;
+      //  position nor a stream of samples to meter is defined)
+      if (n_streams_ != 1 || dith || mixed || meter) return SPEEXHIP_ERR_BAD_STATE;
       split = true;
     }
-  if (same_bytes(in, out, dith)) {
+  if (same_bytes(in, out, dith || meter)) {
+    // (with the meter on: F32 or F32N, the float call's bytes as ever, read once more by meter_image)
     const int rc = process_device(in.base, in.stride, in_len, out.base, out.stride, out_len, in.fmt != SPEEXHIP_FMT_S16, stream);
+    if (meter && ran(rc)) {
+      const int mrc = meter_result(out.base, out.stride, out_len, in.fmt == SPEEXHIP_FMT_F32N ? 32768.0f : 1.0f, stream);
+      if (mrc != SPEEXHIP_ERR_SUCCESS) return mrc;
+      meter_count(out_len, channels_);
+    }
     if (dith && ran(rc)) dither_advance(out_len);
     return rc;
   }
-  if (planar_float_call(in, out) && !split) {
+  // (with the meter on the planar float pairs run between planes_in and the metered planes_out)
+  if (planar_float_call(in, out) && !split && !meter) {
     const int rc = process_planar_device(in.base, in.stride, in.plane_stride, in_len, out.base, out.stride, out.plane_stride,
                                          out_len, true, stream);
     if (dith && ran(rc)) dither_advance(out_len);
@@ -158,7 +166,12 @@ int Batch::process_sides_device(const CallSide &in_side, uint32_t *in_len, const
     // (out_len: what the float call produced)
     const int prc = side_pass(out, false, d_planar_out_, out_pitch, out_len, stream, split ? plans.data() : nullptr);
     if (prc != SPEEXHIP_ERR_SUCCESS) return prc;
+  } else if (meter) {
+    // (interleaved F32 without a matrix: the FIR wrote the caller's buffer)
+    const int mrc = meter_result(out.base, out.stride, out_len, 1.0f, stream);
+    if (mrc != SPEEXHIP_ERR_SUCCESS) return mrc;
   }
+  if (meter) meter_count(out_len, out.channels);
   if (dith) dither_advance(out_len);
   return rc;
 }
@@ -184,10 +197,14 @@ int Batch::process_host_many_sides(uint32_t n, Batch *const *st, const CallSide 
     // fused: both sides interleaved (or of one channel) in one buffer each, no matrix
     e.fusable = !planar(in[i]) && !planar(out[i]) && in[i].mix == nullptr && out[i].mix == nullptr && in[i].planes == nullptr &&
                 out[i].planes == nullptr;
+    // (a metered result that no pass of kernels_convert_many.hip writes -- F32, or the float call on the same bytes --
+    //  takes its own call, which runs meter_image behind it)
+    if (b->meter_on_ && (out[i].fmt == SPEEXHIP_FMT_F32 || (in[i].fmt == out[i].fmt && out[i].fmt == SPEEXHIP_FMT_F32N)))
+      e.fusable = false;
     if (!e.fusable) continue;
     e.in = in[i].base;
     e.out = out[i].base;
-    e.kind = !same_bytes(in[i], out[i], b->dither_on()) ? ManyEntry::Image
+    e.kind = !same_bytes(in[i], out[i], b->dither_on() || b->meter_on_) ? ManyEntry::Image
              : in[i].fmt == SPEEXHIP_FMT_S16            ? ManyEntry::Int16
                                                         : ManyEntry::Float;
   }
@@ -213,8 +230,9 @@ int Batch::process_sides_host(const CallSide &in, uint32_t *in_len, const CallSi
   }
   if (out.base == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
   const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), split = !uniform(0);
-  if (split && dith && !mixed) return SPEEXHIP_ERR_BAD_STATE;
-  if (same_bytes(in, out, dith)) {
+  if (split && (dith || meter_on_) && !mixed) return SPEEXHIP_ERR_BAD_STATE;
+  // (with the meter on the float pairs go on below: process_sides_device runs meter_image behind the float call)
+  if (same_bytes(in, out, dith) && !meter_on_) {
     const int rc = process_host(in.base, in_len, out.base, out_len, in.fmt != SPEEXHIP_FMT_S16);
     if (dith && ran(rc)) dither_advance(out_len);
     return rc;
@@ -321,11 +339,13 @@ int Batch::process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, cons
   for (uint32_t i = 0; i < n_chunks; i++)
     for (uint32_t c = 1; entry(i, 0) != nullptr && c < per; c++)
       if (entry(i, c) == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
-  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), split = !uniform(0);
-  if (split && (dith || mixed)) return SPEEXHIP_ERR_BAD_STATE;
-  const bool same = same_bytes(in, out, dith), own_calls = split || zero_mode_;
+  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), meter = meter_on_, split = !uniform(0);
+  if (split && (dith || mixed || meter)) return SPEEXHIP_ERR_BAD_STATE;
+  // same: the call on the same bytes; with the meter on (F32 or F32N then) it still goes through here, without passes,
+  // and meter_image reads the result
+  const bool same = same_bytes(in, out, dith || meter), own_calls = split || zero_mode_;
   const size_t bin = sample_bytes(in.fmt), bout = sample_bytes(out.fmt);
-  if (own_calls && !same) {  // rare states: the separate calls, one after the other, each output side behind the frames written
+  if (own_calls && (!same || meter)) {  // rare states: the separate calls, one after the other, each output side behind the frames written
     int last = SPEEXHIP_ERR_SUCCESS;
     uint64_t written = 0;
     std::vector<void *> planes(out.channels);
@@ -349,7 +369,7 @@ int Batch::process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, cons
     return last;
   }
   const ChunkPlans p = plan_chunks(filter_.num, filter_.den, n_chunks, in_len, out_len, P(0, 0), entry_rules(!same || in.fmt != SPEEXHIP_FMT_S16));
-  if (same) {  // process_host_chunks on the same bytes (which serves the rare states itself)
+  if (same && !meter) {  // process_host_chunks on the same bytes (which serves the rare states itself)
     const int rc = process_host_chunks(n_chunks, in_data, in_len, out.base, out_len, in.fmt != SPEEXHIP_FMT_S16);
     if (!ran(rc)) return rc;
     uint32_t made = 0;
@@ -387,8 +407,8 @@ int Batch::process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, cons
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   // The passes of process_sides_device, once over all chunks: conversion, matrix and dither are per sample or per frame,
   // and the dither index runs on over the chunks' output frames as the position does.
-  const bool pass_in = (in.mix != nullptr || in.fmt != SPEEXHIP_FMT_F32 || pl_in) && frames != 0;
-  const bool pass_out = out.mix != nullptr || out.fmt != SPEEXHIP_FMT_F32 || pl_out;
+  const bool pass_in = !same && (in.mix != nullptr || in.fmt != SPEEXHIP_FMT_F32 || pl_in) && frames != 0;
+  const bool pass_out = !same && (out.mix != nullptr || out.fmt != SPEEXHIP_FMT_F32 || pl_out);
   const size_t fi = channels_ * sizeof(float);  // bytes of a frame of the float images
   rc = ensure_planar_scratch(pass_in ? align64(static_cast<size_t>(frames) * channels_) * sizeof(float) : 0,
                              pass_out ? align64(static_cast<size_t>(made) * channels_) * sizeof(float) : 0);
@@ -416,7 +436,11 @@ int Batch::process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, cons
   if (pass_out) {
     rc = side_pass(pl_out ? planes_at(out, call.dst, out_pitch) : at(out, call.dst), false, d_planar_out_, 0, &made, own_stream_);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  } else if (meter) {
+    rc = meter_result(call.dst, 0, &made, out.fmt == SPEEXHIP_FMT_F32N ? 32768.0f : 1.0f, own_stream_);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
+  if (meter) meter_count(&made, out.channels);
   if (dith) dither_advance(&made);
   if (pl_out) {
     std::vector<void *> planes(out.channels);
@@ -443,7 +467,7 @@ int Batch::process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, cons
 int Batch::planes_host_call(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len) {
   const bool pl_in = planar(in), pl_out = planar(out);
   const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), split = !uniform(0);
-  if (split && (dith || mixed)) return SPEEXHIP_ERR_BAD_STATE;
+  if (split && (dith || mixed || meter_on_)) return SPEEXHIP_ERR_BAD_STATE;
   // (a mono side given as its one plane is an interleaved buffer)
   CallSide in_flat = in, out_flat = out;
   if ((!pl_in && in.planes != nullptr && in.planes[0] == nullptr) || (!pl_out && out.planes != nullptr && out.planes[0] == nullptr))

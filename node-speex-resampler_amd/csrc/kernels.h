@@ -263,16 +263,35 @@ struct DitherPack {         // like ConvertPack: up to 32 streams, in the kernel
   uint32_t reserved;
 };
 
+// ---- the meter on the way out (meter.h): the metered instances of the output passes -- convert_out_meter<F>,
+// convert_many_out_meter, mix_out_meter<F>, planes_out_meter<F> -- and meter_image, of a state with the meter on.  Each
+// workgroup adds what its samples came to into its stream's cell; the cells' addresses travel in a last kernel argument.
+struct MeterCell {          // one stream's totals, in device memory
+  uint64_t hi, lo, nan;     // samples clipped at the upper rail / at the lower rail / that were NaN
+  uint32_t peak_bits;       // bits of the largest |y| (int16 units) among the samples that were not NaN
+  uint32_t pad;
+};
+struct MeterPack {          // like ConvertPack: up to 32 streams, in the kernel-argument segment (256 bytes)
+  MeterCell *cell[kMaxPackedStreams];  // convert_many_out_meter: NULL = a stream that is not metered
+};
+
 // ---- the launchers of a pass over streams [0, n) of `pack` -------------------------------------------------------------
 // fmt = the storage side's format: any SPEEXHIP_FMT_* for a mix, any but F32 for a conversion (that IS the image's
 // format).  out: image -> storage, otherwise storage -> image.  dith = NULL: the plain instances; otherwise the dithered
 // ones (out only, a dithered_fmt, every ConvertStream::step 1: sample k of a stream has idx first + k).  most = the
 // largest ConvertStream::n / MixStream::frames among the streams.  What a launcher refuses (and channel counts of a
 // matrix outside 1..8) it refuses with hipErrorInvalidValue before it launches.
+// meter = NULL: exactly the above.  Otherwise (out only, every step 1) the metered instances, for every format: the
+// formats of dithered_fmt through the dithered body -- dith = NULL: kind NONE, d = 0, the undithered bytes -- and the
+// float ones through the plain body; stream j is judged into meter->cell[j].
 hipError_t launch_convert(int fmt, bool out, const ConvertPack &pack, const DitherPack *dith, uint32_t n, uint64_t most,
-                          hipStream_t stream);
+                          hipStream_t stream, const MeterPack *meter = nullptr);
 hipError_t launch_mix(int fmt, bool out, const MixPack &pack, const DitherPack *dith, uint32_t n, uint32_t most,
-                      hipStream_t stream);
+                      hipStream_t stream, const MeterPack *meter = nullptr);
+// meter_image (kernels_convert.hip): reads the n samples at pack.s[j].src (floats; dst and step are not read) and judges
+// stored * scale as a float format into meter.cell[j] -- the result of a call that has no output pass.  Writes nothing else.
+hipError_t launch_meter_image(const ConvertPack &pack, const MeterPack &meter, float scale, uint32_t n, uint64_t most,
+                              hipStream_t stream);
 
 // ---- ... with a format per stream (kernels_convert_many.hip): the passes of a launch group of the formatted many-states
 // call.  Stream j's format and dither kind travel in its ConvertStream::reserved (convert_many_tag); every step is 1.  out:
@@ -281,8 +300,10 @@ hipError_t launch_mix(int fmt, bool out, const MixPack &pack, const DitherPack *
 constexpr uint32_t convert_many_tag(int fmt, int dither_kind) {
   return static_cast<uint32_t>(fmt) | (static_cast<uint32_t>(dither_kind) << 8);
 }
+// meter (out only) = the launch of a group with a metered state in it: a stream whose cell is not NULL leaves through the
+// metered body of its format (meter.h), every other one exactly as without.
 hipError_t launch_convert_many(bool out, const ConvertPack &pack, const DitherPack &dith, uint32_t n, uint64_t most,
-                               hipStream_t stream);
+                               hipStream_t stream, const MeterPack *meter = nullptr);
 
 // ---- channel planes of any format <-> the float image (kernels_sides.hip): the pass of a side whose layout is planar --
 // planes_in: C planes of the call's format -> the interleaved float image; planes_out: the image -> planes.  Conversion,
@@ -307,7 +328,8 @@ struct PlanePack {          // like MixPack: up to 32 streams and the matrix, in
   uint32_t mixed;             // 0: plane c is channel c of the image (any channel count); otherwise m applies, 1..8 a side
 };
 // dith as for launch_mix: DitherStream::first = the stream's position, idx = (first + frame) * storage_channels + plane
+// meter as for launch_mix
 hipError_t launch_planes(int fmt, bool out, const PlanePack &pack, const DitherPack *dith, uint32_t n, uint32_t most,
-                         hipStream_t stream);
+                         hipStream_t stream, const MeterPack *meter = nullptr);
 
 }  // namespace speexhip

@@ -34,6 +34,12 @@
 // lane's group on the vector path is a run of G consecutive idx: the inner half of the generator's word, which changes
 // once per 2^32 samples, is taken once per group (twice for the one group that crosses such a boundary), once per sample
 // on the element path.  The kind is one per launch: wave-uniform.
+//
+// convert_out_meter<F> (every format; a state with the meter on): convert_out judged on its way (meter.h) -- the dithered
+// body for the formats of dithered_fmt, where kind NONE gives d = 0 and the undithered bytes, the plain body for the float
+// formats.  A lane counts in registers, the workgroup folds its four waves and adds into the stream's MeterCell, whose
+// address travels in a third kernel argument (MeterPack).  meter_image reads a float result that no pass writes and
+// judges it the same way.  The plain and dithered instances are untouched: the meter is a compile-time flag of the body.
 #include <hip/hip_runtime.h>
 
 #include "../../include/speexhip_resampler.h"
@@ -67,20 +73,68 @@ template <int F>
 __global__ __launch_bounds__(kLanes) void convert_out_dither(const ConvertPack pack, const DitherPack dith) {
   convert_tile<F, true, true>(pack, &dith);
 }
+// the metered instance of a format (meter.h): the dithered body for the formats of dithered_fmt (kind NONE: d = 0), the
+// plain one for the float formats; the stream's cell travels in the third argument
+template <int F>
+__global__ __launch_bounds__(kLanes) void convert_out_meter(const ConvertPack pack, const DitherPack dith, const MeterPack meter) {
+  constexpr bool kDither = dithered_fmt(F);
+  stream_tile<F, true, kDither, true>(pack.s[blockIdx.y], kDither ? &dith.s[blockIdx.y] : nullptr, kDither ? dith.kind : 0,
+                                      meter.cell[blockIdx.y]);
+}
+
+// meter_image: the tile blockIdx.x of stream blockIdx.y of a float result, read and judged, nothing written but the cell.
+// Whole 16-byte aligned tiles 16 bytes per lane (lane t on group pass * 256 + t, as convert_out<F32N> reads), the rest
+// sample by sample.
+__global__ __launch_bounds__(kLanes) void meter_image(const ConvertPack pack, const MeterPack meter, const float scale) {
+  const ConvertStream &s = pack.s[blockIdx.y];
+  const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kTile;
+  if (s.src == nullptr || tile0 >= s.n) return;
+  const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(kTile), s.n - tile0));
+  const float *src = static_cast<const float *>(s.src) + tile0;
+  meter::Lane m;
+  if (n == kTile && (reinterpret_cast<uintptr_t>(s.src) & 15u) == 0) {
+#pragma unroll
+    for (uint32_t pass = 0; pass < kTile / (kLanes * 4); pass++) {
+      const float4 v = reinterpret_cast<const float4 *>(src)[pass * kLanes + threadIdx.x];
+      meter::judge<SPEEXHIP_FMT_F32>(m, v.x * scale, 0.0);
+      meter::judge<SPEEXHIP_FMT_F32>(m, v.y * scale, 0.0);
+      meter::judge<SPEEXHIP_FMT_F32>(m, v.z * scale, 0.0);
+      meter::judge<SPEEXHIP_FMT_F32>(m, v.w * scale, 0.0);
+    }
+  } else {
+    for (uint32_t i = threadIdx.x; i < n; i += kLanes) meter::judge<SPEEXHIP_FMT_F32>(m, src[i] * scale, 0.0);
+  }
+  meter::commit(m, meter.cell[blockIdx.y]);
+}
 
 }  // namespace
 
-hipError_t launch_convert(int fmt, bool out, const ConvertPack &pack, const DitherPack *dith, uint32_t n, uint64_t most,
-                          hipStream_t stream) {
+hipError_t launch_meter_image(const ConvertPack &pack, const MeterPack &meter, float scale, uint32_t n, uint64_t most,
+                              hipStream_t stream) {
   if (n == 0 || most == 0) return hipSuccess;
-  for (uint32_t j = 0; dith != nullptr && j < n; j++)
-    if (!out || pack.s[j].step != 1) return hipErrorInvalidValue;
+  if (n > kMaxPackedStreams) return hipErrorInvalidValue;
+  for (uint32_t j = 0; j < n; j++)
+    if (pack.s[j].src != nullptr && pack.s[j].n != 0 && (meter.cell[j] == nullptr || pack.s[j].n > most)) return hipErrorInvalidValue;
+  const dim3 grid(static_cast<uint32_t>((most + kTile - 1) / kTile), n), block(kLanes);
+  hipLaunchKernelGGL(meter_image, grid, block, 0, stream, pack, meter, scale);
+  return hipGetLastError();
+}
+
+hipError_t launch_convert(int fmt, bool out, const ConvertPack &pack, const DitherPack *dith, uint32_t n, uint64_t most,
+                          hipStream_t stream, const MeterPack *meter) {
+  if (n == 0 || most == 0) return hipSuccess;
+  for (uint32_t j = 0; (dith != nullptr || meter != nullptr) && j < n; j++)
+    if (!out || pack.s[j].step != 1 || (meter != nullptr && meter->cell[j] == nullptr)) return hipErrorInvalidValue;
   const dim3 grid(static_cast<uint32_t>((most + kTile - 1) / kTile), n), block(kLanes);
   return with_format(fmt, [&](auto format) -> hipError_t {
     constexpr int F = decltype(format)::value;
     // (F32 is the image's own format: nothing to convert; the float formats are not dithered)
     if constexpr (F == SPEEXHIP_FMT_F32) {
       return hipErrorInvalidValue;
+    } else if (meter != nullptr) {
+      if (dith != nullptr && !dithered_fmt(F)) return hipErrorInvalidValue;
+      DitherPack none = {};  // (kind NONE)
+      hipLaunchKernelGGL((convert_out_meter<F>), grid, block, 0, stream, pack, dith != nullptr ? *dith : none, *meter);
     } else if (dith == nullptr) {
       if (out)
         hipLaunchKernelGGL((convert_out<F>), grid, block, 0, stream, pack);

@@ -10,6 +10,7 @@
 #include "dither.h"
 #include "format_device.h"
 #include "kernels.h"
+#include "meter.h"
 
 namespace speexhip {
 namespace convert_impl {
@@ -40,9 +41,11 @@ __device__ __forceinline__ void put_raw(uint32_t *w, uint32_t j, uint32_t raw) {
   if (k + 1 < words) w[k + 1] |= static_cast<uint32_t>(pair >> 32);
 }
 
-// kDither (kOut only): the dithered instances; d and kind are theirs alone
-template <int F, bool kOut, bool kDither>
-__device__ __forceinline__ void vector_tile(const ConvertStream &s, const DitherStream *d, int kind, uint64_t tile0) {
+// kDither (kOut only): the dithered instances; d and kind are theirs alone.  kMeter (kOut only): the metered instances;
+// m takes what the lane's samples come to (meter.h) and is theirs alone
+template <int F, bool kOut, bool kDither, bool kMeter>
+__device__ __forceinline__ void vector_tile(const ConvertStream &s, const DitherStream *d, int kind, uint64_t tile0,
+                                            meter::Lane &m) {
   constexpr uint32_t B = sample_bytes(F), G = group_of(F), words = G * B / 4;
   constexpr int W = word_format(F);  // (S16BE / S32BE: the words are reversed as dwords, the samples then the twin's)
   const char *src = static_cast<const char *>(s.src);
@@ -77,7 +80,7 @@ __device__ __forceinline__ void vector_tile(const ConvertStream &s, const Dither
       for (uint32_t i = 0; i < words; i++) w[i] = 0;
 #pragma unroll
       for (uint32_t j = 0; j < G; j++)
-        put_raw<W>(w, j, encode<W, kDither>(e[j], [&] { return dither::noise_in(kind, run, j); }));
+        put_raw<W>(w, j, meter::encode<W, kDither, kMeter>(m, e[j], [&] { return dither::noise_in(kind, run, j); }));
       swap_words<F, words>(w);
       uint4 *out = reinterpret_cast<uint4 *>(dst + first * B);
 #pragma unroll
@@ -88,9 +91,9 @@ __device__ __forceinline__ void vector_tile(const ConvertStream &s, const Dither
 
 // ---- sample by sample ----------------------------------------------------------------------------------------------
 // samples [tile0, tile0 + n) of the stream; sample k lies k * step elements into both buffers (dithered: step is 1)
-template <int F, bool kOut, bool kDither>
+template <int F, bool kOut, bool kDither, bool kMeter>
 __device__ __forceinline__ void element_tile(const ConvertStream &s, const DitherStream *d, int kind, uint64_t tile0,
-                                             uint32_t n) {
+                                             uint32_t n, meter::Lane &m) {
   constexpr uint32_t B = sample_bytes(F);
   const char *src = static_cast<const char *>(s.src);
   char *dst = static_cast<char *>(s.dst);
@@ -99,23 +102,27 @@ __device__ __forceinline__ void element_tile(const ConvertStream &s, const Dithe
     if (!kOut)
       *reinterpret_cast<float *>(dst + at * sizeof(float)) = to_internal<F>(load_raw<F>(src + at * B));
     else
-      store_raw<F>(dst + at * B, encode<F, kDither>(*reinterpret_cast<const float *>(src + at * sizeof(float)),
-                                                    [&] { return dither::noise(kind, d->seed, d->first + at); }));
+      store_raw<F>(dst + at * B,
+                   meter::encode<F, kDither, kMeter>(m, *reinterpret_cast<const float *>(src + at * sizeof(float)),
+                                                     [&] { return dither::noise(kind, d->seed, d->first + at); }));
   }
 }
 
 // The tile blockIdx.x of one stream: the vector path for whole tiles with storage and image 16-byte aligned and step 1,
 // the element path for everything else.  s, d and kind are wave-uniform (kernel arguments selected by blockIdx.y).
-template <int F, bool kOut, bool kDither>
-__device__ __forceinline__ void stream_tile(const ConvertStream &s, const DitherStream *d, int kind) {
+// kMeter: the workgroup's totals go into *cell (wave-uniform too) behind its tile.
+template <int F, bool kOut, bool kDither, bool kMeter = false>
+__device__ __forceinline__ void stream_tile(const ConvertStream &s, const DitherStream *d, int kind, MeterCell *cell = nullptr) {
   const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kTile;
   if (s.src == nullptr || tile0 >= s.n) return;  // (nothing to convert, or a shorter stream of the launch)
   const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(kTile), s.n - tile0));
   const bool aligned = ((reinterpret_cast<uintptr_t>(s.src) | reinterpret_cast<uintptr_t>(s.dst)) & 15u) == 0;
+  meter::Lane m;
   if (n == kTile && aligned && (kDither || s.step == 1))
-    vector_tile<F, kOut, kDither>(s, d, kind, tile0);
+    vector_tile<F, kOut, kDither, kMeter>(s, d, kind, tile0, m);
   else
-    element_tile<F, kOut, kDither>(s, d, kind, tile0, n);
+    element_tile<F, kOut, kDither, kMeter>(s, d, kind, tile0, n, m);
+  if constexpr (kMeter) meter::commit(m, cell);  // (every lane of the workgroup: the early return above is the workgroup's)
 }
 
 }  // namespace convert_impl

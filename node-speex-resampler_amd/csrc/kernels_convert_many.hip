@@ -12,6 +12,11 @@
 //
 // Arguments: the ConvertPack (1024 bytes) and, for the output pass, a DitherPack (520 bytes) whose per-stream seed and
 // first index are read only by streams whose kind is not NONE; its own `kind` word is unused here.
+//
+// convert_many_out_meter: the output pass of a group with a metered state in it (meter.h).  A third argument (MeterPack)
+// holds a cell pointer per stream; a stream whose pointer is not NULL leaves through the metered body of its format --
+// stream_tile<F, true, dithered_fmt(F), true>, the statements of convert_out_meter<F> -- every other stream exactly as in
+// convert_many_out, which is launched as ever when no state of the group has the meter on.
 #include <hip/hip_runtime.h>
 
 #include "../../include/speexhip_resampler.h"
@@ -19,6 +24,7 @@
 #include "format_device.h"
 #include "kernels.h"
 #include "kernels_convert_impl.h"
+#include "meter.h"
 
 namespace speexhip {
 
@@ -28,13 +34,22 @@ namespace {
 
 using namespace convert_impl;
 
-template <bool kOut>
-__device__ __forceinline__ void many_tile(const ConvertPack &pack, const DitherPack *dith) {
+// kMeter (kOut only): the launch of a group with a metered state in it -- a stream with a cell leaves through the metered
+// body of its format (meter.h: the dithered one at the stream's kind, NONE included, or the plain one of a float format)
+template <bool kOut, bool kMeter>
+__device__ __forceinline__ void many_tile(const ConvertPack &pack, const DitherPack *dith, const MeterPack *meter) {
   const ConvertStream &s = pack.s[blockIdx.y];
+  MeterCell *const cell = kMeter ? meter->cell[blockIdx.y] : nullptr;
   const int fmt = static_cast<int>(s.reserved & 0xffu), kind = static_cast<int>((s.reserved >> 8) & 0xffu);
   switch (fmt) {
 #define SPEEXHIP_MANY_CASE(F)                                                  \
   case F:                                                                      \
+    if constexpr (kMeter) {                                                    \
+      if (cell != nullptr) {                                                   \
+        stream_tile<F, true, dithered_fmt(F), true>(s, &dith->s[blockIdx.y], kind, cell); \
+        break;                                                                 \
+      }                                                                        \
+    }                                                                          \
     if constexpr (kOut && dithered_fmt(F)) {                                   \
       if (kind != SPEEXHIP_DITHER_NONE) {                                      \
         stream_tile<F, true, true>(s, &dith->s[blockIdx.y], kind);             \
@@ -60,17 +75,20 @@ __device__ __forceinline__ void many_tile(const ConvertPack &pack, const DitherP
   }
 }
 
-__global__ __launch_bounds__(kLanes) void convert_many_in(const ConvertPack pack) { many_tile<false>(pack, nullptr); }
+__global__ __launch_bounds__(kLanes) void convert_many_in(const ConvertPack pack) { many_tile<false, false>(pack, nullptr, nullptr); }
 __global__ __launch_bounds__(kLanes) void convert_many_out(const ConvertPack pack, const DitherPack dith) {
-  many_tile<true>(pack, &dith);
+  many_tile<true, false>(pack, &dith, nullptr);
+}
+__global__ __launch_bounds__(kLanes) void convert_many_out_meter(const ConvertPack pack, const DitherPack dith, const MeterPack meter) {
+  many_tile<true, true>(pack, &dith, &meter);
 }
 
 }  // namespace
 
 hipError_t launch_convert_many(bool out, const ConvertPack &pack, const DitherPack &dith, uint32_t n, uint64_t most,
-                               hipStream_t stream) {
+                               hipStream_t stream, const MeterPack *meter) {
   if (n == 0 || most == 0) return hipSuccess;
-  if (n > kMaxPackedStreams) return hipErrorInvalidValue;
+  if (n > kMaxPackedStreams || (meter != nullptr && !out)) return hipErrorInvalidValue;
   for (uint32_t j = 0; j < n; j++) {
     const ConvertStream &s = pack.s[j];
     if (s.src == nullptr || s.n == 0) continue;
@@ -80,7 +98,9 @@ hipError_t launch_convert_many(bool out, const ConvertPack &pack, const DitherPa
     if (kind != SPEEXHIP_DITHER_NONE && (!out || !dithered_fmt(fmt) || !dither::known_kind(kind))) return hipErrorInvalidValue;
   }
   const dim3 grid(static_cast<uint32_t>((most + kTile - 1) / kTile), n), block(kLanes);
-  if (out)
+  if (meter != nullptr)
+    hipLaunchKernelGGL(convert_many_out_meter, grid, block, 0, stream, pack, dith, *meter);
+  else if (out)
     hipLaunchKernelGGL(convert_many_out, grid, block, 0, stream, pack, dith);
   else
     hipLaunchKernelGGL(convert_many_in, grid, block, 0, stream, pack);

@@ -34,6 +34,10 @@
 // (p + f) * dst_channels + o: a frame is a run of consecutive idx, so the inner half of the generator's word is taken
 // once per frame (twice for the one frame that crosses a 2^32 boundary of idx).
 //
+// mix_out_meter<F> (every format; a state with the meter on): mix_out judged on its way (meter.h), behind the matrix and
+// before the dither -- the dithered body for the formats of dithered_fmt (kind NONE: d = 0), the plain one for the float
+// formats; the streams' cells travel in a third kernel argument.
+//
 // The image mix_in writes is read by the very next kernel and mix_out's source was written by the previous one: plain
 // loads and stores throughout, so that the images can stay in L2 / Infinity Cache.
 #include <hip/hip_runtime.h>
@@ -42,6 +46,7 @@
 #include "dither.h"
 #include "format_device.h"
 #include "kernels.h"
+#include "meter.h"
 
 namespace speexhip {
 
@@ -117,10 +122,11 @@ __device__ __forceinline__ void tile_path(const MixPack &pack, const MixStream &
 }
 
 // ---- frame by frame --------------------------------------------------------------------------------------------------
-// frames [tile0, tile0 + n) of the stream; kDither (kOut only): the dithered instances; d and kind are theirs alone
-template <int F, bool kOut, bool kDither>
+// frames [tile0, tile0 + n) of the stream; kDither (kOut only): the dithered instances; d and kind are theirs alone;
+// kMeter (kOut only): the metered instances, m (meter.h) is theirs alone
+template <int F, bool kOut, bool kDither, bool kMeter>
 __device__ __forceinline__ void element_path(const MixPack &pack, const MixStream &s, const DitherStream *d, int kind,
-                                             uint64_t tile0, uint32_t n, uint32_t ns, uint32_t nd) {
+                                             uint64_t tile0, uint32_t n, uint32_t ns, uint32_t nd, meter::Lane &m) {
   constexpr uint32_t B = sample_bytes(F);
   for (uint32_t f = threadIdx.x; f < n; f += kLanes) {
     const uint64_t frame = tile0 + f;
@@ -137,14 +143,14 @@ __device__ __forceinline__ void element_path(const MixPack &pack, const MixStrea
       mix_frame(
           pack, ns, nd, [&](uint32_t i) { return src[i]; },
           [&](uint32_t o, float y) {
-            store_raw<F>(dst + o * B, encode<F, kDither>(y, [&] { return dither::noise_in(kind, run, o); }));
+            store_raw<F>(dst + o * B, meter::encode<F, kDither, kMeter>(m, y, [&] { return dither::noise_in(kind, run, o); }));
           });
     }
   }
 }
 
-template <int F, bool kOut, bool kDither>
-__device__ __forceinline__ void mix_tile(const MixPack &pack, const DitherPack *dith, uint32_t *lds) {
+template <int F, bool kOut, bool kDither, bool kMeter = false>
+__device__ __forceinline__ void mix_tile(const MixPack &pack, const DitherPack *dith, uint32_t *lds, const MeterPack *meter = nullptr) {
   const MixStream &s = pack.s[blockIdx.y];
   const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kTileFrames;
   if (s.src == nullptr || tile0 >= s.frames) return;  // (nothing to mix, or a shorter stream of the launch)
@@ -153,10 +159,12 @@ __device__ __forceinline__ void mix_tile(const MixPack &pack, const DitherPack *
   const DitherStream *d = kDither ? &dith->s[blockIdx.y] : nullptr;
   const int kind = kDither ? dith->kind : 0;
   const bool aligned = ((reinterpret_cast<uintptr_t>(s.src) | reinterpret_cast<uintptr_t>(s.dst)) & 15u) == 0;
+  meter::Lane m;
   if (!kOut && n == kTileFrames && aligned)
     tile_path<F>(pack, s, tile0, ns, nd, ns * sample_bytes(F), nd * 4u, lds);
   else
-    element_path<F, kOut, kDither>(pack, s, d, kind, tile0, n, ns, nd);
+    element_path<F, kOut, kDither, kMeter>(pack, s, d, kind, tile0, n, ns, nd, m);
+  if constexpr (kMeter) meter::commit(m, meter->cell[blockIdx.y]);  // (every lane: the early return above is the workgroup's)
 }
 
 template <int F>
@@ -173,22 +181,34 @@ template <int F>
 __global__ __launch_bounds__(kLanes) void mix_out_dither(const MixPack pack, const DitherPack dith) {
   mix_tile<F, true, true>(pack, &dith, nullptr);
 }
+// the metered instance of a format (meter.h): the dithered body for the formats of dithered_fmt (kind NONE: d = 0), the
+// plain one for the float formats
+template <int F>
+__global__ __launch_bounds__(kLanes) void mix_out_meter(const MixPack pack, const DitherPack dith, const MeterPack meter) {
+  mix_tile<F, true, dithered_fmt(F), true>(pack, &dith, nullptr, &meter);
+}
 
 }  // namespace
 
 hipError_t launch_mix(int fmt, bool out, const MixPack &pack, const DitherPack *dith, uint32_t n, uint32_t most,
-                      hipStream_t stream) {
+                      hipStream_t stream, const MeterPack *meter) {
   if (n == 0 || most == 0) return hipSuccess;
   if (pack.src_channels == 0 || pack.src_channels > kMixMaxChannels || pack.dst_channels == 0 ||
-      pack.dst_channels > kMixMaxChannels || (dith != nullptr && !out))
+      pack.dst_channels > kMixMaxChannels || ((dith != nullptr || meter != nullptr) && !out))
     return hipErrorInvalidValue;
+  for (uint32_t j = 0; meter != nullptr && j < n; j++)
+    if (meter->cell[j] == nullptr) return hipErrorInvalidValue;
   // the two LDS areas of mix_in's tile path (at most 33.8 KB: no opt-in needed)
   const uint32_t src_fb = pack.src_channels * sample_bytes(fmt), dst_fb = pack.dst_channels * 4u;
   const uint32_t lds = out ? 0u : (area_dwords(kTileFrames * src_fb / 4) + area_dwords(kTileFrames * dst_fb / 4)) * 4;
   const dim3 grid((most + kTileFrames - 1) / kTileFrames, n), block(kLanes);
   return with_format(fmt, [&](auto format) -> hipError_t {
     constexpr int F = decltype(format)::value;
-    if (dith == nullptr) {
+    if (meter != nullptr) {
+      if (dith != nullptr && !dithered_fmt(F)) return hipErrorInvalidValue;
+      DitherPack none = {};  // (kind NONE)
+      hipLaunchKernelGGL((mix_out_meter<F>), grid, block, 0, stream, pack, dith != nullptr ? *dith : none, *meter);
+    } else if (dith == nullptr) {
       if (out)
         hipLaunchKernelGGL((mix_out<F>), grid, block, lds, stream, pack);
       else

@@ -31,6 +31,10 @@
 //
 // Dither: output c of frame f of a stream at position p has idx (p + f) * planes + c, as in the interleaved passes.
 //
+// planes_out_meter<F> (every format; a state with the meter on): planes_out judged on its way (meter.h), on both paths --
+// the dithered body for the formats of dithered_fmt (kind NONE: d = 0), the plain one for the float formats.  The samples
+// and their d are the interleaved pass's, so the totals are too.
+//
 // The image planes_in writes is read by the very next kernel and planes_out's source was written by the previous one:
 // plain loads and stores throughout, so that the images can stay in L2 / Infinity Cache.
 #include <hip/hip_runtime.h>
@@ -39,6 +43,7 @@
 #include "dither.h"
 #include "format_device.h"
 #include "kernels.h"
+#include "meter.h"
 
 namespace speexhip {
 
@@ -129,10 +134,11 @@ __device__ __forceinline__ void vector_in(const PlanePack &pack, const PlaneStre
   }
 }
 
-// ... image -> planes; kDither: the dithered instances, d and kind are theirs alone
-template <int F, bool kDither>
+// ... image -> planes; kDither: the dithered instances, d and kind are theirs alone; kMeter: the metered instances, m
+// (meter.h) is theirs alone
+template <int F, bool kDither, bool kMeter>
 __device__ __forceinline__ void vector_out(const PlanePack &pack, const PlaneStream &s, const DitherStream *d, int kind,
-                                           uint64_t tile0, uint32_t *lds) {
+                                           uint64_t tile0, uint32_t *lds, meter::Lane &m) {
   constexpr uint32_t B = sample_bytes(F), G = group_of(F), words = G * B / 4, pieces = kTile / G;
   constexpr int W = word_format(F);
   const uint32_t sc = pack.storage_channels, ic = pack.image_channels;
@@ -160,7 +166,7 @@ __device__ __forceinline__ void vector_out(const PlanePack &pack, const PlaneStr
 #pragma unroll
     for (uint32_t j = 0; j < G; j++) {
       const float y = __uint_as_float(lds[pad_dword((f0 + j) * sc + c)]);
-      put_raw<W>(w, j, encode<W, kDither>(y, [&] { return dither::noise(kind, d->seed, (d->first + tile0 + f0 + j) * sc + c); }));
+      put_raw<W>(w, j, meter::encode<W, kDither, kMeter>(m, y, [&] { return dither::noise(kind, d->seed, (d->first + tile0 + f0 + j) * sc + c); }));
     }
     swap_words<F, words>(w);
     uint4 *out = reinterpret_cast<uint4 *>(planes + (c * s.plane_stride + tile0 + f0) * B);
@@ -171,9 +177,9 @@ __device__ __forceinline__ void vector_out(const PlanePack &pack, const PlaneStr
 
 // ---- frame by frame --------------------------------------------------------------------------------------------------
 // frames [tile0, tile0 + n) of the stream
-template <int F, bool kOut, bool kDither>
+template <int F, bool kOut, bool kDither, bool kMeter>
 __device__ __forceinline__ void element_path(const PlanePack &pack, const PlaneStream &s, const DitherStream *d, int kind,
-                                             uint64_t tile0, uint32_t n) {
+                                             uint64_t tile0, uint32_t n, meter::Lane &m) {
   constexpr uint32_t B = sample_bytes(F);
   const uint32_t sc = pack.storage_channels, ic = pack.image_channels;
   const uint64_t plane_bytes = s.plane_stride * B;
@@ -192,7 +198,7 @@ __device__ __forceinline__ void element_path(const PlanePack &pack, const PlaneS
       char *dst = static_cast<char *>(s.dst) + frame * B;
       const dither::Run run = kDither ? dither::run_of(d->seed, (d->first + frame) * sc, sc) : dither::Run{};
       const auto put = [&](uint32_t o, float y) {
-        store_raw<F>(dst + o * plane_bytes, encode<F, kDither>(y, [&] { return dither::noise_in(kind, run, o); }));
+        store_raw<F>(dst + o * plane_bytes, meter::encode<F, kDither, kMeter>(m, y, [&] { return dither::noise_in(kind, run, o); }));
       };
       if (pack.mixed == 0)
         for (uint32_t c = 0; c < sc; c++) put(c, src[c]);
@@ -202,8 +208,8 @@ __device__ __forceinline__ void element_path(const PlanePack &pack, const PlaneS
   }
 }
 
-template <int F, bool kOut, bool kDither>
-__device__ __forceinline__ void planes_tile(const PlanePack &pack, const DitherPack *dith, uint32_t *lds) {
+template <int F, bool kOut, bool kDither, bool kMeter = false>
+__device__ __forceinline__ void planes_tile(const PlanePack &pack, const DitherPack *dith, uint32_t *lds, const MeterPack *meter = nullptr) {
   const PlaneStream &s = pack.s[blockIdx.y];
   const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kTile;
   if (s.src == nullptr || tile0 >= s.frames) return;  // (nothing to move, or a shorter stream of the launch)
@@ -214,14 +220,16 @@ __device__ __forceinline__ void planes_tile(const PlanePack &pack, const DitherP
                          (s.plane_stride * sample_bytes(F))) & 15u) == 0;
   const bool tiled = pack.storage_channels <= kMixMaxChannels && pack.image_channels <= kMixMaxChannels &&
                      pack.image_pitch == pack.image_channels;
+  meter::Lane m;
   if (n == kTile && aligned && tiled) {
     if (kOut)
-      vector_out<F, kDither>(pack, s, d, kind, tile0, lds);
+      vector_out<F, kDither, kMeter>(pack, s, d, kind, tile0, lds, m);
     else
       vector_in<F>(pack, s, tile0, lds);
   } else {
-    element_path<F, kOut, kDither>(pack, s, d, kind, tile0, n);
+    element_path<F, kOut, kDither, kMeter>(pack, s, d, kind, tile0, n, m);
   }
+  if constexpr (kMeter) meter::commit(m, meter->cell[blockIdx.y]);  // (every lane: the early return above is the workgroup's)
 }
 
 template <int F>
@@ -239,21 +247,34 @@ __global__ __launch_bounds__(kLanes) void planes_out_dither(const PlanePack pack
   extern __shared__ uint32_t sides_lds[];
   planes_tile<F, true, true>(pack, &dith, sides_lds);
 }
+// the metered instance of a format (meter.h): the dithered body for the formats of dithered_fmt (kind NONE: d = 0), the
+// plain one for the float formats
+template <int F>
+__global__ __launch_bounds__(kLanes) void planes_out_meter(const PlanePack pack, const DitherPack dith, const MeterPack meter) {
+  extern __shared__ uint32_t sides_lds[];
+  planes_tile<F, true, dithered_fmt(F), true>(pack, &dith, sides_lds, &meter);
+}
 
 }  // namespace
 
 hipError_t launch_planes(int fmt, bool out, const PlanePack &pack, const DitherPack *dith, uint32_t n, uint32_t most,
-                         hipStream_t stream) {
+                         hipStream_t stream, const MeterPack *meter) {
   if (n == 0 || most == 0) return hipSuccess;
   const uint32_t sc = pack.storage_channels, ic = pack.image_channels;
-  if (sc == 0 || ic == 0 || pack.image_pitch < ic || (dith != nullptr && !out)) return hipErrorInvalidValue;
+  if (sc == 0 || ic == 0 || pack.image_pitch < ic || ((dith != nullptr || meter != nullptr) && !out)) return hipErrorInvalidValue;
+  for (uint32_t j = 0; meter != nullptr && j < n; j++)
+    if (meter->cell[j] == nullptr) return hipErrorInvalidValue;
   if (pack.mixed != 0 ? (sc > kMixMaxChannels || ic > kMixMaxChannels) : sc != ic) return hipErrorInvalidValue;
   // the LDS tile of the vector path (at most 33.8 KB: no opt-in needed); more than 8 planes take the element path alone
   const uint32_t lds = sc <= kMixMaxChannels ? area_dwords(kTile * sc) * 4 : 0u;
   const dim3 grid((most + kTile - 1) / kTile, n), block(kLanes);
   return with_format(fmt, [&](auto format) -> hipError_t {
     constexpr int F = decltype(format)::value;
-    if (dith == nullptr) {
+    if (meter != nullptr) {
+      if (dith != nullptr && !dithered_fmt(F)) return hipErrorInvalidValue;
+      DitherPack none = {};  // (kind NONE)
+      hipLaunchKernelGGL((planes_out_meter<F>), grid, block, lds, stream, pack, dith != nullptr ? *dith : none, *meter);
+    } else if (dith == nullptr) {
       if (out)
         hipLaunchKernelGGL((planes_out<F>), grid, block, lds, stream, pack);
       else

@@ -229,6 +229,8 @@ void Batch::ManyUnit::commit_item(Item &it, bool work) {
   out_len[it.i] = it.plan.produced;
   // (a formatted call of a state with dither on moves its position by the frames produced, whatever the format)
   if (it.e->sides && it.b->dither_on()) it.b->dither_advance(&out_len[it.i]);
+  // (... and of a state with the meter on is metered: its output pass has judged these frames into the state's cell)
+  if (it.e->sides && it.b->meter_on_) it.b->meter_count(&out_len[it.i], it.b->channels_);
   rcs[it.i] = SPEEXHIP_ERR_SUCCESS;
 }
 
@@ -242,6 +244,9 @@ int Batch::ManyUnit::launch_group(const std::vector<uint32_t> &g, hipStream_t st
   // name, over the entries whose storage is not their image
   ConvertPack to_image, from_image;
   DitherPack dith;
+  MeterPack cells;  // (beside the dither seeds: the cell of each entry whose state has the meter on)
+  bool metered = false;
+  std::memset(&cells, 0, sizeof(cells));
   uint64_t most_to = 0, most_from = 0;
   std::memset(&to_image, 0, sizeof(to_image));
   std::memset(&from_image, 0, sizeof(from_image));
@@ -274,6 +279,7 @@ int Batch::ManyUnit::launch_group(const std::vector<uint32_t> &g, hipStream_t st
       const bool dithered = b->dither_on() && dithered_fmt(it.e->out_fmt);
       c.reserved = convert_many_tag(it.e->out_fmt, dithered ? b->dither_kind_ : SPEEXHIP_DITHER_NONE);
       if (dithered) dith.s[j] = b->dither_pack(0, 1, b->channels_).s[0];
+      if (b->meter_on_) cells.cell[j] = b->d_meter_, metered = true;
       most_from = std::max(most_from, c.n);
     }
     max_out = std::max(max_out, it.plan.produced);
@@ -286,7 +292,7 @@ int Batch::ManyUnit::launch_group(const std::vector<uint32_t> &g, hipStream_t st
   if (lrc != SPEEXHIP_ERR_SUCCESS) return lrc;
   count_many(0);
   if (most_from != 0) {
-    if (hip_failed(launch_convert_many(true, from_image, dith, cnt, most_from, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+    if (hip_failed(launch_convert_many(true, from_image, dith, cnt, most_from, stream, metered ? &cells : nullptr), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
     count_many(2);
   }
   // A state moves as ONE step, the moment its launch is queued: the history ping-pong, the position and the counters

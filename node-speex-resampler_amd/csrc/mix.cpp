@@ -22,11 +22,18 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
   // With dither on (set_dither) the formats of dithered_fmt leave through the dithered instances of either pass, at the
   // streams' positions: the index runs over the samples of the OUTPUT frames.
   const bool dithered = !to_image && dither_on() && dithered_fmt(side.fmt);
+  // With the meter on (set_meter) every format leaves through the metered instance of its pass, stream by stream into
+  // the stream's cell.  (Channels that stand apart are no stream of samples to judge: the callers have refused them.)
+  const bool metered = !to_image && meter_on_;
+  if (metered && apart != nullptr) return SPEEXHIP_ERR_BAD_STATE;
   const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
   for (uint32_t first = 0; first < items; first += kChunk) {
     const uint32_t n = std::min(kChunk, items - first);
     DitherPack dith;
     if (dithered) dith = dither_pack(first, n, side.mix != nullptr ? 1 : channels_);
+    MeterPack cells;
+    if (metered) cells = meter_pack(first, n);
+    const MeterPack *meter = metered ? &cells : nullptr;
     // item first + j is entry j of the launch's pack: where it reads, where it writes, its frames
     const auto place = [&](uint32_t j, const void **src, void **dst) {
       const uint32_t item = first + j;
@@ -58,7 +65,7 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
         most = std::max(most, pack.s[j].frames);
       }
       if (dithered) dith = dither_pack(first, n, 1);
-      e = launch_planes(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream);
+      e = launch_planes(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream, meter);
     } else if (side.mix != nullptr) {
       MixPack pack;
       std::memset(&pack, 0, sizeof(pack));
@@ -70,7 +77,7 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
         pack.s[j].frames = place(j, &pack.s[j].src, &pack.s[j].dst);
         most = std::max(most, pack.s[j].frames);
       }
-      e = launch_mix(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream);
+      e = launch_mix(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream, meter);
     } else {
       ConvertPack pack;
       std::memset(&pack, 0, sizeof(pack));
@@ -82,7 +89,7 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
         pack.s[j].step = apart != nullptr ? channels_ : 1;
         most = std::max(most, pack.s[j].n);
       }
-      e = launch_convert(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream);
+      e = launch_convert(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream, meter);
     }
     if (hip_failed(e, "kernel launch")) return SPEEXHIP_ERR_DEVICE;
   }

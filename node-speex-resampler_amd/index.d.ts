@@ -22,6 +22,8 @@ export type SampleFormat = 'u8' | 's16le' | 's24le' | 's32le' | 'f32le' | 'f32le
     's16be' | 's24be' | 's32be' | 'f16le-normalized' | 'bf16le-normalized';
 /** dither of the integer results of processChunkFormat / processChunkMix (setDither) */
 export type DitherKind = 'none' | 'rectangular' | 'triangular';
+/** what getMeter reports: samples judged, samples clipped at either rail, NaN samples, the largest |value| in int16 units */
+export interface MeterTotals { on: boolean, samples: bigint, clippedHigh: bigint, clippedLow: bigint, nan: bigint, peak: number }
 
 export interface SpeexResamplerTransformOptions {
     /**
@@ -63,6 +65,11 @@ export interface SpeexResamplerTransformOptions {
      */
     inFormat?: SampleFormat;
     outFormat?: SampleFormat;
+    /**
+     * The output meter on from the first chunk (SpeexResampler.setMeter); read the totals from the Transform's `meter`.
+     * The stream then runs through the formatted calls (default 's16le' each side), which alone are metered.
+     */
+    meter?: boolean;
 }
 
 /**
@@ -196,6 +203,14 @@ declare class SpeexResampler {
     setDither(kind: DitherKind, seed?: bigint | number, position?: bigint | number): void;
     /** position: output frames made by processChunkFormat / processChunkMix since setDither, plus its position */
     getDither(): { kind: DitherKind, seed: bigint, position: bigint };
+    /**
+     * The output meter of processChunkFormat / processChunkMix / processChunkSides and their chunk-list, many-instance and
+     * asynchronous forms: clip counts and peak level of what they encode.  Totals are kept while it is off; while it is on
+     * 's16le' -> 's16le' runs as processChunkFloat between the two conversions.
+     */
+    setMeter(on: boolean): void;
+    /** totals since the last reset; peak in int16 units (above 32768: beyond +-1.0).  reset: clear them behind the read */
+    getMeter(options?: { reset?: boolean }): MeterTotals;
     skipZeros(): void;
     resetMem(): void;
     /** filter delay in frames at the input rate / at the output rate */
@@ -223,6 +238,8 @@ export declare class SpeexResamplerTransform extends Transform {
     quality: number;
     resampler: SpeexResampler;
     _alignementBuffer: Buffer;
+    /** the stream's totals so far (option `meter`) */
+    readonly meter: MeterTotals;
 
     constructor(channels: any, inRate: any, outRate: any, quality?: number,
                 options?: SpeexResamplerTransformOptions);
@@ -261,6 +278,10 @@ export declare class SpeexResamplerBatch {
     setDither(kind: DitherKind, seed?: bigint | number, position?: bigint | number): void;
     /** getDither of stream k (default 0) */
     getDither(stream?: number): { kind: DitherKind, seed: bigint, position: bigint };
+    /** setMeter of every stream */
+    setMeter(on: boolean): void;
+    /** getMeter of stream k (default 0); reset clears that stream only */
+    getMeter(stream?: number, options?: { reset?: boolean }): MeterTotals;
     destroy(): void;
 }
 

@@ -538,6 +538,30 @@ class SpeexResampler {
     return { kind: DITHER_KINDS[code], seed: (BigInt(sHi) << 32n) | BigInt(sLo), position: (BigInt(pHi) << 32n) | BigInt(pLo) };
   }
 
+  /**
+   * The output meter of processChunkFormat, processChunkMix and processChunkSides (and their chunk-list, many-instance and
+   * asynchronous forms): while on, every sample they encode is judged on its way out -- clipped at the upper or the lower rail of
+   * an integer or companded format, NaN, and the peak |value| in int16 units (above 32768: beyond +-1.0; the float results
+   * count no clips, their callers read the peak).  processChunk, processChunkFloat and the planar calls are never metered.
+   * The totals are kept while the meter is off.  While on, 's16le' -> 's16le' runs as processChunkFloat between the two
+   * conversions.  The totals of a stream do not depend on how it is cut into chunks.
+   */
+  setMeter(on) {
+    this._refuseWhileAsyncPending('setMeter');
+    speexModule.setMeter(this._ensureNative(), !!on);
+  }
+
+  /**
+   * { on, samples, clippedHigh, clippedLow, nan, peak } since the last reset; the counts are bigints.  Waits for this
+   * instance's own last call only.  { reset: true } clears the totals behind the read.
+   */
+  getMeter(options = undefined) {
+    this._refuseWhileAsyncPending('getMeter');
+    const v = speexModule.getMeter(this._ensureNative(), !!(options && options.reset));
+    const big = (i) => (BigInt(v[i + 1]) << 32n) | BigInt(v[i]);
+    return { on: v[0] !== 0, samples: big(1), clippedHigh: big(3), clippedLow: big(5), nan: big(7), peak: v[9] };
+  }
+
   /** Start half a filter in, so the stream does not begin with the filter's ramp-up. */
   skipZeros() {
     this._refuseWhileAsyncPending('skipZeros');
@@ -872,6 +896,12 @@ class SpeexResamplerBatch {
   /** getDither of stream k (its own seed and position) */
   getDither(stream = 0) { return this.streams[stream].getDither(); }
 
+  /** setMeter of every stream */
+  setMeter(on) { for (const r of this.streams) r.setMeter(on); }
+
+  /** getMeter of stream k: its own totals; { reset: true } clears that stream only */
+  getMeter(stream = 0, options = undefined) { return this.streams[stream].getMeter(options); }
+
   destroy() { for (const r of this.streams) r.destroy(); }
 }
 /**
@@ -908,6 +938,9 @@ class SpeexResamplerTransform extends Transform {
    *                         inFormat are written, bytes in outFormat are read, in every mode above -- a G.711 RTP payload
    *                         stream to a model's floats: { inFormat: 'mulaw', outFormat: 'f32le-normalized' }.  Without
    *                         either the Transform is the reference's and calls what it always called.
+   *   meter: true         -- the output meter (SpeexResampler.setMeter) on from the first chunk; the `meter` getter reads the
+   *                         totals.  The stream then runs through the formatted calls (default 's16le' each side): only
+   *                         they are metered.
    */
   constructor(channels, inRate, outRate, quality = 7, options = undefined) {
     super();
@@ -925,6 +958,10 @@ class SpeexResamplerTransform extends Transform {
       const names = [this._options.inFormat || 's16le', this._options.outFormat || 's16le'];
       for (const name of names) if (!SAMPLE_FORMATS[name]) throw new Error('Unknown sample format: ' + name);
       this._formats = names;
+    }
+    if (this._options.meter) {
+      if (!this._formats) this._formats = ['s16le', 's16le'];
+      this._meterPending = true;  // (switched on with the first call: the constructor works before initPromise)
     }
     if (this._options.pipeline) {
       this._busy = false;       // a processChunksAsync call is in flight
@@ -954,6 +991,19 @@ class SpeexResamplerTransform extends Transform {
           callback(e);
         }
       };
+    }
+  }
+
+  /** the stream's totals so far (SpeexResampler.getMeter) */
+  get meter() {
+    this._armMeter();
+    return this.resampler.getMeter();
+  }
+
+  _armMeter() {
+    if (this._meterPending) {
+      this._meterPending = false;
+      this.resampler.setMeter(true);
     }
   }
 
@@ -989,20 +1039,24 @@ class SpeexResamplerTransform extends Transform {
 
   // The calls of every mode: the stream's formats where it names them, else the reference's s16le calls as ever.
   _one(chunk) {
+    this._armMeter();
     return this._formats ? this.resampler.processChunkFormat(chunk, this._formats[0], this._formats[1]) : this.resampler.processChunk(chunk);
   }
 
   _oneAsync(chunk) {
+    this._armMeter();
     return this._formats ? this.resampler.processChunkFormatAsync(chunk, this._formats[0], this._formats[1])
       : this.resampler.processChunkAsync(chunk);
   }
 
   _many(chunks) {
+    this._armMeter();
     return this._formats ? this.resampler.processChunksFormat(chunks, this._formats[0], this._formats[1])
       : this.resampler.processChunks(chunks);
   }
 
   _manyAsync(chunks) {
+    this._armMeter();
     return this._formats ? this.resampler.processChunksFormatAsync(chunks, this._formats[0], this._formats[1])
       : this.resampler.processChunksAsync(chunks);
   }

@@ -33,6 +33,7 @@
 typedef struct {
   SpeexHipResamplerState *st;
   pthread_mutex_t lock;
+  int meter_on; /* setMeter: while on, s16 -> s16 has the float call's counters (read and written under the lock) */
 } Handle;
 
 static void finalize_state(napi_env env, void *data, void *hint) {
@@ -106,7 +107,7 @@ static napi_value Init(napi_env env, napi_callback_info info) {
     napi_throw_error(env, NULL, speexhip_resampler_strerror(err));
     return NULL;
   }
-  Handle *h = (Handle *)malloc(sizeof(Handle));
+  Handle *h = (Handle *)calloc(1, sizeof(Handle));
   if (h == NULL) {
     speexhip_resampler_destroy(st);
     napi_throw_error(env, NULL, speexhip_resampler_strerror(SPEEXHIP_ERR_ALLOC_FAILED));
@@ -388,7 +389,7 @@ static napi_value ProcessFormat(napi_env env, napi_callback_info info) {
     return NULL;
   }
   /* (s16 -> s16 is the int16 call, with its counters; every other pair has the float call's) */
-  const int float_entry = !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
+  const int float_entry = h->meter_on || !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
   uint32_t will_use = 0, will_make = 0;
   speexhip_resampler_peek(st, in_len, out_len, float_entry, &will_use, &will_make);
   napi_value out;
@@ -471,7 +472,7 @@ static napi_value ProcessMix(napi_env env, napi_callback_info info) {
     return NULL;
   }
   /* (without a matrix s16 -> s16 is the int16 call, with its counters; everything else has the float call's) */
-  const int float_entry = in_mix != NULL || out_mix != NULL || !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
+  const int float_entry = h->meter_on || in_mix != NULL || out_mix != NULL || !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
   uint32_t will_use = 0, will_make = 0;
   speexhip_resampler_peek(st, in_len, out_len, float_entry, &will_use, &will_make);
   napi_value out;
@@ -596,7 +597,7 @@ static napi_value ProcessSides(napi_env env, napi_callback_info info) {
   /* (a side of one channel is the same bytes in either layout; with a planar side, as with a matrix, every pair has the
    *  float call's counters -- otherwise s16 -> s16 is the int16 call) */
   const int planar_side = (in_planar && in_channels > 1) || (out_planar && out_channels > 1);
-  const int float_entry = planar_side || in_mix != NULL || out_mix != NULL || !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
+  const int float_entry = h->meter_on || planar_side || in_mix != NULL || out_mix != NULL || !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
   uint32_t will_use = 0, will_make = 0;
   speexhip_resampler_peek(st, in_len, out_len, float_entry, &will_use, &will_make);
   napi_value result = NULL;
@@ -1203,6 +1204,63 @@ static napi_value GetDither(napi_env env, napi_callback_info info) {
   return arr;
 }
 
+/* setMeter(handle, on) */
+static napi_value SetMeter(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 2) {
+    napi_throw_type_error(env, NULL, "setMeter(handle, on)");
+    return NULL;
+  }
+  Handle *h = NULL;
+  SpeexHipResamplerState *st = lock_state(env, argv[0], &h);
+  if (st == NULL) return NULL;
+  bool on = false;
+  NAPI_OK_LOCKED(h, napi_get_value_bool(env, argv[1], &on));
+  const int rc = speexhip_resampler_set_meter(st, on ? 1 : 0);
+  if (rc == 0) h->meter_on = on ? 1 : 0;
+  UNLOCK(h);
+  return control_result(env, rc);
+}
+
+/* getMeter(handle, reset) -> [on, samplesLo, samplesHi, highLo, highHi, lowLo, lowHi, nanLo, nanHi, peak]: the counts
+ * travel as uint32 halves (index.js joins them into BigInts), the peak as a number */
+static napi_value GetMeter(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 2) {
+    napi_throw_type_error(env, NULL, "getMeter(handle, reset)");
+    return NULL;
+  }
+  Handle *h = NULL;
+  SpeexHipResamplerState *st = lock_state(env, argv[0], &h);
+  if (st == NULL) return NULL;
+  bool reset = false;
+  NAPI_OK_LOCKED(h, napi_get_value_bool(env, argv[1], &reset));
+  SpeexHipMeter m;
+  memset(&m, 0, sizeof(m));
+  m.struct_size = (uint32_t)sizeof(m);
+  const int rc = speexhip_resampler_get_meter(st, &m, reset ? 1 : 0);
+  UNLOCK(h);
+  if (rc != 0) return control_result(env, rc);
+  const uint64_t counts[4] = {m.samples, m.clipped_high, m.clipped_low, m.nan};
+  napi_value arr, v;
+  NAPI_OK(napi_create_array_with_length(env, 10, &arr));
+  NAPI_OK(napi_create_uint32(env, m.on, &v));
+  NAPI_OK(napi_set_element(env, arr, 0, v));
+  for (uint32_t i = 0; i < 4; i++) {
+    NAPI_OK(napi_create_uint32(env, (uint32_t)counts[i], &v));
+    NAPI_OK(napi_set_element(env, arr, 1 + 2 * i, v));
+    NAPI_OK(napi_create_uint32(env, (uint32_t)(counts[i] >> 32), &v));
+    NAPI_OK(napi_set_element(env, arr, 2 + 2 * i, v));
+  }
+  NAPI_OK(napi_create_double(env, (double)m.peak, &v));
+  NAPI_OK(napi_set_element(env, arr, 9, v));
+  return arr;
+}
+
 static napi_value pair_u32(napi_env env, uint32_t a, uint32_t b) {
   napi_value arr, v;
   NAPI_OK(napi_create_array_with_length(env, 2, &arr));
@@ -1520,10 +1578,12 @@ static ManyJob *many_prepare(napi_env env, napi_callback_info info, napi_value *
       }
       int float_entry = 0;
       if (formatted) {
-        /* (the entry's rules: S16 -> S16 is the int16 call unless the state's dither is on; everything else the float call) */
+        /* (the entry's rules: S16 -> S16 is the int16 call unless the state's dither or meter is on; everything else the
+         *  float call) */
         int kind = SPEEXHIP_DITHER_NONE;
         (void)speexhip_resampler_get_dither(st, &kind, NULL, NULL);
-        float_entry = !(j->in_fmt[i] == SPEEXHIP_FMT_S16 && j->out_fmt[i] == SPEEXHIP_FMT_S16 && kind == SPEEXHIP_DITHER_NONE);
+        float_entry = !(j->in_fmt[i] == SPEEXHIP_FMT_S16 && j->out_fmt[i] == SPEEXHIP_FMT_S16 && kind == SPEEXHIP_DITHER_NONE &&
+                        !j->h[i]->meter_on);
         j->float_entry[i] = float_entry;
       }
       uint32_t will_use = 0;
@@ -1780,6 +1840,8 @@ NAPI_MODULE_INIT() {
       {"resetMem", NULL, ResetMem, NULL, NULL, NULL, napi_default, NULL},
       {"setDither", NULL, SetDither, NULL, NULL, NULL, napi_default, NULL},
       {"getDither", NULL, GetDither, NULL, NULL, NULL, napi_default, NULL},
+      {"setMeter", NULL, SetMeter, NULL, NULL, NULL, napi_default, NULL},
+      {"getMeter", NULL, GetMeter, NULL, NULL, NULL, napi_default, NULL},
       {"getLatency", NULL, GetLatency, NULL, NULL, NULL, napi_default, NULL},
       {"setMode", NULL, SetMode, NULL, NULL, NULL, napi_default, NULL},
       {"getInfo", NULL, GetInfo, NULL, NULL, NULL, napi_default, NULL},

@@ -119,7 +119,24 @@ EXPORTS = [
     "speexhip_resampler_process_many_sides", "speexhip_resampler_process_many_fmt", "speexhip_debug_many_counters",
     # chunk coalescing, formatted: a side per direction
     "speexhip_resampler_process_chunks_sides", "speexhip_resampler_process_chunks_fmt", "speexhip_debug_chunk_counters",
+    # metering: clip counts and peak level of the formatted, mixed and sides calls' outputs
+    "speexhip_resampler_set_meter", "speexhip_resampler_get_meter", "speexhip_batch_set_meter", "speexhip_batch_get_meter",
+    "speexhip_debug_meter",
 ]
+
+
+class Meter(C.Structure):
+    """SpeexHipMeter: a stream's totals since the last reset"""
+    _fields_ = [("struct_size", C.c_uint32), ("on", C.c_uint32), ("samples", C.c_uint64), ("clipped_high", C.c_uint64),
+                ("clipped_low", C.c_uint64), ("nan", C.c_uint64), ("peak", C.c_float), ("reserved", C.c_uint32)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(Meter)
+
+    def as_dict(self):
+        return {"on": bool(self.on), "samples": int(self.samples), "clipped_high": int(self.clipped_high),
+                "clipped_low": int(self.clipped_low), "nan": int(self.nan), "peak": float(self.peak)}
 
 # layout of a side of the sides calls (SPEEXHIP_LAYOUT_*)
 LAYOUT_INTERLEAVED, LAYOUT_PLANAR = 0, 1
@@ -412,6 +429,18 @@ def lib():
             L.speexhip_resampler_process_chunks_fmt.argtypes = [p, u32, i32, pp, pu32, i32, p, pu32]
             L.speexhip_debug_chunk_counters.restype = None
             L.speexhip_debug_chunk_counters.argtypes = [C.POINTER(C.c_uint64)]
+        if hasattr(L, "speexhip_resampler_set_meter") or "SPEEXHIP_LIB_PATH" not in os.environ:
+            pm = C.POINTER(Meter)
+            L.speexhip_resampler_set_meter.restype = i32
+            L.speexhip_resampler_set_meter.argtypes = [p, i32]
+            L.speexhip_resampler_get_meter.restype = i32
+            L.speexhip_resampler_get_meter.argtypes = [p, pm, i32]
+            L.speexhip_batch_set_meter.restype = i32
+            L.speexhip_batch_set_meter.argtypes = [p, i32]
+            L.speexhip_batch_get_meter.restype = i32
+            L.speexhip_batch_get_meter.argtypes = [p, u32, pm, i32]
+            L.speexhip_debug_meter.restype = i32
+            L.speexhip_debug_meter.argtypes = [i32, p, p, u32, pm]
         _lib = L
     return _lib
 
@@ -473,6 +502,25 @@ def debug_dither(kind, seed, first_index, n):
     if rc:
         raise ValueError(strerror(rc))
     return d[:n]
+
+
+def debug_meter(fmt, y, d=None):
+    """host-only: the library's meter over FIR values y (float32, int16 units) on their way to format fmt; d: None or the
+    dither of each sample (float64, in LSB of the format; the formats of dithered_fmt only).  The totals as a dict
+    (get_meter's, without 'on')."""
+    y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
+    if d is not None:
+        d = np.ascontiguousarray(d, dtype=np.float64).reshape(-1)
+        if d.size != y.size:
+            raise ValueError("one dither value per sample")
+    m = Meter()
+    rc = lib().speexhip_debug_meter(fmt, C.c_void_p(y.ctypes.data), C.c_void_p(d.ctypes.data) if d is not None else None,
+                                    y.size, C.byref(m))
+    if rc:
+        raise ValueError(strerror(rc))
+    out = m.as_dict()
+    del out["on"]
+    return out
 
 
 def debug_g711_decode(fmt, codes):
@@ -1206,6 +1254,20 @@ class Resampler:
             raise RuntimeError(strerror(rc))
         return k.value, s.value, p_.value
 
+    def set_meter(self, on):
+        """The output meter of the formatted, mixed and sides calls: clip counts and peak level of what they encode.  The
+        totals are kept across the switch.  Returns the C call's code (INVALID_ARG for anything but 0 / 1 / a bool)."""
+        return lib().speexhip_resampler_set_meter(self._h, int(on))
+
+    def get_meter(self, reset=False):
+        """{'on', 'samples', 'clipped_high', 'clipped_low', 'nan', 'peak'} since the last reset; peak in int16 units.
+        Waits for this state's last call only."""
+        m = Meter()
+        rc = lib().speexhip_resampler_get_meter(self._h, C.byref(m), int(bool(reset)))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return m.as_dict()
+
     def peek(self, in_frames, out_capacity, float_entry=False):
         """(consumed, produced) of the next call, state untouched"""
         c, p_ = C.c_uint32(), C.c_uint32()
@@ -1346,6 +1408,20 @@ class Batch:
         if rc:
             raise RuntimeError(strerror(rc))
         return k.value, s.value, p_.value
+
+    def set_meter(self, on):
+        """The output meter of every stream in the formatted, mixed and sides calls (process_tensor through them); the
+        totals are kept per stream.  Returns the C call's code."""
+        return lib().speexhip_batch_set_meter(self._h, int(on))
+
+    def get_meter(self, stream, reset=False):
+        """The stream's {'on', 'samples', 'clipped_high', 'clipped_low', 'nan', 'peak'}; reset clears that stream only.
+        Waits for this batch's last call only."""
+        m = Meter()
+        rc = lib().speexhip_batch_get_meter(self._h, int(stream), C.byref(m), int(bool(reset)))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return m.as_dict()
 
     def lines(self, stream):
         """(taps-1+pending, channels) float32 of one stream: history then pending frames"""

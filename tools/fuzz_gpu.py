@@ -191,17 +191,35 @@ def one_trial(seed, max_frames, many_channels=False):
             in_fmt, out_fmt = int(rng.randint(0, 6)), int(rng.randint(0, 6))
             raw = sf.from_internal(in_fmt, x.astype(np.float32))
             xin = sf.to_internal(in_fmt, raw).reshape(-1, ch)
-            if in_fmt == out_fmt == sf.S16:
+            # ... in a share of them with the output meter on (S16 -> S16 then runs as the float call): the totals against
+            # speexhip_debug_meter on the oracle's floats -- equal in EXACT mode, where those are the floats the pass encoded
+            metered = rng.rand() < 0.3
+            if metered:
+                got_r.set_meter(1)
+            if in_fmt == out_fmt == sf.S16 and not metered:
                 a = ref.raw_call("int", raw, cap)
             else:
                 a = ref.raw_call("float", raw if in_fmt == out_fmt == sf.F32N else xin, cap)
             b = got_r.fmt_call(raw, in_fmt, out_fmt, cap)
-            tag = "call %d (formatted %s -> %s, %d frames, cap %d)" % (call, sf.NAMES[in_fmt], sf.NAMES[out_fmt], frames, cap)
+            tag = "call %d (formatted %s -> %s, %d frames, cap %d%s)" % (call, sf.NAMES[in_fmt], sf.NAMES[out_fmt], frames, cap,
+                                                                       ", metered" if metered else "")
+            totals = None
+            if metered:
+                totals = got_r.get_meter(reset=True)
+                got_r.set_meter(0)
             if a[:3] != b[:3]:
                 return "%s: rc/used/made %s, oracle %s" % (tag, b[:3], a[:3]), what
             if got_r.positions() != ref.positions():
                 return "%s: positions %s, oracle %s" % (tag, got_r.positions(), ref.positions()), what
             y = a[3][: a[2]].reshape(-1)
+            if metered:
+                yf = y.astype(np.float32) * np.float32(32768.0 if in_fmt == out_fmt == sf.F32N else 1.0)
+                model = speexhip.debug_meter(out_fmt, yf)
+                keys = ("samples", "clipped_high", "clipped_low", "nan") if mode == speexhip.MODE_EXACT else ("samples", "nan")
+                if any(totals[k] != model[k] for k in keys) or (mode == speexhip.MODE_EXACT and totals["peak"] != model["peak"]):
+                    return "%s: meter %s, debug_meter on the oracle's floats %s" % (tag, totals, model), what
+            if in_fmt == out_fmt == sf.S16 and metered:
+                y = sf.from_internal(sf.S16, y)   # (the float call's result, converted: what the metered call stores)
             same_bytes = in_fmt == out_fmt and in_fmt in (sf.S16, sf.F32, sf.F32N)
             want = y if same_bytes else sf.from_internal(out_fmt, y)
             got = b[3][: want.size]
