@@ -581,6 +581,7 @@ SPEEXHIP_API int speexhip_batch_process_interleaved_mix_device(SpeexHipBatch *b,
  * 2^k (the table's "from a FIR value" column) as, in fp64 and evaluated as written,
  *
  *   v = (double)y * 2^k  (exact);   t = v + d  (one rounding);   q = floor(t + 0.5)  (one rounding)
+ * (with a stream's gain on -- "Gain" -- y is the gained value: v = (double)y' * 2^k)
  *
  * then the U8 offset and the clamp to the format's range; NaN becomes the format's zero and +-inf go
  * to the rails, as without dither.  With d = 0 these are the undithered bytes.  (For S32 the noise
@@ -622,16 +623,16 @@ SPEEXHIP_API int speexhip_debug_dither(int kind, uint64_t seed, uint64_t first_i
  * that they did.  A band-limiting filter overshoots on full-scale material, so a stream that did not
  * clip at one rate may clip at another; a conversion from float adds whatever gain the producer
  * applied.  With the meter on, a state counts what its formatted, mixed and sides calls had to throw
- * away and keeps the peak level, per stream.  (The remedy is in the library already: a diagonal
- * out_mix is a gain.)  Off by default; while it is off every call is exactly what it is without this
- * section, shortcuts and kernels included.
+ * away and keeps the peak level, per stream.  (The remedy is in the library: "Gain" below, per
+ * stream and with a ramp; a diagonal out_mix is a gain too.)  Off by default; while it is off every
+ * call is exactly what it is without this section, shortcuts and kernels included.
  *
  * For one value y that an output pass is about to encode to format F, with d the dither of that sample
  * ("Dither"; 0 when dither is off):
  *
  *   nan           y != y.  Nothing else is counted for that sample.
  *   peak          |y| in int16 units: the value the format's "from a FIR value" rule takes -- behind the
- *                 output matrix, before the dither.  +inf is a legal peak.  0 when nothing was metered.
+ *                 output matrix, behind the gain ("Gain"), before the dither.  +inf is a legal peak.  0 when nothing was metered.
  *   clipped_high  r > hi,   clipped_low  r < lo,   in fp64 and evaluated as written:
  *                   v = (double)y * 2^k  (exact);   t = v + d  (one rounding);   r = floor(t + 0.5)  (one rounding)
  *                 that is the dither section's q before the U8 offset and the clamp; lo and hi are the format's
@@ -681,6 +682,67 @@ SPEEXHIP_API int speexhip_batch_get_meter(SpeexHipBatch *b, uint32_t stream, Spe
  * not written).  d = NULL: no dither; d != NULL for a float format: INVALID_ARG, like an unknown format or a short
  * struct_size. */
 SPEEXHIP_API int speexhip_debug_meter(int fmt, const float *y, const double *d, uint32_t n, SpeexHipMeter *m);
+
+/* ------------------------------------------------------------------------------------------
+ * Gain: the volume control of a stream, applied in the output pass that already converts, mixes, dithers and meters each
+ * sample as it leaves -- per stream of a batch, with a linear ramp so that a change is no click.  (A diagonal out_mix is
+ * a gain too, but one for all streams of a batch, at most 8 channels wide, a step between two calls, and not fused in
+ * the many-states call.)  A stream's gain state is (from, to, total, done): from and to fp32, total the output frames of
+ * the ramp (0: none), done <= total the frames of it already produced.  The gain of the output frame that stands k
+ * frames behind the start of the ramp -- k = done + f, f the output frame within the call, formed in 64 bits -- is
+ *
+ *   step = ((double)to - (double)from) / (double)total      formed ONCE, by set_gain
+ *   g(k) = (float)( (double)from + (double)k * step )       for k <  total  (the product rounded once, the sum once more,
+ *                                                                            never contracted; then nearest-even to fp32)
+ *   g(k) = to                                               for k >= total
+ *
+ * and every sample of that frame becomes y' = y * g: one correctly rounded fp32 product, behind the output matrix's
+ * rounding to fp32, before the meter's judgement, the dither and the format's "from a FIR value" rule.  Nothing is clamped
+ * on the float image; NaN stays NaN; inf * 0 is NaN, counted as nan and encoded as the format's zero; 0 * negative is
+ * -0.0f, and a float output format stores those bits.  g depends on an integer index of the stream alone, so with gain on
+ * a stream's bytes still do not depend on the chunking, on what shares its launch, or on the GPU -- with one
+ * qualification for the float output formats: where the product itself makes a NaN (inf * 0) its sign and payload are
+ * the hardware's default NaN; a NaN that is passed on (NaN * g) keeps its payload, quieted.
+ *
+ * Off means to == 1.0f and (total == 0 or done == total): the default, and what a ramp that ends at 1.0 returns to.  While
+ * every stream of a state is off, every call is exactly what it is without this section: the same kernels, the same
+ * shortcuts, the same bytes.  A stream that is off in a batch (or an entry of a many-states call) where another is on is
+ * not multiplied -- it is selected per stream, not multiplied by 1.0f -- so its bytes stay what they are without gain, NaN
+ * payloads and signed zeros included; the batch's call form follows the state, though: see S16 -> S16 below.
+ *
+ * set_gain: the new from is the gain the stream's next output frame would have had -- g(done) of the old state, so a new
+ * target in mid-ramp is continuous -- the new to is `gain`, the new total is `ramp_frames` (0: a step at the next output
+ * frame), and done becomes 0.  A gain that is not finite: INVALID_ARG, the state as it was.  Negative gains (polarity) and
+ * 0 (mute) are legal.  get_gain reports current = g(done), target = to, remaining = total - done; any pointer may be NULL.
+ * In a batch `stream` selects the stream; set_gain takes UINT32_MAX for every stream.
+ *
+ * Gain applies to the formatted, mixed and sides calls only -- host, device, batch, many-states and chunks forms: the set
+ * that is dithered and metered.  The int16, float, planar, per-channel, chunks_int / _float, many_int / _float and take
+ * calls neither apply it nor move done; set_rate, set_quality, reset_mem, skip_zeros, set_dither and set_meter do not
+ * touch it.  While any stream of a state has its gain on
+ *   - every such call moves each stream's done by the frames it produced, up to total; a stream that produced nothing
+ *     does not move;
+ *   - S16 -> S16 is no longer the int16 call: it runs as the float call between the two conversions, with the float
+ *     entry's counter rules (as with dither or the meter on);
+ *   - a result that no output pass writes (F32 -> F32, F32N -> F32N without matrix or planar side; interleaved F32 out)
+ *     is multiplied in place behind the FIR launch -- an F32N result as stored, which is the rule's bytes short of overflow
+ *     and underflow, the remark made for F32N -> F32N above -- and judged in that same pass when the meter is on; the
+ *     planar float pairs run through the plane passes;
+ *   - the zero fallback's zeros are multiplied like any value (gain -1: -0.0f in F32, the format's zero elsewhere);
+ *   - a state whose channels the per-channel calls moved apart returns BAD_STATE, untouched;
+ *   - in a chunks call the ramp's index runs on across the chunk boundaries;
+ *   - in a many-states call each entry has its own state's gain and stays fused: gain takes no entry out of a launch
+ *     group.  (An entry whose F32 result the FIR writes itself is multiplied by one more kernel over the group.)
+ * The meter's peak is |y'| and its clips are judged on y'; the dither's v is (double)y' * 2^k.
+ *
+ * ABI note: adds these five entry points; SpeexHipInfo, SpeexHipSide, SpeexHipMeter, the enums, the error codes and the
+ * version string are unchanged. */
+SPEEXHIP_API int speexhip_resampler_set_gain(SpeexHipResamplerState *st, float gain, uint32_t ramp_frames);
+SPEEXHIP_API int speexhip_resampler_get_gain(SpeexHipResamplerState *st, float *current, float *target, uint32_t *remaining);
+SPEEXHIP_API int speexhip_batch_set_gain(SpeexHipBatch *b, uint32_t stream, float gain, uint32_t ramp_frames);
+SPEEXHIP_API int speexhip_batch_get_gain(SpeexHipBatch *b, uint32_t stream, float *current, float *target, uint32_t *remaining);
+/* Host only, no GPU: g[i] = g(first + i) of (from, to, total), the very statement the kernels compile. */
+SPEEXHIP_API int speexhip_debug_gain(float from, float to, uint32_t total, uint64_t first, uint32_t n, float *g);
 
 /* ------------------------------------------------------------------------------------------
  * Companded formats: G.711 as telephony carries it (RTP PCMU / PCMA, 8 kHz), one byte per sample, no

@@ -8,6 +8,7 @@
 #include "../../include/speexhip_resampler.h"
 #include "devices.h"
 #include "dither.h"
+#include "gain.h"
 #include "meter.h"
 #include "engine.h"
 #include "filter_plans.h"
@@ -789,6 +790,25 @@ int speexhip_debug_meter(int fmt, const float *y, const double *d, uint32_t n, S
   now.clipped_high = hi, now.clipped_low = lo, now.nan = nan;
   std::memcpy(&now.peak, &peak, sizeof(peak));
   std::memcpy(m, &now, sizeof(now));
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+int speexhip_resampler_set_gain(SpeexHipResamplerState *st, float gain, uint32_t ramp_frames) {
+  return guarded([&] { return st ? st->batch->set_gain(0, gain, ramp_frames) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_resampler_get_gain(SpeexHipResamplerState *st, float *current, float *target, uint32_t *remaining) {
+  return guarded([&] { return st ? st->batch->get_gain(0, current, target, remaining) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_batch_set_gain(SpeexHipBatch *b, uint32_t stream, float gain, uint32_t ramp_frames) {
+  return guarded([&] { return b ? b->batch->set_gain(stream, gain, ramp_frames) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_batch_get_gain(SpeexHipBatch *b, uint32_t stream, float *current, float *target, uint32_t *remaining) {
+  return guarded([&] { return b ? b->batch->get_gain(stream, current, target, remaining) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_debug_gain(float from, float to, uint32_t total, uint64_t first, uint32_t n, float *g) {
+  if (g == nullptr && n != 0) return SPEEXHIP_ERR_INVALID_ARG;
+  const double step = speexhip::gain::step_of(from, to, total);
+  for (uint32_t i = 0; i < n; i++) g[i] = speexhip::gain::at(step, from, to, total, first + i);
   return SPEEXHIP_ERR_SUCCESS;
 }
 

@@ -3,6 +3,7 @@
 
 #include "devices.h"
 #include "engine_detail.h"
+#include "gain.h"
 #include "host_transfer.h"
 #include "pool.h"
 #include "unit_workers.h"
@@ -12,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstring>
 #include <list>
@@ -875,6 +877,83 @@ int Batch::meter_result(const void *result, uint64_t stride, const uint32_t *len
       most = std::max(most, pack.s[j].n);
     }
     if (hip_failed(launch_meter_image(pack, meter_pack(first, n), scale, n, most, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+  }
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+// ---- the output gain (engine.h) ----------------------------------------------------------------------------------------
+int Batch::set_gain(uint32_t stream, float gain, uint32_t ramp_frames) {
+  if (stream != UINT32_MAX && stream >= n_streams_) return SPEEXHIP_ERR_INVALID_ARG;
+  if (!std::isfinite(gain)) return SPEEXHIP_ERR_INVALID_ARG;
+  if (gain_.empty()) gain_.assign(n_streams_, Gain());
+  for (uint32_t s = stream == UINT32_MAX ? 0 : stream; s < (stream == UINT32_MAX ? n_streams_ : stream + 1); s++) {
+    Gain &g = gain_[s];
+    const float now = gain::at(g.step, g.from, g.to, g.total, g.done);  // (what the next output frame would have had)
+    g.from = now;
+    g.to = gain;
+    g.total = ramp_frames;
+    g.done = 0;
+    g.step = gain::step_of(g.from, g.to, g.total);
+  }
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+int Batch::get_gain(uint32_t stream, float *current, float *target, uint32_t *remaining) const {
+  if (stream >= n_streams_) return SPEEXHIP_ERR_INVALID_ARG;
+  const Gain g = gain_.empty() ? Gain() : gain_[stream];
+  if (current != nullptr) *current = gain::at(g.step, g.from, g.to, g.total, g.done);
+  if (target != nullptr) *target = g.to;
+  if (remaining != nullptr) *remaining = g.total - g.done;
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+bool Batch::gain_on() const {
+  for (const Gain &g : gain_)
+    if (!gain::is_off(g.to, g.total, g.done)) return true;
+  return false;
+}
+
+GainPack Batch::gain_pack(uint32_t s0, uint32_t n, uint32_t per_frame) const {
+  GainPack p;
+  std::memset(&p, 0, sizeof(p));
+  for (uint32_t j = 0; j < n && !gain_.empty(); j++) {
+    const Gain &g = gain_[s0 + j];
+    if (gain::is_off(g.to, g.total, g.done)) continue;  // (channels 0: not multiplied)
+    p.s[j].step = g.step;
+    p.s[j].first = g.done;
+    p.s[j].from = g.from, p.s[j].to = g.to;
+    p.s[j].total = g.total;
+    p.s[j].channels = per_frame;
+  }
+  return p;
+}
+
+void Batch::gain_advance(const uint32_t *produced) {
+  for (uint32_t s = 0; s < n_streams_ && !gain_.empty(); s++) {
+    Gain &g = gain_[s];
+    g.done += std::min(produced[s], g.total - g.done);  // (saturates at total)
+  }
+}
+
+int Batch::image_result(void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream) {
+  if (!gain_on()) return meter_on_ ? meter_result(result, stride, lens, scale, stream) : SPEEXHIP_ERR_SUCCESS;
+  const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
+  for (uint32_t first = 0; first < n_streams_; first += kChunk) {
+    const uint32_t n = std::min(kChunk, n_streams_ - first);
+    ConvertPack pack;
+    std::memset(&pack, 0, sizeof(pack));
+    uint64_t most = 0;
+    for (uint32_t j = 0; j < n; j++) {
+      pack.s[j].dst = static_cast<float *>(result) + (first + j) * stride;
+      pack.s[j].n = static_cast<uint64_t>(lens[first + j]) * channels_;
+      pack.s[j].step = 1;
+      most = std::max(most, pack.s[j].n);
+    }
+    MeterPack cells;
+    if (meter_on_) cells = meter_pack(first, n);
+    if (hip_failed(launch_gain_image(pack, gain_pack(first, n, channels_), meter_on_ ? &cells : nullptr, scale, n, most, stream),
+                   "kernel launch"))
+      return SPEEXHIP_ERR_DEVICE;
   }
   return SPEEXHIP_ERR_SUCCESS;
 }

@@ -156,6 +156,22 @@ class Batch {
   // The totals of `stream` (m may be null): waits on the host for this state's own last call, as the control calls do --
   // never for the device -- and fetches the cells in one small copy.  reset: that stream's totals are zero from here on.
   int get_meter(uint32_t stream, SpeexHipMeter *m, bool reset);
+  // The output gain of the formatted, mixed and sides calls (gain.h; include/speexhip_resampler.h, "Gain"): per stream
+  // (from, to, total, done), off by default (to == 1 and no ramp in flight).  While any stream of the state has its gain
+  // on, every such call -- host, device, batch, many-states, chunks -- leaves through the gained instance of its output
+  // pass, which multiplies every sample of output frame f of a stream by g(done + f); a result that no pass writes (the
+  // float call on the same bytes, interleaved F32 without a matrix) is multiplied in place by gain_image behind the FIR
+  // launch, which judges it as well when the meter is on.  S16 -> S16 then runs as the float call between the two
+  // conversions, the planar float pairs between planes_in and planes_out, and a state whose channels stand apart returns
+  // BAD_STATE, as with dither or the meter on.  A stream whose own gain is off is not multiplied (selected per stream,
+  // wave-uniformly).  Every such call moves done by the frames produced, up to total.  The int16, float, planar,
+  // per-channel, chunks_int / _float, many_int / _float and take calls neither apply the gain nor move done, and no
+  // control call (set_rate, set_quality, reset_mem, skip_zeros, set_dither, set_meter) touches it.
+  // set_gain: from = the gain the stream's next output frame would have had, to = gain, total = ramp_frames, done = 0;
+  // stream = UINT32_MAX: every stream.  A gain that is not finite: INVALID_ARG, nothing changed.
+  int set_gain(uint32_t stream, float gain, uint32_t ramp_frames);
+  // current = g(done), target = to, remaining = total - done (any may be null)
+  int get_gain(uint32_t stream, float *current, float *target, uint32_t *remaining) const;
   // Host-buffer call for a single-stream batch; synchronous (H2D, kernels, D2H).
   int process_host(const void *in, uint32_t *in_len, void *out, uint32_t *out_len, bool float_io);
   // The same call with the result left in a pinned block of the pool that the caller then OWNS (release_block):
@@ -271,6 +287,15 @@ class Batch {
   // meter_image over what a call without an output pass wrote: stream s is lens[s] frames of channels() floats at
   // result + s * stride (floats), judged as stored * scale
   int meter_result(const void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream);
+  // whether any stream's gain is on: the state's formatted calls then take the gained routes
+  bool gain_on() const;
+  // the gains of streams [s0, s0 + n), as a gained launch takes them: first = the stream's done; per_frame = the samples
+  // of an output frame in a pass that walks samples, 1 in the passes that walk frames (a stream whose gain is off: 0)
+  GainPack gain_pack(uint32_t s0, uint32_t n, uint32_t per_frame) const;
+  void gain_advance(const uint32_t *produced);  // after a formatted or mixed call with gain on
+  // What a call without an output pass wrote (meter_result's arguments), finished in place: gain_image when gain is on --
+  // which judges its product too when the meter is on -- meter_image otherwise.
+  int image_result(void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream);
   // process_sides_host of a call with a planar side
   int planes_host_call(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len);
   int fetch_history(std::vector<float> *host);
@@ -424,6 +449,12 @@ class Batch {
   MeterCell *d_meter_ = nullptr;            // one cell per stream (null until the meter is first turned on), meter_bytes_ in all
   size_t meter_bytes_ = 0;
   std::vector<uint64_t> meter_samples_;     // per stream: samples metered since the last reset
+  struct Gain {                             // one stream's gain (gain.h)
+    double step = 0.0;                      // (to - from) / total, formed by set_gain
+    float from = 1.0f, to = 1.0f;
+    uint32_t total = 0, done = 0;
+  };
+  std::vector<Gain> gain_;                  // per stream (empty until set_gain: off)
   uint32_t done_seq_ = 0;  // completion word of the small host-buffer calls (engine.cpp, process_host)
   size_t stage_in_cap_ = 0, stage_out_cap_ = 0, pin_in_cap_ = 0, pin_out_cap_ = 0;  // bytes
 };

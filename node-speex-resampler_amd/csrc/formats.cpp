@@ -96,22 +96,26 @@ int Batch::process_sides_device(const CallSide &in_side, uint32_t *in_len, const
   if (!planar(in)) in.layout = SPEEXHIP_LAYOUT_INTERLEAVED;
   if (!planar(out)) out.layout = SPEEXHIP_LAYOUT_INTERLEAVED;
   ON_DEVICE();
-  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), meter = meter_on_;
+  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), gained = gain_on();
+  // (what the meter asks of the routes below a gained stream asks too: no shortcut past the output side)
+  const bool meter = meter_on_ || gained;
   bool split = false;
   for (uint32_t s = 0; s < n_streams_; s++)
     if (!uniform(s)) {
       // (channels that stand apart produce different numbers of frames: neither an output frame of a matrix nor a dither
-      //  position nor a stream of samples to meter is defined)
+      //  position nor a stream of samples to meter nor a frame index of a gain is defined)
       if (n_streams_ != 1 || dith || mixed || meter) return SPEEXHIP_ERR_BAD_STATE;
       split = true;
     }
   if (same_bytes(in, out, dith || meter)) {
-    // (with the meter on: F32 or F32N, the float call's bytes as ever, read once more by meter_image)
+    // (with the meter on: F32 or F32N, the float call's bytes as ever, read once more by meter_image; with gain on:
+    //  multiplied in place by gain_image, an F32N result as stored, and judged in that same pass)
     const int rc = process_device(in.base, in.stride, in_len, out.base, out.stride, out_len, in.fmt != SPEEXHIP_FMT_S16, stream);
     if (meter && ran(rc)) {
-      const int mrc = meter_result(out.base, out.stride, out_len, in.fmt == SPEEXHIP_FMT_F32N ? 32768.0f : 1.0f, stream);
+      const int mrc = image_result(out.base, out.stride, out_len, in.fmt == SPEEXHIP_FMT_F32N ? 32768.0f : 1.0f, stream);
       if (mrc != SPEEXHIP_ERR_SUCCESS) return mrc;
-      meter_count(out_len, channels_);
+      if (meter_on_) meter_count(out_len, channels_);
+      if (gained) gain_advance(out_len);
     }
     if (dith && ran(rc)) dither_advance(out_len);
     return rc;
@@ -168,10 +172,11 @@ int Batch::process_sides_device(const CallSide &in_side, uint32_t *in_len, const
     if (prc != SPEEXHIP_ERR_SUCCESS) return prc;
   } else if (meter) {
     // (interleaved F32 without a matrix: the FIR wrote the caller's buffer)
-    const int mrc = meter_result(out.base, out.stride, out_len, 1.0f, stream);
+    const int mrc = image_result(out.base, out.stride, out_len, 1.0f, stream);
     if (mrc != SPEEXHIP_ERR_SUCCESS) return mrc;
   }
-  if (meter) meter_count(out_len, out.channels);
+  if (meter_on_) meter_count(out_len, out.channels);
+  if (gained) gain_advance(out_len);
   if (dith) dither_advance(out_len);
   return rc;
 }
@@ -204,7 +209,8 @@ int Batch::process_host_many_sides(uint32_t n, Batch *const *st, const CallSide 
     if (!e.fusable) continue;
     e.in = in[i].base;
     e.out = out[i].base;
-    e.kind = !same_bytes(in[i], out[i], b->dither_on() || b->meter_on_) ? ManyEntry::Image
+    // (a gained entry stays fused: S16 -> S16 between its two passes, a float result multiplied by gain_image in the group)
+    e.kind = !same_bytes(in[i], out[i], b->dither_on() || b->meter_on_ || b->gain_on()) ? ManyEntry::Image
              : in[i].fmt == SPEEXHIP_FMT_S16            ? ManyEntry::Int16
                                                         : ManyEntry::Float;
   }
@@ -230,9 +236,11 @@ int Batch::process_sides_host(const CallSide &in, uint32_t *in_len, const CallSi
   }
   if (out.base == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
   const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), split = !uniform(0);
-  if (split && (dith || meter_on_) && !mixed) return SPEEXHIP_ERR_BAD_STATE;
-  // (with the meter on the float pairs go on below: process_sides_device runs meter_image behind the float call)
-  if (same_bytes(in, out, dith) && !meter_on_) {
+  const bool gained = gain_on();
+  if (split && (dith || meter_on_ || gained) && !mixed) return SPEEXHIP_ERR_BAD_STATE;
+  // (with the meter or gain on the float pairs go on below: process_sides_device runs meter_image or gain_image behind the
+  //  float call)
+  if (same_bytes(in, out, dith) && !meter_on_ && !gained) {
     const int rc = process_host(in.base, in_len, out.base, out_len, in.fmt != SPEEXHIP_FMT_S16);
     if (dith && ran(rc)) dither_advance(out_len);
     return rc;
@@ -339,10 +347,12 @@ int Batch::process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, cons
   for (uint32_t i = 0; i < n_chunks; i++)
     for (uint32_t c = 1; entry(i, 0) != nullptr && c < per; c++)
       if (entry(i, c) == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
-  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), meter = meter_on_, split = !uniform(0);
+  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), gained = gain_on(), split = !uniform(0);
+  const bool meter = meter_on_ || gained;  // (a gained stream asks of the routes what the meter asks)
   if (split && (dith || mixed || meter)) return SPEEXHIP_ERR_BAD_STATE;
   // same: the call on the same bytes; with the meter on (F32 or F32N then) it still goes through here, without passes,
-  // and meter_image reads the result
+  // and meter_image reads the result -- or gain_image multiplies it, once over all chunks: the ramp's index runs on
+  // across the chunk boundaries as the dither's does
   const bool same = same_bytes(in, out, dith || meter), own_calls = split || zero_mode_;
   const size_t bin = sample_bytes(in.fmt), bout = sample_bytes(out.fmt);
   if (own_calls && (!same || meter)) {  // rare states: the separate calls, one after the other, each output side behind the frames written
@@ -437,10 +447,11 @@ int Batch::process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, cons
     rc = side_pass(pl_out ? planes_at(out, call.dst, out_pitch) : at(out, call.dst), false, d_planar_out_, 0, &made, own_stream_);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   } else if (meter) {
-    rc = meter_result(call.dst, 0, &made, out.fmt == SPEEXHIP_FMT_F32N ? 32768.0f : 1.0f, own_stream_);
+    rc = image_result(call.dst, 0, &made, out.fmt == SPEEXHIP_FMT_F32N ? 32768.0f : 1.0f, own_stream_);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
-  if (meter) meter_count(&made, out.channels);
+  if (meter_on_) meter_count(&made, out.channels);
+  if (gained) gain_advance(&made);
   if (dith) dither_advance(&made);
   if (pl_out) {
     std::vector<void *> planes(out.channels);
@@ -467,7 +478,7 @@ int Batch::process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, cons
 int Batch::planes_host_call(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len) {
   const bool pl_in = planar(in), pl_out = planar(out);
   const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), split = !uniform(0);
-  if (split && (dith || mixed || meter_on_)) return SPEEXHIP_ERR_BAD_STATE;
+  if (split && (dith || mixed || meter_on_ || gain_on())) return SPEEXHIP_ERR_BAD_STATE;
   // (a mono side given as its one plane is an interleaved buffer)
   CallSide in_flat = in, out_flat = out;
   if ((!pl_in && in.planes != nullptr && in.planes[0] == nullptr) || (!pl_out && out.planes != nullptr && out.planes[0] == nullptr))

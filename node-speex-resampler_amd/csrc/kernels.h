@@ -275,6 +275,21 @@ struct MeterPack {          // like ConvertPack: up to 32 streams, in the kernel
   MeterCell *cell[kMaxPackedStreams];  // convert_many_out_meter: NULL = a stream that is not metered
 };
 
+// ---- the gain on the way out (gain.h): the gained instances of the output passes -- convert_out_gain<F>,
+// convert_many_out_gain, mix_out_gain<F>, planes_out_gain<F> -- and gain_image, of a state with a stream's gain on.  One
+// instance per format and pass: dither and meter are taken at run time (kind NONE: d = 0; a NULL cell: nothing committed).
+struct GainStream {         // one stream's share: g(k) = (float)(from + k * step) for k < total, to from there on
+  double step;              // (to - from) / total, formed on the host by set_gain
+  uint64_t first;           // k of the stream's frame 0 of this launch
+  float from, to;
+  uint32_t total;
+  uint32_t channels;        // 0: the stream's gain is off, nothing is multiplied; otherwise the samples of an output
+                            // frame in a converting pass (frame = sample / channels), 1 in the passes that walk frames
+};
+struct GainPack {           // like ConvertPack: up to 32 streams, in the kernel-argument segment (1024 bytes; the largest
+  GainStream s[kMaxPackedStreams];  // pass, PlanePack + DitherPack + MeterPack + GainPack, is 3096 of its 4096)
+};
+
 // ---- the launchers of a pass over streams [0, n) of `pack` -------------------------------------------------------------
 // fmt = the storage side's format: any SPEEXHIP_FMT_* for a mix, any but F32 for a conversion (that IS the image's
 // format).  out: image -> storage, otherwise storage -> image.  dith = NULL: the plain instances; otherwise the dithered
@@ -284,10 +299,18 @@ struct MeterPack {          // like ConvertPack: up to 32 streams, in the kernel
 // meter = NULL: exactly the above.  Otherwise (out only, every step 1) the metered instances, for every format: the
 // formats of dithered_fmt through the dithered body -- dith = NULL: kind NONE, d = 0, the undithered bytes -- and the
 // float ones through the plain body; stream j is judged into meter->cell[j].
+// gain = NULL: exactly the above.  Otherwise (out only, every step 1) the gained instance of the format: stream j's
+// samples are multiplied by its g (gain->s[j]; channels 0: not at all) and then leave as above -- dithered when dith is
+// given, judged when meter is (both at run time).
 hipError_t launch_convert(int fmt, bool out, const ConvertPack &pack, const DitherPack *dith, uint32_t n, uint64_t most,
-                          hipStream_t stream, const MeterPack *meter = nullptr);
+                          hipStream_t stream, const MeterPack *meter = nullptr, const GainPack *gain = nullptr);
 hipError_t launch_mix(int fmt, bool out, const MixPack &pack, const DitherPack *dith, uint32_t n, uint32_t most,
-                      hipStream_t stream, const MeterPack *meter = nullptr);
+                      hipStream_t stream, const MeterPack *meter = nullptr, const GainPack *gain = nullptr);
+// gain_image (kernels_convert.hip): multiplies the n floats at pack.s[j].dst in place by the stream's g (frame = sample /
+// gain.s[j].channels; channels 0: left alone) -- the result of a call that has no output pass.  meter != NULL: a stream
+// whose cell is not NULL is judged in the same pass, product * scale as a float format (launch_meter_image's rule).
+hipError_t launch_gain_image(const ConvertPack &pack, const GainPack &gain, const MeterPack *meter, float scale, uint32_t n,
+                             uint64_t most, hipStream_t stream);
 // meter_image (kernels_convert.hip): reads the n samples at pack.s[j].src (floats; dst and step are not read) and judges
 // stored * scale as a float format into meter.cell[j] -- the result of a call that has no output pass.  Writes nothing else.
 hipError_t launch_meter_image(const ConvertPack &pack, const MeterPack &meter, float scale, uint32_t n, uint64_t most,
@@ -302,8 +325,11 @@ constexpr uint32_t convert_many_tag(int fmt, int dither_kind) {
 }
 // meter (out only) = the launch of a group with a metered state in it: a stream whose cell is not NULL leaves through the
 // metered body of its format (meter.h), every other one exactly as without.
+// gain (out only) = the launch of a group with a gained state in it: convert_many_out_gain, where every stream leaves
+// through the gained body of its format -- multiplied by its own g (channels 0: not at all), dithered at its kind, judged
+// into its cell when it has one.
 hipError_t launch_convert_many(bool out, const ConvertPack &pack, const DitherPack &dith, uint32_t n, uint64_t most,
-                               hipStream_t stream, const MeterPack *meter = nullptr);
+                               hipStream_t stream, const MeterPack *meter = nullptr, const GainPack *gain = nullptr);
 
 // ---- channel planes of any format <-> the float image (kernels_sides.hip): the pass of a side whose layout is planar --
 // planes_in: C planes of the call's format -> the interleaved float image; planes_out: the image -> planes.  Conversion,
@@ -328,8 +354,8 @@ struct PlanePack {          // like MixPack: up to 32 streams and the matrix, in
   uint32_t mixed;             // 0: plane c is channel c of the image (any channel count); otherwise m applies, 1..8 a side
 };
 // dith as for launch_mix: DitherStream::first = the stream's position, idx = (first + frame) * storage_channels + plane
-// meter as for launch_mix
+// meter and gain as for launch_mix
 hipError_t launch_planes(int fmt, bool out, const PlanePack &pack, const DitherPack *dith, uint32_t n, uint32_t most,
-                         hipStream_t stream, const MeterPack *meter = nullptr);
+                         hipStream_t stream, const MeterPack *meter = nullptr, const GainPack *gain = nullptr);
 
 }  // namespace speexhip

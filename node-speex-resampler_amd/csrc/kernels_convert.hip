@@ -40,6 +40,15 @@
 // formats.  A lane counts in registers, the workgroup folds its four waves and adds into the stream's MeterCell, whose
 // address travels in a third kernel argument (MeterPack).  meter_image reads a float result that no pass writes and
 // judges it the same way.  The plain and dithered instances are untouched: the meter is a compile-time flag of the body.
+//
+// convert_out_gain<F> (every format; a state with a stream's gain on): one instance per format.  Each sample is
+// multiplied by the g of its frame (gain.h) and then leaves through the metered body, which takes dither and meter at
+// run time -- kind NONE: d = 0; no cell: nothing judged or committed; neither: from_internal, the same bytes without the
+// fp64 sum.  The pass walks samples, not frames: a stream past its ramp has one wave-uniform g and forms no index; in a
+// ramp the tile's first sample is split into frame and channel once, in 64 bits, and a lane's offset divided in 32 -- once
+// per 16-byte group on the vector path, frame and channel then walking on through the group, which may straddle frames;
+// once per sample on the element path.  The stream's mode and what it asks of the encoder are branched on once per group.
+// gain_image does the same in place over a float result that no pass writes.
 #include <hip/hip_runtime.h>
 
 #include "../../include/speexhip_resampler.h"
@@ -82,6 +91,53 @@ __global__ __launch_bounds__(kLanes) void convert_out_meter(const ConvertPack pa
                                       meter.cell[blockIdx.y]);
 }
 
+// the gained instance of a format (gain.h): every sample times the g of its frame, then the metered body above with
+// dither and meter taken at run time
+template <int F>
+__global__ __launch_bounds__(kLanes) void convert_out_gain(const ConvertPack pack, const DitherPack dith, const MeterPack meter,
+                                                           const GainPack gain) {
+  stream_tile<F, true, dithered_fmt(F), true, true>(pack.s[blockIdx.y], &dith.s[blockIdx.y], dithered_fmt(F) ? dith.kind : 0,
+                                                    meter.cell[blockIdx.y], &gain.s[blockIdx.y]);
+}
+
+// gain_image: the tile blockIdx.x of stream blockIdx.y of a float result that no pass writes, multiplied in place by the
+// g of each sample's frame (gain.h); 16 bytes per lane where the tile is whole and aligned, sample by sample otherwise.
+// A stream with a cell is judged on the product * scale in the same pass (meter_image's rule, without its second read).
+// A stream whose gain is off is not written.
+__global__ __launch_bounds__(kLanes) void gain_image(const ConvertPack pack, const GainPack gain, const MeterPack meter,
+                                                     const float scale) {
+  const ConvertStream &s = pack.s[blockIdx.y];
+  const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kTile;
+  if (s.dst == nullptr || tile0 >= s.n) return;
+  const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(kTile), s.n - tile0));
+  float *img = static_cast<float *>(s.dst) + tile0;
+  MeterCell *const cell = meter.cell[blockIdx.y];
+  const gain::Tile gt = gain::tile_of(gain.s[blockIdx.y], true);
+  if (gt.mode == gain::kOff && cell == nullptr) return;
+  const gain::Split sp = gain::split_of(gt, tile0);
+  meter::Lane m;
+  const auto one = [&](float y, uint32_t i) {
+    const float v = gain::apply(gt, y, gain::frame_of(gt, sp, i));
+    if (cell != nullptr) meter::judge<SPEEXHIP_FMT_F32>(m, v * scale, 0.0);
+    return v;
+  };
+  if (n == kTile && (reinterpret_cast<uintptr_t>(s.dst) & 15u) == 0) {
+#pragma unroll
+    for (uint32_t pass = 0; pass < kTile / (kLanes * 4); pass++) {
+      const uint32_t i = (pass * kLanes + threadIdx.x) * 4;
+      float4 v = reinterpret_cast<const float4 *>(img)[pass * kLanes + threadIdx.x];
+      v.x = one(v.x, i), v.y = one(v.y, i + 1), v.z = one(v.z, i + 2), v.w = one(v.w, i + 3);
+      if (gt.mode != gain::kOff) reinterpret_cast<float4 *>(img)[pass * kLanes + threadIdx.x] = v;
+    }
+  } else {
+    for (uint32_t i = threadIdx.x; i < n; i += kLanes) {
+      const float v = one(img[i], i);
+      if (gt.mode != gain::kOff) img[i] = v;
+    }
+  }
+  if (cell != nullptr) meter::commit(m, cell);
+}
+
 // meter_image: the tile blockIdx.x of stream blockIdx.y of a float result, read and judged, nothing written but the cell.
 // Whole 16-byte aligned tiles 16 bytes per lane (lane t on group pass * 256 + t, as convert_out<F32N> reads), the rest
 // sample by sample.
@@ -120,17 +176,37 @@ hipError_t launch_meter_image(const ConvertPack &pack, const MeterPack &meter, f
   return hipGetLastError();
 }
 
-hipError_t launch_convert(int fmt, bool out, const ConvertPack &pack, const DitherPack *dith, uint32_t n, uint64_t most,
-                          hipStream_t stream, const MeterPack *meter) {
+hipError_t launch_gain_image(const ConvertPack &pack, const GainPack &gain, const MeterPack *meter, float scale, uint32_t n,
+                             uint64_t most, hipStream_t stream) {
   if (n == 0 || most == 0) return hipSuccess;
-  for (uint32_t j = 0; (dith != nullptr || meter != nullptr) && j < n; j++)
-    if (!out || pack.s[j].step != 1 || (meter != nullptr && meter->cell[j] == nullptr)) return hipErrorInvalidValue;
+  if (n > kMaxPackedStreams) return hipErrorInvalidValue;
+  for (uint32_t j = 0; j < n; j++)
+    if (pack.s[j].dst != nullptr && pack.s[j].n != 0 && (pack.s[j].n > most || gain.s[j].channels > 0x7fffffffu)) return hipErrorInvalidValue;
+  const MeterPack none = {};
+  const dim3 grid(static_cast<uint32_t>((most + kTile - 1) / kTile), n), block(kLanes);
+  hipLaunchKernelGGL(gain_image, grid, block, 0, stream, pack, gain, meter != nullptr ? *meter : none, scale);
+  return hipGetLastError();
+}
+
+hipError_t launch_convert(int fmt, bool out, const ConvertPack &pack, const DitherPack *dith, uint32_t n, uint64_t most,
+                          hipStream_t stream, const MeterPack *meter, const GainPack *gain) {
+  if (n == 0 || most == 0) return hipSuccess;
+  for (uint32_t j = 0; (dith != nullptr || meter != nullptr || gain != nullptr) && j < n; j++)
+    if (!out || pack.s[j].step != 1 || (meter != nullptr && meter->cell[j] == nullptr) ||
+        (gain != nullptr && gain->s[j].channels > 0x7fffffffu))
+      return hipErrorInvalidValue;
   const dim3 grid(static_cast<uint32_t>((most + kTile - 1) / kTile), n), block(kLanes);
   return with_format(fmt, [&](auto format) -> hipError_t {
     constexpr int F = decltype(format)::value;
     // (F32 is the image's own format: nothing to convert; the float formats are not dithered)
     if constexpr (F == SPEEXHIP_FMT_F32) {
       return hipErrorInvalidValue;
+    } else if (gain != nullptr) {
+      if (dith != nullptr && !dithered_fmt(F)) return hipErrorInvalidValue;
+      const DitherPack none = {};    // (kind NONE)
+      const MeterPack no_cells = {};  // (nothing judged)
+      hipLaunchKernelGGL((convert_out_gain<F>), grid, block, 0, stream, pack, dith != nullptr ? *dith : none,
+                         meter != nullptr ? *meter : no_cells, *gain);
     } else if (meter != nullptr) {
       if (dith != nullptr && !dithered_fmt(F)) return hipErrorInvalidValue;
       DitherPack none = {};  // (kind NONE)

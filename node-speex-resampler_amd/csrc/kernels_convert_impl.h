@@ -9,6 +9,7 @@
 #include "../../include/speexhip_resampler.h"
 #include "dither.h"
 #include "format_device.h"
+#include "gain.h"
 #include "kernels.h"
 #include "meter.h"
 
@@ -42,14 +43,17 @@ __device__ __forceinline__ void put_raw(uint32_t *w, uint32_t j, uint32_t raw) {
 }
 
 // kDither (kOut only): the dithered instances; d and kind are theirs alone.  kMeter (kOut only): the metered instances;
-// m takes what the lane's samples come to (meter.h) and is theirs alone
-template <int F, bool kOut, bool kDither, bool kMeter>
+// m takes what the lane's samples come to (meter.h) and is theirs alone.  kGain (kOut, kMeter and kDither = dithered_fmt(F)
+// only): the gained instances; gt (gain.h) is theirs alone -- a sample is multiplied by the g of its frame, then leaves as
+// its stream asks
+template <int F, bool kOut, bool kDither, bool kMeter, bool kGain>
 __device__ __forceinline__ void vector_tile(const ConvertStream &s, const DitherStream *d, int kind, uint64_t tile0,
-                                            meter::Lane &m) {
+                                            meter::Lane &m, const gain::Tile &gt) {
   constexpr uint32_t B = sample_bytes(F), G = group_of(F), words = G * B / 4;
   constexpr int W = word_format(F);  // (S16BE / S32BE: the words are reversed as dwords, the samples then the twin's)
   const char *src = static_cast<const char *>(s.src);
   char *dst = static_cast<char *>(s.dst);
+  const gain::Split sp = kGain ? gain::split_of(gt, tile0) : gain::Split{};
 #pragma unroll
   for (uint32_t pass = 0; pass < kTile / (kLanes * G); pass++) {
     const uint64_t first = tile0 + static_cast<uint64_t>(pass * kLanes + threadIdx.x) * G;  // the lane's first sample
@@ -78,9 +82,23 @@ __device__ __forceinline__ void vector_tile(const ConvertStream &s, const Dither
       }
 #pragma unroll
       for (uint32_t i = 0; i < words; i++) w[i] = 0;
+      if constexpr (kGain) {
+        // The group is multiplied, then encoded, each in one straight run: the stream's mode and what it asks of the
+        // encoder are wave-uniform, so they are branched on once per group, not once per sample.
+        gain::apply_group<G>(gt, sp, (pass * kLanes + threadIdx.x) * G, e);
+        if (gt.plain) {
 #pragma unroll
-      for (uint32_t j = 0; j < G; j++)
-        put_raw<W>(w, j, meter::encode<W, kDither, kMeter>(m, e[j], [&] { return dither::noise_in(kind, run, j); }));
+          for (uint32_t j = 0; j < G; j++) put_raw<W>(w, j, from_internal<W>(e[j]));
+        } else {
+#pragma unroll
+          for (uint32_t j = 0; j < G; j++)
+            put_raw<W>(w, j, meter::encode<W, kDither, true>(m, e[j], [&] { return dither::noise_in(kind, run, j); }));
+        }
+      } else {
+#pragma unroll
+        for (uint32_t j = 0; j < G; j++)
+          put_raw<W>(w, j, meter::encode<W, kDither, kMeter>(m, e[j], [&] { return dither::noise_in(kind, run, j); }));
+      }
       swap_words<F, words>(w);
       uint4 *out = reinterpret_cast<uint4 *>(dst + first * B);
 #pragma unroll
@@ -91,16 +109,21 @@ __device__ __forceinline__ void vector_tile(const ConvertStream &s, const Dither
 
 // ---- sample by sample ----------------------------------------------------------------------------------------------
 // samples [tile0, tile0 + n) of the stream; sample k lies k * step elements into both buffers (dithered: step is 1)
-template <int F, bool kOut, bool kDither, bool kMeter>
+template <int F, bool kOut, bool kDither, bool kMeter, bool kGain>
 __device__ __forceinline__ void element_tile(const ConvertStream &s, const DitherStream *d, int kind, uint64_t tile0,
-                                             uint32_t n, meter::Lane &m) {
+                                             uint32_t n, meter::Lane &m, const gain::Tile &gt) {
   constexpr uint32_t B = sample_bytes(F);
   const char *src = static_cast<const char *>(s.src);
   char *dst = static_cast<char *>(s.dst);
+  const gain::Split sp = kGain ? gain::split_of(gt, tile0) : gain::Split{};
   for (uint32_t i = threadIdx.x; i < n; i += kLanes) {
     const uint64_t at = kDither ? tile0 + i : (tile0 + i) * s.step;
     if (!kOut)
       *reinterpret_cast<float *>(dst + at * sizeof(float)) = to_internal<F>(load_raw<F>(src + at * B));
+    else if constexpr (kGain)
+      store_raw<F>(dst + at * B,
+                   gain::encode<F>(gt, m, *reinterpret_cast<const float *>(src + at * sizeof(float)), gain::frame_of(gt, sp, i),
+                                   [&] { return dither::noise(kind, d->seed, d->first + at); }));
     else
       store_raw<F>(dst + at * B,
                    meter::encode<F, kDither, kMeter>(m, *reinterpret_cast<const float *>(src + at * sizeof(float)),
@@ -110,19 +133,27 @@ __device__ __forceinline__ void element_tile(const ConvertStream &s, const Dithe
 
 // The tile blockIdx.x of one stream: the vector path for whole tiles with storage and image 16-byte aligned and step 1,
 // the element path for everything else.  s, d and kind are wave-uniform (kernel arguments selected by blockIdx.y).
-// kMeter: the workgroup's totals go into *cell (wave-uniform too) behind its tile.
-template <int F, bool kOut, bool kDither, bool kMeter = false>
-__device__ __forceinline__ void stream_tile(const ConvertStream &s, const DitherStream *d, int kind, MeterCell *cell = nullptr) {
+// kMeter: the workgroup's totals go into *cell (wave-uniform too) behind its tile.  kGain: the gained body, the stream's
+// gain in *g; dither and meter are then taken at run time -- kind NONE: d = 0, a NULL cell: nothing committed.
+template <int F, bool kOut, bool kDither, bool kMeter = false, bool kGain = false>
+__device__ __forceinline__ void stream_tile(const ConvertStream &s, const DitherStream *d, int kind, MeterCell *cell = nullptr,
+                                            const GainStream *g = nullptr) {
   const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kTile;
   if (s.src == nullptr || tile0 >= s.n) return;  // (nothing to convert, or a shorter stream of the launch)
   const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(kTile), s.n - tile0));
   const bool aligned = ((reinterpret_cast<uintptr_t>(s.src) | reinterpret_cast<uintptr_t>(s.dst)) & 15u) == 0;
   meter::Lane m;
-  if (n == kTile && aligned && (kDither || s.step == 1))
-    vector_tile<F, kOut, kDither, kMeter>(s, d, kind, tile0, m);
+  const gain::Tile gt = kGain ? gain::tile_of(*g, cell == nullptr && kind == SPEEXHIP_DITHER_NONE) : gain::Tile{};
+  if (n == kTile && aligned && (kDither || kGain || s.step == 1))
+    vector_tile<F, kOut, kDither, kMeter, kGain>(s, d, kind, tile0, m, gt);
   else
-    element_tile<F, kOut, kDither, kMeter>(s, d, kind, tile0, n, m);
-  if constexpr (kMeter) meter::commit(m, cell);  // (every lane of the workgroup: the early return above is the workgroup's)
+    element_tile<F, kOut, kDither, kMeter, kGain>(s, d, kind, tile0, n, m, gt);
+  // (every lane of the workgroup: the early return above is the workgroup's, and so is the cell)
+  if constexpr (kGain) {
+    if (cell != nullptr) meter::commit(m, cell);
+  } else if constexpr (kMeter) {
+    meter::commit(m, cell);
+  }
 }
 
 }  // namespace convert_impl

@@ -17,6 +17,10 @@
 // holds a cell pointer per stream; a stream whose pointer is not NULL leaves through the metered body of its format --
 // stream_tile<F, true, dithered_fmt(F), true>, the statements of convert_out_meter<F> -- every other stream exactly as in
 // convert_many_out, which is launched as ever when no state of the group has the meter on.
+//
+// convert_many_out_gain: the output pass of a group with a gained state in it (gain.h).  A fourth argument (GainPack)
+// holds every stream's gain; a stream whose gain is off (channels 0) is not multiplied and leaves with the bytes of
+// convert_many_out / _meter.
 #include <hip/hip_runtime.h>
 
 #include "../../include/speexhip_resampler.h"
@@ -36,27 +40,34 @@ using namespace convert_impl;
 
 // kMeter (kOut only): the launch of a group with a metered state in it -- a stream with a cell leaves through the metered
 // body of its format (meter.h: the dithered one at the stream's kind, NONE included, or the plain one of a float format)
-template <bool kOut, bool kMeter>
-__device__ __forceinline__ void many_tile(const ConvertPack &pack, const DitherPack *dith, const MeterPack *meter) {
+// kGain (kOut and kMeter only): the launch of a group with a gained state in it -- every stream leaves through the gained
+// body of its format (gain.h), which takes the stream's gain (or none), its kind and its cell (or none) at run time
+template <bool kOut, bool kMeter, bool kGain = false>
+__device__ __forceinline__ void many_tile(const ConvertPack &pack, const DitherPack *dith, const MeterPack *meter,
+                                          const GainPack *gain = nullptr) {
   const ConvertStream &s = pack.s[blockIdx.y];
   MeterCell *const cell = kMeter ? meter->cell[blockIdx.y] : nullptr;
   const int fmt = static_cast<int>(s.reserved & 0xffu), kind = static_cast<int>((s.reserved >> 8) & 0xffu);
   switch (fmt) {
 #define SPEEXHIP_MANY_CASE(F)                                                  \
   case F:                                                                      \
-    if constexpr (kMeter) {                                                    \
-      if (cell != nullptr) {                                                   \
-        stream_tile<F, true, dithered_fmt(F), true>(s, &dith->s[blockIdx.y], kind, cell); \
-        break;                                                                 \
+    if constexpr (kGain) {                                                     \
+      stream_tile<F, true, dithered_fmt(F), true, true>(s, &dith->s[blockIdx.y], kind, cell, &gain->s[blockIdx.y]); \
+    } else {                                                                   \
+      if constexpr (kMeter) {                                                  \
+        if (cell != nullptr) {                                                 \
+          stream_tile<F, true, dithered_fmt(F), true>(s, &dith->s[blockIdx.y], kind, cell); \
+          break;                                                               \
+        }                                                                      \
       }                                                                        \
-    }                                                                          \
-    if constexpr (kOut && dithered_fmt(F)) {                                   \
-      if (kind != SPEEXHIP_DITHER_NONE) {                                      \
-        stream_tile<F, true, true>(s, &dith->s[blockIdx.y], kind);             \
-        break;                                                                 \
+      if constexpr (kOut && dithered_fmt(F)) {                                 \
+        if (kind != SPEEXHIP_DITHER_NONE) {                                    \
+          stream_tile<F, true, true>(s, &dith->s[blockIdx.y], kind);           \
+          break;                                                               \
+        }                                                                      \
       }                                                                        \
+      stream_tile<F, kOut, false>(s, nullptr, 0);                              \
     }                                                                          \
-    stream_tile<F, kOut, false>(s, nullptr, 0);                                \
     break
     SPEEXHIP_MANY_CASE(SPEEXHIP_FMT_U8);
     SPEEXHIP_MANY_CASE(SPEEXHIP_FMT_S16);
@@ -82,13 +93,19 @@ __global__ __launch_bounds__(kLanes) void convert_many_out(const ConvertPack pac
 __global__ __launch_bounds__(kLanes) void convert_many_out_meter(const ConvertPack pack, const DitherPack dith, const MeterPack meter) {
   many_tile<true, true>(pack, &dith, &meter);
 }
+__global__ __launch_bounds__(kLanes) void convert_many_out_gain(const ConvertPack pack, const DitherPack dith, const MeterPack meter,
+                                                                const GainPack gain) {
+  many_tile<true, true, true>(pack, &dith, &meter, &gain);
+}
 
 }  // namespace
 
 hipError_t launch_convert_many(bool out, const ConvertPack &pack, const DitherPack &dith, uint32_t n, uint64_t most,
-                               hipStream_t stream, const MeterPack *meter) {
+                               hipStream_t stream, const MeterPack *meter, const GainPack *gain) {
   if (n == 0 || most == 0) return hipSuccess;
-  if (n > kMaxPackedStreams || (meter != nullptr && !out)) return hipErrorInvalidValue;
+  if (n > kMaxPackedStreams || ((meter != nullptr || gain != nullptr) && !out)) return hipErrorInvalidValue;
+  for (uint32_t j = 0; gain != nullptr && j < n; j++)
+    if (gain->s[j].channels > 0x7fffffffu) return hipErrorInvalidValue;
   for (uint32_t j = 0; j < n; j++) {
     const ConvertStream &s = pack.s[j];
     if (s.src == nullptr || s.n == 0) continue;
@@ -98,7 +115,10 @@ hipError_t launch_convert_many(bool out, const ConvertPack &pack, const DitherPa
     if (kind != SPEEXHIP_DITHER_NONE && (!out || !dithered_fmt(fmt) || !dither::known_kind(kind))) return hipErrorInvalidValue;
   }
   const dim3 grid(static_cast<uint32_t>((most + kTile - 1) / kTile), n), block(kLanes);
-  if (meter != nullptr)
+  const MeterPack no_cells = {};
+  if (gain != nullptr)
+    hipLaunchKernelGGL(convert_many_out_gain, grid, block, 0, stream, pack, dith, meter != nullptr ? *meter : no_cells, *gain);
+  else if (meter != nullptr)
     hipLaunchKernelGGL(convert_many_out_meter, grid, block, 0, stream, pack, dith, *meter);
   else if (out)
     hipLaunchKernelGGL(convert_many_out, grid, block, 0, stream, pack, dith);

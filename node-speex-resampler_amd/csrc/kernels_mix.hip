@@ -38,6 +38,10 @@
 // before the dither -- the dithered body for the formats of dithered_fmt (kind NONE: d = 0), the plain one for the float
 // formats; the streams' cells travel in a third kernel argument.
 //
+// mix_out_gain<F> (every format; a state with a stream's gain on): one instance per format.  The outputs of a frame are
+// multiplied by the frame's g (gain.h) behind the matrix's rounding to fp32, then judged and dithered as the stream asks,
+// both at run time.  The pass walks frames: the ramp's index is tile0 + f, no division anywhere.
+//
 // The image mix_in writes is read by the very next kernel and mix_out's source was written by the previous one: plain
 // loads and stores throughout, so that the images can stay in L2 / Infinity Cache.
 #include <hip/hip_runtime.h>
@@ -45,6 +49,7 @@
 #include "../../include/speexhip_resampler.h"
 #include "dither.h"
 #include "format_device.h"
+#include "gain.h"
 #include "kernels.h"
 #include "meter.h"
 
@@ -123,10 +128,12 @@ __device__ __forceinline__ void tile_path(const MixPack &pack, const MixStream &
 
 // ---- frame by frame --------------------------------------------------------------------------------------------------
 // frames [tile0, tile0 + n) of the stream; kDither (kOut only): the dithered instances; d and kind are theirs alone;
-// kMeter (kOut only): the metered instances, m (meter.h) is theirs alone
-template <int F, bool kOut, bool kDither, bool kMeter>
+// kMeter (kOut only): the metered instances, m (meter.h) is theirs alone; kGain (kOut, kMeter and kDither =
+// dithered_fmt(F) only): the gained instances, gt (gain.h) is theirs alone -- the frame's g, behind the matrix's rounding
+template <int F, bool kOut, bool kDither, bool kMeter, bool kGain>
 __device__ __forceinline__ void element_path(const MixPack &pack, const MixStream &s, const DitherStream *d, int kind,
-                                             uint64_t tile0, uint32_t n, uint32_t ns, uint32_t nd, meter::Lane &m) {
+                                             uint64_t tile0, uint32_t n, uint32_t ns, uint32_t nd, meter::Lane &m,
+                                             const gain::Tile &gt) {
   constexpr uint32_t B = sample_bytes(F);
   for (uint32_t f = threadIdx.x; f < n; f += kLanes) {
     const uint64_t frame = tile0 + f;
@@ -143,14 +150,18 @@ __device__ __forceinline__ void element_path(const MixPack &pack, const MixStrea
       mix_frame(
           pack, ns, nd, [&](uint32_t i) { return src[i]; },
           [&](uint32_t o, float y) {
-            store_raw<F>(dst + o * B, meter::encode<F, kDither, kMeter>(m, y, [&] { return dither::noise_in(kind, run, o); }));
+            if constexpr (kGain)
+              store_raw<F>(dst + o * B, gain::encode<F>(gt, m, y, frame, [&] { return dither::noise_in(kind, run, o); }));
+            else
+              store_raw<F>(dst + o * B, meter::encode<F, kDither, kMeter>(m, y, [&] { return dither::noise_in(kind, run, o); }));
           });
     }
   }
 }
 
-template <int F, bool kOut, bool kDither, bool kMeter = false>
-__device__ __forceinline__ void mix_tile(const MixPack &pack, const DitherPack *dith, uint32_t *lds, const MeterPack *meter = nullptr) {
+template <int F, bool kOut, bool kDither, bool kMeter = false, bool kGain = false>
+__device__ __forceinline__ void mix_tile(const MixPack &pack, const DitherPack *dith, uint32_t *lds, const MeterPack *meter = nullptr,
+                                         const GainPack *gain = nullptr) {
   const MixStream &s = pack.s[blockIdx.y];
   const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kTileFrames;
   if (s.src == nullptr || tile0 >= s.frames) return;  // (nothing to mix, or a shorter stream of the launch)
@@ -160,11 +171,19 @@ __device__ __forceinline__ void mix_tile(const MixPack &pack, const DitherPack *
   const int kind = kDither ? dith->kind : 0;
   const bool aligned = ((reinterpret_cast<uintptr_t>(s.src) | reinterpret_cast<uintptr_t>(s.dst)) & 15u) == 0;
   meter::Lane m;
+  MeterCell *const cell = kGain ? meter->cell[blockIdx.y] : nullptr;
+  // (kGain: dither and meter at run time -- kind NONE: d = 0, no cell: nothing judged or committed)
+  const gain::Tile gt = kGain ? gain::tile_of(gain->s[blockIdx.y], cell == nullptr && kind == SPEEXHIP_DITHER_NONE) : gain::Tile{};
   if (!kOut && n == kTileFrames && aligned)
     tile_path<F>(pack, s, tile0, ns, nd, ns * sample_bytes(F), nd * 4u, lds);
   else
-    element_path<F, kOut, kDither, kMeter>(pack, s, d, kind, tile0, n, ns, nd, m);
-  if constexpr (kMeter) meter::commit(m, meter->cell[blockIdx.y]);  // (every lane: the early return above is the workgroup's)
+    element_path<F, kOut, kDither, kMeter, kGain>(pack, s, d, kind, tile0, n, ns, nd, m, gt);
+  // (every lane: the early return above is the workgroup's, and so is the cell)
+  if constexpr (kGain) {
+    if (cell != nullptr) meter::commit(m, cell);
+  } else if constexpr (kMeter) {
+    meter::commit(m, meter->cell[blockIdx.y]);
+  }
 }
 
 template <int F>
@@ -187,14 +206,21 @@ template <int F>
 __global__ __launch_bounds__(kLanes) void mix_out_meter(const MixPack pack, const DitherPack dith, const MeterPack meter) {
   mix_tile<F, true, dithered_fmt(F), true>(pack, &dith, nullptr, &meter);
 }
+// the gained instance of a format (gain.h): every output of a frame times the frame's g, then the metered body with
+// dither and meter taken at run time
+template <int F>
+__global__ __launch_bounds__(kLanes) void mix_out_gain(const MixPack pack, const DitherPack dith, const MeterPack meter,
+                                                       const GainPack gain) {
+  mix_tile<F, true, dithered_fmt(F), true, true>(pack, &dith, nullptr, &meter, &gain);
+}
 
 }  // namespace
 
 hipError_t launch_mix(int fmt, bool out, const MixPack &pack, const DitherPack *dith, uint32_t n, uint32_t most,
-                      hipStream_t stream, const MeterPack *meter) {
+                      hipStream_t stream, const MeterPack *meter, const GainPack *gain) {
   if (n == 0 || most == 0) return hipSuccess;
   if (pack.src_channels == 0 || pack.src_channels > kMixMaxChannels || pack.dst_channels == 0 ||
-      pack.dst_channels > kMixMaxChannels || ((dith != nullptr || meter != nullptr) && !out))
+      pack.dst_channels > kMixMaxChannels || ((dith != nullptr || meter != nullptr || gain != nullptr) && !out))
     return hipErrorInvalidValue;
   for (uint32_t j = 0; meter != nullptr && j < n; j++)
     if (meter->cell[j] == nullptr) return hipErrorInvalidValue;
@@ -204,7 +230,13 @@ hipError_t launch_mix(int fmt, bool out, const MixPack &pack, const DitherPack *
   const dim3 grid((most + kTileFrames - 1) / kTileFrames, n), block(kLanes);
   return with_format(fmt, [&](auto format) -> hipError_t {
     constexpr int F = decltype(format)::value;
-    if (meter != nullptr) {
+    if (gain != nullptr) {
+      if (dith != nullptr && !dithered_fmt(F)) return hipErrorInvalidValue;
+      const DitherPack none = {};    // (kind NONE)
+      const MeterPack no_cells = {};  // (nothing judged)
+      hipLaunchKernelGGL((mix_out_gain<F>), grid, block, 0, stream, pack, dith != nullptr ? *dith : none,
+                         meter != nullptr ? *meter : no_cells, *gain);
+    } else if (meter != nullptr) {
       if (dith != nullptr && !dithered_fmt(F)) return hipErrorInvalidValue;
       DitherPack none = {};  // (kind NONE)
       hipLaunchKernelGGL((mix_out_meter<F>), grid, block, 0, stream, pack, dith != nullptr ? *dith : none, *meter);

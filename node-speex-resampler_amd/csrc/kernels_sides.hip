@@ -35,6 +35,10 @@
 // the dithered body for the formats of dithered_fmt (kind NONE: d = 0), the plain one for the float formats.  The samples
 // and their d are the interleaved pass's, so the totals are too.
 //
+// planes_out_gain<F> (every format; a state with a stream's gain on): one instance per format, on both paths.  The
+// outputs of a frame are multiplied by the frame's g (gain.h) behind the matrix's rounding, then judged and dithered as
+// the stream asks, both at run time.  The pass walks frames: no division.
+//
 // The image planes_in writes is read by the very next kernel and planes_out's source was written by the previous one:
 // plain loads and stores throughout, so that the images can stay in L2 / Infinity Cache.
 #include <hip/hip_runtime.h>
@@ -42,6 +46,7 @@
 #include "../../include/speexhip_resampler.h"
 #include "dither.h"
 #include "format_device.h"
+#include "gain.h"
 #include "kernels.h"
 #include "meter.h"
 
@@ -135,10 +140,11 @@ __device__ __forceinline__ void vector_in(const PlanePack &pack, const PlaneStre
 }
 
 // ... image -> planes; kDither: the dithered instances, d and kind are theirs alone; kMeter: the metered instances, m
-// (meter.h) is theirs alone
-template <int F, bool kDither, bool kMeter>
+// (meter.h) is theirs alone; kGain (kMeter and kDither = dithered_fmt(F) only): the gained instances, gt (gain.h) is
+// theirs alone -- the frame's g, behind the matrix's rounding
+template <int F, bool kDither, bool kMeter, bool kGain>
 __device__ __forceinline__ void vector_out(const PlanePack &pack, const PlaneStream &s, const DitherStream *d, int kind,
-                                           uint64_t tile0, uint32_t *lds, meter::Lane &m) {
+                                           uint64_t tile0, uint32_t *lds, meter::Lane &m, const gain::Tile &gt) {
   constexpr uint32_t B = sample_bytes(F), G = group_of(F), words = G * B / 4, pieces = kTile / G;
   constexpr int W = word_format(F);
   const uint32_t sc = pack.storage_channels, ic = pack.image_channels;
@@ -166,7 +172,10 @@ __device__ __forceinline__ void vector_out(const PlanePack &pack, const PlaneStr
 #pragma unroll
     for (uint32_t j = 0; j < G; j++) {
       const float y = __uint_as_float(lds[pad_dword((f0 + j) * sc + c)]);
-      put_raw<W>(w, j, meter::encode<W, kDither, kMeter>(m, y, [&] { return dither::noise(kind, d->seed, (d->first + tile0 + f0 + j) * sc + c); }));
+      if constexpr (kGain)
+        put_raw<W>(w, j, gain::encode<W>(gt, m, y, tile0 + f0 + j, [&] { return dither::noise(kind, d->seed, (d->first + tile0 + f0 + j) * sc + c); }));
+      else
+        put_raw<W>(w, j, meter::encode<W, kDither, kMeter>(m, y, [&] { return dither::noise(kind, d->seed, (d->first + tile0 + f0 + j) * sc + c); }));
     }
     swap_words<F, words>(w);
     uint4 *out = reinterpret_cast<uint4 *>(planes + (c * s.plane_stride + tile0 + f0) * B);
@@ -177,9 +186,9 @@ __device__ __forceinline__ void vector_out(const PlanePack &pack, const PlaneStr
 
 // ---- frame by frame --------------------------------------------------------------------------------------------------
 // frames [tile0, tile0 + n) of the stream
-template <int F, bool kOut, bool kDither, bool kMeter>
+template <int F, bool kOut, bool kDither, bool kMeter, bool kGain>
 __device__ __forceinline__ void element_path(const PlanePack &pack, const PlaneStream &s, const DitherStream *d, int kind,
-                                             uint64_t tile0, uint32_t n, meter::Lane &m) {
+                                             uint64_t tile0, uint32_t n, meter::Lane &m, const gain::Tile &gt) {
   constexpr uint32_t B = sample_bytes(F);
   const uint32_t sc = pack.storage_channels, ic = pack.image_channels;
   const uint64_t plane_bytes = s.plane_stride * B;
@@ -198,7 +207,10 @@ __device__ __forceinline__ void element_path(const PlanePack &pack, const PlaneS
       char *dst = static_cast<char *>(s.dst) + frame * B;
       const dither::Run run = kDither ? dither::run_of(d->seed, (d->first + frame) * sc, sc) : dither::Run{};
       const auto put = [&](uint32_t o, float y) {
-        store_raw<F>(dst + o * plane_bytes, meter::encode<F, kDither, kMeter>(m, y, [&] { return dither::noise_in(kind, run, o); }));
+        if constexpr (kGain)
+          store_raw<F>(dst + o * plane_bytes, gain::encode<F>(gt, m, y, frame, [&] { return dither::noise_in(kind, run, o); }));
+        else
+          store_raw<F>(dst + o * plane_bytes, meter::encode<F, kDither, kMeter>(m, y, [&] { return dither::noise_in(kind, run, o); }));
       };
       if (pack.mixed == 0)
         for (uint32_t c = 0; c < sc; c++) put(c, src[c]);
@@ -208,8 +220,9 @@ __device__ __forceinline__ void element_path(const PlanePack &pack, const PlaneS
   }
 }
 
-template <int F, bool kOut, bool kDither, bool kMeter = false>
-__device__ __forceinline__ void planes_tile(const PlanePack &pack, const DitherPack *dith, uint32_t *lds, const MeterPack *meter = nullptr) {
+template <int F, bool kOut, bool kDither, bool kMeter = false, bool kGain = false>
+__device__ __forceinline__ void planes_tile(const PlanePack &pack, const DitherPack *dith, uint32_t *lds, const MeterPack *meter = nullptr,
+                                            const GainPack *gain = nullptr) {
   const PlaneStream &s = pack.s[blockIdx.y];
   const uint64_t tile0 = static_cast<uint64_t>(blockIdx.x) * kTile;
   if (s.src == nullptr || tile0 >= s.frames) return;  // (nothing to move, or a shorter stream of the launch)
@@ -221,15 +234,23 @@ __device__ __forceinline__ void planes_tile(const PlanePack &pack, const DitherP
   const bool tiled = pack.storage_channels <= kMixMaxChannels && pack.image_channels <= kMixMaxChannels &&
                      pack.image_pitch == pack.image_channels;
   meter::Lane m;
+  // (kGain: dither and meter at run time -- kind NONE: d = 0, no cell: nothing judged or committed)
+  MeterCell *const cell = kGain ? meter->cell[blockIdx.y] : nullptr;
+  const gain::Tile gt = kGain ? gain::tile_of(gain->s[blockIdx.y], cell == nullptr && kind == SPEEXHIP_DITHER_NONE) : gain::Tile{};
   if (n == kTile && aligned && tiled) {
     if (kOut)
-      vector_out<F, kDither, kMeter>(pack, s, d, kind, tile0, lds, m);
+      vector_out<F, kDither, kMeter, kGain>(pack, s, d, kind, tile0, lds, m, gt);
     else
       vector_in<F>(pack, s, tile0, lds);
   } else {
-    element_path<F, kOut, kDither, kMeter>(pack, s, d, kind, tile0, n, m);
+    element_path<F, kOut, kDither, kMeter, kGain>(pack, s, d, kind, tile0, n, m, gt);
   }
-  if constexpr (kMeter) meter::commit(m, meter->cell[blockIdx.y]);  // (every lane: the early return above is the workgroup's)
+  // (every lane: the early return above is the workgroup's, and so is the cell)
+  if constexpr (kGain) {
+    if (cell != nullptr) meter::commit(m, cell);
+  } else if constexpr (kMeter) {
+    meter::commit(m, meter->cell[blockIdx.y]);
+  }
 }
 
 template <int F>
@@ -254,14 +275,22 @@ __global__ __launch_bounds__(kLanes) void planes_out_meter(const PlanePack pack,
   extern __shared__ uint32_t sides_lds[];
   planes_tile<F, true, dithered_fmt(F), true>(pack, &dith, sides_lds, &meter);
 }
+// the gained instance of a format (gain.h): every output of a frame times the frame's g, then the metered body with
+// dither and meter taken at run time
+template <int F>
+__global__ __launch_bounds__(kLanes) void planes_out_gain(const PlanePack pack, const DitherPack dith, const MeterPack meter,
+                                                          const GainPack gain) {
+  extern __shared__ uint32_t sides_lds[];
+  planes_tile<F, true, dithered_fmt(F), true, true>(pack, &dith, sides_lds, &meter, &gain);
+}
 
 }  // namespace
 
 hipError_t launch_planes(int fmt, bool out, const PlanePack &pack, const DitherPack *dith, uint32_t n, uint32_t most,
-                         hipStream_t stream, const MeterPack *meter) {
+                         hipStream_t stream, const MeterPack *meter, const GainPack *gain) {
   if (n == 0 || most == 0) return hipSuccess;
   const uint32_t sc = pack.storage_channels, ic = pack.image_channels;
-  if (sc == 0 || ic == 0 || pack.image_pitch < ic || ((dith != nullptr || meter != nullptr) && !out)) return hipErrorInvalidValue;
+  if (sc == 0 || ic == 0 || pack.image_pitch < ic || ((dith != nullptr || meter != nullptr || gain != nullptr) && !out)) return hipErrorInvalidValue;
   for (uint32_t j = 0; meter != nullptr && j < n; j++)
     if (meter->cell[j] == nullptr) return hipErrorInvalidValue;
   if (pack.mixed != 0 ? (sc > kMixMaxChannels || ic > kMixMaxChannels) : sc != ic) return hipErrorInvalidValue;
@@ -270,7 +299,13 @@ hipError_t launch_planes(int fmt, bool out, const PlanePack &pack, const DitherP
   const dim3 grid((most + kTile - 1) / kTile, n), block(kLanes);
   return with_format(fmt, [&](auto format) -> hipError_t {
     constexpr int F = decltype(format)::value;
-    if (meter != nullptr) {
+    if (gain != nullptr) {
+      if (dith != nullptr && !dithered_fmt(F)) return hipErrorInvalidValue;
+      const DitherPack none = {};    // (kind NONE)
+      const MeterPack no_cells = {};  // (nothing judged)
+      hipLaunchKernelGGL((planes_out_gain<F>), grid, block, lds, stream, pack, dith != nullptr ? *dith : none,
+                         meter != nullptr ? *meter : no_cells, *gain);
+    } else if (meter != nullptr) {
       if (dith != nullptr && !dithered_fmt(F)) return hipErrorInvalidValue;
       DitherPack none = {};  // (kind NONE)
       hipLaunchKernelGGL((planes_out_meter<F>), grid, block, lds, stream, pack, dith != nullptr ? *dith : none, *meter);

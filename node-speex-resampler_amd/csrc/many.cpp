@@ -231,6 +231,8 @@ void Batch::ManyUnit::commit_item(Item &it, bool work) {
   if (it.e->sides && it.b->dither_on()) it.b->dither_advance(&out_len[it.i]);
   // (... and of a state with the meter on is metered: its output pass has judged these frames into the state's cell)
   if (it.e->sides && it.b->meter_on_) it.b->meter_count(&out_len[it.i], it.b->channels_);
+  // (... and of a state with gain on has left at its g: the ramp moves by the frames produced)
+  if (it.e->sides && it.b->gain_on()) it.b->gain_advance(&out_len[it.i]);
   rcs[it.i] = SPEEXHIP_ERR_SUCCESS;
 }
 
@@ -247,6 +249,16 @@ int Batch::ManyUnit::launch_group(const std::vector<uint32_t> &g, hipStream_t st
   MeterPack cells;  // (beside the dither seeds: the cell of each entry whose state has the meter on)
   bool metered = false;
   std::memset(&cells, 0, sizeof(cells));
+  // The gain of each entry whose state has it on: gains rides beside the dither seeds into the output pass; an entry
+  // whose result no pass writes (F32 storage IS the FIR's image) is multiplied in place by one gain_image over the group.
+  // Either way the entry stays in its group.
+  GainPack gains, image_gains;
+  ConvertPack in_place;
+  bool gained = false;
+  uint64_t most_in_place = 0;
+  std::memset(&gains, 0, sizeof(gains));
+  std::memset(&image_gains, 0, sizeof(image_gains));
+  std::memset(&in_place, 0, sizeof(in_place));
   uint64_t most_to = 0, most_from = 0;
   std::memset(&to_image, 0, sizeof(to_image));
   std::memset(&from_image, 0, sizeof(from_image));
@@ -280,7 +292,15 @@ int Batch::ManyUnit::launch_group(const std::vector<uint32_t> &g, hipStream_t st
       c.reserved = convert_many_tag(it.e->out_fmt, dithered ? b->dither_kind_ : SPEEXHIP_DITHER_NONE);
       if (dithered) dith.s[j] = b->dither_pack(0, 1, b->channels_).s[0];
       if (b->meter_on_) cells.cell[j] = b->d_meter_, metered = true;
+      if (it.e->sides && b->gain_on()) gains.s[j] = b->gain_pack(0, 1, b->channels_).s[0], gained = true;
       most_from = std::max(most_from, c.n);
+    } else if (it.e->sides && it.float_io && b->gain_on() && it.plan.produced != 0) {
+      ConvertStream &c = in_place.s[j];
+      c.dst = storage_out;
+      c.n = static_cast<uint64_t>(it.plan.produced) * b->channels_;
+      c.step = 1;
+      image_gains.s[j] = b->gain_pack(0, 1, b->channels_).s[0];
+      most_in_place = std::max(most_in_place, c.n);
     }
     max_out = std::max(max_out, it.plan.produced);
   }
@@ -292,7 +312,14 @@ int Batch::ManyUnit::launch_group(const std::vector<uint32_t> &g, hipStream_t st
   if (lrc != SPEEXHIP_ERR_SUCCESS) return lrc;
   count_many(0);
   if (most_from != 0) {
-    if (hip_failed(launch_convert_many(true, from_image, dith, cnt, most_from, stream, metered ? &cells : nullptr), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+    if (hip_failed(launch_convert_many(true, from_image, dith, cnt, most_from, stream, metered ? &cells : nullptr, gained ? &gains : nullptr),
+                   "kernel launch"))
+      return SPEEXHIP_ERR_DEVICE;
+    count_many(2);
+  }
+  if (most_in_place != 0) {
+    // (a metered F32 result is no entry of a group -- process_host_many_sides -- so nothing is judged here)
+    if (hip_failed(launch_gain_image(in_place, image_gains, nullptr, 1.0f, cnt, most_in_place, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
     count_many(2);
   }
   // A state moves as ONE step, the moment its launch is queued: the history ping-pong, the position and the counters

@@ -26,6 +26,11 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
   // the stream's cell.  (Channels that stand apart are no stream of samples to judge: the callers have refused them.)
   const bool metered = !to_image && meter_on_;
   if (metered && apart != nullptr) return SPEEXHIP_ERR_BAD_STATE;
+  // With a stream's gain on (set_gain) every format leaves through the gained instance of its pass, each stream at its own
+  // g from its own frame index on; dither and meter ride along in the same instance.  (Channels that stand apart have no
+  // output frame to index: the callers have refused them.)
+  const bool gained = !to_image && gain_on();
+  if (gained && apart != nullptr) return SPEEXHIP_ERR_BAD_STATE;
   const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
   for (uint32_t first = 0; first < items; first += kChunk) {
     const uint32_t n = std::min(kChunk, items - first);
@@ -34,6 +39,9 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
     MeterPack cells;
     if (metered) cells = meter_pack(first, n);
     const MeterPack *meter = metered ? &cells : nullptr;
+    GainPack gains;  // (the flat converting pass walks samples: it divides by channels(); the others walk frames)
+    if (gained) gains = gain_pack(first, n, side.layout != SPEEXHIP_LAYOUT_PLANAR && side.mix == nullptr ? channels_ : 1);
+    const GainPack *gain = gained ? &gains : nullptr;
     // item first + j is entry j of the launch's pack: where it reads, where it writes, its frames
     const auto place = [&](uint32_t j, const void **src, void **dst) {
       const uint32_t item = first + j;
@@ -65,7 +73,7 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
         most = std::max(most, pack.s[j].frames);
       }
       if (dithered) dith = dither_pack(first, n, 1);
-      e = launch_planes(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream, meter);
+      e = launch_planes(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream, meter, gain);
     } else if (side.mix != nullptr) {
       MixPack pack;
       std::memset(&pack, 0, sizeof(pack));
@@ -77,7 +85,7 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
         pack.s[j].frames = place(j, &pack.s[j].src, &pack.s[j].dst);
         most = std::max(most, pack.s[j].frames);
       }
-      e = launch_mix(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream, meter);
+      e = launch_mix(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream, meter, gain);
     } else {
       ConvertPack pack;
       std::memset(&pack, 0, sizeof(pack));
@@ -89,7 +97,7 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
         pack.s[j].step = apart != nullptr ? channels_ : 1;
         most = std::max(most, pack.s[j].n);
       }
-      e = launch_convert(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream, meter);
+      e = launch_convert(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream, meter, gain);
     }
     if (hip_failed(e, "kernel launch")) return SPEEXHIP_ERR_DEVICE;
   }

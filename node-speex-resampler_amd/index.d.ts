@@ -24,6 +24,8 @@ export type SampleFormat = 'u8' | 's16le' | 's24le' | 's32le' | 'f32le' | 'f32le
 export type DitherKind = 'none' | 'rectangular' | 'triangular';
 /** what getMeter reports: samples judged, samples clipped at either rail, NaN samples, the largest |value| in int16 units */
 export interface MeterTotals { on: boolean, samples: bigint, clippedHigh: bigint, clippedLow: bigint, nan: bigint, peak: number }
+/** what getGain reports: the next output frame's gain, the ramp's target, its output frames still to come */
+export interface GainState { current: number, target: number, remaining: number }
 
 export interface SpeexResamplerTransformOptions {
     /**
@@ -70,6 +72,11 @@ export interface SpeexResamplerTransformOptions {
      * The stream then runs through the formatted calls (default 's16le' each side), which alone are metered.
      */
     meter?: boolean;
+    /**
+     * The output gain from the first chunk on (SpeexResampler.setGain): a number, or a gain reached over rampFrames output
+     * frames.  The stream then runs through the formatted calls (default 's16le' each side), which alone are gained.
+     */
+    gain?: number | { gain: number, rampFrames?: number };
 }
 
 /**
@@ -211,6 +218,14 @@ declare class SpeexResampler {
     setMeter(on: boolean): void;
     /** totals since the last reset; peak in int16 units (above 32768: beyond +-1.0).  reset: clear them behind the read */
     getMeter(options?: { reset?: boolean }): MeterTotals;
+    /**
+     * The output gain of processChunkFormat / processChunkMix / processChunkSides, their chunk-list, many-instance and
+     * asynchronous forms and flushFormat: `gain` from the next output frame on, reached linearly over rampFrames output
+     * frames (0: a step) from the gain that frame would have had.  Negative gains and 0 are legal; a gain that is not
+     * finite throws.  While the gain is on 's16le' -> 's16le' runs as processChunkFloat between the two conversions.
+     */
+    setGain(gain: number, rampFrames?: number): void;
+    getGain(): GainState;
     skipZeros(): void;
     resetMem(): void;
     /** filter delay in frames at the input rate / at the output rate */
@@ -240,6 +255,9 @@ export declare class SpeexResamplerTransform extends Transform {
     _alignementBuffer: Buffer;
     /** the stream's totals so far (option `meter`) */
     readonly meter: MeterTotals;
+    /** the stream's gain from the next chunk's first output frame on; needs the formatted calls (formats or the `gain` option) */
+    setGain(gain: number, rampFrames?: number): void;
+    getGain(): GainState;
 
     constructor(channels: any, inRate: any, outRate: any, quality?: number,
                 options?: SpeexResamplerTransformOptions);
@@ -282,6 +300,10 @@ export declare class SpeexResamplerBatch {
     setMeter(on: boolean): void;
     /** getMeter of stream k (default 0); reset clears that stream only */
     getMeter(stream?: number, options?: { reset?: boolean }): MeterTotals;
+    /** setGain of stream k, or of every stream when none is named */
+    setGain(gain: number, rampFrames?: number, stream?: number): void;
+    /** getGain of stream k (default 0) */
+    getGain(stream?: number): GainState;
     destroy(): void;
 }
 

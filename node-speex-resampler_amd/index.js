@@ -54,6 +54,12 @@ const globalModulePromise = new Promise((resolve, reject) => {
   return m.warmup().then(done, done);
 });
 
+// setGain's arguments, refused where they are given: a finite gain, a ramp of 0 .. 2^32 - 1 whole output frames
+function checkGain(gain, rampFrames) {
+  if (typeof gain !== 'number' || !Number.isFinite(gain)) throw new Error('gain must be a finite number');
+  if (!Number.isInteger(rampFrames) || rampFrames < 0 || rampFrames > 0xFFFFFFFF) throw new Error('rampFrames must be an integer in 0 .. 2^32 - 1');
+}
+
 class SpeexResampler {
   /**
    * Same four arguments as the reference class: channel count (>= 1), input and output sample
@@ -562,6 +568,29 @@ class SpeexResampler {
     return { on: v[0] !== 0, samples: big(1), clippedHigh: big(3), clippedLow: big(5), nan: big(7), peak: v[9] };
   }
 
+  /**
+   * The output gain of processChunkFormat, processChunkMix and processChunkSides (and their chunk-list, many-instance and
+   * asynchronous forms, flushFormat included): `gain` from the next output frame on, reached over rampFrames output frames
+   * from the gain that frame would have had, linearly -- a change without a click; rampFrames = 0 is a step.  Each sample
+   * is multiplied once, in float, before it is judged by the meter, dithered and encoded.  Negative gains (polarity) and 0
+   * (mute) are legal; a gain that is not finite throws.  A new target in mid-ramp starts from where the ramp stands.
+   * processChunk, processChunkFloat and the planar calls never apply it.  While the gain is not 1 (or a ramp is in flight)
+   * 's16le' -> 's16le' runs as processChunkFloat between the two conversions.  A stream's bytes do not depend on how it
+   * is cut into chunks.
+   */
+  setGain(gain, rampFrames = 0) {
+    this._refuseWhileAsyncPending('setGain');
+    checkGain(gain, rampFrames);
+    speexModule.setGain(this._ensureNative(), gain, rampFrames);
+  }
+
+  /** { current, target, remaining }: the next output frame's gain, the ramp's target, its output frames still to come */
+  getGain() {
+    this._refuseWhileAsyncPending('getGain');
+    const v = speexModule.getGain(this._ensureNative());
+    return { current: v[0], target: v[1], remaining: v[2] };
+  }
+
   /** Start half a filter in, so the stream does not begin with the filter's ramp-up. */
   skipZeros() {
     this._refuseWhileAsyncPending('skipZeros');
@@ -902,6 +931,15 @@ class SpeexResamplerBatch {
   /** getMeter of stream k: its own totals; { reset: true } clears that stream only */
   getMeter(stream = 0, options = undefined) { return this.streams[stream].getMeter(options); }
 
+  /** setGain of stream k, or of every stream when none is named */
+  setGain(gain, rampFrames = 0, stream = undefined) {
+    if (stream === undefined) for (const r of this.streams) r.setGain(gain, rampFrames);
+    else this.streams[stream].setGain(gain, rampFrames);
+  }
+
+  /** getGain of stream k */
+  getGain(stream = 0) { return this.streams[stream].getGain(); }
+
   destroy() { for (const r of this.streams) r.destroy(); }
 }
 /**
@@ -941,6 +979,10 @@ class SpeexResamplerTransform extends Transform {
    *   meter: true         -- the output meter (SpeexResampler.setMeter) on from the first chunk; the `meter` getter reads the
    *                         totals.  The stream then runs through the formatted calls (default 's16le' each side): only
    *                         they are metered.
+   *   gain: g | { gain, rampFrames }
+   *                       -- the output gain (SpeexResampler.setGain) from the first chunk on; setGain(gain, rampFrames) on
+   *                         the Transform changes it in mid-stream, from the next chunk's first output frame.  The stream
+   *                         then runs through the formatted calls (default 's16le' each side): only they are gained.
    */
   constructor(channels, inRate, outRate, quality = 7, options = undefined) {
     super();
@@ -962,6 +1004,12 @@ class SpeexResamplerTransform extends Transform {
     if (this._options.meter) {
       if (!this._formats) this._formats = ['s16le', 's16le'];
       this._meterPending = true;  // (switched on with the first call: the constructor works before initPromise)
+    }
+    if (this._options.gain !== undefined) {
+      const g = typeof this._options.gain === 'number' ? { gain: this._options.gain } : (this._options.gain || {});
+      checkGain(g.gain, g.rampFrames || 0);
+      if (!this._formats) this._formats = ['s16le', 's16le'];
+      this._gainPending = [g.gain, g.rampFrames || 0];  // (set with the first call: the constructor works before initPromise)
     }
     if (this._options.pipeline) {
       this._busy = false;       // a processChunksAsync call is in flight
@@ -1007,6 +1055,34 @@ class SpeexResamplerTransform extends Transform {
     }
   }
 
+  // the gain asked for -- by the option or by setGain -- takes hold with the next call, between two calls of the stream
+  _armGain() {
+    if (this._gainPending && !(this.resampler._inFlight > 0)) {
+      const [gain, rampFrames] = this._gainPending;
+      this._gainPending = null;
+      this.resampler.setGain(gain, rampFrames);
+    }
+  }
+
+  // what the options and setGain asked for, in force before the stream's next call
+  _arm() {
+    this._armMeter();
+    this._armGain();
+  }
+
+  /**
+   * The stream's output gain from the next chunk's first output frame on (SpeexResampler.setGain).  A Transform that named
+   * no formats and no `gain` option runs the reference's int16 calls, which are never gained: it throws.
+   */
+  setGain(gain, rampFrames = 0) {
+    checkGain(gain, rampFrames);
+    if (!this._formats) throw new Error('setGain needs a Transform of the formatted calls: name inFormat / outFormat or the gain option');
+    this._gainPending = [gain, rampFrames];
+  }
+
+  /** { current, target, remaining } of the stream (a gain asked for and not yet in force is not shown) */
+  getGain() { return this.resampler.getGain(); }
+
   // pipeline: send what is held as one asynchronous call; when it returns, push its results in order and go again
   _pump() {
     if (this._busy || this._held.length === 0) return;
@@ -1039,29 +1115,32 @@ class SpeexResamplerTransform extends Transform {
 
   // The calls of every mode: the stream's formats where it names them, else the reference's s16le calls as ever.
   _one(chunk) {
-    this._armMeter();
+    this._arm();
     return this._formats ? this.resampler.processChunkFormat(chunk, this._formats[0], this._formats[1]) : this.resampler.processChunk(chunk);
   }
 
   _oneAsync(chunk) {
-    this._armMeter();
+    this._arm();
     return this._formats ? this.resampler.processChunkFormatAsync(chunk, this._formats[0], this._formats[1])
       : this.resampler.processChunkAsync(chunk);
   }
 
   _many(chunks) {
-    this._armMeter();
+    this._arm();
     return this._formats ? this.resampler.processChunksFormat(chunks, this._formats[0], this._formats[1])
       : this.resampler.processChunks(chunks);
   }
 
   _manyAsync(chunks) {
-    this._armMeter();
+    this._arm();
     return this._formats ? this.resampler.processChunksFormatAsync(chunks, this._formats[0], this._formats[1])
       : this.resampler.processChunksAsync(chunks);
   }
 
-  _tail() { return this._formats ? this.resampler.flushFormat(this._formats[1]) : this.resampler.flush(); }
+  _tail() {
+    this._arm();
+    return this._formats ? this.resampler.flushFormat(this._formats[1]) : this.resampler.flush();
+  }
 
   // pinned: a copy of `chunk` in a pinned chunk of the library (a plain copy when none is to be had).  Chunks come from a
   // small free list by size class; one is free again once the call that read it has returned -- _recycle().

@@ -36,6 +36,14 @@ typedef struct {
   int meter_on; /* setMeter: while on, s16 -> s16 has the float call's counters (read and written under the lock) */
 } Handle;
 
+/* whether the state's output gain is on (speexhip_resampler_set_gain): s16 -> s16 then has the float call's counters */
+static int gain_is_on(SpeexHipResamplerState *st) {
+  float target = 1.0f;
+  uint32_t remaining = 0;
+  if (speexhip_resampler_get_gain(st, NULL, &target, &remaining) != 0) return 0;
+  return !(target == 1.0f && remaining == 0);
+}
+
 static void finalize_state(napi_env env, void *data, void *hint) {
   (void)env;
   (void)hint;
@@ -389,7 +397,7 @@ static napi_value ProcessFormat(napi_env env, napi_callback_info info) {
     return NULL;
   }
   /* (s16 -> s16 is the int16 call, with its counters; every other pair has the float call's) */
-  const int float_entry = h->meter_on || !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
+  const int float_entry = h->meter_on || gain_is_on(st) || !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
   uint32_t will_use = 0, will_make = 0;
   speexhip_resampler_peek(st, in_len, out_len, float_entry, &will_use, &will_make);
   napi_value out;
@@ -472,7 +480,7 @@ static napi_value ProcessMix(napi_env env, napi_callback_info info) {
     return NULL;
   }
   /* (without a matrix s16 -> s16 is the int16 call, with its counters; everything else has the float call's) */
-  const int float_entry = h->meter_on || in_mix != NULL || out_mix != NULL || !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
+  const int float_entry = h->meter_on || gain_is_on(st) || in_mix != NULL || out_mix != NULL || !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
   uint32_t will_use = 0, will_make = 0;
   speexhip_resampler_peek(st, in_len, out_len, float_entry, &will_use, &will_make);
   napi_value out;
@@ -597,7 +605,7 @@ static napi_value ProcessSides(napi_env env, napi_callback_info info) {
   /* (a side of one channel is the same bytes in either layout; with a planar side, as with a matrix, every pair has the
    *  float call's counters -- otherwise s16 -> s16 is the int16 call) */
   const int planar_side = (in_planar && in_channels > 1) || (out_planar && out_channels > 1);
-  const int float_entry = h->meter_on || planar_side || in_mix != NULL || out_mix != NULL || !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
+  const int float_entry = h->meter_on || gain_is_on(st) || planar_side || in_mix != NULL || out_mix != NULL || !(in_fmt == SPEEXHIP_FMT_S16 && out_fmt == SPEEXHIP_FMT_S16);
   uint32_t will_use = 0, will_make = 0;
   speexhip_resampler_peek(st, in_len, out_len, float_entry, &will_use, &will_make);
   napi_value result = NULL;
@@ -1261,6 +1269,51 @@ static napi_value GetMeter(napi_env env, napi_callback_info info) {
   return arr;
 }
 
+/* setGain(handle, gain, rampFrames) */
+static napi_value SetGain(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 3) {
+    napi_throw_type_error(env, NULL, "setGain(handle, gain, rampFrames)");
+    return NULL;
+  }
+  Handle *h = NULL;
+  SpeexHipResamplerState *st = lock_state(env, argv[0], &h);
+  if (st == NULL) return NULL;
+  double gain = 1.0;
+  uint32_t ramp = 0;
+  NAPI_OK_LOCKED(h, napi_get_value_double(env, argv[1], &gain));
+  NAPI_OK_LOCKED(h, napi_get_value_uint32(env, argv[2], &ramp));
+  const int rc = speexhip_resampler_set_gain(st, (float)gain, ramp);
+  UNLOCK(h);
+  return control_result(env, rc);
+}
+
+/* getGain(handle) -> [current, target, remaining] */
+static napi_value GetGain(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  Handle *h = NULL;
+  SpeexHipResamplerState *st = lock_state(env, argv[0], &h);
+  if (st == NULL) return NULL;
+  float current = 1.0f, target = 1.0f;
+  uint32_t remaining = 0;
+  const int rc = speexhip_resampler_get_gain(st, &current, &target, &remaining);
+  UNLOCK(h);
+  if (rc != 0) return control_result(env, rc);
+  napi_value arr, v;
+  NAPI_OK(napi_create_array_with_length(env, 3, &arr));
+  NAPI_OK(napi_create_double(env, (double)current, &v));
+  NAPI_OK(napi_set_element(env, arr, 0, v));
+  NAPI_OK(napi_create_double(env, (double)target, &v));
+  NAPI_OK(napi_set_element(env, arr, 1, v));
+  NAPI_OK(napi_create_uint32(env, remaining, &v));
+  NAPI_OK(napi_set_element(env, arr, 2, v));
+  return arr;
+}
+
 static napi_value pair_u32(napi_env env, uint32_t a, uint32_t b) {
   napi_value arr, v;
   NAPI_OK(napi_create_array_with_length(env, 2, &arr));
@@ -1583,7 +1636,7 @@ static ManyJob *many_prepare(napi_env env, napi_callback_info info, napi_value *
         int kind = SPEEXHIP_DITHER_NONE;
         (void)speexhip_resampler_get_dither(st, &kind, NULL, NULL);
         float_entry = !(j->in_fmt[i] == SPEEXHIP_FMT_S16 && j->out_fmt[i] == SPEEXHIP_FMT_S16 && kind == SPEEXHIP_DITHER_NONE &&
-                        !j->h[i]->meter_on);
+                        !j->h[i]->meter_on && !gain_is_on(st));
         j->float_entry[i] = float_entry;
       }
       uint32_t will_use = 0;
@@ -1842,6 +1895,8 @@ NAPI_MODULE_INIT() {
       {"getDither", NULL, GetDither, NULL, NULL, NULL, napi_default, NULL},
       {"setMeter", NULL, SetMeter, NULL, NULL, NULL, napi_default, NULL},
       {"getMeter", NULL, GetMeter, NULL, NULL, NULL, napi_default, NULL},
+      {"setGain", NULL, SetGain, NULL, NULL, NULL, napi_default, NULL},
+      {"getGain", NULL, GetGain, NULL, NULL, NULL, napi_default, NULL},
       {"getLatency", NULL, GetLatency, NULL, NULL, NULL, napi_default, NULL},
       {"setMode", NULL, SetMode, NULL, NULL, NULL, napi_default, NULL},
       {"getInfo", NULL, GetInfo, NULL, NULL, NULL, napi_default, NULL},

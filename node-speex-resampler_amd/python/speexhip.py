@@ -122,6 +122,9 @@ EXPORTS = [
     # metering: clip counts and peak level of the formatted, mixed and sides calls' outputs
     "speexhip_resampler_set_meter", "speexhip_resampler_get_meter", "speexhip_batch_set_meter", "speexhip_batch_get_meter",
     "speexhip_debug_meter",
+    # gain: per-stream volume with click-free ramps in the formatted, mixed and sides calls
+    "speexhip_resampler_set_gain", "speexhip_resampler_get_gain", "speexhip_batch_set_gain", "speexhip_batch_get_gain",
+    "speexhip_debug_gain",
 ]
 
 
@@ -441,6 +444,18 @@ def lib():
             L.speexhip_batch_get_meter.argtypes = [p, u32, pm, i32]
             L.speexhip_debug_meter.restype = i32
             L.speexhip_debug_meter.argtypes = [i32, p, p, u32, pm]
+        if hasattr(L, "speexhip_resampler_set_gain") or "SPEEXHIP_LIB_PATH" not in os.environ:
+            pf = C.POINTER(C.c_float)
+            L.speexhip_resampler_set_gain.restype = i32
+            L.speexhip_resampler_set_gain.argtypes = [p, C.c_float, u32]
+            L.speexhip_resampler_get_gain.restype = i32
+            L.speexhip_resampler_get_gain.argtypes = [p, pf, pf, pu32]
+            L.speexhip_batch_set_gain.restype = i32
+            L.speexhip_batch_set_gain.argtypes = [p, u32, C.c_float, u32]
+            L.speexhip_batch_get_gain.restype = i32
+            L.speexhip_batch_get_gain.argtypes = [p, u32, pf, pf, pu32]
+            L.speexhip_debug_gain.restype = i32
+            L.speexhip_debug_gain.argtypes = [C.c_float, C.c_float, u32, C.c_uint64, u32, pf]
         _lib = L
     return _lib
 
@@ -502,6 +517,15 @@ def debug_dither(kind, seed, first_index, n):
     if rc:
         raise ValueError(strerror(rc))
     return d[:n]
+
+
+def debug_gain(from_gain, to_gain, total, first, n):
+    """host-only: the library's gains g(first) .. g(first + n - 1) (float32) of the ramp (from_gain, to_gain, total)"""
+    g = np.zeros(max(int(n), 1), np.float32)
+    rc = lib().speexhip_debug_gain(from_gain, to_gain, total, first, n, g.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc:
+        raise ValueError(strerror(rc))
+    return g[:n]
 
 
 def debug_meter(fmt, y, d=None):
@@ -1268,6 +1292,21 @@ class Resampler:
             raise RuntimeError(strerror(rc))
         return m.as_dict()
 
+    def set_gain(self, gain, ramp_frames=0):
+        """The output gain of the formatted, mixed and sides calls: `gain` from the next output frame on, reached over
+        ramp_frames output frames from the gain that frame would have had (0: a step).  Returns the C call's code
+        (INVALID_ARG for a gain that is not finite)."""
+        return lib().speexhip_resampler_set_gain(self._h, float(gain), int(ramp_frames))
+
+    def get_gain(self):
+        """{'current', 'target', 'remaining'}: the next output frame's gain (numpy float32), the ramp's target, its
+        frames still to come"""
+        cur, tgt, rem = C.c_float(), C.c_float(), C.c_uint32()
+        rc = lib().speexhip_resampler_get_gain(self._h, C.byref(cur), C.byref(tgt), C.byref(rem))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return {"current": np.float32(cur.value), "target": np.float32(tgt.value), "remaining": rem.value}
+
     def peek(self, in_frames, out_capacity, float_entry=False):
         """(consumed, produced) of the next call, state untouched"""
         c, p_ = C.c_uint32(), C.c_uint32()
@@ -1422,6 +1461,19 @@ class Batch:
         if rc:
             raise RuntimeError(strerror(rc))
         return m.as_dict()
+
+    def set_gain(self, gain, ramp_frames=0, stream=None):
+        """The output gain of one stream (None: of every stream) in the formatted, mixed and sides calls; see
+        Resampler.set_gain.  Returns the C call's code."""
+        return lib().speexhip_batch_set_gain(self._h, 0xFFFFFFFF if stream is None else int(stream), float(gain), int(ramp_frames))
+
+    def get_gain(self, stream):
+        """The stream's {'current', 'target', 'remaining'}"""
+        cur, tgt, rem = C.c_float(), C.c_float(), C.c_uint32()
+        rc = lib().speexhip_batch_get_gain(self._h, int(stream), C.byref(cur), C.byref(tgt), C.byref(rem))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return {"current": np.float32(cur.value), "target": np.float32(tgt.value), "remaining": rem.value}
 
     def lines(self, stream):
         """(taps-1+pending, channels) float32 of one stream: history then pending frames"""

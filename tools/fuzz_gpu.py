@@ -36,6 +36,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "node-speex-resampler_amd", "python"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle as orc  # noqa: E402
+import gain_model as gm  # noqa: E402  (tests/: the numpy statement of the output gain)
 import sample_formats as sf  # noqa: E402  (tests/: the numpy statement of the sample formats)
 import speexhip  # noqa: E402
 
@@ -196,13 +197,25 @@ def one_trial(seed, max_frames, many_channels=False):
             metered = rng.rand() < 0.3
             if metered:
                 got_r.set_meter(1)
-            if in_fmt == out_fmt == sf.S16 and not metered:
+            # ... and in a share with a random output gain and ramp (S16 -> S16 then runs as the float call too): the bytes
+            # against tests/gain_model.py on the oracle's floats.  The gain goes back to unity behind the call.
+            gained = rng.rand() < 0.4
+            gain, ramp = float(np.float32(rng.uniform(-1.0, 1.0))), int(rng.choice([0, 1, 37, 1000, 100000]))
+            if gained:
+                got_r.set_gain(gain, ramp)
+            if in_fmt == out_fmt == sf.S16 and not metered and not gained:
                 a = ref.raw_call("int", raw, cap)
             else:
                 a = ref.raw_call("float", raw if in_fmt == out_fmt == sf.F32N else xin, cap)
             b = got_r.fmt_call(raw, in_fmt, out_fmt, cap)
             tag = "call %d (formatted %s -> %s, %d frames, cap %d%s)" % (call, sf.NAMES[in_fmt], sf.NAMES[out_fmt], frames, cap,
-                                                                       ", metered" if metered else "")
+                                                                       (", metered" if metered else "") +
+                                                                       (", gain %r over %d" % (gain, ramp) if gained else ""))
+            if gained:
+                left = got_r.get_gain()["remaining"]
+                got_r.set_gain(1.0, 0)
+                if b[0] == 0 and left != max(0, ramp - b[2]):
+                    return "%s: %d frames of the ramp left after %d produced" % (tag, left, b[2]), what
             totals = None
             if metered:
                 totals = got_r.get_meter(reset=True)
@@ -212,14 +225,16 @@ def one_trial(seed, max_frames, many_channels=False):
             if got_r.positions() != ref.positions():
                 return "%s: positions %s, oracle %s" % (tag, got_r.positions(), ref.positions()), what
             y = a[3][: a[2]].reshape(-1)
+            if gained:
+                y = gm.apply(y.astype(np.float32), gm.g(1.0, gain, ramp, 0, a[2]), ch)
             if metered:
                 yf = y.astype(np.float32) * np.float32(32768.0 if in_fmt == out_fmt == sf.F32N else 1.0)
                 model = speexhip.debug_meter(out_fmt, yf)
                 keys = ("samples", "clipped_high", "clipped_low", "nan") if mode == speexhip.MODE_EXACT else ("samples", "nan")
                 if any(totals[k] != model[k] for k in keys) or (mode == speexhip.MODE_EXACT and totals["peak"] != model["peak"]):
                     return "%s: meter %s, debug_meter on the oracle's floats %s" % (tag, totals, model), what
-            if in_fmt == out_fmt == sf.S16 and metered:
-                y = sf.from_internal(sf.S16, y)   # (the float call's result, converted: what the metered call stores)
+            if in_fmt == out_fmt == sf.S16 and (metered or gained):
+                y = sf.from_internal(sf.S16, y)   # (the float call's result, converted: what the metered or gained call stores)
             same_bytes = in_fmt == out_fmt and in_fmt in (sf.S16, sf.F32, sf.F32N)
             want = y if same_bytes else sf.from_internal(out_fmt, y)
             got = b[3][: want.size]
