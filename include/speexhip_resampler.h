@@ -1123,6 +1123,77 @@ SPEEXHIP_API void speexhip_debug_fail_device_allocs(int n);
  * 0 = no pool).  This hands everything idle back to the driver; returns the bytes released. */
 SPEEXHIP_API uint64_t speexhip_release_cached_memory(void);
 
+/* ------------------------------------------------------------------------------------------
+ * Buses: weighted sums of a batch's streams in one device call -- a conference bridge, an N-1 "mix-minus" feed per
+ * participant (W = ones - identity), a stem sum -- with the output side's pass of the sides call behind the sum, so
+ * that a bus is converted, dithered and metered like a stream.  A SpeexHipBatch may carry a bus matrix W: n_buses x
+ * n_streams floats, row-major, host memory; the library copies it.  Off by default; while it is off every call is
+ * exactly what it is without this section.
+ *
+ * For one bus call, with produced[s] the output frames of stream s and C the state's channels:
+ *
+ *   y'_s[f]     output frame f of this call of stream s, on the state's C channels: the float call's value, times
+ *               g_s(done_s + f) in fp32 when that stream's gain is on, exactly as "Gain" says; a stream whose gain is off
+ *               is not multiplied.  For f >= produced[s]:  y'_s[f] = +0.0f.
+ *   bus_frames  = max over s of produced[s].  Every bus has this length.
+ *   bus j, channel c, frame f < bus_frames:
+ *               acc = (double)W[j][0] * (double)y'_0
+ *               acc = acc + (double)W[j][s] * (double)y'_s        for s = 1 .. n_streams - 1, in ascending order
+ *               then one rounding of acc to fp32, nearest even.
+ *
+ * Every term is included: a zero weight is not skipped, so 0 * inf is NaN, and nothing is clamped on the float image.
+ * Each product is exact in fp64 (two 24-bit significands), so a fused multiply-add and a separate multiply and add give
+ * the same bits.  The first term is the product itself, not 0 + the product: a sum of -0.0 terms is -0.0f.  Where the sum
+ * makes or passes on a NaN, which payload and sign survive is the implementation's choice.  The bus image then leaves by
+ * the output side's rule, like a stream's image: the format's "from a FIR value" rule, dither, meter.
+ *
+ * Dither: the buses take the batch's kind and seed ("Dither").  Bus j draws from seed + (n_streams + j) *
+ * 0x9E3779B97F4A7C15 (mod 2^64): the stream rule continued behind the last stream.  All buses share ONE bus position,
+ * because all buses have one length: idx = (bus_position + f) * C + c.  set_dither sets the bus position to its
+ * `position`, set_buses sets it to 0.  With kind != NONE a bus call advances the bus position by bus_frames, whatever the
+ * output format.
+ *
+ * Meter: with the batch's meter on ("Metering") bus j is judged into a cell of its own, by the rules of that section, and
+ * samples += bus_frames * C.  speexhip_batch_get_bus_meter is speexhip_batch_get_meter of a bus's cell.
+ *
+ * What a bus call moves: each stream's gain `done` by produced[s], up to total.  It does NOT move the streams' own dither
+ * positions or meter totals: nothing of theirs is encoded.  Counters, history and positions of every stream are the float
+ * call's; a peek with float_entry = 1 (speexhip_plan_call_ex) sizes it.  There are no identity shortcuts, for S16 or
+ * any other format.  The zero fallback's zeros are summed like any value.  A stream whose channels the per-channel calls
+ * moved apart: BAD_STATE, the state untouched.  The OVERFLOW rule of "Extents" holds, with everything untouched.  The
+ * ordering contract of the device calls holds, speexhip_batch_release_stream included.
+ *
+ * speexhip_batch_set_buses is a control call: it waits for the batch's own last call, as the other control calls do,
+ * uploads W to device memory, makes the buses' meter cells, zeroes their totals and zeroes the bus position.  n_buses = 0
+ * or weights = NULL: off.  INVALID_ARG, the state as it was: n_buses > 32; a batch of more than 32 streams (the streams'
+ * image pointers travel in one kernel-argument pack of 32); a weight that is not finite.  set_rate, set_quality,
+ * reset_mem, skip_zeros, set_meter and set_gain do not touch the bus state.  speexhip_batch_get_buses reports n_buses (0:
+ * off) and, when weights != NULL, copies the n_buses x n_streams floats back.
+ *
+ * speexhip_batch_process_bus_device: `in` and in_len[s] are exactly speexhip_batch_process_sides_device's -- format,
+ * matrix and layout are all allowed.  out_len[s] is stream s's capacity on entry and its produced frames on return.
+ * `out` describes the BUSES: bus j starts j * stream_stride samples after bus 0; any format, interleaved or planar;
+ * `channels` must be the state's C.  The caller's bus buffers hold max over s of out_len[s] frames.  *bus_frames receives
+ * the length; it may not be NULL.  Every argument error leaves the state and all lengths untouched: no buses set:
+ * BAD_STATE; out->mix != NULL (a matrix on the sum is deliberately no part of this call): INVALID_ARG; any other side
+ * error: as in the sides call.  Asynchronous on hip_stream, ordered like the other device calls.
+ *
+ * A host-fed bus call and a bus over many separate states are not part of this version.
+ *
+ * ABI note: adds these six entry points; SpeexHipInfo, SpeexHipSide, SpeexHipMeter, the enums, the error codes and the
+ * version string are unchanged. */
+SPEEXHIP_API int speexhip_batch_set_buses(SpeexHipBatch *b, uint32_t n_buses, const float *weights);
+SPEEXHIP_API int speexhip_batch_get_buses(SpeexHipBatch *b, uint32_t *n_buses, float *weights);
+SPEEXHIP_API int speexhip_batch_process_bus_device(SpeexHipBatch *b, const SpeexHipSide *in, uint32_t *in_len,
+                                                   const SpeexHipSide *out, uint32_t *out_len, uint32_t *bus_frames,
+                                                   void *hip_stream);
+SPEEXHIP_API int speexhip_batch_get_bus_meter(SpeexHipBatch *b, uint32_t bus, SpeexHipMeter *m, int reset);
+SPEEXHIP_API int speexhip_batch_get_bus_position(SpeexHipBatch *b, uint64_t *position);
+/* Host only, no GPU: the very statement the kernel compiles -- z[j * n + i] = bus j of y[s * n + i] (already gained),
+ * i < n, s < n_streams. */
+SPEEXHIP_API int speexhip_debug_bus(uint32_t n_streams, uint32_t n_buses, const float *weights, const float *y, uint32_t n,
+                                    float *z);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/speexhip_resampler.h"
+#include "bus.h"
 #include "devices.h"
 #include "dither.h"
 #include "gain.h"
@@ -809,6 +810,36 @@ int speexhip_debug_gain(float from, float to, uint32_t total, uint64_t first, ui
   if (g == nullptr && n != 0) return SPEEXHIP_ERR_INVALID_ARG;
   const double step = speexhip::gain::step_of(from, to, total);
   for (uint32_t i = 0; i < n; i++) g[i] = speexhip::gain::at(step, from, to, total, first + i);
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+int speexhip_batch_set_buses(SpeexHipBatch *b, uint32_t n_buses, const float *weights) {
+  return guarded([&] { return b ? b->batch->set_buses(n_buses, weights) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_batch_get_buses(SpeexHipBatch *b, uint32_t *n_buses, float *weights) {
+  return guarded([&] { return b ? b->batch->get_buses(n_buses, weights) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_batch_process_bus_device(SpeexHipBatch *bt, const SpeexHipSide *in, uint32_t *in_len, const SpeexHipSide *out,
+                                      uint32_t *out_len, uint32_t *bus_frames, void *hip_stream) {
+  speexhip::CallSide a, b;
+  if (bt == nullptr || in_len == nullptr || out_len == nullptr || bus_frames == nullptr || !side_of(in, false, &a) ||
+      !side_of(out, false, &b) || b.base == nullptr)
+    return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] { return bt->batch->process_bus_device(a, in_len, b, out_len, bus_frames, static_cast<hipStream_t>(hip_stream)); });
+}
+int speexhip_batch_get_bus_meter(SpeexHipBatch *b, uint32_t bus, SpeexHipMeter *m, int reset) {
+  return guarded([&] { return b ? b->batch->get_bus_meter(bus, m, reset != 0) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_batch_get_bus_position(SpeexHipBatch *b, uint64_t *position) {
+  if (b == nullptr || position == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  *position = b->batch->bus_position();
+  return SPEEXHIP_ERR_SUCCESS;
+}
+int speexhip_debug_bus(uint32_t n_streams, uint32_t n_buses, const float *weights, const float *y, uint32_t n, float *z) {
+  if (n_streams == 0 || n_buses == 0 || weights == nullptr || ((y == nullptr || z == nullptr) && n != 0)) return SPEEXHIP_ERR_INVALID_ARG;
+  for (uint32_t j = 0; j < n_buses; j++)
+    for (uint32_t i = 0; i < n; i++)
+      z[static_cast<size_t>(j) * n + i] = speexhip::bus::sum(weights + static_cast<size_t>(j) * n_streams, y + i, n, n_streams);
   return SPEEXHIP_ERR_SUCCESS;
 }
 

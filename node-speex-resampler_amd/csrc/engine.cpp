@@ -35,6 +35,9 @@ using namespace detail;  // (engine_detail.h: HIP_TRY, ON_DEVICE, DeviceScope, D
 
 namespace {
 std::atomic<int> g_fail_allocs{0};
+}  // namespace
+
+namespace detail {  // (engine_detail.h: the control-plane helpers that bus.cpp shares)
 
 // Device allocation of the filter installs: ALLOC_FAILED when the device is out of memory (or the
 // test hook says so) -- the caller then falls back to resampler_basic_zero like the reference
@@ -68,6 +71,7 @@ int dev_alloc(int device, void **ptr, size_t bytes) {
 // -- the device buffers involved are allocated at least that big -- and runs on the copy engines from / to a
 // pinned image, beside whatever the device is doing.
 const size_t kCtlCopyMin = 20 * 1024;
+namespace {
 struct PinnedImage {
   char *p = nullptr;
   size_t bytes = 0;
@@ -77,6 +81,7 @@ struct PinnedImage {
     return pool::pinned_get(reinterpret_cast<void **>(&p), bytes);
   }
 };
+}  // namespace
 // host `src` (bytes) -> device `dst` (capacity >= max(bytes, kCtlCopyMin)); waits for the copy
 int ctl_upload(void *dst, const void *src, size_t bytes, hipStream_t stream) {
   PinnedImage img;
@@ -99,6 +104,9 @@ int ctl_download(void *dst, const char *base, size_t total, size_t off, size_t l
   std::memcpy(dst, img.p + (off - first), len);
   return SPEEXHIP_ERR_SUCCESS;
 }
+}  // namespace detail
+
+namespace {
 
 const size_t kLdsBudget = 150 * 1024;  // of the CU's 160 KiB
 static_assert(kStagedLdsBytes <= kLdsBudget, "the period kernel's staged-store instance asks for more LDS than the budget");
@@ -787,6 +795,8 @@ Batch::~Batch() {
   pool::device_put(device_, d_planar_in_);
   pool::device_put(device_, d_planar_out_);
   pool::device_put(device_, d_meter_);
+  pool::device_put(device_, d_bus_);
+  pool::device_put(device_, d_bus_image_);
   pool::pinned_put(h_pin_in_);
   pool::pinned_put(h_pin_out_);
   for (int i = 0; i < kMaxPieces; i++) pool::event_put(device_, piece_ev_[i]);
@@ -1575,6 +1585,7 @@ int warm_device(int device) {
   warm_unit_convert_many(s);
   warm_unit_mix(s);
   warm_unit_sides(s);
+  warm_unit_bus(s);
   HIP_TRY(hipStreamSynchronize(s));
   return SPEEXHIP_ERR_SUCCESS;
 }

@@ -72,6 +72,15 @@ struct CallSide {
   void *const *planes;             // planar, host calls only: plane c = planes[c] (separate allocations) instead of
                                    // base + c * plane_stride
 };
+// a side the formatted calls can read: with a matrix both channel counts are 1..8, without one the caller's count is the state's
+inline bool side_ok(const CallSide &side, uint32_t state_channels) {
+  if (sample_bytes(side.fmt) == 0) return false;
+  if (side.layout != SPEEXHIP_LAYOUT_INTERLEAVED && side.layout != SPEEXHIP_LAYOUT_PLANAR) return false;
+  if (side.mix == nullptr) return side.channels == state_channels;
+  return state_channels <= kMixMaxChannels && side.channels >= 1 && side.channels <= kMixMaxChannels;
+}
+// ... whose planes a pass has to walk (a side of one channel is the same bytes in either layout)
+inline bool side_planar(const CallSide &side) { return side.layout == SPEEXHIP_LAYOUT_PLANAR && side.channels != 1; }
 
 class Batch {
  public:
@@ -172,6 +181,26 @@ class Batch {
   int set_gain(uint32_t stream, float gain, uint32_t ramp_frames);
   // current = g(done), target = to, remaining = total - done (any may be null)
   int get_gain(uint32_t stream, float *current, float *target, uint32_t *remaining) const;
+  // Mix buses (bus.cpp, bus.h; include/speexhip_resampler.h, "Buses"): a state may carry a matrix W of n_buses x
+  // n_streams() weights, off by default; while it is off nothing here is read.  set_buses copies W (host, row-major) and
+  // uploads its device copy, makes the buses' meter cells, zeroes their totals and the bus position; n_buses == 0 or
+  // weights == nullptr: off.  More than 32 buses, a state of more than 32 streams (the streams' image pointers travel in
+  // one kernel-argument pack) or a weight that is not finite: INVALID_ARG, the state as it was.  No other control call
+  // touches any of this.
+  int set_buses(uint32_t n_buses, const float *weights);
+  int get_buses(uint32_t *n_buses, float *weights) const;  // (either may be null)
+  // The bus call: the input side's pass -> process_device(float) into the state's image -> bus_sum (kernels_bus.hip: every
+  // bus the fp64 sum of all streams' samples behind their gains, a stream that has ended supplying +0.0f) into a grow-only
+  // image of the buses -> side_pass over that image with the buses in the place of the streams, dithered from the bus
+  // seeds at the bus position and judged into the bus cells.  An interleaved F32 bus side is written by bus_sum itself
+  // (and read by meter_image when the meter is on).  Counters, history and positions of every stream are the float
+  // call's; the streams' gains move by what they produced, their dither positions and meter totals do not move: nothing
+  // of theirs is encoded.  out_len: the streams' capacities in, their produced frames out; *bus_frames = the largest of
+  // them, the length of every bus.  No buses set, or a stream whose channels stand apart: BAD_STATE; out.mix: INVALID_ARG.
+  int process_bus_device(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len, uint32_t *bus_frames,
+                         hipStream_t stream);
+  int get_bus_meter(uint32_t bus, SpeexHipMeter *m, bool reset);  // as get_meter, of a bus's cell
+  uint64_t bus_position() const { return bus_pos_; }             // the buses' one dither position
   // Host-buffer call for a single-stream batch; synchronous (H2D, kernels, D2H).
   int process_host(const void *in, uint32_t *in_len, void *out, uint32_t *out_len, bool float_io);
   // The same call with the result left in a pinned block of the pool that the caller then OWNS (release_block):
@@ -275,8 +304,10 @@ class Batch {
   // image -> storage, dithered when the state and the format say so.  Stream s is lens[s] frames at side.base + s *
   // side.stride and image + s * pitch (elements).  apart (an output side without a matrix): the plans of the one
   // stream's channels, which stand apart -- channel c is plans[c].produced samples, channels() elements from one to the next.
+  // buses (an output side of a bus call): the items are the state's buses in the place of its streams -- lens[j] frames
+  // of bus j, dithered from the bus seeds at the bus position, judged into the bus cells, never gained.
   int side_pass(const CallSide &side, bool to_image, char *image, size_t pitch, const uint32_t *lens, hipStream_t stream,
-                const CallPlan *apart = nullptr);
+                const CallPlan *apart = nullptr, bool buses = false);
   bool dither_on() const { return dither_kind_ != SPEEXHIP_DITHER_NONE; }
   // the DitherPack of streams [s0, s0 + n): first = position * per_frame (per_frame = 1: the position itself)
   DitherPack dither_pack(uint32_t s0, uint32_t n, uint32_t per_frame) const;
@@ -293,6 +324,10 @@ class Batch {
   // of an output frame in a pass that walks samples, 1 in the passes that walk frames (a stream whose gain is off: 0)
   GainPack gain_pack(uint32_t s0, uint32_t n, uint32_t per_frame) const;
   void gain_advance(const uint32_t *produced);  // after a formatted or mixed call with gain on
+  // the packs of the buses, as an output pass over the bus image takes them: bus j draws from dither::stream_seed(seed,
+  // n_streams() + j), first = the bus position * per_frame; its cell is d_bus_ + j
+  DitherPack bus_dither_pack(uint32_t per_frame) const;
+  MeterPack bus_meter_pack() const;
   // What a call without an output pass wrote (meter_result's arguments), finished in place: gain_image when gain is on --
   // which judges its product too when the meter is on -- meter_image otherwise.
   int image_result(void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream);
@@ -455,6 +490,15 @@ class Batch {
     uint32_t total = 0, done = 0;
   };
   std::vector<Gain> gain_;                  // per stream (empty until set_gain: off)
+  // buses (bus.cpp): n_buses_ == 0 = off.  One device block, allocated by the first set_buses: the buses' 32 meter cells
+  // at its front, behind them the 32 x 32 floats of W as bus_sum reads it (BusPack::w).
+  uint32_t n_buses_ = 0;
+  std::vector<float> bus_w_;                // W as the caller gave it: n_buses_ x n_streams_, row-major
+  char *d_bus_ = nullptr;
+  uint64_t bus_pos_ = 0;                    // index of every bus's next output frame (set_dither, set_buses)
+  std::vector<uint64_t> bus_samples_;       // per bus: samples metered since the last reset
+  char *d_bus_image_ = nullptr;             // the float image of the buses, grow-only
+  size_t bus_image_cap_ = 0;                // bytes
   uint32_t done_seq_ = 0;  // completion word of the small host-buffer calls (engine.cpp, process_host)
   size_t stage_in_cap_ = 0, stage_out_cap_ = 0, pin_in_cap_ = 0, pin_out_cap_ = 0;  // bytes
 };

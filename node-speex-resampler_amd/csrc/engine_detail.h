@@ -78,6 +78,14 @@ int wait_call(hipStream_t stream, const Wait &w, void *word, uint32_t seq);
 int grow_stage(int device, char **buf, size_t *cap_now, size_t want, bool pinned);
 // engine.cpp: the address the device sees when all of [p, p + bytes) is pinned memory, else nullptr
 void *pinned_view(const void *p, size_t bytes);
+// engine.cpp: control-plane data (histories, tables, meter cells, a bus matrix) moves through the copy engines, whole, in
+// copies of at least kCtlCopyMin bytes -- the device buffers involved are allocated at least that big.  ctl_upload: host
+// `src` (bytes) -> device `dst`; ctl_download: bytes [off, off + len) of the device buffer `base` of `total` bytes -> host
+// `dst`.  Both wait for their copy.  dev_alloc: ALLOC_FAILED when the device is out of memory, DEVICE for anything else.
+extern const size_t kCtlCopyMin;
+int dev_alloc(int device, void **ptr, size_t bytes);
+int ctl_upload(void *dst, const void *src, size_t bytes, hipStream_t stream);
+int ctl_download(void *dst, const char *base, size_t total, size_t off, size_t len, hipStream_t stream);
 
 }  // namespace detail
 }  // namespace speexhip

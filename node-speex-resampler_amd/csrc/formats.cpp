@@ -18,17 +18,10 @@ namespace speexhip {
 using namespace detail;
 
 namespace {
-// with a matrix both channel counts are 1..8, without one the caller's count is the state's
-inline bool side_ok(const CallSide &side, uint32_t state_channels) {
-  if (sample_bytes(side.fmt) == 0) return false;
-  if (side.layout != SPEEXHIP_LAYOUT_INTERLEAVED && side.layout != SPEEXHIP_LAYOUT_PLANAR) return false;
-  if (side.mix == nullptr) return side.channels == state_channels;
-  return state_channels <= kMixMaxChannels && side.channels >= 1 && side.channels <= kMixMaxChannels;
-}
+inline bool planar(const CallSide &side) { return side_planar(side); }
 // The calls that are an existing call on the same bytes: nothing is converted, nothing extra launched.  (F32N -> F32N: a
 // power-of-two scale commutes exactly with the FIR.)  With dither on S16 -> S16 is no such call -- it runs as the float
 // call between convert_in and the dithered convert_out -- and the float pairs, written as ever, still count their frames.
-inline bool planar(const CallSide &side) { return side.layout == SPEEXHIP_LAYOUT_PLANAR && side.channels != 1; }
 inline bool same_bytes(const CallSide &in, const CallSide &out, bool dith) {
   if (in.mix != nullptr || out.mix != nullptr || in.fmt != out.fmt || planar(in) || planar(out)) return false;
   return in.fmt == SPEEXHIP_FMT_S16 ? !dith : in.fmt == SPEEXHIP_FMT_F32 || in.fmt == SPEEXHIP_FMT_F32N;
@@ -63,6 +56,7 @@ int Batch::set_dither(int kind, uint64_t seed, uint64_t position) {
   dither_kind_ = kind;
   dither_seed_ = seed;
   dither_pos_.assign(n_streams_, position);
+  bus_pos_ = position;  // (the buses' one position: bus.cpp)
   return SPEEXHIP_ERR_SUCCESS;
 }
 int Batch::get_dither(uint32_t stream, int *kind, uint64_t *seed, uint64_t *position) const {

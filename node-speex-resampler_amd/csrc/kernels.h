@@ -358,4 +358,25 @@ struct PlanePack {          // like MixPack: up to 32 streams and the matrix, in
 hipError_t launch_planes(int fmt, bool out, const PlanePack &pack, const DitherPack *dith, uint32_t n, uint32_t most,
                          hipStream_t stream, const MeterPack *meter = nullptr, const GainPack *gain = nullptr);
 
+// ---- mix buses (kernels_bus.hip): the weighted sums of a batch's streams, between the float call and the output pass of
+// a bus call (bus.h states the sum).  Stream s is frames[s] frames of `channels` floats at src[s]; bus j is bus_frames
+// frames at dst + j * dst_pitch, every sample the sum over ALL n_streams streams of W[j][s] times the stream's sample
+// behind its gain (gain.s[s], GainStream::channels = `channels`, or 0: not multiplied), a stream that has ended
+// supplying +0.0f.  w is the device copy of W, transposed and padded: W[j][s] at w[s * 32 + j], 32 x 32 floats, zeros
+// behind n_buses -- the eight weights a workgroup needs of a stream are one aligned scalar load.
+struct BusPack {            // like ConvertPack: up to 32 streams, in the kernel-argument segment
+  const float *src[kMaxPackedStreams];
+  uint32_t frames[kMaxPackedStreams];
+  float *dst;               // bus 0
+  uint64_t dst_pitch;       // floats between two buses (>= bus_frames * channels)
+  const float *w;           // device memory
+  uint32_t n_streams, n_buses;   // 1..32 each
+  uint32_t channels;
+  uint32_t bus_frames;      // >= every frames[s]
+};
+// buses a workgroup sums in one trip: 8 x 4 fp64 accumulators beside a lane's four samples (DESIGN, "Mix buses")
+constexpr uint32_t kBusGroup = 8;
+hipError_t launch_bus_sum(const BusPack &pack, const GainPack &gain, hipStream_t stream);
+void warm_unit_bus(hipStream_t s);
+
 }  // namespace speexhip

@@ -14,9 +14,10 @@ namespace speexhip {
 using namespace detail;
 
 int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pitch, const uint32_t *lens, hipStream_t stream,
-                     const CallPlan *apart) {
-  // an item of the pass: a stream of the batch, or a channel of the one stream whose channels stand apart
-  const uint32_t items = apart != nullptr ? channels_ : n_streams_;
+                     const CallPlan *apart, bool buses) {
+  // an item of the pass: a stream of the batch, or a channel of the one stream whose channels stand apart -- or a bus of
+  // a bus call's output side (bus.cpp), which takes the bus seeds, position and cells where a stream takes its own
+  const uint32_t items = buses ? n_buses_ : apart != nullptr ? channels_ : n_streams_;
   const size_t storage_step = (apart != nullptr ? 1 : side.stride) * sample_bytes(side.fmt);
   const size_t image_step = (apart != nullptr ? 1 : pitch) * sizeof(float);
   // With dither on (set_dither) the formats of dithered_fmt leave through the dithered instances of either pass, at the
@@ -29,15 +30,15 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
   // With a stream's gain on (set_gain) every format leaves through the gained instance of its pass, each stream at its own
   // g from its own frame index on; dither and meter ride along in the same instance.  (Channels that stand apart have no
   // output frame to index: the callers have refused them.)
-  const bool gained = !to_image && gain_on();
+  const bool gained = !to_image && !buses && gain_on();  // (a bus's streams were gained before they were summed)
   if (gained && apart != nullptr) return SPEEXHIP_ERR_BAD_STATE;
   const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
   for (uint32_t first = 0; first < items; first += kChunk) {
     const uint32_t n = std::min(kChunk, items - first);
     DitherPack dith;
-    if (dithered) dith = dither_pack(first, n, side.mix != nullptr ? 1 : channels_);
+    if (dithered) dith = buses ? bus_dither_pack(channels_) : dither_pack(first, n, side.mix != nullptr ? 1 : channels_);
     MeterPack cells;
-    if (metered) cells = meter_pack(first, n);
+    if (metered) cells = buses ? bus_meter_pack() : meter_pack(first, n);
     const MeterPack *meter = metered ? &cells : nullptr;
     GainPack gains;  // (the flat converting pass walks samples: it divides by channels(); the others walk frames)
     if (gained) gains = gain_pack(first, n, side.layout != SPEEXHIP_LAYOUT_PLANAR && side.mix == nullptr ? channels_ : 1);
@@ -72,7 +73,7 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
         pack.s[j].frames = apart != nullptr ? apart[item].produced : lens[item];
         most = std::max(most, pack.s[j].frames);
       }
-      if (dithered) dith = dither_pack(first, n, 1);
+      if (dithered) dith = buses ? bus_dither_pack(1) : dither_pack(first, n, 1);
       e = launch_planes(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream, meter, gain);
     } else if (side.mix != nullptr) {
       MixPack pack;

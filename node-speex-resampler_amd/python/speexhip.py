@@ -125,6 +125,9 @@ EXPORTS = [
     # gain: per-stream volume with click-free ramps in the formatted, mixed and sides calls
     "speexhip_resampler_set_gain", "speexhip_resampler_get_gain", "speexhip_batch_set_gain", "speexhip_batch_get_gain",
     "speexhip_debug_gain",
+    # buses: weighted sums of a batch's streams in one device call
+    "speexhip_batch_set_buses", "speexhip_batch_get_buses", "speexhip_batch_process_bus_device",
+    "speexhip_batch_get_bus_meter", "speexhip_batch_get_bus_position", "speexhip_debug_bus",
 ]
 
 
@@ -456,6 +459,19 @@ def lib():
             L.speexhip_batch_get_gain.argtypes = [p, u32, pf, pf, pu32]
             L.speexhip_debug_gain.restype = i32
             L.speexhip_debug_gain.argtypes = [C.c_float, C.c_float, u32, C.c_uint64, u32, pf]
+        if hasattr(L, "speexhip_batch_set_buses") or "SPEEXHIP_LIB_PATH" not in os.environ:
+            L.speexhip_batch_set_buses.restype = i32
+            L.speexhip_batch_set_buses.argtypes = [p, u32, p]
+            L.speexhip_batch_get_buses.restype = i32
+            L.speexhip_batch_get_buses.argtypes = [p, pu32, p]
+            L.speexhip_batch_process_bus_device.restype = i32
+            L.speexhip_batch_process_bus_device.argtypes = [p, C.POINTER(Side), pu32, C.POINTER(Side), pu32, pu32, p]
+            L.speexhip_batch_get_bus_meter.restype = i32
+            L.speexhip_batch_get_bus_meter.argtypes = [p, u32, C.POINTER(Meter), i32]
+            L.speexhip_batch_get_bus_position.restype = i32
+            L.speexhip_batch_get_bus_position.argtypes = [p, C.POINTER(C.c_uint64)]
+            L.speexhip_debug_bus.restype = i32
+            L.speexhip_debug_bus.argtypes = [u32, u32, p, p, u32, p]
         _lib = L
     return _lib
 
@@ -526,6 +542,22 @@ def debug_gain(from_gain, to_gain, total, first, n):
     if rc:
         raise ValueError(strerror(rc))
     return g[:n]
+
+
+def debug_bus(weights, y):
+    """host-only: the library's bus sums z (n_buses, n) float32 of the (already gained) stream samples y (n_streams, n)
+    under the matrix weights (n_buses, n_streams): the very statement the kernel compiles"""
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    if w.ndim != 2 or y.ndim != 2 or w.shape[1] != y.shape[0]:
+        raise ValueError("weights (n_buses, n_streams) and y (n_streams, n)")
+    z = np.zeros((w.shape[0], max(y.shape[1], 1)), np.float32)[:, : y.shape[1]]
+    z = np.ascontiguousarray(z)
+    rc = lib().speexhip_debug_bus(w.shape[1], w.shape[0], C.c_void_p(w.ctypes.data), C.c_void_p(y.ctypes.data), y.shape[1],
+                                  C.c_void_p(z.ctypes.data))
+    if rc:
+        raise ValueError(strerror(rc))
+    return z
 
 
 def debug_meter(fmt, y, d=None):
@@ -1475,6 +1507,48 @@ class Batch:
             raise RuntimeError(strerror(rc))
         return {"current": np.float32(cur.value), "target": np.float32(tgt.value), "remaining": rem.value}
 
+    def set_buses(self, weights):
+        """The bus matrix (n_buses, n_streams) of process_bus_device: bus j is the sum over the streams of weights[j][s]
+        times the stream's gained output (mix-minus: ones - identity).  None: off.  Zeroes the bus meters and the bus
+        position.  Returns the C call's code."""
+        if weights is None:
+            return lib().speexhip_batch_set_buses(self._h, 0, None)
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        if w.ndim != 2 or w.shape[1] != self.n_streams:
+            raise ValueError("weights must be (n_buses, %d)" % self.n_streams)
+        return lib().speexhip_batch_set_buses(self._h, w.shape[0], C.c_void_p(w.ctypes.data))
+
+    def get_buses(self):
+        """the bus matrix (n_buses, n_streams) float32, or None when the buses are off"""
+        n = C.c_uint32()
+        rc = lib().speexhip_batch_get_buses(self._h, C.byref(n), None)
+        if rc:
+            raise RuntimeError(strerror(rc))
+        if n.value == 0:
+            return None
+        w = np.zeros((n.value, self.n_streams), np.float32)
+        rc = lib().speexhip_batch_get_buses(self._h, C.byref(n), C.c_void_p(w.ctypes.data))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return w
+
+    def get_bus_meter(self, bus, reset=False):
+        """The bus's {'on', 'samples', 'clipped_high', 'clipped_low', 'nan', 'peak'}; reset clears that bus only.  Waits
+        for this batch's last call only."""
+        m = Meter()
+        rc = lib().speexhip_batch_get_bus_meter(self._h, int(bus), C.byref(m), int(bool(reset)))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return m.as_dict()
+
+    def bus_position(self):
+        """the buses' one dither position: the index of every bus's next output frame"""
+        pos = C.c_uint64()
+        rc = lib().speexhip_batch_get_bus_position(self._h, C.byref(pos))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return pos.value
+
     def lines(self, stream):
         """(taps-1+pending, channels) float32 of one stream: history then pending frames"""
         i = self.info(stream)
@@ -1559,6 +1633,79 @@ class Batch:
         if rc:
             raise RuntimeError(strerror(rc))
         return list(il), list(ol)
+
+    def bus_call(self, in_side, in_frames, out_side, out_capacity, stream_ptr=0):
+        """process_bus_device without the exception: (code, consumed per stream, produced per stream, bus_frames)"""
+        n = self.n_streams
+        il = (C.c_uint32 * n)(*([in_frames] * n if np.isscalar(in_frames) else in_frames))
+        ol = (C.c_uint32 * n)(*([out_capacity] * n if np.isscalar(out_capacity) else out_capacity))
+        made = C.c_uint32(0)
+        rc = lib().speexhip_batch_process_bus_device(self._h, C.byref(in_side), il, C.byref(out_side), ol, C.byref(made),
+                                                     C.c_void_p(stream_ptr))
+        return rc, list(il), list(ol), made.value
+
+    def process_bus_device(self, in_side, in_frames, out_side, out_capacity, stream_ptr=0):
+        """Bus call of the batch: in_side / in_frames as in process_sides_device; out_side describes the BUSES (bus j
+        stream_stride samples behind bus j - 1, the state's channel count, any format and layout, no matrix), each with
+        room for max(out_capacity) frames.  Returns (consumed per stream, produced per stream, bus_frames)."""
+        rc, used, made, bus_frames = self.bus_call(in_side, in_frames, out_side, out_capacity, stream_ptr)
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return used, made, bus_frames
+
+    def process_bus_tensor(self, x, weights=None, out_dtype=None, normalized=False, in_layout=None, out_layout=None,
+                           out_capacity=None, in_frames=None, in_format=None, out_format=None):
+        """The buses of a CUDA tensor of streams: x is (B, T, C) -- (B, C, T) with in_layout='planar' -- of uint8, int16,
+        int32, float16, bfloat16 or float32 (normalized: +-1.0 full scale), as in process_tensor's formatted form.
+        weights: set_buses(weights) first (None: the matrix the batch already has).  Returns (the buses, (n_buses, T', C)
+        or with out_layout='planar' (n_buses, C, T'), of out_dtype (default: x's); bus_frames = T'; frames produced per
+        stream).  Runs on torch's current stream."""
+        import torch
+        if weights is not None:
+            rc = self.set_buses(weights)
+            if rc:
+                raise ValueError(strerror(rc))
+        w = self.get_buses()
+        if w is None:
+            raise ValueError("no buses set")
+        fmt_of = {torch.uint8: FMT_U8, torch.int16: FMT_S16, torch.int32: FMT_S32,
+                  torch.float32: FMT_F32N if normalized else FMT_F32, torch.float16: FMT_F16N, torch.bfloat16: FMT_BF16N}
+        out_dtype = x.dtype if out_dtype is None else out_dtype
+        if not x.is_cuda or x.dim() != 3 or x.dtype not in fmt_of or out_dtype not in fmt_of:
+            raise ValueError("process_bus_tensor wants a CUDA tensor of rank 3 of uint8, int16, int32, float16, bfloat16 or float32")
+        in_fmt = fmt_of[x.dtype] if in_format is None else in_format
+        out_fmt = fmt_of[out_dtype] if out_format is None else out_format
+        if fmt_bytes(in_fmt) != x.element_size() or fmt_bytes(out_fmt) != torch.empty(0, dtype=out_dtype).element_size():
+            raise ValueError("a named format must have the size of the tensor's elements")
+        planar_in, planar_out = _layout(in_layout) == LAYOUT_PLANAR, _layout(out_layout) == LAYOUT_PLANAR
+        if planar_in:
+            B, Cn, T = x.shape
+            if T > 1 and x.stride(-1) != 1:
+                raise ValueError("the last dimension of a planar tensor must be dense (stride 1)")
+        else:
+            B, T, Cn = x.shape
+            if not x[0].is_contiguous():
+                raise ValueError("the frames of a stream must be dense (T, C)")
+        if B != self.n_streams or Cn != self.channels:
+            raise ValueError("tensor of %d streams x %d channels for a batch of %d x %d" % (B, Cn, self.n_streams, self.channels))
+        i = self.info()
+        if out_capacity is None:
+            out_capacity = (T * i["den_rate"] + i["num_rate"] - 1) // i["num_rate"] + 1
+        cap = max(int(np.max(out_capacity)), 1)
+        nb = w.shape[0]
+        if planar_out:
+            pitch = (cap + 127) & ~127
+            out = torch.empty((nb, Cn, pitch), dtype=out_dtype, device=x.device)
+            b = make_side(out_fmt, Cn, LAYOUT_PLANAR, None, out.data_ptr(), out.stride(1), out.stride(0))
+        else:
+            out = torch.empty((nb, cap, Cn), dtype=out_dtype, device=x.device)
+            b = make_side(out_fmt, Cn, LAYOUT_INTERLEAVED, None, out.data_ptr(), 0, out.stride(0))
+        a = make_side(in_fmt, Cn, _layout(in_layout), None, x.data_ptr(), x.stride(1) if planar_in else 0,
+                      x.stride(0) if B > 1 else 0)
+        _, made, bus_frames = self.process_bus_device(a, T if in_frames is None else in_frames, b, out_capacity,
+                                                      torch.cuda.current_stream(x.device).cuda_stream)
+        out = out[:, :, :bus_frames] if planar_out else out[:, :bus_frames]
+        return out, bus_frames, made
 
     def _process_tensor_fmt(self, x, out_capacity, in_frames, out_dtype, normalized, in_mix=None, out_mix=None,
                             in_format=None, out_format=None, in_layout=None, out_layout=None):
