@@ -127,39 +127,17 @@ int Batch::process_bus_device(const CallSide &in_side, uint32_t *in_len, const C
   if (!side_planar(out)) out.layout = SPEEXHIP_LAYOUT_INTERLEAVED;
   ON_DEVICE();
   // (channels that stand apart produce different numbers of frames: a bus has no frame to sum them in)
-  for (uint32_t s = 0; s < n_streams_; s++)
-    if (!uniform(s)) return SPEEXHIP_ERR_BAD_STATE;
-  // what the float call will do, known before anything is launched (integer arithmetic): sizes the images
-  const EntryRules rules = entry_rules(true);
-  uint32_t most_in = 0, most_out = 0;
-  for (uint32_t s = 0; s < n_streams_; s++) {
-    most_in = std::max(most_in, in_len[s]);
-    most_out = std::max(most_out, plan_call(filter_.num, filter_.den, in_len[s], out_len[s], P(s, 0), rules).produced);
-  }
+  const SidesRoute r = route_sides_call(SidesForm::Bus, side_kind(in), side_kind(out), sides_state());
+  if (r.refuse != SPEEXHIP_ERR_SUCCESS) return r.refuse;
   // the input side as in process_sides_device; the streams' results always lie in the state's image, whatever the buses'
   // format: bus_sum reads them there.  An interleaved F32 bus side IS the buses' image.
-  const bool pass_in = (in.mix != nullptr || in.fmt != SPEEXHIP_FMT_F32 || side_planar(in)) && in.base != nullptr && most_in != 0;
-  const bool pass_out = out.fmt != SPEEXHIP_FMT_F32 || side_planar(out);
-  const size_t in_pitch = align64(static_cast<size_t>(most_in) * channels_);
-  const size_t out_pitch = align64(static_cast<size_t>(most_out) * channels_);
-  int rc = ensure_planar_scratch(pass_in ? in_pitch * n_streams_ * sizeof(float) : 0, out_pitch * n_streams_ * sizeof(float));
+  SideImages im;
+  int rc = prepare_images(in, in_len, out_len, r, false, true, stream, &im);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  const size_t bus_bytes = pass_out ? out_pitch * n_buses_ * sizeof(float) : 0;
-  if (bus_bytes > bus_image_cap_) {
-    rc = quiesce();  // (a grow waits for the state's own last call, which may still read the old image)
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-    rc = grow_stage(device_, &d_bus_image_, &bus_image_cap_, bus_bytes, false);
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  }
-  // (the images and the cells belong to the state: a call on another stream than the previous one waits for it first)
-  rc = chain_to(stream);
-  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  if (pass_in) {
-    rc = side_pass(in, true, d_planar_in_, in_pitch, in_len, stream);
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  }
-  const void *image_in = pass_in ? static_cast<const void *>(d_planar_in_) : in.base;
-  rc = process_device(image_in, pass_in ? in_pitch : in.stride, in_len, d_planar_out_, out_pitch, out_len, true, stream);
+  const bool pass_out = r.pass_out;
+  const size_t out_pitch = im.out_pitch;
+  const uint32_t most_out = im.most_out;
+  rc = process_device(im.in, im.in_stride, in_len, d_planar_out_, out_pitch, out_len, true, stream);
   if (!ran(rc)) return rc;
   // (out_len: what the float call produced; the zero fallback's zeros are summed like any value)
   BusPack pack;
@@ -175,28 +153,20 @@ int Batch::process_bus_device(const CallSide &in_side, uint32_t *in_len, const C
   pack.n_buses = n_buses_;
   pack.channels = channels_;
   pack.bus_frames = most_out;
-  const bool gained = gain_on();
   if (hip_failed(launch_bus_sum(pack, gain_pack(0, n_streams_, channels_), stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
   const std::vector<uint32_t> lens(n_buses_, most_out);
   if (pass_out) {
     const int prc = side_pass(out, false, d_bus_image_, out_pitch, lens.data(), stream, nullptr, true);
     if (prc != SPEEXHIP_ERR_SUCCESS) return prc;
-  } else if (meter_on_) {
+  } else if (r.finish != SidesRoute::Nothing) {
     // (interleaved F32: bus_sum wrote the caller's buffer, meter_image reads it once more)
-    ConvertPack result;
-    std::memset(&result, 0, sizeof(result));
-    const uint64_t n = static_cast<uint64_t>(most_out) * channels_;
-    for (uint32_t j = 0; j < n_buses_; j++) {
-      result.s[j].src = static_cast<const float *>(out.base) + j * out.stride;
-      result.s[j].n = n;
-      result.s[j].step = 1;
-    }
-    if (hip_failed(launch_meter_image(result, bus_meter_pack(), 1.0f, n_buses_, n, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+    const int mrc = meter_result(out.base, out.stride, lens.data(), r.finish_scale, stream, true);
+    if (mrc != SPEEXHIP_ERR_SUCCESS) return mrc;
   }
-  if (meter_on_)
+  if (r.counts_meter)
     for (uint32_t j = 0; j < n_buses_; j++) bus_samples_[j] += static_cast<uint64_t>(most_out) * channels_;
-  if (gained) gain_advance(out_len);
-  if (dither_on()) bus_pos_ += most_out;
+  if (r.moves_gain) gain_advance(out_len);
+  if (r.moves_dither) bus_pos_ += most_out;
   *bus_frames = most_out;
   return rc;
 }

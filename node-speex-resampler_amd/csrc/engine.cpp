@@ -873,10 +873,10 @@ void Batch::meter_count(const uint32_t *produced, uint32_t per_frame) {
   for (uint32_t s = 0; s < n_streams_; s++) meter_samples_[s] += static_cast<uint64_t>(produced[s]) * per_frame;
 }
 
-int Batch::meter_result(const void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream) {
-  const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
-  for (uint32_t first = 0; first < n_streams_; first += kChunk) {
-    const uint32_t n = std::min(kChunk, n_streams_ - first);
+int Batch::meter_result(const void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream, bool buses) {
+  const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams), items = buses ? n_buses_ : n_streams_;
+  for (uint32_t first = 0; first < items; first += kChunk) {
+    const uint32_t n = std::min(kChunk, items - first);
     ConvertPack pack;
     std::memset(&pack, 0, sizeof(pack));
     uint64_t most = 0;
@@ -886,7 +886,8 @@ int Batch::meter_result(const void *result, uint64_t stride, const uint32_t *len
       pack.s[j].step = 1;
       most = std::max(most, pack.s[j].n);
     }
-    if (hip_failed(launch_meter_image(pack, meter_pack(first, n), scale, n, most, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+    const MeterPack cells = buses ? bus_meter_pack() : meter_pack(first, n);
+    if (hip_failed(launch_meter_image(pack, cells, scale, n, most, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
   }
   return SPEEXHIP_ERR_SUCCESS;
 }

@@ -15,6 +15,7 @@
 #include "filter_plans.h"
 #include "host_transfer.h"
 #include "kernels.h"
+#include "sides_route.h"
 #include "stream_plan.h"
 
 namespace speexhip {
@@ -81,6 +82,8 @@ inline bool side_ok(const CallSide &side, uint32_t state_channels) {
 }
 // ... whose planes a pass has to walk (a side of one channel is the same bytes in either layout)
 inline bool side_planar(const CallSide &side) { return side.layout == SPEEXHIP_LAYOUT_PLANAR && side.channels != 1; }
+// ... as the route of its call sees it (sides_route.h)
+inline SideKind side_kind(const CallSide &side) { return SideKind{side.fmt, side.mix != nullptr, side_planar(side), side.planes != nullptr}; }
 
 class Batch {
  public:
@@ -112,18 +115,12 @@ class Batch {
   // Formatted and mixed calls (formats.cpp): the caller names each side's sample format, and a side may carry a channel
   // matrix (CallSide).  One pipeline: storage --the input side's pass--> float image of channels() channels
   // --process_device(float)--> float image --the output side's pass--> storage, on the state's scratch images (the
-  // planar calls' ones: calls on a state are ordered).  A side's pass is convert_* (kernels_convert.hip) or, with a
-  // matrix, mix_* (kernels_mix.hip) in its place; a side without a matrix whose storage is F32 IS its image and has no
-  // pass.  S16 -> S16, F32 -> F32 and F32N -> F32N without a matrix go straight to process_device.  Counters, positions
-  // and the history are the float call's.  A state whose channels stand apart is served channel by channel when it is one
-  // stream, has no matrix and dither is off (plans_out: the plan of every channel then, empty otherwise), else BAD_STATE.
-  // A planar side (CallSide::layout) is the same call on the same samples: its pass is planes_* (kernels_sides.hip) in
-  // the place of convert_* / mix_*, which converts, mixes and dithers while it transposes -- F32 without a matrix
-  // included, whose planes are not the image.  With a planar side every format pair runs as the float call (S16 -> S16
-  // too); both sides planar, F32 -> F32 or F32N -> F32N, no matrix: process_planar_device on the same bytes.
-  // With the meter on (set_meter) the output side's pass is its metered instance, a result that no pass writes is read by
-  // meter_image behind the float call, the planar float pairs run between planes_in and the metered planes_out, S16 -> S16
-  // runs as the float call, and a state whose channels stand apart returns BAD_STATE.
+  // planar calls' ones: calls on a state are ordered).  A side's pass is convert_* (kernels_convert.hip), with a matrix
+  // mix_* (kernels_mix.hip), of a planar side planes_* (kernels_sides.hip), which converts, mixes and dithers while it
+  // transposes.  Counters, positions and the history are the float call's.  Which calls are an existing call on the
+  // caller's own bytes, which passes run, who finishes a result that no pass writes, what moves afterwards and which
+  // states are refused with BAD_STATE: route_sides_call (sides_route.h), for this and every other form of the call.
+  // plans_out: the plan of every channel of a state whose channels stand apart, empty otherwise.
   int process_sides_device(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len, hipStream_t stream,
                            std::vector<CallPlan> *plans_out = nullptr);
   // ... on host buffers of a single-stream batch (strides unused); synchronous.  The raw bytes of both sides move by the
@@ -139,25 +136,22 @@ class Batch {
   // in_data == nullptr or a null (first) entry: a chunk of silence.  `out` is an ordinary host output side with room for
   // the sum of the capacities: the results lie back to back in its buffer, or in every plane.  Only the frames a chunk
   // consumes travel (process_host_chunks); the passes run once over all chunks, the FIR once per run of chunks without
-  // dropped input.  S16 -> S16, F32 -> F32 and F32N -> F32N without matrix, planar side or dither IS process_host_chunks.
-  // A state whose channels stand apart (no matrix, dither off; else BAD_STATE) or in the zero fallback: the separate calls.
+  // dropped input.  Which calls ARE process_host_chunks and which states take the separate calls: SidesForm::Chunks.
   int process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, const void *const *in_data, uint32_t *in_len,
                                 const CallSide &out, uint32_t *out_len);
   // Dither of the integer output formats of the formatted and mixed calls (dither.h; include/speexhip_resampler.h,
   // "Dither"): a property of the state, off by default.  kind = SPEEXHIP_DITHER_*; stream s draws from
   // dither::stream_seed(seed, s); position = index of the next output frame of every stream.  While the kind is not NONE
-  // every formatted or mixed call advances each stream's position by the frames it produced, the formats of dithered_fmt
-  // (kernels.h) leave through the dithered instances of their pass, S16 -> S16 runs as the float call between convert_in
-  // and the dithered convert_out, and a state whose channels stand apart returns BAD_STATE.  No
-  // other call reads or moves any of this, and no control call (set_rate, set_quality, reset_mem, skip_zeros) touches it.
+  // every formatted or mixed call advances each stream's position by the frames it produced and the formats of
+  // dithered_fmt (kernels.h) leave through the dithered instances of their pass (the routes: sides_route.h).  No other
+  // call reads or moves any of this, and no control call (set_rate, set_quality, reset_mem, skip_zeros) touches it.
   int set_dither(int kind, uint64_t seed, uint64_t position);
   int get_dither(uint32_t stream, int *kind, uint64_t *seed, uint64_t *position) const;  // seed: the stream's own
   // The output meter of the formatted, mixed and sides calls (meter.h; include/speexhip_resampler.h, "Metering"): a
   // property of the state, off by default.  While it is on every such call -- host, device, batch, many-states, chunks --
   // is judged on its output side, sample by sample as it is encoded, into the stream's MeterCell in device memory: by the
   // metered instances of its output pass, or, where the call has none (a float result written by the FIR itself), by
-  // meter_image over the result.  S16 -> S16 then runs as the float call between convert_in and the metered convert_out,
-  // and a state whose channels stand apart returns BAD_STATE, as with dither on.  The int16, float, planar, per-channel,
+  // meter_image over the result (the routes: sides_route.h).  The int16, float, planar, per-channel,
   // chunks_int / _float, many_int / _float and take calls are never metered.  `samples` is kept here on the host: frames
   // produced x samples of an output frame, added when a call commits.  set_meter keeps the totals; no control call
   // (set_rate, set_quality, reset_mem, skip_zeros, set_dither) touches the switch or the totals.
@@ -170,10 +164,8 @@ class Batch {
   // on, every such call -- host, device, batch, many-states, chunks -- leaves through the gained instance of its output
   // pass, which multiplies every sample of output frame f of a stream by g(done + f); a result that no pass writes (the
   // float call on the same bytes, interleaved F32 without a matrix) is multiplied in place by gain_image behind the FIR
-  // launch, which judges it as well when the meter is on.  S16 -> S16 then runs as the float call between the two
-  // conversions, the planar float pairs between planes_in and planes_out, and a state whose channels stand apart returns
-  // BAD_STATE, as with dither or the meter on.  A stream whose own gain is off is not multiplied (selected per stream,
-  // wave-uniformly).  Every such call moves done by the frames produced, up to total.  The int16, float, planar,
+  // launch, which judges it as well when the meter is on (the routes: sides_route.h).  A stream whose own gain is off is
+  // not multiplied (selected per stream, wave-uniformly).  Every such call moves done by the frames produced, up to total.  The int16, float, planar,
   // per-channel, chunks_int / _float, many_int / _float and take calls neither apply the gain nor move done, and no
   // control call (set_rate, set_quality, reset_mem, skip_zeros, set_dither, set_meter) touches it.
   // set_gain: from = the gain the stream's next output frame would have had, to = gain, total = ramp_frames, done = 0;
@@ -218,12 +210,10 @@ class Batch {
   // ... with a format per state (formats.cpp): entry i is exactly process_sides_host(in[i], &in_len[i], out[i],
   // &out_len[i]) on states[i] -- bytes (in the modes whose bytes do not depend on the launch's shape: FAST_FIXED, EXACT),
   // counters, history, position, dither position and code.  bad (may be null): bad[i]
-  // != 0 = the caller's side could not be read (INVALID_ARG, nothing runs for it).  An entry whose state is one uniform
-  // stream out of the zero fallback and not named earlier in the call, and whose sides are interleaved (or of one channel)
-  // and have no matrix, is fused: S16 -> S16 without dither as the int16 call, F32 -> F32 and F32N -> F32N as the float
-  // call on the same bytes, everything else as the float call between the passes of kernels_convert_many.hip -- per launch
-  // group of <= 32 states one input pass, one FIR launch and one output pass, whatever formats the states name.  Every
-  // other entry takes its own process_sides_host call, in the caller's order, after the fused ones.
+  // != 0 = the caller's side could not be read (INVALID_ARG, nothing runs for it).  The entries that SidesForm::ManyEntry
+  // calls fusable are fused -- per launch group of <= 32 states one input pass (kernels_convert_many.hip), one FIR launch
+  // and one output pass, whatever formats the states name.  Every other entry takes its own process_sides_host call, in
+  // the caller's order, after the fused ones.
   static int process_host_many_sides(uint32_t n, Batch *const *states, const CallSide *in, uint32_t *in_len,
                                      const CallSide *out, uint32_t *out_len, const uint8_t *bad, int *codes);
   int device() const { return device_; }
@@ -316,8 +306,9 @@ class Batch {
   MeterPack meter_pack(uint32_t s0, uint32_t n) const;
   void meter_count(const uint32_t *produced, uint32_t per_frame);  // after a formatted or mixed call with the meter on
   // meter_image over what a call without an output pass wrote: stream s is lens[s] frames of channels() floats at
-  // result + s * stride (floats), judged as stored * scale
-  int meter_result(const void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream);
+  // result + s * stride (floats), judged as stored * scale.  buses: the state's buses and their cells in the place of its
+  // streams, as in side_pass
+  int meter_result(const void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream, bool buses = false);
   // whether any stream's gain is on: the state's formatted calls then take the gained routes
   bool gain_on() const;
   // the gains of streams [s0, s0 + n), as a gained launch takes them: first = the stream's done; per_frame = the samples
@@ -331,6 +322,19 @@ class Batch {
   // What a call without an output pass wrote (meter_result's arguments), finished in place: gain_image when gain is on --
   // which judges its product too when the meter is on -- meter_image otherwise.
   int image_result(void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream);
+  // The route of a formatted call (sides_route.h): the state as the rule sees it; what a call that ran moves afterwards --
+  // meter totals (per_frame samples a frame), gain ramps, dither positions; and the float images with the input pass
+  // (formats.cpp), shared by the sides call and the bus call.
+  SidesState sides_state(bool repeated = false) const;
+  void sides_moved(const SidesRoute &r, const uint32_t *produced, uint32_t per_frame);
+  struct SideImages {
+    const void *in;      // what the float call reads: the input image, or the caller's F32 storage
+    uint64_t in_stride;  // floats between two streams there
+    size_t out_pitch;    // floats between two streams of the output image
+    uint32_t most_out;   // the most frames any stream (or channel that stands apart) will produce
+  };
+  int prepare_images(const CallSide &in, const uint32_t *in_len, const uint32_t *out_len, const SidesRoute &r, bool split, bool bus,
+                     hipStream_t stream, SideImages *im);
   // process_sides_host of a call with a planar side
   int planes_host_call(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len);
   int fetch_history(std::vector<float> *host);
@@ -407,19 +411,16 @@ class Batch {
   int take_in_pieces(const void *in, uint32_t *in_len, uint32_t *out_len, bool float_io, void *blk, uint32_t pieces);
   // One entry of a many-states call, as many_run takes it.
   struct ManyEntry {
-    enum Kind { Int16, Float, Image };  // the int16 call / the float call on the entry's own bytes / the float call on
-                                        // float images, between the passes that convert the entry's formats
     Batch *b = nullptr;
     int rc = SPEEXHIP_ERR_SUCCESS;      // not SUCCESS: an argument error found already; nothing runs for the entry
     const void *in = nullptr;           // the entry's interleaved host buffers, in_fmt / out_fmt samples
     void *out = nullptr;
     int in_fmt = SPEEXHIP_FMT_S16, out_fmt = SPEEXHIP_FMT_S16;
-    Kind kind = Int16;
-    bool fusable = false;               // the sides are ones a launch group serves (the state decides the rest)
     bool sides = false;                 // an entry of process_host_many_sides: its own call is process_sides_host on
-    CallSide in_side = {}, out_side = {};  // these, and its dither position moves
+    CallSide in_side = {}, out_side = {};  // these, and the state's dither, meter and gain count
+    SidesRoute route;                   // many_run's: fused or its own call, and as what (SidesForm::ManyEntry)
   };
-  static int many_run(uint32_t n, const ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *codes);
+  static int many_run(uint32_t n, ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *codes);
   struct ManyUnit;  // many.cpp: the fused entries of one (device, lane), planned by many_plan.h and carried out
   bool have_copy_stream();  // copy_stream_ = a pool stream other than own_stream_ (false: none -> no piecewise call)
 

@@ -18,14 +18,6 @@ namespace speexhip {
 using namespace detail;
 
 namespace {
-inline bool planar(const CallSide &side) { return side_planar(side); }
-// The calls that are an existing call on the same bytes: nothing is converted, nothing extra launched.  (F32N -> F32N: a
-// power-of-two scale commutes exactly with the FIR.)  With dither on S16 -> S16 is no such call -- it runs as the float
-// call between convert_in and the dithered convert_out -- and the float pairs, written as ever, still count their frames.
-inline bool same_bytes(const CallSide &in, const CallSide &out, bool dith) {
-  if (in.mix != nullptr || out.mix != nullptr || in.fmt != out.fmt || planar(in) || planar(out)) return false;
-  return in.fmt == SPEEXHIP_FMT_S16 ? !dith : in.fmt == SPEEXHIP_FMT_F32 || in.fmt == SPEEXHIP_FMT_F32N;
-}
 // the side with its one stream at `base` (a staging buffer of a host call)
 inline CallSide at(const CallSide &side, const void *base) {
   return CallSide{side.fmt, side.channels, side.mix, const_cast<void *>(base), 0};
@@ -37,16 +29,41 @@ inline CallSide planes_at(const CallSide &side, const void *base, uint64_t pitch
   staged.plane_stride = pitch;
   return staged;
 }
-// Both sides planar, the same float format, no matrix: the planar float call on the same bytes (F32N: a power-of-two scale
-// commutes exactly with the FIR).
-inline bool planar_float_call(const CallSide &in, const CallSide &out) {
-  return planar(in) && planar(out) && in.mix == nullptr && out.mix == nullptr && in.fmt == out.fmt &&
-         (in.fmt == SPEEXHIP_FMT_F32 || in.fmt == SPEEXHIP_FMT_F32N);
-}
 // plane c of a host side
 inline char *host_plane(const CallSide &side, uint32_t c) {
   return side.planes != nullptr ? static_cast<char *>(side.planes[c])
                                 : static_cast<char *>(side.base) + c * side.plane_stride * sample_bytes(side.fmt);
+}
+// ... all of them, each `skip` bytes in
+inline std::vector<void *> host_planes(const CallSide &side, size_t skip = 0) {
+  std::vector<void *> planes(side.channels);
+  for (uint32_t c = 0; c < side.channels; c++) planes[c] = host_plane(side, c) + skip;
+  return planes;
+}
+// A host side that is not planar, as one buffer: a mono side given as its one plane is that plane.
+inline int flatten(CallSide *side) {
+  if (side_planar(*side) || side->planes == nullptr) return SPEEXHIP_ERR_SUCCESS;
+  if (side->planes[0] == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  side->base = side->planes[0];
+  side->planes = nullptr;
+  return SPEEXHIP_ERR_SUCCESS;
+}
+// a side given as plane pointers with one of them null
+inline bool lacks_plane(const CallSide &side) {
+  for (uint32_t c = 0; side.planes != nullptr && c < side.channels; c++)
+    if (side.planes[c] == nullptr) return true;
+  return false;
+}
+// whether the `out_bytes` written to a plane of a planar host result overlap another of its planes, or the `in_bytes`
+// read from a plane of `in` (may be null: no planar input to compare)
+inline bool planes_overlap(const CallSide &out, size_t out_bytes, const CallSide *in, size_t in_bytes) {
+  for (uint32_t c = 0; c < out.channels; c++) {
+    for (uint32_t k = 0; k < c; k++)
+      if (buffers_overlap(host_plane(out, c), out_bytes, host_plane(out, k), out_bytes)) return true;
+    for (uint32_t k = 0; in != nullptr && k < in->channels; k++)
+      if (buffers_overlap(host_plane(out, c), out_bytes, host_plane(*in, k), in_bytes)) return true;
+  }
+  return false;
 }
 }  // namespace
 
@@ -81,68 +98,49 @@ void Batch::dither_advance(const uint32_t *produced) {
   for (uint32_t s = 0; s < n_streams_; s++) dither_pos_[s] += produced[s];
 }
 
-int Batch::process_sides_device(const CallSide &in_side, uint32_t *in_len, const CallSide &out_side, uint32_t *out_len,
-                                hipStream_t stream, std::vector<CallPlan> *plans_out) {
-  if (!side_ok(in_side, channels_) || !side_ok(out_side, channels_)) return SPEEXHIP_ERR_INVALID_ARG;
-  if (!lengths_fit(in_len, out_len, n_streams_)) return SPEEXHIP_ERR_OVERFLOW;  // (engine.h; nothing touched)
-  // (a side of one channel is the same bytes in either layout)
-  CallSide in = in_side, out = out_side;
-  if (!planar(in)) in.layout = SPEEXHIP_LAYOUT_INTERLEAVED;
-  if (!planar(out)) out.layout = SPEEXHIP_LAYOUT_INTERLEAVED;
-  ON_DEVICE();
-  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), gained = gain_on();
-  // (what the meter asks of the routes below a gained stream asks too: no shortcut past the output side)
-  const bool meter = meter_on_ || gained;
-  bool split = false;
-  for (uint32_t s = 0; s < n_streams_; s++)
-    if (!uniform(s)) {
-      // (channels that stand apart produce different numbers of frames: neither an output frame of a matrix nor a dither
-      //  position nor a stream of samples to meter nor a frame index of a gain is defined)
-      if (n_streams_ != 1 || dith || mixed || meter) return SPEEXHIP_ERR_BAD_STATE;
-      split = true;
-    }
-  if (same_bytes(in, out, dith || meter)) {
-    // (with the meter on: F32 or F32N, the float call's bytes as ever, read once more by meter_image; with gain on:
-    //  multiplied in place by gain_image, an F32N result as stored, and judged in that same pass)
-    const int rc = process_device(in.base, in.stride, in_len, out.base, out.stride, out_len, in.fmt != SPEEXHIP_FMT_S16, stream);
-    if (meter && ran(rc)) {
-      const int mrc = image_result(out.base, out.stride, out_len, in.fmt == SPEEXHIP_FMT_F32N ? 32768.0f : 1.0f, stream);
-      if (mrc != SPEEXHIP_ERR_SUCCESS) return mrc;
-      if (meter_on_) meter_count(out_len, channels_);
-      if (gained) gain_advance(out_len);
-    }
-    if (dith && ran(rc)) dither_advance(out_len);
-    return rc;
-  }
-  // (with the meter on the planar float pairs run between planes_in and the metered planes_out)
-  if (planar_float_call(in, out) && !split && !meter) {
-    const int rc = process_planar_device(in.base, in.stride, in.plane_stride, in_len, out.base, out.stride, out.plane_stride,
-                                         out_len, true, stream);
-    if (dith && ran(rc)) dither_advance(out_len);
-    return rc;
-  }
+// ---- the route (sides_route.h), described and obeyed ----------------------------------------------------------------------
+SidesState Batch::sides_state(bool repeated) const {
+  SidesState st = {dither_on(), meter_on_, gain_on(), false, zero_mode_, n_streams_ == 1, repeated};
+  for (uint32_t s = 0; s < n_streams_ && !st.split; s++) st.split = !uniform(s);
+  return st;
+}
+void Batch::sides_moved(const SidesRoute &r, const uint32_t *produced, uint32_t per_frame) {
+  if (r.counts_meter) meter_count(produced, per_frame);
+  if (r.moves_gain) gain_advance(produced);
+  if (r.moves_dither) dither_advance(produced);
+}
+
+// The float images of a call and its input pass: one stream after the other, whole 128-byte lines each, sized from what
+// this call moves.  (The zero fallback goes through them as well: its history still takes the converted input, and its
+// silence is whatever the float call writes, converted -- and dithered.)  bus: the streams' results always lie in the
+// state's image, whatever the route, and the image of the buses is sized here as well.
+int Batch::prepare_images(const CallSide &in, const uint32_t *in_len, const uint32_t *out_len, const SidesRoute &r, bool split,
+                          bool bus, hipStream_t stream, SideImages *im) {
+  // what the float call will do, known before anything is launched (integer arithmetic)
   const EntryRules rules = entry_rules(true);
-  // what the float call will do, known before anything is launched (integer arithmetic): sizes the images
-  uint32_t most_in = 0, most_out = 0;
+  uint32_t most_in = 0;
+  im->most_out = 0;
   for (uint32_t s = 0; s < n_streams_; s++) {
     most_in = std::max(most_in, in_len[s]);
     for (uint32_t c = 0; c < (split ? channels_ : 1u); c++)
-      most_out = std::max(most_out, plan_call(filter_.num, filter_.den, in_len[s], out_len[s], P(s, c), rules).produced);
+      im->most_out = std::max(im->most_out, plan_call(filter_.num, filter_.den, in_len[s], out_len[s], P(s, c), rules).produced);
   }
-  // a side passes through an image unless it has no matrix and its storage IS the image (interleaved F32); a present but
-  // empty input is not silence: no frame is read, any non-null address serves
-  const bool pass_in = (in.mix != nullptr || in.fmt != SPEEXHIP_FMT_F32 || planar(in)) && in.base != nullptr && most_in != 0;
-  const bool pass_out = out.mix != nullptr || out.fmt != SPEEXHIP_FMT_F32 || planar(out);
-  // The float images: one stream after the other, whole 128-byte lines each, sized from what this call moves.  (The zero
-  // fallback goes through them as well: its history still takes the converted input, and its silence is whatever the
-  // float call writes, converted -- and dithered.)
+  // a present but empty input is not silence: no frame is read, any non-null address serves
+  const bool pass_in = r.pass_in && in.base != nullptr && most_in != 0;
   const size_t in_pitch = align64(static_cast<size_t>(most_in) * channels_);
-  const size_t out_pitch = align64(static_cast<size_t>(most_out) * channels_);
+  im->out_pitch = align64(static_cast<size_t>(im->most_out) * channels_);
   int rc = ensure_planar_scratch(pass_in ? in_pitch * n_streams_ * sizeof(float) : 0,
-                                 pass_out ? out_pitch * n_streams_ * sizeof(float) : 0);
+                                 bus || r.pass_out ? im->out_pitch * n_streams_ * sizeof(float) : 0);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  if (pass_in || (pass_out && most_out != 0)) {
-    // (the images belong to the state: a call on another stream than the previous one waits for it first)
+  const size_t bus_bytes = bus && r.pass_out ? im->out_pitch * n_buses_ * sizeof(float) : 0;
+  if (bus_bytes > bus_image_cap_) {
+    rc = quiesce();  // (a grow waits for the state's own last call, which may still read the old image)
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+    rc = grow_stage(device_, &d_bus_image_, &bus_image_cap_, bus_bytes, false);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  }
+  if (bus || pass_in || (r.pass_out && im->most_out != 0)) {
+    // (the images and the cells belong to the state: a call on another stream than the previous one waits for it first)
     rc = chain_to(stream);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
@@ -150,33 +148,59 @@ int Batch::process_sides_device(const CallSide &in_side, uint32_t *in_len, const
     rc = side_pass(in, true, d_planar_in_, in_pitch, in_len, stream);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
-  const void *image_in = pass_in ? static_cast<const void *>(d_planar_in_) : in.base;
-  void *image_out = pass_out ? static_cast<void *>(d_planar_out_) : out.base;
+  im->in = pass_in ? static_cast<const void *>(d_planar_in_) : in.base;
+  im->in_stride = pass_in ? in_pitch : in.stride;
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+int Batch::process_sides_device(const CallSide &in_side, uint32_t *in_len, const CallSide &out_side, uint32_t *out_len,
+                                hipStream_t stream, std::vector<CallPlan> *plans_out) {
+  if (!side_ok(in_side, channels_) || !side_ok(out_side, channels_)) return SPEEXHIP_ERR_INVALID_ARG;
+  if (!lengths_fit(in_len, out_len, n_streams_)) return SPEEXHIP_ERR_OVERFLOW;  // (engine.h; nothing touched)
+  // (a side of one channel is the same bytes in either layout)
+  CallSide in = in_side, out = out_side;
+  if (!side_planar(in)) in.layout = SPEEXHIP_LAYOUT_INTERLEAVED;
+  if (!side_planar(out)) out.layout = SPEEXHIP_LAYOUT_INTERLEAVED;
+  ON_DEVICE();
+  const SidesState st = sides_state();
+  const SidesRoute r = route_sides_call(SidesForm::Device, side_kind(in), side_kind(out), st);
+  if (r.refuse != SPEEXHIP_ERR_SUCCESS) return r.refuse;
+  int rc;
+  void *result = out.base;  // what a call without an output pass wrote
   std::vector<CallPlan> plans;  // of the channels of a state whose channels stand apart
-  if (split)
-    rc = process_split(image_in, in_len, image_out, out_len, true, stream, &plans);
-  else
-    rc = process_device(image_in, pass_in ? in_pitch : in.stride, in_len, image_out, pass_out ? out_pitch : out.stride, out_len,
-                        true, stream);
-  if (!ran(rc)) return rc;
-  if (plans_out != nullptr) *plans_out = plans;
-  if (pass_out) {
-    // (out_len: what the float call produced)
-    const int prc = side_pass(out, false, d_planar_out_, out_pitch, out_len, stream, split ? plans.data() : nullptr);
-    if (prc != SPEEXHIP_ERR_SUCCESS) return prc;
-  } else if (meter) {
-    // (interleaved F32 without a matrix: the FIR wrote the caller's buffer)
-    const int mrc = image_result(out.base, out.stride, out_len, 1.0f, stream);
-    if (mrc != SPEEXHIP_ERR_SUCCESS) return mrc;
+  if (r.kind == SidesRoute::PlanarFloatCall) {
+    rc = process_planar_device(in.base, in.stride, in.plane_stride, in_len, out.base, out.stride, out.plane_stride, out_len, true,
+                               stream);
+  } else if (r.kind != SidesRoute::Images) {
+    rc = process_device(in.base, in.stride, in_len, out.base, out.stride, out_len, r.kind == SidesRoute::FloatCall, stream);
+  } else {
+    SideImages im;
+    rc = prepare_images(in, in_len, out_len, r, st.split, false, stream, &im);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+    if (r.pass_out) result = d_planar_out_;
+    if (st.split)
+      rc = process_split(im.in, in_len, result, out_len, true, stream, &plans);
+    else
+      rc = process_device(im.in, im.in_stride, in_len, result, r.pass_out ? im.out_pitch : out.stride, out_len, true, stream);
+    if (ran(rc) && plans_out != nullptr) *plans_out = plans;
+    if (ran(rc) && r.pass_out) {
+      // (out_len: what the float call produced)
+      const int prc = side_pass(out, false, d_planar_out_, im.out_pitch, out_len, stream, st.split ? plans.data() : nullptr);
+      if (prc != SPEEXHIP_ERR_SUCCESS) return prc;
+    }
   }
-  if (meter_on_) meter_count(out_len, out.channels);
-  if (gained) gain_advance(out_len);
-  if (dith) dither_advance(out_len);
+  if (!ran(rc)) return rc;
+  if (r.finish != SidesRoute::Nothing) {
+    // (the FIR wrote the caller's buffer: read once more by meter_image, or multiplied in place by gain_image, an F32N
+    //  result as stored, and judged in that same pass)
+    const int frc = image_result(result, out.stride, out_len, r.finish_scale, stream);
+    if (frc != SPEEXHIP_ERR_SUCCESS) return frc;
+  }
+  sides_moved(r, out_len, out.channels);
   return rc;
 }
 
-// The formatted many-states call (engine.h): which entries a launch group can serve and as what -- the rules of
-// process_sides_host above, entry by entry -- then many_run (many.cpp).
+// The formatted many-states call (engine.h): the entries as many_run takes them, which asks the route of each (many.cpp).
 int Batch::process_host_many_sides(uint32_t n, Batch *const *st, const CallSide *in, uint32_t *in_len, const CallSide *out,
                                    uint32_t *out_len, const uint8_t *bad, int *codes) {
   std::vector<ManyEntry> entries(n);
@@ -193,20 +217,8 @@ int Batch::process_host_many_sides(uint32_t n, Batch *const *st, const CallSide 
     e.out_side = out[i];
     e.in_fmt = in[i].fmt;
     e.out_fmt = out[i].fmt;
-    // fused: both sides interleaved (or of one channel) in one buffer each, no matrix
-    e.fusable = !planar(in[i]) && !planar(out[i]) && in[i].mix == nullptr && out[i].mix == nullptr && in[i].planes == nullptr &&
-                out[i].planes == nullptr;
-    // (a metered result that no pass of kernels_convert_many.hip writes -- F32, or the float call on the same bytes --
-    //  takes its own call, which runs meter_image behind it)
-    if (b->meter_on_ && (out[i].fmt == SPEEXHIP_FMT_F32 || (in[i].fmt == out[i].fmt && out[i].fmt == SPEEXHIP_FMT_F32N)))
-      e.fusable = false;
-    if (!e.fusable) continue;
-    e.in = in[i].base;
+    e.in = in[i].base;  // (read where the entry is fused: one interleaved buffer a side)
     e.out = out[i].base;
-    // (a gained entry stays fused: S16 -> S16 between its two passes, a float result multiplied by gain_image in the group)
-    e.kind = !same_bytes(in[i], out[i], b->dither_on() || b->meter_on_ || b->gain_on()) ? ManyEntry::Image
-             : in[i].fmt == SPEEXHIP_FMT_S16            ? ManyEntry::Int16
-                                                        : ManyEntry::Float;
   }
   return many_run(n, entries.data(), in_len, out_len, codes);
 }
@@ -214,33 +226,24 @@ int Batch::process_host_many_sides(uint32_t n, Batch *const *st, const CallSide 
 // process_sides_device on own_stream_ around a single-stream call's host buffers: the raw bytes of both sides move by the
 // rule of host_transfer.h -- in place when pinned, through the bounce buffers when small, by the runtime's staged copy when
 // large; channels that stand apart as in process_host.
-int Batch::process_sides_host(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len) {
+int Batch::process_sides_host(const CallSide &in_side, uint32_t *in_len, const CallSide &out_side, uint32_t *out_len) {
   if (n_streams_ != 1) return SPEEXHIP_ERR_BAD_STATE;
-  if (!side_ok(in, channels_) || !side_ok(out, channels_)) return SPEEXHIP_ERR_INVALID_ARG;
+  if (!side_ok(in_side, channels_) || !side_ok(out_side, channels_)) return SPEEXHIP_ERR_INVALID_ARG;
   if (!lengths_fit(in_len, out_len, 1)) return SPEEXHIP_ERR_OVERFLOW;
-  if (planar(in) || planar(out)) return planes_host_call(in, in_len, out, out_len);
-  // (a mono side given as its one plane)
-  if (in.planes != nullptr || out.planes != nullptr) {
-    if ((in.planes != nullptr && in.planes[0] == nullptr) || (out.planes != nullptr && out.planes[0] == nullptr))
-      return SPEEXHIP_ERR_INVALID_ARG;
-    CallSide in1 = in, out1 = out;
-    if (in.planes != nullptr) in1.base = in.planes[0], in1.planes = nullptr;
-    if (out.planes != nullptr) out1.base = out.planes[0], out1.planes = nullptr;
-    return process_sides_host(in1, in_len, out1, out_len);
-  }
-  if (out.base == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
-  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), split = !uniform(0);
-  const bool gained = gain_on();
-  if (split && (dith || meter_on_ || gained) && !mixed) return SPEEXHIP_ERR_BAD_STATE;
-  // (with the meter or gain on the float pairs go on below: process_sides_device runs meter_image or gain_image behind the
-  //  float call)
-  if (same_bytes(in, out, dith) && !meter_on_ && !gained) {
-    const int rc = process_host(in.base, in_len, out.base, out_len, in.fmt != SPEEXHIP_FMT_S16);
-    if (dith && ran(rc)) dither_advance(out_len);
+  if (side_planar(in_side) || side_planar(out_side)) return planes_host_call(in_side, in_len, out_side, out_len);
+  CallSide in = in_side, out = out_side;
+  if (flatten(&in) != SPEEXHIP_ERR_SUCCESS || flatten(&out) != SPEEXHIP_ERR_SUCCESS || out.base == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  const SidesState st = sides_state();
+  const SidesRoute r = route_sides_call(SidesForm::Host, side_kind(in), side_kind(out), st);
+  if (r.refuse != SPEEXHIP_ERR_SUCCESS && !r.refuse_late) return r.refuse;
+  if (r.direct) {
+    const int rc = process_host(in.base, in_len, out.base, out_len, r.kind == SidesRoute::FloatCall);
+    if (ran(rc)) sides_moved(r, out_len, out.channels);
     return rc;
   }
   ON_DEVICE();
-  if (split && mixed) return SPEEXHIP_ERR_BAD_STATE;
+  if (r.refuse != SPEEXHIP_ERR_SUCCESS) return r.refuse;
+  const bool split = st.split;
   const size_t bout = sample_bytes(out.fmt);
   // (only as many output frames as this call can produce need a device buffer)
   const size_t in_bytes = static_cast<size_t>(*in_len) * in.channels * sample_bytes(in.fmt);
@@ -328,38 +331,32 @@ int Batch::process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, cons
                                      const CallSide &out_side, uint32_t *out_len) {
   if (n_streams_ != 1) return SPEEXHIP_ERR_BAD_STATE;
   if (!side_ok(in, channels_) || !side_ok(out_side, channels_)) return SPEEXHIP_ERR_INVALID_ARG;
-  const bool pl_in = planar(in), pl_out = planar(out_side);
-  // (a mono side given as its one plane is an interleaved buffer)
+  const bool pl_in = side_planar(in), pl_out = side_planar(out_side);
   CallSide out = out_side;
-  if (!pl_out && out.planes != nullptr) out.base = out.planes[0], out.planes = nullptr;
-  if (out.base == nullptr && out.planes == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
-  for (uint32_t c = 0; out.planes != nullptr && c < out.channels; c++)
-    if (out.planes[c] == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  if (flatten(&out) != SPEEXHIP_ERR_SUCCESS || (out.base == nullptr && out.planes == nullptr) || lacks_plane(out))
+    return SPEEXHIP_ERR_INVALID_ARG;
   // entries of in_data per chunk; a present chunk has all its planes
   const uint32_t per = pl_in ? in.channels : 1u;
   const auto entry = [&](uint32_t i, uint32_t c) { return in_data != nullptr ? in_data[static_cast<size_t>(i) * per + c] : nullptr; };
   for (uint32_t i = 0; i < n_chunks; i++)
     for (uint32_t c = 1; entry(i, 0) != nullptr && c < per; c++)
       if (entry(i, c) == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
-  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), gained = gain_on(), split = !uniform(0);
-  const bool meter = meter_on_ || gained;  // (a gained stream asks of the routes what the meter asks)
-  if (split && (dith || mixed || meter)) return SPEEXHIP_ERR_BAD_STATE;
-  // same: the call on the same bytes; with the meter on (F32 or F32N then) it still goes through here, without passes,
-  // and meter_image reads the result -- or gain_image multiplies it, once over all chunks: the ramp's index runs on
-  // across the chunk boundaries as the dither's does
-  const bool same = same_bytes(in, out, dith || meter), own_calls = split || zero_mode_;
+  // With the meter or gain on the call on the same bytes (F32 or F32N then) is staged here without passes and finished
+  // once over all chunks: the ramp's index runs on across the chunk boundaries as the dither's does.
+  const SidesRoute r = route_sides_call(SidesForm::Chunks, side_kind(in), side_kind(out), sides_state());
+  if (r.refuse != SPEEXHIP_ERR_SUCCESS) return r.refuse;
   const size_t bin = sample_bytes(in.fmt), bout = sample_bytes(out.fmt);
-  if (own_calls && (!same || meter)) {  // rare states: the separate calls, one after the other, each output side behind the frames written
+  if (r.kind == SidesRoute::OwnCalls) {  // rare states: the separate calls, one after the other, each output side behind the frames written
     int last = SPEEXHIP_ERR_SUCCESS;
     uint64_t written = 0;
-    std::vector<void *> planes(out.channels);
     for (uint32_t i = 0; i < n_chunks; i++) {
       CallSide a = in, b = out;
       a.base = const_cast<void *>(entry(i, 0));
       a.planes = nullptr;
       if (pl_in && a.base != nullptr) a.planes = const_cast<void *const *>(in_data + static_cast<size_t>(i) * per), a.base = nullptr;
+      std::vector<void *> planes;
       if (pl_out) {
-        for (uint32_t c = 0; c < out.channels; c++) planes[c] = host_plane(out, c) + written * bout;
+        planes = host_planes(out, written * bout);
         if (out.planes != nullptr) b.planes = planes.data();
         else b.base = planes[0];
       } else {
@@ -372,22 +369,20 @@ int Batch::process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, cons
     }
     return last;
   }
-  const ChunkPlans p = plan_chunks(filter_.num, filter_.den, n_chunks, in_len, out_len, P(0, 0), entry_rules(!same || in.fmt != SPEEXHIP_FMT_S16));
-  if (same && !meter) {  // process_host_chunks on the same bytes (which serves the rare states itself)
-    const int rc = process_host_chunks(n_chunks, in_data, in_len, out.base, out_len, in.fmt != SPEEXHIP_FMT_S16);
+  const ChunkPlans p = plan_chunks(filter_.num, filter_.den, n_chunks, in_len, out_len, P(0, 0), entry_rules(r.kind != SidesRoute::Int16Call));
+  if (r.direct) {  // process_host_chunks on the same bytes (which serves the rare states itself)
+    const int rc = process_host_chunks(n_chunks, in_data, in_len, out.base, out_len, r.kind == SidesRoute::FloatCall);
     if (!ran(rc)) return rc;
     uint32_t made = 0;
     for (uint32_t i = 0; i < n_chunks; i++) made += out_len[i];
-    if (dith) dither_advance(&made);
-    if (own_calls) count_chunks(3, n_chunks);
-    else count_chunks(0, p.launches);
+    sides_moved(r, &made, out.channels);
+    if (r.fusable) count_chunks(0, p.launches);
+    else count_chunks(3, n_chunks);
     return rc;
   }
   if (p.frames > 0x7fffffffull || p.made > 0x7fffffffull) return SPEEXHIP_ERR_OVERFLOW;
   // (only so many frames are written to a plane: the sum of what the chunks will make)
-  for (uint32_t c = 0; pl_out && c < out.channels; c++)
-    for (uint32_t k = 0; k < c; k++)
-      if (buffers_overlap(host_plane(out, c), p.made * bout, host_plane(out, k), p.made * bout)) return SPEEXHIP_ERR_PTR_OVERLAP;
+  if (pl_out && planes_overlap(out, p.made * bout, nullptr, 0)) return SPEEXHIP_ERR_PTR_OVERLAP;
   ON_DEVICE();
   for (uint32_t i = 0; i < n_chunks; i++)
     if (in_len[i] != 0 && out_len[i] != 0) started_[0] = 1;
@@ -411,8 +406,7 @@ int Batch::process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, cons
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   // The passes of process_sides_device, once over all chunks: conversion, matrix and dither are per sample or per frame,
   // and the dither index runs on over the chunks' output frames as the position does.
-  const bool pass_in = !same && (in.mix != nullptr || in.fmt != SPEEXHIP_FMT_F32 || pl_in) && frames != 0;
-  const bool pass_out = !same && (out.mix != nullptr || out.fmt != SPEEXHIP_FMT_F32 || pl_out);
+  const bool pass_in = r.pass_in && frames != 0, pass_out = r.pass_out;
   const size_t fi = channels_ * sizeof(float);  // bytes of a frame of the float images
   rc = ensure_planar_scratch(pass_in ? align64(static_cast<size_t>(frames) * channels_) * sizeof(float) : 0,
                              pass_out ? align64(static_cast<size_t>(made) * channels_) * sizeof(float) : 0);
@@ -440,17 +434,13 @@ int Batch::process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, cons
   if (pass_out) {
     rc = side_pass(pl_out ? planes_at(out, call.dst, out_pitch) : at(out, call.dst), false, d_planar_out_, 0, &made, own_stream_);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  } else if (meter) {
-    rc = image_result(call.dst, 0, &made, out.fmt == SPEEXHIP_FMT_F32N ? 32768.0f : 1.0f, own_stream_);
+  } else if (r.finish != SidesRoute::Nothing) {
+    rc = image_result(call.dst, 0, &made, r.finish_scale, own_stream_);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
-  if (meter_on_) meter_count(&made, out.channels);
-  if (gained) gain_advance(&made);
-  if (dith) dither_advance(&made);
+  sides_moved(r, &made, out.channels);
   if (pl_out) {
-    std::vector<void *> planes(out.channels);
-    for (uint32_t c = 0; c < out.channels; c++) planes[c] = host_plane(out, c);
-    rc = call.finish_planes(planes.data(), out.channels, out_pitch * bout, bout, std::vector<uint32_t>(out.channels, made).data());
+    rc = call.finish_planes(host_planes(out).data(), out.channels, out_pitch * bout, bout, std::vector<uint32_t>(out.channels, made).data());
   } else {
     rc = call.finish_whole(out.base, static_cast<size_t>(made) * out.channels * bout);
   }
@@ -470,31 +460,21 @@ int Batch::process_sides_host_chunks(uint32_t n_chunks, const CallSide &in, cons
 // a planar side plane by plane into an image whose planes lie whole 128-byte lines apart, as in process_planar_host (all
 // planes of a side have one size, so one route serves the side).  process_sides_device then runs on the images.
 int Batch::planes_host_call(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len) {
-  const bool pl_in = planar(in), pl_out = planar(out);
-  const bool mixed = in.mix != nullptr || out.mix != nullptr, dith = dither_on(), split = !uniform(0);
-  if (split && (dith || mixed || meter_on_ || gain_on())) return SPEEXHIP_ERR_BAD_STATE;
-  // (a mono side given as its one plane is an interleaved buffer)
+  const bool pl_in = side_planar(in), pl_out = side_planar(out);
+  const SidesState st = sides_state();
+  const SidesRoute r = route_sides_call(SidesForm::PlanesHost, side_kind(in), side_kind(out), st);
+  if (r.refuse != SPEEXHIP_ERR_SUCCESS) return r.refuse;
+  const bool split = st.split;
   CallSide in_flat = in, out_flat = out;
-  if ((!pl_in && in.planes != nullptr && in.planes[0] == nullptr) || (!pl_out && out.planes != nullptr && out.planes[0] == nullptr))
-    return SPEEXHIP_ERR_INVALID_ARG;
-  if (!pl_in && in.planes != nullptr) in_flat.base = in.planes[0];
-  if (!pl_out && out.planes != nullptr) out_flat.base = out.planes[0];
-  const bool present = pl_in ? in.planes != nullptr || in.base != nullptr : in_flat.base != nullptr;
-  if (pl_out ? out.planes == nullptr && out.base == nullptr : out_flat.base == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
-  for (uint32_t c = 0; pl_in && in.planes != nullptr && c < in.channels; c++)
-    if (in.planes[c] == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
-  for (uint32_t c = 0; pl_out && out.planes != nullptr && c < out.channels; c++)
-    if (out.planes[c] == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  if (flatten(&in_flat) != SPEEXHIP_ERR_SUCCESS || flatten(&out_flat) != SPEEXHIP_ERR_SUCCESS) return SPEEXHIP_ERR_INVALID_ARG;
+  const bool present = in_flat.planes != nullptr || in_flat.base != nullptr;
+  if (out_flat.planes == nullptr && out_flat.base == nullptr) return SPEEXHIP_ERR_INVALID_ARG;
+  if (lacks_plane(in_flat) || lacks_plane(out_flat)) return SPEEXHIP_ERR_INVALID_ARG;
   const uint32_t frames = *in_len;
   const uint32_t most = will_make(frames, *out_len);  // only so many output frames are written (and need a device buffer)
   const size_t bin = sample_bytes(in.fmt), bout = sample_bytes(out.fmt);
   const size_t plane_in = frames * bin, plane_out = most * bout;
-  for (uint32_t c = 0; pl_out && c < out.channels; c++) {
-    for (uint32_t k = 0; k < c; k++)
-      if (buffers_overlap(host_plane(out, c), plane_out, host_plane(out, k), plane_out)) return SPEEXHIP_ERR_PTR_OVERLAP;
-    for (uint32_t k = 0; pl_in && present && k < in.channels; k++)
-      if (buffers_overlap(host_plane(out, c), plane_out, host_plane(in, k), plane_in)) return SPEEXHIP_ERR_PTR_OVERLAP;
-  }
+  if (pl_out && planes_overlap(out, plane_out, pl_in && present ? &in : nullptr, plane_in)) return SPEEXHIP_ERR_PTR_OVERLAP;
   ON_DEVICE();
   // what each side moves (payload) and the image the device call works on
   const size_t in_pitch = align64(frames), out_pitch = align64(most);
@@ -523,9 +503,7 @@ int Batch::planes_host_call(const CallSide &in, uint32_t *in_len, const CallSide
   const std::vector<uint32_t> made = made_per_channel(out.channels, *out_len, split ? plans.data() : nullptr);
   int frc;
   if (pl_out) {
-    std::vector<void *> planes(out.channels);
-    for (uint32_t c = 0; c < out.channels; c++) planes[c] = host_plane(out, c);
-    frc = call.finish_planes(planes.data(), out.channels, out_pitch * bout, bout, made.data());
+    frc = call.finish_planes(host_planes(out).data(), out.channels, out_pitch * bout, bout, made.data());
   } else if (split) {
     frc = call.finish_samples(out_flat.base, out.channels, out.channels, bout, made.data());
   } else {

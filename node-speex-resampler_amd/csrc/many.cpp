@@ -32,7 +32,7 @@ struct ManyStage {
   std::vector<hipEvent_t> events;
   char *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
   size_t d_in_cap = 0, d_out_cap = 0, h_in_cap = 0, h_out_cap = 0;
-  // the float images of the entries whose storage is not the image (ManyEntry::Image): device scratch either side of the
+  // the float images of the entries whose storage is not the image (SidesRoute::Images): device scratch either side of the
   // FIR launch, one range per entry
   char *d_img_in = nullptr, *d_img_out = nullptr;
   size_t d_img_in_cap = 0, d_img_out_cap = 0;
@@ -158,17 +158,16 @@ void Batch::ManyUnit::describe(const std::vector<uint32_t> &idx, const ManyEntry
     it.i = idx[k];
     it.e = &entries[it.i];
     it.b = it.e->b;
-    it.float_io = it.e->kind != ManyEntry::Int16;
+    const SidesRoute &r = it.e->route;
+    it.float_io = r.kind != SidesRoute::Int16Call;
     it.plan = plan_call(it.b->filter_.num, it.b->filter_.den, in_len[it.i], out_len[it.i], it.b->P(0, 0), it.b->entry_rules(it.float_io));
     // the raw bytes of either side, in the side's own format: what every size decision goes by
     s.in_present = it.e->in != nullptr;
     s.in_bytes = s.in_present ? raw_bytes(*it.e, in_len[it.i], true) : 0;
     s.out_bytes = raw_bytes(*it.e, it.plan.produced, false);
-    // (formats.cpp, process_sides_device: F32 storage IS the image; a present but empty input is not silence, no frame of
-    //  it is read)
-    const bool image = it.e->kind == ManyEntry::Image;
-    s.pass_in = image && it.e->in_fmt != SPEEXHIP_FMT_F32 && s.in_present && in_len[it.i] != 0;
-    s.pass_out = image && it.e->out_fmt != SPEEXHIP_FMT_F32;
+    // (a present but empty input is not silence, no frame of it is read)
+    s.pass_in = r.pass_in && s.in_present && in_len[it.i] != 0;
+    s.pass_out = r.pass_out;
     s.image_in = static_cast<size_t>(in_len[it.i]) * it.b->channels_ * sizeof(float);
     s.image_out = static_cast<size_t>(it.plan.produced) * it.b->channels_ * sizeof(float);
     pinned_sides(it.e->in, s.in_bytes, it.e->out, s.out_bytes, &it.pin_in, &it.pin_out);
@@ -227,12 +226,9 @@ void Batch::ManyUnit::commit_item(Item &it, bool work) {
   if (!it.float_io && work) it.b->int16_call_done(&it.plan, 1);
   in_len[it.i] = it.plan.consumed;
   out_len[it.i] = it.plan.produced;
-  // (a formatted call of a state with dither on moves its position by the frames produced, whatever the format)
-  if (it.e->sides && it.b->dither_on()) it.b->dither_advance(&out_len[it.i]);
-  // (... and of a state with the meter on is metered: its output pass has judged these frames into the state's cell)
-  if (it.e->sides && it.b->meter_on_) it.b->meter_count(&out_len[it.i], it.b->channels_);
-  // (... and of a state with gain on has left at its g: the ramp moves by the frames produced)
-  if (it.e->sides && it.b->gain_on()) it.b->gain_advance(&out_len[it.i]);
+  // (a formatted call moves the state's dither position, meter totals and gain ramp by the frames produced, whatever the
+  //  format: its output pass has judged these frames into the state's cell and left them at its g)
+  it.b->sides_moved(it.e->route, &out_len[it.i], it.b->channels_);
   rcs[it.i] = SPEEXHIP_ERR_SUCCESS;
 }
 
@@ -291,10 +287,10 @@ int Batch::ManyUnit::launch_group(const std::vector<uint32_t> &g, hipStream_t st
       const bool dithered = b->dither_on() && dithered_fmt(it.e->out_fmt);
       c.reserved = convert_many_tag(it.e->out_fmt, dithered ? b->dither_kind_ : SPEEXHIP_DITHER_NONE);
       if (dithered) dith.s[j] = b->dither_pack(0, 1, b->channels_).s[0];
-      if (b->meter_on_) cells.cell[j] = b->d_meter_, metered = true;
-      if (it.e->sides && b->gain_on()) gains.s[j] = b->gain_pack(0, 1, b->channels_).s[0], gained = true;
+      if (it.e->route.counts_meter) cells.cell[j] = b->d_meter_, metered = true;
+      if (it.e->route.moves_gain) gains.s[j] = b->gain_pack(0, 1, b->channels_).s[0], gained = true;
       most_from = std::max(most_from, c.n);
-    } else if (it.e->sides && it.float_io && b->gain_on() && it.plan.produced != 0) {
+    } else if (it.e->route.finish == SidesRoute::GainImage && it.plan.produced != 0) {
       ConvertStream &c = in_place.s[j];
       c.dst = storage_out;
       c.n = static_cast<uint64_t>(it.plan.produced) * b->channels_;
@@ -319,6 +315,7 @@ int Batch::ManyUnit::launch_group(const std::vector<uint32_t> &g, hipStream_t st
   }
   if (most_in_place != 0) {
     // (a metered F32 result is no entry of a group -- process_host_many_sides -- so nothing is judged here)
+    // (the route's finish_scale is 1 for every fused entry)
     if (hip_failed(launch_gain_image(in_place, image_gains, nullptr, 1.0f, cnt, most_in_place, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
     count_many(2);
   }
@@ -469,8 +466,6 @@ int Batch::process_host_many(uint32_t n, Batch *const *st, const void *const *in
     e.in = in[i];
     e.out = out[i];
     e.in_fmt = e.out_fmt = float_io ? SPEEXHIP_FMT_F32 : SPEEXHIP_FMT_S16;
-    e.kind = float_io ? ManyEntry::Float : ManyEntry::Int16;
-    e.fusable = true;
     if (st[i] == nullptr || (out[i] == nullptr && out_len[i] != 0)) e.rc = SPEEXHIP_ERR_INVALID_ARG;
   }
   return many_run(n, entries.data(), in_len, out_len, codes);
@@ -500,7 +495,7 @@ std::vector<Unit> Batch::ManyUnit::units_of(const std::map<int, std::vector<uint
   return units;
 }
 
-int Batch::many_run(uint32_t n, const ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *codes) {
+int Batch::many_run(uint32_t n, ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *codes) {
   std::vector<int> rcs(n, SPEEXHIP_ERR_SUCCESS);
   std::map<int, std::vector<uint32_t>> by_device;  // (ordered: two concurrent calls lock their devices in one order)
   std::vector<uint32_t> apart;                     // states that take the single call (in the caller's order)
@@ -517,8 +512,14 @@ int Batch::many_run(uint32_t n, const ManyEntry *entries, uint32_t *in_len, uint
     bool earlier = false;  // a state named twice: its second call must see the first one's end state
     for (uint32_t j = 0; j < i && !earlier; j++) earlier = entries[j].b == b;
     // (rare states -- channels moved apart by the per-channel calls, the zero fallback, batches of several streams --
-    //  and the sides a launch group does not serve -- a matrix, planes of several channels -- keep their own call's rules)
-    if (earlier || !entries[i].fusable || b->n_streams_ != 1 || !b->uniform(0) || b->zero_mode_)
+    //  and the sides a launch group does not serve -- a matrix, planes of several channels -- keep their own call's rules.
+    //  An entry of process_host_many is its format on both sides of a state with nothing on: never read, never moved.)
+    ManyEntry &e = entries[i];
+    SidesState st = b->sides_state(earlier);
+    if (!e.sides) st.dither = st.meter = st.gain = false;
+    const SideKind plain_in = {e.in_fmt, false, false, false}, plain_out = {e.out_fmt, false, false, false};
+    e.route = route_sides_call(SidesForm::ManyEntry, e.sides ? side_kind(e.in_side) : plain_in, e.sides ? side_kind(e.out_side) : plain_out, st);
+    if (!e.route.fusable)
       apart.push_back(i);
     else
       by_device[b->device_].push_back(i);
@@ -580,7 +581,7 @@ int Batch::many_run(uint32_t n, const ManyEntry *entries, uint32_t *in_len, uint
   for (uint32_t i : apart) {
     const ManyEntry &e = entries[i];
     rcs[i] = e.sides ? e.b->process_sides_host(e.in_side, &in_len[i], e.out_side, &out_len[i])
-                     : e.b->process_host(e.in, &in_len[i], e.out, &out_len[i], e.kind != ManyEntry::Int16);
+                     : e.b->process_host(e.in, &in_len[i], e.out, &out_len[i], e.in_fmt != SPEEXHIP_FMT_S16);
   }
   count_many(3, apart.size());
   int first = SPEEXHIP_ERR_SUCCESS;

@@ -1,7 +1,8 @@
 // tools/san_host.cpp -- the host-only half of the product (filter_design.cpp, stream_plan.cpp) under ASan + UBSan:
 // every rate pair of a grid incl. absurd ones, random positions / pending frames / capacities up to 2^32; and the
 // host-buffer calls' decisions (host_transfer.h, route_host_call; many_plan.h, plan_many_unit and plan_many_lanes -- the
-// functions the product calls) against their tables, the many-states one over random units as well.
+// functions the product calls; sides_route.h, route_sides_call) against their tables, the many-states one over random units
+// and the formatted calls' one over its whole input space as well.
 // Built and run by tests/test_cpu_sanitizers.py (GPU sanitizers are not available on the pool).
 #include <cstdio>
 #include <cstdlib>
@@ -10,6 +11,7 @@
 #include "filter_design.h"
 #include "host_transfer.h"
 #include "many_plan.h"
+#include "sides_route.h"
 #include "stream_plan.h"
 using namespace speexhip;
 
@@ -345,6 +347,217 @@ bool check_many_invariants(std::mt19937 &rng, long *units) {
   }
   return true;
 }
+
+// ---- the route of a formatted call (sides_route.h: route_sides_call -- the function formats.cpp, many.cpp and bus.cpp call) ----
+// The rows were read off the commit before the rule existed ("Mix buses: weighted sums of a batch's streams in one device
+// call"): csrc/formats.cpp, many.cpp and bus.cpp; each cites the lines it was read from.
+struct RouteRow {
+  const char *name;  // (with the lines it was read from)
+  SidesForm form;
+  SideKind in, out;
+  SidesState st;
+  int refuse;
+  bool late;
+  SidesRoute::Kind kind;
+  bool direct, pass_in, pass_out;
+  SidesRoute::Finish finish;
+  float scale;
+  bool dither, meter, gain, fusable;  // moves_dither, counts_meter, moves_gain, fusable
+};
+bool check_sides_routes(long *rows, long *walked) {
+  const int S16 = SPEEXHIP_FMT_S16, F32 = SPEEXHIP_FMT_F32, F32N = SPEEXHIP_FMT_F32N, S24 = SPEEXHIP_FMT_S24, U8 = SPEEXHIP_FMT_U8;
+  const int OK = SPEEXHIP_ERR_SUCCESS, BAD = SPEEXHIP_ERR_BAD_STATE, ARG = SPEEXHIP_ERR_INVALID_ARG;
+  const auto flat = [](int fmt) { return SideKind{fmt, false, false, false}; };
+  const auto mix = [](int fmt) { return SideKind{fmt, true, false, false}; };
+  const auto planar = [](int fmt) { return SideKind{fmt, false, true, false}; };
+  const auto ptrs = [](int fmt) { return SideKind{fmt, false, false, true}; };  // a mono side given as its one plane
+  // the state flags: dither, meter, gain, split, zero_mode, single_stream, repeated
+  const SidesState one = {false, false, false, false, false, true, false}, batch = {false, false, false, false, false, false, false};
+  const auto with = [](SidesState s, const char *flags) {
+    for (const char *f = flags; *f != 0; f++) {
+      if (*f == 'd') s.dither = true;
+      if (*f == 'm') s.meter = true;
+      if (*f == 'g') s.gain = true;
+      if (*f == 's') s.split = true;
+      if (*f == 'z') s.zero_mode = true;
+      if (*f == 'r') s.repeated = true;
+    }
+    return s;
+  };
+  const SidesForm Dev = SidesForm::Device, Host = SidesForm::Host, Planes = SidesForm::PlanesHost, Chunks = SidesForm::Chunks,
+                  Many = SidesForm::ManyEntry, Bus = SidesForm::Bus;
+  const SidesRoute::Kind I16 = SidesRoute::Int16Call, Flt = SidesRoute::FloatCall, PFl = SidesRoute::PlanarFloatCall,
+                         Img = SidesRoute::Images, Own = SidesRoute::OwnCalls;
+  const SidesRoute::Finish None = SidesRoute::Nothing, MeterI = SidesRoute::MeterImage, GainI = SidesRoute::GainImage;
+  const bool n = false, y = true;
+  const RouteRow table[] = {
+      // ---- Device: formats.cpp, process_sides_device
+      {"device s16 same, :104-116", Dev, flat(S16), flat(S16), batch, OK, n, I16, n, n, n, None, 1, n, n, n, n},
+      {"device f32 same, :104-116", Dev, flat(F32), flat(F32), batch, OK, n, Flt, n, n, n, None, 1, n, n, n, n},
+      {"device f32 same dithered still counts, :114", Dev, flat(F32), flat(F32), with(batch, "d"), OK, n, Flt, n, n, n, None, 1, y, n, n, n},
+      {"device s16 dithered is images, :25-28, :134-135", Dev, flat(S16), flat(S16), with(batch, "d"), OK, n, Img, n, y, y, None, 1, y, n, n, n},
+      {"device s16 metered is images, :95, :104", Dev, flat(S16), flat(S16), with(batch, "m"), OK, n, Img, n, y, y, None, 1, n, y, n, n},
+      {"device s16 gained is images, :95, :104", Dev, flat(S16), flat(S16), with(batch, "g"), OK, n, Img, n, y, y, None, 1, n, n, y, n},
+      {"device f32n same metered, :108-113", Dev, flat(F32N), flat(F32N), with(batch, "m"), OK, n, Flt, n, n, n, MeterI, 32768, n, y, n, n},
+      {"device f32 same gained, :108-113", Dev, flat(F32), flat(F32), with(batch, "g"), OK, n, Flt, n, n, n, GainI, 1, n, n, y, n},
+      {"device f32n same gained metered dithered, :108-114", Dev, flat(F32N), flat(F32N), with(batch, "dmg"), OK, n, Flt, n, n, n, GainI, 32768, y, y, y, n},
+      {"device s16 to f32 metered: meter_image, :134-135, :167-170", Dev, flat(S16), flat(F32), with(batch, "m"), OK, n, Img, n, y, n, MeterI, 1, n, y, n, n},
+      {"device s16 to f32 gained: gain_image, :167-173", Dev, flat(S16), flat(F32), with(batch, "g"), OK, n, Img, n, y, n, GainI, 1, n, n, y, n},
+      {"device f32 to s16, :134-135", Dev, flat(F32), flat(S16), batch, OK, n, Img, n, n, y, None, 1, n, n, n, n},
+      {"device f32 to f32n, :134-135", Dev, flat(F32), flat(F32N), batch, OK, n, Img, n, n, y, None, 1, n, n, n, n},
+      {"device matrix in on f32, :26, :134", Dev, mix(F32), flat(F32), batch, OK, n, Img, n, y, n, None, 1, n, n, n, n},
+      {"device matrix out on f32 metered, :135, :163", Dev, flat(F32), mix(F32), with(batch, "m"), OK, n, Img, n, n, y, None, 1, n, y, n, n},
+      {"device planar f32 pair, :118-123", Dev, planar(F32), planar(F32), batch, OK, n, PFl, n, n, n, None, 1, n, n, n, n},
+      {"device planar f32n pair dithered moves, :121", Dev, planar(F32N), planar(F32N), with(batch, "d"), OK, n, PFl, n, n, n, None, 1, y, n, n, n},
+      {"device planar f32 pair metered: passes, :117-118", Dev, planar(F32), planar(F32), with(batch, "m"), OK, n, Img, n, y, y, None, 1, n, y, n, n},
+      {"device planar f32 pair gained: passes, :95, :118", Dev, planar(F32), planar(F32), with(batch, "g"), OK, n, Img, n, y, y, None, 1, n, n, y, n},
+      {"device planar f32 pair split: passes, :118", Dev, planar(F32), planar(F32), with(one, "s"), OK, n, Img, n, y, y, None, 1, n, n, n, n},
+      {"device planar s16 to f32n, :134-135", Dev, planar(S16), flat(F32N), batch, OK, n, Img, n, y, y, None, 1, n, n, n, n},
+      {"device planar f32 to flat f32, :26, :134-135", Dev, planar(F32), flat(F32), batch, OK, n, Img, n, y, n, None, 1, n, n, n, n},
+      {"device split one stream, :97-103, :156-157", Dev, flat(S16), flat(F32), with(one, "s"), OK, n, Img, n, y, n, None, 1, n, n, n, n},
+      {"device split same bytes, :101-107", Dev, flat(S16), flat(S16), with(one, "s"), OK, n, I16, n, n, n, None, 1, n, n, n, n},
+      {"device split of a batch, :101", Dev, flat(S16), flat(F32), with(batch, "s"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"device split dithered, :101", Dev, flat(S16), flat(F32), with(one, "sd"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"device split matrix, :101", Dev, mix(S16), flat(F32), with(one, "s"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"device split metered, :101", Dev, flat(F32), flat(F32), with(one, "sm"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"device split gained, :95, :101", Dev, flat(F32), flat(F32), with(one, "sg"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      // ---- Host: formats.cpp, process_sides_host
+      {"host s16 same: process_host, :237-241", Host, flat(S16), flat(S16), one, OK, n, I16, y, n, n, None, 1, n, n, n, n},
+      {"host f32n same dithered: process_host, moves, :237-239", Host, flat(F32N), flat(F32N), with(one, "d"), OK, n, Flt, y, n, n, None, 1, y, n, n, n},
+      {"host same, split: process_host serves it, :234, :237", Host, flat(F32), flat(F32), with(one, "s"), OK, n, Flt, y, n, n, None, 1, n, n, n, n},
+      {"host f32 same metered goes on, :235-237, :108-113", Host, flat(F32), flat(F32), with(one, "m"), OK, n, Flt, n, n, n, MeterI, 1, n, y, n, n},
+      {"host f32n same gained goes on, :235-237, :108-113", Host, flat(F32N), flat(F32N), with(one, "g"), OK, n, Flt, n, n, n, GainI, 32768, n, n, y, n},
+      {"host s16 dithered: images, :237, :134-135", Host, flat(S16), flat(S16), with(one, "d"), OK, n, Img, n, y, y, None, 1, y, n, n, n},
+      {"host s16 to f32, :260", Host, flat(S16), flat(F32), one, OK, n, Img, n, y, n, None, 1, n, n, n, n},
+      {"host split served, :250-262", Host, flat(S16), flat(F32), with(one, "s"), OK, n, Img, n, y, n, None, 1, n, n, n, n},
+      {"host split dithered, no matrix: early, :234", Host, flat(S16), flat(S16), with(one, "sd"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"host split metered same bytes: early, :234", Host, flat(F32), flat(F32), with(one, "sm"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"host split gained: early, :234", Host, flat(S16), flat(F32), with(one, "sg"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"host split matrix: late, :242-243", Host, mix(S16), flat(F32), with(one, "s"), BAD, y, Img, n, n, n, None, 1, n, n, n, n},
+      {"host split matrix dithered: late, :234, :243", Host, flat(S16), mix(S16), with(one, "sd"), BAD, y, Img, n, n, n, None, 1, n, n, n, n},
+      {"host planar side: planes_host_call, :221, :474-475", Host, planar(S16), flat(F32N), with(one, "s"), OK, n, Img, n, y, y, None, 1, n, n, n, n},
+      // ---- PlanesHost: formats.cpp, planes_host_call
+      {"planes planar f32 pair, :519, :118", Planes, planar(F32), planar(F32), one, OK, n, PFl, n, n, n, None, 1, n, n, n, n},
+      {"planes s16 to planar f32 metered, :519, :163", Planes, flat(S16), planar(F32), with(one, "m"), OK, n, Img, n, y, y, None, 1, n, y, n, n},
+      {"planes split dithered, :475", Planes, planar(S16), flat(S16), with(one, "sd"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"planes split matrix: not late, :475", Planes, planar(S16), mix(S16), with(one, "s"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"planes split metered, :475", Planes, planar(F32), planar(F32), with(one, "sm"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"planes split gained, :475", Planes, planar(F32), planar(F32), with(one, "sg"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      // ---- Chunks: formats.cpp, process_sides_host_chunks
+      {"chunks s16 same: process_host_chunks, :376-384", Chunks, flat(S16), flat(S16), one, OK, n, I16, y, n, n, None, 1, n, n, n, y},
+      {"chunks f32 same dithered, :376-381", Chunks, flat(F32), flat(F32), with(one, "d"), OK, n, Flt, y, n, n, None, 1, y, n, n, y},
+      {"chunks same, split: process_host_chunks all the same, :352, :376, :382", Chunks, flat(F32), flat(F32), with(one, "s"), OK, n, Flt, y, n, n, None, 1, n, n, n, n},
+      {"chunks same, zero mode, :350, :382", Chunks, flat(S16), flat(S16), with(one, "z"), OK, n, I16, y, n, n, None, 1, n, n, n, n},
+      {"chunks not same, split: own calls, :352-374", Chunks, flat(S16), flat(F32), with(one, "s"), OK, n, Own, n, n, n, None, 1, n, n, n, n},
+      {"chunks not same, zero mode dithered: own calls, :350-352", Chunks, flat(S16), flat(S16), with(one, "zd"), OK, n, Own, n, n, n, None, 1, n, n, n, n},
+      {"chunks same metered, zero mode: own calls, :352", Chunks, flat(F32), flat(F32), with(one, "zm"), OK, n, Own, n, n, n, None, 1, n, n, n, n},
+      {"chunks same gained, zero mode: own calls, :345, :352", Chunks, flat(F32N), flat(F32N), with(one, "zg"), OK, n, Own, n, n, n, None, 1, n, n, n, n},
+      {"chunks f32n same metered: staged, no passes, :414-415, :443-447", Chunks, flat(F32N), flat(F32N), with(one, "m"), OK, n, Flt, n, n, n, MeterI, 32768, n, y, n, y},
+      {"chunks f32 same gained dithered, :443-449", Chunks, flat(F32), flat(F32), with(one, "gd"), OK, n, Flt, n, n, n, GainI, 1, y, n, y, y},
+      {"chunks s16 to f32 metered, :414-415, :443-444", Chunks, flat(S16), flat(F32), with(one, "m"), OK, n, Img, n, y, n, MeterI, 1, n, y, n, y},
+      {"chunks s24 to u8 dithered, :414-415, :449", Chunks, flat(S24), flat(U8), with(one, "d"), OK, n, Img, n, y, y, None, 1, y, n, n, y},
+      {"chunks planar f32 pair: passes, no planar float call, :350, :414-415", Chunks, planar(F32), planar(F32), one, OK, n, Img, n, y, y, None, 1, n, n, n, y},
+      {"chunks matrix out, :415", Chunks, flat(F32), mix(F32), one, OK, n, Img, n, n, y, None, 1, n, n, n, y},
+      {"chunks split dithered, :346", Chunks, flat(F32), flat(F32), with(one, "sd"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"chunks split matrix, :346", Chunks, mix(S16), flat(S16), with(one, "s"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"chunks split gained, :345-346", Chunks, flat(F32), flat(F32), with(one, "sg"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      // ---- ManyEntry: formats.cpp, process_host_many_sides; many.cpp
+      {"many s16 same: int16, formats :207-208", Many, flat(S16), flat(S16), one, OK, n, I16, n, n, n, None, 1, n, n, n, y},
+      {"many f32n same: float, formats :207-209", Many, flat(F32N), flat(F32N), one, OK, n, Flt, n, n, n, None, 1, n, n, n, y},
+      {"many f32 same dithered moves, many :231", Many, flat(F32), flat(F32), with(one, "d"), OK, n, Flt, n, n, n, None, 1, y, n, n, y},
+      {"many s16 dithered: image, formats :207, many :170-171", Many, flat(S16), flat(S16), with(one, "d"), OK, n, Img, n, y, y, None, 1, y, n, n, y},
+      {"many s16 metered: image, formats :207, many :233, :294", Many, flat(S16), flat(S16), with(one, "m"), OK, n, Img, n, y, y, None, 1, n, y, n, y},
+      {"many s16 to f32: image, many :170-171", Many, flat(S16), flat(F32), one, OK, n, Img, n, y, n, None, 1, n, n, n, y},
+      {"many f32 to s24 gained stays fused, many :295", Many, flat(F32), flat(S24), with(one, "g"), OK, n, Img, n, n, y, None, 1, n, n, y, y},
+      {"many f32 same gained stays fused: gain_image, formats :206, many :297-304", Many, flat(F32), flat(F32), with(one, "g"), OK, n, Flt, n, n, n, GainI, 1, n, n, y, y},
+      {"many f32n same gained: gain_image at 1, many :322", Many, flat(F32N), flat(F32N), with(one, "g"), OK, n, Flt, n, n, n, GainI, 1, n, n, y, y},
+      {"many s16 to f32 gained: gain_image, many :297", Many, flat(S16), flat(F32), with(one, "g"), OK, n, Img, n, y, n, GainI, 1, n, n, y, y},
+      {"many f32 to f32n metered stays fused, formats :201", Many, flat(F32), flat(F32N), with(one, "m"), OK, n, Img, n, n, y, None, 1, n, y, n, y},
+      {"many f32 result metered: own call, formats :199-202", Many, flat(S16), flat(F32), with(one, "m"), OK, n, Own, n, n, n, None, 1, n, n, n, n},
+      {"many f32n same metered: own call, formats :201", Many, flat(F32N), flat(F32N), with(one, "mg"), OK, n, Own, n, n, n, None, 1, n, n, n, n},
+      {"many matrix: own call, formats :197", Many, mix(S16), flat(S16), one, OK, n, Own, n, n, n, None, 1, n, n, n, n},
+      {"many planar: own call, formats :197", Many, flat(S16), planar(S16), one, OK, n, Own, n, n, n, None, 1, n, n, n, n},
+      {"many planes pointer: own call, formats :197-198", Many, ptrs(S16), flat(S16), one, OK, n, Own, n, n, n, None, 1, n, n, n, n},
+      {"many named twice: own call, many :517-521", Many, flat(S16), flat(S16), with(one, "r"), OK, n, Own, n, n, n, None, 1, n, n, n, n},
+      {"many split: own call, many :521", Many, flat(S16), flat(S16), with(one, "s"), OK, n, Own, n, n, n, None, 1, n, n, n, n},
+      {"many zero mode: own call, many :521", Many, flat(F32), flat(F32), with(one, "z"), OK, n, Own, n, n, n, None, 1, n, n, n, n},
+      {"many batch of several: own call, many :521", Many, flat(F32), flat(F32), batch, OK, n, Own, n, n, n, None, 1, n, n, n, n},
+      // ---- Bus: bus.cpp, process_bus_device
+      {"bus f32 to f32: no same-bytes route, :139-142", Bus, flat(F32), flat(F32), batch, OK, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"bus planar f32 pair: no planar float route, :141-142", Bus, planar(F32), planar(F32), batch, OK, n, Img, n, y, y, None, 1, n, n, n, n},
+      {"bus s16 to s16 dithered: the bus position, :182, :199", Bus, flat(S16), flat(S16), with(batch, "d"), OK, n, Img, n, y, y, None, 1, y, n, n, n},
+      {"bus f32 side metered: meter_image, :184-197", Bus, flat(S16), flat(F32), with(batch, "m"), OK, n, Img, n, y, n, MeterI, 1, n, y, n, n},
+      {"bus f32 side gained: never gain_image, gain moves, :178-198", Bus, flat(S16), flat(F32), with(batch, "g"), OK, n, Img, n, y, n, None, 1, n, n, y, n},
+      {"bus f32 side gained metered: meter_image only, :184, :196-198", Bus, mix(S16), flat(F32), with(batch, "gm"), OK, n, Img, n, y, n, MeterI, 1, n, y, y, n},
+      {"bus f32n side metered: the pass, :142, :181-183", Bus, flat(F32), flat(F32N), with(batch, "m"), OK, n, Img, n, n, y, None, 1, n, y, n, n},
+      {"bus matrix on the sum, :122", Bus, flat(S16), mix(S16), batch, ARG, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"bus split, :129-131", Bus, flat(S16), flat(S16), with(one, "s"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+  };
+  for (const RouteRow &w : table) {
+    const SidesRoute r = route_sides_call(w.form, w.in, w.out, w.st);
+    if (r.refuse != w.refuse || r.refuse_late != w.late || r.kind != w.kind || r.direct != w.direct || r.pass_in != w.pass_in ||
+        r.pass_out != w.pass_out || r.finish != w.finish || r.finish_scale != w.scale || r.moves_dither != w.dither ||
+        r.counts_meter != w.meter || r.moves_gain != w.gain || r.fusable != w.fusable) {
+      printf("BAD sides route (%s): refuse %d late %d kind %d direct %d passes %d / %d finish %d at %g, moves %d %d %d, fusable %d\n", w.name,
+             r.refuse, r.refuse_late, static_cast<int>(r.kind), r.direct, r.pass_in, r.pass_out, static_cast<int>(r.finish), r.finish_scale,
+             r.moves_dither, r.counts_meter, r.moves_gain, r.fusable);
+      return false;
+    }
+    (*rows)++;
+  }
+  // The whole input space: what holds of every route, whatever the table says.
+  const int fmts[] = {SPEEXHIP_FMT_U8,   SPEEXHIP_FMT_S16,  SPEEXHIP_FMT_S24,   SPEEXHIP_FMT_S32,   SPEEXHIP_FMT_F32,   SPEEXHIP_FMT_F32N, SPEEXHIP_FMT_ULAW,
+                      SPEEXHIP_FMT_ALAW, SPEEXHIP_FMT_F16N, SPEEXHIP_FMT_BF16N, SPEEXHIP_FMT_S16BE, SPEEXHIP_FMT_S24BE, SPEEXHIP_FMT_S32BE};
+  const auto is_float = [](int fmt) { return fmt == SPEEXHIP_FMT_F32 || fmt == SPEEXHIP_FMT_F32N; };
+#define ROUTE_EXPECT(cond)                                                                                                     \
+  do {                                                                                                                         \
+    if (!(cond)) {                                                                                                             \
+      printf("BAD sides route: not %s (form %d, %d%s%s -> %d%s%s, state %x)\n", #cond, static_cast<int>(form), in.fmt,          \
+             in.mix ? " mix" : "", in.planar ? " planar" : "", out.fmt, out.mix ? " mix" : "", out.planar ? " planar" : "", bits); \
+      return false;                                                                                                            \
+    }                                                                                                                          \
+  } while (0)
+  for (SidesForm form : {Dev, Host, Planes, Chunks, Many, Bus})
+    for (int fi : fmts) for (int fo : fmts)
+      for (int sides = 0; sides < 64; sides++)  // mix, planar, planes of either side
+        for (int bits = 0; bits < 128; bits++) {
+          if (form != Many && (sides & (4 | 32)) != 0) continue;  // (only the many-states call asks for plane pointers)
+          const SideKind in ={fi, (sides & 1) != 0, (sides & 2) != 0, (sides & 4) != 0};
+          const SideKind out = {fo, (sides & 8) != 0, (sides & 16) != 0, (sides & 32) != 0};
+          const SidesState st = {(bits & 1) != 0, (bits & 2) != 0, (bits & 4) != 0, (bits & 8) != 0, (bits & 16) != 0, (bits & 32) != 0, (bits & 64) != 0};
+          const SidesRoute r = route_sides_call(form, in, out, st);
+          (*walked)++;
+          const bool delegates = r.kind == SidesRoute::OwnCalls;  // (the next form down asks again)
+          if (r.refuse != SPEEXHIP_ERR_SUCCESS || delegates) {
+            // a refused route names no passes -- nor does one that hands the call on; neither moves anything
+            ROUTE_EXPECT(!r.pass_in && !r.pass_out && r.finish == SidesRoute::Nothing && !r.direct && !r.fusable);
+            ROUTE_EXPECT(!r.moves_dither && !r.counts_meter && !r.moves_gain);
+            continue;
+          }
+          ROUTE_EXPECT(!r.refuse_late);
+          if (r.kind == SidesRoute::Int16Call)
+            ROUTE_EXPECT(fi == SPEEXHIP_FMT_S16 && fo == SPEEXHIP_FMT_S16 && !st.dither && !st.meter && !st.gain && !in.mix && !out.mix);
+          if (r.kind != SidesRoute::Images) ROUTE_EXPECT(!r.pass_in && !r.pass_out);
+          if (r.kind == SidesRoute::FloatCall) ROUTE_EXPECT(fi == fo && is_float(fi) && !in.mix && !out.mix && !in.planar && !out.planar);
+          if (r.finish != SidesRoute::Nothing) ROUTE_EXPECT(!r.pass_out && is_float(fo));
+          if (r.finish_scale != 1.0f) ROUTE_EXPECT(r.finish_scale == 32768.0f && r.finish != SidesRoute::Nothing && fi == SPEEXHIP_FMT_F32N && fo == fi && r.kind == SidesRoute::FloatCall);
+          // pass_out and finish together cover every call with the meter on, and every one with gain on -- but a bus
+          // call's, whose streams bus_sum gains before it sums them
+          if (st.meter || (st.gain && form != Bus)) ROUTE_EXPECT(r.pass_out || r.finish != SidesRoute::Nothing);
+          if (r.kind == SidesRoute::PlanarFloatCall) ROUTE_EXPECT(in.planar && out.planar && fi == fo && is_float(fi) && !in.mix && !out.mix);
+          // whatever counts the meter or moves gain has an output pass or a finish (the bus call's gain as above)
+          if (r.counts_meter || (r.moves_gain && form != Bus)) ROUTE_EXPECT(r.pass_out || r.finish != SidesRoute::Nothing);
+          // ... and every call that is obeyed here moves exactly what the state has on; the host's own calls only the dither
+          ROUTE_EXPECT(r.moves_dither == st.dither);
+          if (!r.direct) ROUTE_EXPECT(r.counts_meter == st.meter && r.moves_gain == st.gain);
+          if (r.direct) ROUTE_EXPECT((form == Host || form == Chunks) && !st.meter && !st.gain && r.kind != SidesRoute::Images && r.kind != SidesRoute::PlanarFloatCall);
+          if (r.fusable) ROUTE_EXPECT(form == Chunks || form == Many);
+          if (form == Many) ROUTE_EXPECT(r.fusable && !in.planar && !out.planar && !in.mix && !out.mix && !in.planes && !out.planes && r.finish != SidesRoute::MeterImage);
+          if (form == Bus) ROUTE_EXPECT(r.kind == SidesRoute::Images && r.finish != SidesRoute::GainImage);
+        }
+#undef ROUTE_EXPECT
+  return true;
+}
 }  // namespace
 
 int main() {
@@ -542,7 +755,10 @@ int main() {
   }
   long many_rows = 0, many_random = 0;
   if (!check_many_plans(&many_rows) || !check_many_invariants(rng, &many_random)) return 1;
-  printf("sanitizer run ok: %ld filters, %ld plans, %ld placements, %ld routes, %ld many-states rows, %ld random many-states units\n",
-         filters, plans, placements, routes, many_rows, many_random);
+  long sides_rows = 0, sides_walked = 0;
+  if (!check_sides_routes(&sides_rows, &sides_walked)) return 1;
+  printf("sanitizer run ok: %ld filters, %ld plans, %ld placements, %ld routes, %ld many-states rows, %ld random many-states units, "
+         "%ld sides routes, %ld walked\n",
+         filters, plans, placements, routes, many_rows, many_random, sides_rows, sides_walked);
   return 0;
 }
