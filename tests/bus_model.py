@@ -22,12 +22,65 @@ def pad(streams, frames, channels):
     return y
 
 
-def buses(weights, y):
-    """(n_buses, n) float32: the buses of y (n_streams, n) float32 under weights (n_buses, n_streams) float32"""
+ORDER_DEFECTS = ("descending", "tree", "evens_then_odds", "fp32_accumulator")
+OTHER_DEFECTS = ("round_each_add", "skip_zero_weight", "zero_plus_first", "skip_ended")
+DEFECTS = ORDER_DEFECTS + OTHER_DEFECTS
+
+
+def _defective(w_row, y64, defect, live):
+    """one bus with one planted DEFECT, as float32 -- what a kernel that got the rule wrong in that way would store:
+      descending         the streams summed from the last to the first
+      tree               pairwise: (p0 + p1) + (p2 + p3) ...
+      evens_then_odds    streams 0, 2, 4 ... then 1, 3, 5 ...
+      fp32_accumulator   products and sums in float32
+      round_each_add     the fp64 sum rounded to float32 after every add (an fp32 fused multiply-add)
+      skip_zero_weight   a stream whose weight is 0 contributes no term
+      zero_plus_first    the first term is 0.0 + the product
+      skip_ended         a stream contributes no term where it has ended (live[s, i] False)
+    A sum without any term is +0.0."""
+    n_streams = y64.shape[0]
+    p = [np.float64(w_row[s]) * y64[s] for s in range(n_streams)]
+    if defect == "tree":
+        while len(p) > 1:
+            p = [p[i] + p[i + 1] if i + 1 < len(p) else p[i] for i in range(0, len(p), 2)]
+        return p[0].astype(np.float32)
+    order = list(range(n_streams))
+    if defect == "descending":
+        order.reverse()
+    elif defect == "evens_then_odds":
+        order = order[0::2] + order[1::2]
+    narrow32 = defect in ("fp32_accumulator", "round_each_add")
+    if defect == "fp32_accumulator":
+        p = [q.astype(np.float32).astype(np.float64) for q in p]
+    acc = np.zeros(y64.shape[1], np.float64)
+    started = np.zeros(y64.shape[1], bool)
+    for s in order:
+        if defect == "skip_zero_weight" and w_row[s] == 0:
+            continue
+        first = np.float64(0.0) + p[s] if defect == "zero_plus_first" else p[s]
+        new = np.where(started, acc + p[s], first)
+        if narrow32:
+            new = new.astype(np.float32).astype(np.float64)
+        take = live[s] if defect == "skip_ended" else np.ones_like(started)
+        acc = np.where(take, new, acc)
+        started = started | take
+    return acc.astype(np.float32)
+
+
+def buses(weights, y, defect=None, live=None):
+    """(n_buses, n) float32: the buses of y (n_streams, n) float32 under weights (n_buses, n_streams) float32.
+    defect: one of DEFECTS planted (None: the rule); live (n_streams, n) bool, for "skip_ended": where a stream has not
+    ended."""
     w = np.asarray(weights, np.float32)
     y = np.asarray(y, np.float32)
     assert w.ndim == 2 and y.ndim == 2 and w.shape[1] == y.shape[0]
     y64 = y.astype(np.float64)
+    if defect is not None:
+        assert defect in DEFECTS, defect
+        live = np.ones(y.shape, bool) if live is None else np.asarray(live, bool)
+        assert live.shape == y.shape
+        with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+            return np.stack([_defective(w[j], y64, defect, live) for j in range(w.shape[0])])
     out = np.empty((w.shape[0], y.shape[1]), np.float32)
     with np.errstate(over="ignore", invalid="ignore", under="ignore"):
         for j in range(w.shape[0]):
@@ -37,6 +90,42 @@ def buses(weights, y):
                 acc = acc + p
             out[j] = acc.astype(np.float32)
     return out
+
+
+def live_of(lengths, n):
+    """(n_streams, n) bool: sample i of stream s lies before the stream's end (lengths in samples)"""
+    return np.arange(n)[None, :] < np.asarray(lengths)[:, None]
+
+
+def changed(a, b):
+    """share of the samples of one bus whose float32 bits differ; two NaNs count as the same value"""
+    a, b = np.asarray(a, np.float32).reshape(-1), np.asarray(b, np.float32).reshape(-1)
+    both_nan = np.isnan(a) & np.isnan(b)
+    return float(((a.view(np.uint32) != b.view(np.uint32)) & ~both_nan).mean()) if a.size else 0.0
+
+
+# The "order" layout: 32 streams whose sum tells every order apart.  A pair of huge values that cancel exactly (2^60: one
+# ulp of the fp64 accumulator is 2^8 there) among values of 2^12 -- what the accumulator loses of the small values depends
+# on how many of them it holds when the huge one arrives and leaves.  Stream 1 is the negation of stream 0 and stream 31
+# of stream 30 throughout; the first half's huge values are in streams 0 and 1, the second half's in streams 30 and 31,
+# everything else is 2^12.  Row 0 sums everything, row 1 its negation, rows 2 and 3 one pair alone with zero weights on
+# everybody else: +0.0, never -0.0.
+ORDER_STREAMS = 32
+ORDER_W = np.zeros((4, ORDER_STREAMS), np.float32)
+ORDER_W[0], ORDER_W[1] = 1.0, -1.0
+ORDER_W[2, :2] = 1.0
+ORDER_W[3, -2:] = 1.0
+
+
+def order_layout(frames, seed=1234):
+    """(32, frames) float32, mono: the layout above, its halves frames // 2 long"""
+    rng = np.random.default_rng(seed)
+    half = frames // 2
+    x = (rng.uniform(-1.0, 1.0, (ORDER_STREAMS, frames)) * 2.0 ** 12).astype(np.float32)
+    huge = (rng.uniform(-1.0, 1.0, frames) * 2.0 ** 60).astype(np.float32)
+    x[0, :half], x[30, half:] = huge[:half], huge[half:]
+    x[1], x[31] = -x[0], -x[30]       # (negations throughout, so that a linear filter keeps them negations)
+    return x
 
 
 def mix_minus(n):

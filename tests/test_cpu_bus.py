@@ -1,7 +1,9 @@
 """The bus rule on the host (include/speexhip_resampler.h, "Buses"): speexhip_debug_bus compiles the very statement the
 kernel compiles (csrc/bus.h) and must equal the numpy model (bus_model.py) bit for bit -- on random data at the pack
 sizes, and at the points where a wrong sum shows: cancelling pairs and negative zeros, values 2^24 apart (a wrong order
-or an fp32 accumulator loses the small ones), inf * 0.  No GPU."""
+or an fp32 accumulator loses the small ones), inf * 0.  Then the defects that bus_model.buses(defect=) can plant, on
+synthetic arrays of the layouts test_gpu_bus_edges.py feeds the kernel: each must change the model's output there (the
+shares are printed with -s).  No GPU."""
 import os
 import re
 
@@ -96,6 +98,82 @@ def test_mix_minus_is_ones_minus_identity():
     y = np.arange(1, 9, dtype=np.float32).reshape(4, 2)
     got = both(w, y)
     assert same_bits(got, (y.sum(0)[None, :] - y).astype(np.float32))
+
+
+# ---- planted defects: what the crafted layouts of test_gpu_bus_edges.py can tell from the rule -------------------------
+SIGNS_W = np.array([[-1.0, 0.0], [1.0, 0.0]], np.float32)    # stream 0 has ended, stream 1 is live
+
+
+def signs_layout(n=320, seed=5):
+    """(2, n) float32 and its live mask: stream 0 ended before the first sample, stream 1 noise of both signs"""
+    y = np.zeros((2, n), np.float32)
+    y[1] = (np.random.default_rng(seed).uniform(-0.9, 0.9, n) * 32767.0).astype(np.float32)
+    return y, bm.live_of([0, n], n)
+
+
+def inf_layout(n=400, seed=6):
+    """(3, n) float32 with one +inf in stream 2, under weights that put 0 on it and 0 on the others"""
+    y = (np.random.default_rng(seed).uniform(-1.3, 1.3, (3, n)) * 32767.0).astype(np.float32)
+    y[2, n - n // 16] = np.inf
+    return y, np.array([[1.0, 1.0, 0.0], [0.0, 0.0, 1.0]], np.float32)
+
+
+def test_the_defect_engine_without_a_defect_is_the_rule():
+    # (_defective with no known defect name walks the streams in ascending order, fp64, first term the product itself)
+    y = bm.order_layout(800)
+    want = bm.buses(bm.ORDER_W, y)
+    got = np.stack([bm._defective(bm.ORDER_W[j], y.astype(np.float64), None, np.ones(y.shape, bool)) for j in range(4)])
+    assert same_bits(got, want)
+    assert same_bits(both(bm.ORDER_W, y), want)
+
+
+def test_every_order_defect_shows_on_the_order_layout():
+    n = 800
+    y = bm.order_layout(n)
+    assert same_bits(y[1], -y[0]) and same_bits(y[31], -y[30])
+    assert np.abs(y[0, : n // 2]).mean() > 2.0 ** 57 and np.abs(y[30, n // 2:]).mean() > 2.0 ** 57
+    assert np.abs(y[2:30]).max() <= 2.0 ** 12 and np.abs(y[0, n // 2:]).max() <= 2.0 ** 12
+    assert np.isfinite(y).all()
+    want = both(bm.ORDER_W, y)
+    assert np.isfinite(want).all()
+    # rows 2 and 3: a pair alone among zero weights is +0.0, never -0.0
+    assert same_bits(want[2:], np.zeros((2, n), np.float32))
+    for defect in bm.ORDER_DEFECTS + ("round_each_add",):
+        z = bm.buses(bm.ORDER_W, y, defect)
+        first = max(bm.changed(z[j, : n // 2], want[j, : n // 2]) for j in (0, 1))
+        second = max(bm.changed(z[j, n // 2:], want[j, n // 2:]) for j in (0, 1))
+        print("order layout, %-16s: %5.1f %% / %5.1f %% of a bus's samples change (first / second half)"
+              % (defect, 100 * first, 100 * second))
+        assert max(first, second) >= 0.01, defect
+    for defect in ("skip_zero_weight", "zero_plus_first", "skip_ended"):
+        # (finite sums far from zero: none of these shows here -- their own rows below do)
+        assert same_bits(bm.buses(bm.ORDER_W[:2], y, defect), want[:2]), defect
+
+
+def test_the_other_defects_show_on_their_own_rows():
+    y, live = signs_layout()
+    want = both(SIGNS_W, y)
+    neg = y[1] < 0
+    assert 0.2 < neg.mean() < 0.8 and (y[1] != 0).all()
+    # -0 + -0 = -0 and -0 + +0 = +0: the sign of the live sample; +0 + either zero = +0
+    assert same_bits(want[0], np.where(neg, np.float32(-0.0), np.float32(0.0)))
+    assert same_bits(want[1], np.zeros(y.shape[1], np.float32))
+    shares = {}
+    for defect, row, where in (("zero_plus_first", 0, neg), ("skip_zero_weight", 0, ~neg), ("skip_ended", 1, neg)):
+        z = bm.buses(SIGNS_W, y, defect, live)
+        diff = z.view(np.uint32)[row] != want.view(np.uint32)[row]
+        assert diff.any() and (diff == where).all(), defect
+        shares[defect] = diff.mean()
+    y, w = inf_layout()
+    want = both(w, y)
+    at = int(np.flatnonzero(np.isinf(y[2]))[0])
+    assert np.isnan(want[0, at]) and np.isnan(want[0]).sum() == 1 and not np.isnan(want[1]).any() and np.isinf(want[1, at])
+    z = bm.buses(w, y, "skip_zero_weight")
+    assert not np.isnan(z).any(), "a skipped zero weight makes no NaN"
+    shares["skip_zero_weight (0 * inf)"] = bm.changed(z[0], want[0])
+    assert shares["skip_zero_weight (0 * inf)"] > 0
+    for k, v in shares.items():
+        print("%-28s: %5.1f %% of the row's samples change" % (k, 100 * v))
 
 
 def test_arguments_and_exports():
