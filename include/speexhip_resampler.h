@@ -1179,6 +1179,7 @@ SPEEXHIP_API uint64_t speexhip_release_cached_memory(void);
  * error: as in the sides call.  Asynchronous on hip_stream, ordered like the other device calls.
  *
  * A host-fed bus call and a bus over many separate states are not part of this version.
+ * (Of this section, that is: both are the mixer's, in the section "Mixer" below.)
  *
  * ABI note: adds these six entry points; SpeexHipInfo, SpeexHipSide, SpeexHipMeter, the enums, the error codes and the
  * version string are unchanged. */
@@ -1193,6 +1194,111 @@ SPEEXHIP_API int speexhip_batch_get_bus_position(SpeexHipBatch *b, uint64_t *pos
  * i < n, s < n_streams. */
 SPEEXHIP_API int speexhip_debug_bus(uint32_t n_streams, uint32_t n_buses, const float *weights, const float *y, uint32_t n,
                                     float *z);
+
+/* ------------------------------------------------------------------------------------------
+ * Mixer: mix buses over many SEPARATE states in one host call -- a conference bridge whose legs are G.711 at 8 kHz,
+ * wideband at 16 kHz and studio feeds at 48 kHz, each an ordinary single-stream SpeexHipResamplerState with its own
+ * rates, quality, mode, gain and ramp, each fed in its own sample format from host memory.  A SpeexHipMixer has n_legs
+ * SLOTS, n_buses buses and one channel count C; it owns what a SpeexHipBatch owns for its buses -- W on the device, the
+ * buses' dither kind, seed and ONE bus position, the buses' meter switch and cells -- and nothing of a leg: the caller
+ * names the state in every slot with every call.
+ *
+ * The sum is the rule of "Buses", unchanged, with the slots in the place of the streams.  For one call, with produced[i]
+ * the output frames of the leg in slot i:
+ *
+ *   y'_i[f]     output frame f OF THIS CALL of leg i, on C channels: the float call's value, times g_i(done_i + f) in
+ *               fp32 when that state's gain is on ("Gain"), not multiplied when it is off.  +0.0f for f >= produced[i];
+ *               +0.0f throughout for an empty slot and for a leg that was refused.
+ *   bus_frames  = max over the legs that ran of produced[i].  Every bus has this length.
+ *   bus j, channel c, frame f < bus_frames:
+ *               (float)( (double)W[j][0] * y'_0 + (double)W[j][1] * y'_1 + ... ), summed in ascending slot order, every
+ *               term included, the first term the product itself, rounded once -- "Buses" word for word.
+ *
+ * The bus image leaves by the output side's rule, as in the Batch's bus call: the format's encode, dither, meter.
+ * Dither: bus j draws from seed + (n_legs + j) * 0x9E3779B97F4A7C15 (mod 2^64); all buses share one bus position, idx =
+ * (bus_position + f) * C + c; speexhip_mixer_set_dither sets it, speexhip_mixer_set_weights zeroes it, a call with kind !=
+ * NONE advances it by bus_frames, whatever the output format.  Meter: one cell per bus, samples += bus_frames * C.
+ *
+ * What a call moves: each leg's position, history and counters as the float call does (in_len[i] / out_len[i] are the
+ * float entry's counters: speexhip_resampler_peek with float_entry = 1 sizes a leg), and each leg's gain `done` by
+ * produced[i], up to total.  It does NOT move a leg's own dither position or meter totals: nothing of a leg is encoded,
+ * and nothing of a leg travels back.
+ *
+ * What follows from "frame f of this call": the buses line the legs up by the frame of THIS CALL, as the Batch's bus
+ * does.  The buses' bytes are therefore independent of how the stream of ticks is cut into calls exactly when every leg
+ * produces bus_frames frames on every call.  Legs of one ratio fed equal lengths do, and so do legs of different ratios
+ * fed the same whole tick -- 160 frames at 8 kHz, 320 at 16 kHz, 882 at 44.1 kHz and 960 at 48 kHz all make 960 frames at
+ * 48 kHz, on the first call as on every other, whatever the filters' lengths: a state produces from its first input
+ * frame on.  Legs whose input per call is not a whole number of their ratio's periods do not (44.1 kHz fed 5 ms brings 220
+ * or 221 frames and makes 239 to 241), nor do legs fed different durations.  Keeping a per-leg residue to line legs up
+ * by stream position is no part of this version.
+ *
+ * speexhip_mixer_process, one host call per tick: one transfer in (the legs' payloads and the table of the legs, gathered),
+ * the legs' input passes and FIR launches grouped exactly as speexhip_resampler_process_many_sides groups them (up to 32
+ * legs that share filter tables, mode and window format a launch), ONE launch of the bus-sum kernel over all slots, the
+ * output pass over the buses (one per 32 buses; none for an interleaved F32 side), one transfer out of the buses.
+ *   legs[i], i < n_legs   the state in slot i; NULL: an empty slot.
+ *   in[i]                 that leg's input side, a HOST buffer; struct_size is checked per leg; stream_stride and planes
+ *                         are not read; data == NULL: a present, silent leg.
+ *   in_len[i], out_len[i] frames available and capacity on entry, frames consumed and produced on return.
+ *   out                   describes the BUSES in host memory: bus j starts j * stream_stride samples after bus 0; any
+ *                         format; interleaved, or planar through plane_stride; channels must be the mixer's; mix and
+ *                         planes must be NULL.  Every bus buffer holds max over i of out_len[i] frames.
+ *   *bus_frames           receives the length of the buses.
+ *   codes                 may be NULL; codes[i] receives the outcome of slot i.  The function returns the first outcome
+ *                         that is not SUCCESS.
+ * A refused leg keeps its state and both its lengths untouched and counts as +0.0f in the sum; the other legs run: one bad
+ * leg does not cost the tick.  Per leg:
+ *   an empty slot                                         SUCCESS, both lengths set to 0
+ *   a side with a short struct_size, an unknown format or layout, a matrix, a planar layout of more than one channel, or
+ *   a channel count that is not the mixer's               INVALID_ARG
+ *   a state of more than one stream, on another device than the mixer, or named by an earlier slot      INVALID_ARG
+ *   lengths that fail "Extents"                           OVERFLOW
+ *   a state whose channels the per-channel calls moved apart                                            BAD_STATE
+ *   a state in the zero fallback                          runs: counters move, zeros are summed (gained), ALLOC_FAILED
+ *                                                         as in every call
+ * Call-level errors, returned before anything is touched, codes not written: m, legs, in, in_len, out_len, out or
+ * bus_frames NULL: INVALID_ARG; an `out` side error (above, or data == NULL): INVALID_ARG; no weights set: BAD_STATE.
+ *
+ * The call is synchronous.  The mixer and its legs must not be used by another thread meanwhile.  A leg whose last call
+ * was a device call on another stream is ordered behind it on the device, as in the many-states calls.  In the default
+ * mode and in SPEEXHIP_MODE_EXACT a leg's floats do not depend on what shares its launch, so the buses' bytes are a
+ * function of the legs' streams and of the cut alone; in FAST and FAST_F32 the usual last-bit caveat holds.
+ *
+ * speexhip_mixer_init: device by the placement rule, or named (_init_on); 0 or more than SPEEXHIP_MIXER_MAX_LEGS legs, 0 or
+ * more than SPEEXHIP_MIXER_MAX_BUSES buses, 0 or more than 8 channels: NULL with INVALID_ARG.
+ * speexhip_mixer_set_weights is a control call: it waits for the mixer's own last call, copies W (n_buses x n_legs floats,
+ * row-major, host), uploads it, zeroes the buses' cells, totals and the bus position.  A weight that is not finite:
+ * INVALID_ARG, the mixer as it was.  weights = NULL: the mixer is off (process: BAD_STATE) until weights are set again.
+ * speexhip_mixer_get_weights copies W back (BAD_STATE while off).  set_dither / get_dither / set_meter /
+ * get_bus_meter are the Batch's, of the buses alone; get_dither reports the mixer's seed as given and the bus position.
+ *
+ * speexhip_debug_mixer_counters: host only, process-wide since start -- FIR launches, input passes, bus-sum launches, output
+ * passes, transfers in, transfers out of the mixer calls.  A transfer in is the call's gathered stage (copied to the
+ * device, or, where the whole call fits the pinned stage, read there by the kernels), plus one for every payload large
+ * enough to travel on its own; a transfer out likewise.
+ *
+ * Not part of this version: a device-pointer form, legs on several GPUs in one mixer, a matrix or planes on a leg's
+ * input side, lining legs up by stream position, resampling a bus back to a leg's own rate (a second many-states call).
+ *
+ * ABI note: adds these eleven entry points and the two limits; SpeexHipInfo, SpeexHipSide, SpeexHipMeter, the enums, the
+ * error codes and the version string are unchanged. */
+typedef struct SpeexHipMixer_ SpeexHipMixer;
+#define SPEEXHIP_MIXER_MAX_LEGS  1024
+#define SPEEXHIP_MIXER_MAX_BUSES 1024
+SPEEXHIP_API SpeexHipMixer *speexhip_mixer_init(uint32_t n_legs, uint32_t n_buses, uint32_t channels, int *err);
+SPEEXHIP_API SpeexHipMixer *speexhip_mixer_init_on(int device, uint32_t n_legs, uint32_t n_buses, uint32_t channels, int *err);
+SPEEXHIP_API void speexhip_mixer_destroy(SpeexHipMixer *m);
+SPEEXHIP_API int speexhip_mixer_set_weights(SpeexHipMixer *m, const float *weights);
+SPEEXHIP_API int speexhip_mixer_get_weights(SpeexHipMixer *m, float *weights);
+SPEEXHIP_API int speexhip_mixer_set_dither(SpeexHipMixer *m, int kind, uint64_t seed, uint64_t position);
+SPEEXHIP_API int speexhip_mixer_get_dither(SpeexHipMixer *m, int *kind, uint64_t *seed, uint64_t *position);
+SPEEXHIP_API int speexhip_mixer_set_meter(SpeexHipMixer *m, int on);
+SPEEXHIP_API int speexhip_mixer_get_bus_meter(SpeexHipMixer *m, uint32_t bus, SpeexHipMeter *meter, int reset);
+SPEEXHIP_API int speexhip_mixer_process(SpeexHipMixer *m, SpeexHipResamplerState *const *legs, const SpeexHipSide *in,
+                                        uint32_t *in_len, uint32_t *out_len, const SpeexHipSide *out, uint32_t *bus_frames,
+                                        int *codes);
+SPEEXHIP_API void speexhip_debug_mixer_counters(uint64_t out[6]);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@
 #include "gain.h"
 #include "meter.h"
 #include "engine.h"
+#include "mixer.h"
 #include "filter_plans.h"
 #include "g711.h"
 #include "halfbe.h"
@@ -44,6 +45,9 @@ struct SpeexHipResamplerState_ {
 };
 struct SpeexHipBatch_ {
   Batch *batch;
+};
+struct SpeexHipMixer_ {
+  speexhip::Mixer *mixer;
 };
 
 extern "C" {
@@ -841,6 +845,77 @@ int speexhip_debug_bus(uint32_t n_streams, uint32_t n_buses, const float *weight
     for (uint32_t i = 0; i < n; i++)
       z[static_cast<size_t>(j) * n + i] = speexhip::bus::sum(weights + static_cast<size_t>(j) * n_streams, y + i, n, n_streams);
   return SPEEXHIP_ERR_SUCCESS;
+}
+
+// ---- the mixer ------------------------------------------------------------------------------------------------------------
+SpeexHipMixer *speexhip_mixer_init(uint32_t n_legs, uint32_t n_buses, uint32_t channels, int *err) {
+  return speexhip_mixer_init_on(-1, n_legs, n_buses, channels, err);
+}
+SpeexHipMixer *speexhip_mixer_init_on(int device, uint32_t n_legs, uint32_t n_buses, uint32_t channels, int *err) {
+  speexhip::Mixer *m = nullptr;
+  int code = SPEEXHIP_ERR_SUCCESS;
+  const int rc = guarded([&] {
+    m = speexhip::Mixer::create(n_legs, n_buses, channels, &code, device);
+    return code;
+  });
+  if (err != nullptr) *err = rc;
+  if (m == nullptr) return nullptr;
+  SpeexHipMixer *h = new (std::nothrow) SpeexHipMixer_{m};
+  if (h == nullptr) {
+    delete m;
+    if (err != nullptr) *err = SPEEXHIP_ERR_ALLOC_FAILED;
+  }
+  return h;
+}
+void speexhip_mixer_destroy(SpeexHipMixer *m) {
+  if (m == nullptr) return;
+  (void)guarded([&] {
+    delete m->mixer;
+    return SPEEXHIP_ERR_SUCCESS;
+  });
+  delete m;
+}
+int speexhip_mixer_set_weights(SpeexHipMixer *m, const float *weights) {
+  return guarded([&] { return m ? m->mixer->set_weights(weights) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_mixer_get_weights(SpeexHipMixer *m, float *weights) {
+  return guarded([&] { return m ? m->mixer->get_weights(weights) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_mixer_set_dither(SpeexHipMixer *m, int kind, uint64_t seed, uint64_t position) {
+  return guarded([&] { return m ? m->mixer->set_dither(kind, seed, position) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_mixer_get_dither(SpeexHipMixer *m, int *kind, uint64_t *seed, uint64_t *position) {
+  return guarded([&] { return m ? m->mixer->get_dither(kind, seed, position) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_mixer_set_meter(SpeexHipMixer *m, int on) {
+  return guarded([&] { return m ? m->mixer->set_meter(on) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_mixer_get_bus_meter(SpeexHipMixer *m, uint32_t bus, SpeexHipMeter *meter, int reset) {
+  return guarded([&] { return m ? m->mixer->get_bus_meter(bus, meter, reset != 0) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_mixer_process(SpeexHipMixer *m, SpeexHipResamplerState *const *legs, const SpeexHipSide *in, uint32_t *in_len,
+                           uint32_t *out_len, const SpeexHipSide *out, uint32_t *bus_frames, int *codes) {
+  speexhip::CallSide o;
+  if (m == nullptr || legs == nullptr || in == nullptr || in_len == nullptr || out_len == nullptr || out == nullptr ||
+      bus_frames == nullptr)
+    return SPEEXHIP_ERR_INVALID_ARG;
+  if (out->planes != nullptr || !side_of(out, false, &o)) return SPEEXHIP_ERR_INVALID_ARG;
+  return guarded([&] {
+    const uint32_t n = m->mixer->n_legs();
+    std::vector<Batch *> b(n);
+    std::vector<speexhip::CallSide> a(n);
+    std::vector<uint8_t> bad(n, 0);
+    for (uint32_t i = 0; i < n; i++) {
+      b[i] = legs[i] != nullptr ? legs[i]->batch : nullptr;
+      // (each leg's struct_size stands at the head of ITS side; stream_stride and planes are not read)
+      if (b[i] != nullptr && !side_of(&in[i], false, &a[i])) bad[i] = 1;
+      a[i].stride = 0;
+    }
+    return m->mixer->process(b.data(), a.data(), bad.data(), in_len, out_len, o, bus_frames, codes);
+  });
+}
+void speexhip_debug_mixer_counters(uint64_t out[6]) {
+  if (out != nullptr) speexhip::mixer_counters(out);
 }
 
 int speexhip_debug_g711_decode(int fmt, const uint8_t *codes, uint32_t n, float *x) {

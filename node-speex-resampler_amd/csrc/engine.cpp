@@ -1587,6 +1587,7 @@ int warm_device(int device) {
   warm_unit_mix(s);
   warm_unit_sides(s);
   warm_unit_bus(s);
+  warm_unit_bus_legs(s);
   HIP_TRY(hipStreamSynchronize(s));
   return SPEEXHIP_ERR_SUCCESS;
 }

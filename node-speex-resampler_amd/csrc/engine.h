@@ -31,6 +31,9 @@ void many_counters(uint64_t out[4]);
 // speexhip_debug_chunk_counters: the same four counts over the formatted chunks call (process_sides_host_chunks); chunks
 // that took a call of their own in the place of entries.
 void chunk_counters(uint64_t out[4]);
+// speexhip_debug_mixer_counters: of the mixer calls -- FIR launches, input passes, bus-sum launches, output passes,
+// transfers in, transfers out.
+void mixer_counters(uint64_t out[6]);
 
 // Everything on the device that depends only on (filter, channel count): the reference-layout sinc
 // table, the fast kernels' tap rows and the launch geometry.  Immutable once built, so states with
@@ -84,6 +87,25 @@ inline bool side_ok(const CallSide &side, uint32_t state_channels) {
 inline bool side_planar(const CallSide &side) { return side.layout == SPEEXHIP_LAYOUT_PLANAR && side.channels != 1; }
 // ... as the route of its call sees it (sides_route.h)
 inline SideKind side_kind(const CallSide &side) { return SideKind{side.fmt, side.mix != nullptr, side_planar(side), side.planes != nullptr}; }
+
+// What a mixer call (mixer.h) hands the unit machinery of the many-states calls (many.cpp, Batch::many_mixer) beside its
+// legs: the buses that stand behind the legs' launches.  The mixer owns all of it; the unit reads it and leaves bus_frames.
+struct MixerCall {
+  int device = 0;
+  uint32_t n_legs = 0, n_buses = 0, channels = 0;
+  const float *d_w = nullptr;    // the resident copy of W as bus_sum_legs reads it (kernels.h)
+  uint32_t w_pitch = 0;
+  CallSide out = {};             // the buses in host memory
+  bool pass_out = false;         // the bus side passes through an image (SidesForm::Bus); else bus_sum_legs writes the stage
+  int dither_kind = SPEEXHIP_DITHER_NONE;  // NONE also where the format is not dithered
+  uint64_t dither_seed = 0, bus_pos = 0;
+  MeterCell *cells = nullptr;    // one per bus; NULL: the meter is off
+  char **bus_image = nullptr;    // the float image of the buses, grow-only
+  size_t *bus_image_cap = nullptr;
+  uint32_t bus_frames = 0;       // out: the length of the buses
+};
+// mix.cpp: the output pass over the buses of a mixer call, beside Batch::side_pass
+int mixer_bus_pass(const MixerCall &mc, const CallSide &side, const char *image, size_t pitch, hipStream_t stream, uint32_t *launches);
 
 class Batch {
  public:
@@ -419,8 +441,15 @@ class Batch {
     bool sides = false;                 // an entry of process_host_many_sides: its own call is process_sides_host on
     CallSide in_side = {}, out_side = {};  // these, and the state's dither, meter and gain count
     SidesRoute route;                   // many_run's: fused or its own call, and as what (SidesForm::ManyEntry)
+    bool leg = false;                   // a leg of a mixer call (SidesForm::MixerLeg): `out` is not read, nothing travels back
   };
   static int many_run(uint32_t n, ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *codes);
+  // The legs of a mixer call (entries[i].leg, rc SUCCESS; i = the slot) as ONE unit on the mixer's device: staged, grouped
+  // and launched as many_run's fused entries are, their results left as float images on the device; behind them the table
+  // of all n slots, bus_sum_legs, the buses' output pass and the one transfer out (many.cpp).  rcs[i] of a leg that ran:
+  // SUCCESS, or the zero fallback's ALLOC_FAILED.
+  static int many_mixer(MixerCall &mc, uint32_t n, ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *rcs);
+  friend class Mixer;  // mixer.cpp: describes its legs as ManyEntry, asks their route and their extents
   struct ManyUnit;  // many.cpp: the fused entries of one (device, lane), planned by many_plan.h and carried out
   bool have_copy_stream();  // copy_stream_ = a pool stream other than own_stream_ (false: none -> no piecewise call)
 

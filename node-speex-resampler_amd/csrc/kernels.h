@@ -379,4 +379,33 @@ constexpr uint32_t kBusGroup = 8;
 hipError_t launch_bus_sum(const BusPack &pack, const GainPack &gain, hipStream_t stream);
 void warm_unit_bus(hipStream_t s);
 
+// ---- ... of a mixer's legs (kernels_bus_legs.hip): the same sum over the slots of a mixer (include/speexhip_resampler.h,
+// "Mixer"), whose legs are too many for a kernel-argument pack.  The legs' records lie in DEVICE memory, one per slot in
+// slot order (they ride in the call's one transfer in), and so does W: the mixer's resident copy, transposed and padded --
+// W[j][s] at w[s * w_pitch + j], w_pitch = n_buses rounded up to kBusGroup (a row's pairs are 8-byte aligned), zeros behind n_buses.  Leg s is frames frames
+// of `channels` floats at src (frames 0: an empty slot, a refused leg, a leg that produced nothing -- +0.0f throughout,
+// summed like any other); bus j is bus_frames frames at dst + j * dst_pitch.
+constexpr uint32_t kBusMaxLegs = SPEEXHIP_MIXER_MAX_LEGS, kBusMaxBuses = SPEEXHIP_MIXER_MAX_BUSES;
+struct BusLeg {             // one slot's record: 64 bytes, so that a record never straddles a cache line
+  const float *src;         // the leg's float image of this call (device memory)
+  uint32_t frames;          // frames it produced
+  uint32_t reserved;
+  GainStream gain;          // first = the leg's done; channels = the mixer's, or 0: not multiplied
+  uint64_t pad[2];
+};
+static_assert(sizeof(BusLeg) == 64, "the leg table is an array of whole lines");
+struct BusLegsArgs {
+  const BusLeg *legs;       // device memory, n_legs records
+  const float *w;           // device memory
+  float *dst;               // bus 0
+  uint64_t dst_pitch;       // floats between two buses (>= bus_frames * channels)
+  uint32_t w_pitch;         // floats between two legs' rows of w
+  uint32_t n_legs, n_buses; // 1..1024 each
+  uint32_t channels;
+  uint32_t bus_frames;      // >= every frames
+};
+// host_legs: the same records where the host can read them (the launcher checks them before it launches)
+hipError_t launch_bus_sum_legs(const BusLegsArgs &a, const BusLeg *host_legs, hipStream_t stream);
+void warm_unit_bus_legs(hipStream_t s);
+
 }  // namespace speexhip

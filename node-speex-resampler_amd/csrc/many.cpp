@@ -41,6 +41,9 @@ struct ManyStage {
 // speexhip_debug_many_counters: FIR launches, input passes, output passes, entries that took their own call
 std::atomic<uint64_t> g_many_counters[4];
 inline void count_many(int which, uint64_t by = 1) { g_many_counters[which].fetch_add(by, std::memory_order_relaxed); }
+// speexhip_debug_mixer_counters: FIR launches, input passes, bus-sum launches, output passes, transfers in, transfers out
+std::atomic<uint64_t> g_mixer_counters[6];
+inline void count_mixer(int which, uint64_t by = 1) { g_mixer_counters[which].fetch_add(by, std::memory_order_relaxed); }
 // (device, lane): a large call on one device runs as two halves side by side, each on a stage of its own (below)
 ManyStage &many_stage(int device, int lane) {
   static std::mutex mu;
@@ -128,7 +131,10 @@ struct Batch::ManyUnit {
   std::vector<ManyShape> shapes;  // (items[k] as the decision sees it; plan.e[k] what was decided)
   ManyUnitPlan plan;
   char *src_base = nullptr, *dst_base = nullptr;  // the stage the kernels read / write: the pinned pair of a small call, else the device pair
+  MixerCall *mixer = nullptr;  // a mixer call's unit (run_mixer): the entries are its legs, the buses stand behind them
 
+  // a FIR launch / an input pass of the unit, in the counters of the call it belongs to
+  void count(int which) const { mixer != nullptr ? count_mixer(which) : count_many(which); }
   static int run(const Unit &unit, const ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *rcs);
   static std::vector<Unit> units_of(const std::map<int, std::vector<uint32_t>> &by_device, const ManyEntry *entries,
                                     const uint32_t *in_len, const uint32_t *out_len);
@@ -138,7 +144,11 @@ struct Batch::ManyUnit {
   }
   void describe(const std::vector<uint32_t> &idx, const ManyEntry *entries);
   int grow();
+  int inputs_in();
   int run_plain();
+  static int run_mixer(const Unit &unit, const ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *rcs, MixerCall &mc);
+  int sum_buses(size_t bus_stride, size_t plane_stride);
+  int buses_out(size_t bus_stride, size_t plane_stride);
   int run_pipelined();
   void launch_behind_copies(HandOver &h);
   int launch_group(const std::vector<uint32_t> &g, hipStream_t stream);
@@ -164,18 +174,20 @@ void Batch::ManyUnit::describe(const std::vector<uint32_t> &idx, const ManyEntry
     // the raw bytes of either side, in the side's own format: what every size decision goes by
     s.in_present = it.e->in != nullptr;
     s.in_bytes = s.in_present ? raw_bytes(*it.e, in_len[it.i], true) : 0;
-    s.out_bytes = raw_bytes(*it.e, it.plan.produced, false);
+    s.leg = it.e->leg;
+    s.out_bytes = s.leg ? 0 : raw_bytes(*it.e, it.plan.produced, false);
     // (a present but empty input is not silence, no frame of it is read)
     s.pass_in = r.pass_in && s.in_present && in_len[it.i] != 0;
     s.pass_out = r.pass_out;
     s.image_in = static_cast<size_t>(in_len[it.i]) * it.b->channels_ * sizeof(float);
     s.image_out = static_cast<size_t>(it.plan.produced) * it.b->channels_ * sizeof(float);
-    pinned_sides(it.e->in, s.in_bytes, it.e->out, s.out_bytes, &it.pin_in, &it.pin_out);
+    pinned_sides(it.e->in, s.in_bytes, s.leg ? nullptr : it.e->out, s.out_bytes, &it.pin_in, &it.pin_out);
     s.in_pinned = it.pin_in != nullptr;
     s.out_pinned = it.pin_out != nullptr;
     s.work = it.plan.produced != 0 || it.plan.magic_used + it.plan.consumed != 0;
     // (the window format as this call will leave it: the state itself is written in run(), once the stage has grown)
-    s.key = ManyKey{reinterpret_cast<uintptr_t>(it.b->tables_.get()), it.b->mode_, it.b->float_seen_ || it.float_io, it.float_io};
+    s.key = ManyKey{reinterpret_cast<uintptr_t>(it.b->tables_.get()), it.b->mode_, it.b->float_seen_ || it.float_io, it.float_io,
+                    it.b->zero_mode_};
   }
 }
 
@@ -229,7 +241,8 @@ void Batch::ManyUnit::commit_item(Item &it, bool work) {
   // (a formatted call moves the state's dither position, meter totals and gain ramp by the frames produced, whatever the
   //  format: its output pass has judged these frames into the state's cell and left them at its g)
   it.b->sides_moved(it.e->route, &out_len[it.i], it.b->channels_);
-  rcs[it.i] = SPEEXHIP_ERR_SUCCESS;
+  // (resample.c:1081: the zero fallback -- among fused entries only a mixer's leg -- reports the failure with every call)
+  rcs[it.i] = it.b->zero_mode_ ? SPEEXHIP_ERR_ALLOC_FAILED : SPEEXHIP_ERR_SUCCESS;
 }
 
 // One launch of the entries g (one of plan.launches) on `stream`, between its passes.
@@ -269,8 +282,9 @@ int Batch::ManyUnit::launch_group(const std::vector<uint32_t> &g, hipStream_t st
     if (crc != SPEEXHIP_ERR_SUCCESS) return crc;
     const void *storage_in = p.in == Via::None ? nullptr : p.in == Via::InPlace ? it.pin_in : src_base + p.in_off;
     void *storage_out = p.out == Via::InPlace ? it.pin_out : dst_base + p.out_off;
-    b->fill_desc(pack.d[j], 0, 0, s.pass_in ? ms.d_img_in + p.img_in : storage_in, s.pass_out ? ms.d_img_out + p.img_out : storage_out,
-                 in_len[it.i], it.plan);
+    // (a mixer's leg: the FIR's image is the result, in a range of its own; no storage stands behind it)
+    b->fill_desc(pack.d[j], 0, 0, s.pass_in ? ms.d_img_in + p.img_in : storage_in,
+                 s.pass_out || s.leg ? ms.d_img_out + p.img_out : storage_out, in_len[it.i], it.plan);
     if (s.pass_in) {
       ConvertStream &c = to_image.s[j];
       c.src = storage_in, c.dst = ms.d_img_in + p.img_in;
@@ -302,11 +316,11 @@ int Batch::ManyUnit::launch_group(const std::vector<uint32_t> &g, hipStream_t st
   }
   if (most_to != 0) {
     if (hip_failed(launch_convert_many(false, to_image, dith, cnt, most_to, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
-    count_many(1);
+    count(1);
   }
   const int lrc = items[g[0]].b->launch_chunk(pack.d, pack, cnt, max_out, float_io, stream);
   if (lrc != SPEEXHIP_ERR_SUCCESS) return lrc;
-  count_many(0);
+  count(0);
   if (most_from != 0) {
     if (hip_failed(launch_convert_many(true, from_image, dith, cnt, most_from, stream, metered ? &cells : nullptr, gained ? &gains : nullptr),
                    "kernel launch"))
@@ -332,7 +346,7 @@ int Batch::ManyUnit::launch_group(const std::vector<uint32_t> &g, hipStream_t st
 }
 
 // One thread, one stream: the inputs in, the launches, the results back, the wait the plan chose.
-int Batch::ManyUnit::run_plain() {
+int Batch::ManyUnit::inputs_in() {
   for (size_t k = 0; k < items.size(); k++) {
     const ManyShape &s = shapes[k];
     const ManyEntryPlan &p = plan.e[k];
@@ -342,6 +356,11 @@ int Batch::ManyUnit::run_plain() {
   }
   // (not small: the gathered range holds the Staged buffers)
   if (!plan.small && plan.gathered_in != 0) HIP_TRY(hipMemcpyAsync(ms.d_in, ms.h_in, plan.gathered_in, hipMemcpyHostToDevice, ms.stream));
+  return SPEEXHIP_ERR_SUCCESS;
+}
+int Batch::ManyUnit::run_plain() {
+  const int irc = inputs_in();
+  if (irc != SPEEXHIP_ERR_SUCCESS) return irc;
   for (const ManyLaunch &l : plan.launches) {
     const int rc = launch_group(l.entries, ms.stream);
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
@@ -453,6 +472,141 @@ void Batch::ManyUnit::launch_behind_copies(HandOver &h) {
 
 void many_counters(uint64_t out[4]) {
   for (int k = 0; k < 4; k++) out[k] = g_many_counters[k].load(std::memory_order_relaxed);
+}
+void mixer_counters(uint64_t out[6]) {
+  for (int k = 0; k < 6; k++) out[k] = g_mixer_counters[k].load(std::memory_order_relaxed);
+}
+
+// ---- the unit of a mixer call (engine.h, many_mixer; include/speexhip_resampler.h, "Mixer") -------------------------------
+// The legs are staged, grouped and launched as run_plain does it -- the table of ALL the call's slots at the head of the
+// range that travels in -- and stay float images on the device; behind the last launch bus_sum_legs (kernels_bus_legs.hip)
+// sums every slot into the buses, the existing output pass encodes them into the head of the range that travels out, and
+// that range goes back as one copy (a small call: the kernels wrote the pinned stage) and from there into the caller's
+// bus buffers.  Never pipelined, never two lanes: a tick is small, and the buses need every leg.
+int Batch::ManyUnit::run_mixer(const Unit &unit, const ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *rcs, MixerCall &mc) {
+  ManyStage &ms = many_stage(unit.device, unit.lane);
+  std::lock_guard<std::mutex> lock(ms.mu);
+  DeviceScope device_scope(unit.device);
+  HIP_TRY(device_scope.error());
+  if (ms.stream == nullptr) HIP_TRY(pool::stream_get(unit.device, &ms.stream));
+  DrainOnExit drain(&ms.stream);
+  ManyUnit u{unit.device, unit.lane, ms, in_len, out_len, rcs, {}, {}, {}};
+  u.mixer = &mc;
+  u.describe(unit.idx, entries);
+  mc.bus_frames = 0;
+  for (const Item &it : u.items) mc.bus_frames = std::max(mc.bus_frames, it.plan.produced);
+  // The buses in the stage, as their side stores them: bus j begins j * bus_stride samples behind bus 0 (whole 64-sample
+  // runs, so that every bus begins on a line whatever the format), a planar side's plane c another c * plane_stride.
+  const bool planar = mc.out.layout == SPEEXHIP_LAYOUT_PLANAR;
+  const size_t plane_stride = planar ? (static_cast<size_t>(mc.bus_frames) + 15) & ~static_cast<size_t>(15) : 0;
+  const size_t bus_samples = planar ? plane_stride * mc.channels : static_cast<size_t>(mc.bus_frames) * mc.channels;
+  const size_t bus_stride = (bus_samples + 63) & ~static_cast<size_t>(63);
+  ManyExtra extra;
+  extra.in_bytes = sizeof(BusLeg) * mc.n_legs;
+  extra.out_bytes = bus_stride * mc.n_buses * sample_bytes(mc.out.fmt);
+  const ManySwitches switches = {1, 0};  // (no pipeline)
+  u.plan = plan_many_unit(u.shapes.data(), u.shapes.size(), switches, extra);
+  int rc = u.grow();
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  if (mc.pass_out) {
+    rc = grow_stage(unit.device, mc.bus_image, mc.bus_image_cap, bus_stride * mc.n_buses * sizeof(float), false);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  }
+  // The table: one record per SLOT, in slot order.  A slot without a leg that runs -- empty, refused -- stays zeros: no
+  // frames, +0.0f throughout.  A leg's gain is read here, before its launch commits and moves it.
+  BusLeg *table = reinterpret_cast<BusLeg *>(ms.h_in);
+  std::memset(table, 0, sizeof(BusLeg) * mc.n_legs);
+  for (size_t k = 0; k < u.items.size(); k++) {
+    const Item &it = u.items[k];
+    BusLeg &leg = table[it.i];
+    leg.src = reinterpret_cast<const float *>(ms.d_img_out + u.plan.e[k].img_out);
+    leg.frames = it.plan.produced;
+    if (it.e->route.moves_gain) leg.gain = it.b->gain_pack(0, 1, mc.channels).s[0];
+  }
+  for (const Item &it : u.items) {
+    it.b->float_seen_ = true;
+    if (in_len[it.i] != 0 && out_len[it.i] != 0) it.b->started_[0] = 1;  // resample.c:886
+  }
+  rc = u.inputs_in();
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  // (the stage is the call's one transfer in -- copied, or read in place by the kernels of a small call; a payload large
+  //  enough to travel on its own counts beside it)
+  count_mixer(4);
+  for (const ManyEntryPlan &e : u.plan.e)
+    if (e.in == Via::Copy) count_mixer(4);
+  for (const ManyLaunch &l : u.plan.launches) {
+    rc = u.launch_group(l.entries, ms.stream);
+    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  }
+  u.commit_idle();
+  rc = u.sum_buses(bus_stride, plane_stride);
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  rc = u.buses_out(bus_stride, plane_stride);
+  if (rc == SPEEXHIP_ERR_SUCCESS) drain.armed = false;
+  return rc;
+}
+
+// bus_sum_legs over the table, then the output pass over the buses, into the stage that travels out
+int Batch::ManyUnit::sum_buses(size_t bus_stride, size_t plane_stride) {
+  MixerCall &mc = *mixer;
+  if (mc.bus_frames == 0) return SPEEXHIP_ERR_SUCCESS;
+  const BusLeg *table = reinterpret_cast<const BusLeg *>(ms.h_in);
+  BusLegsArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.legs = reinterpret_cast<const BusLeg *>(src_base);  // (the head of the range that travelled in)
+  a.w = mc.d_w;
+  a.w_pitch = mc.w_pitch;
+  // (an interleaved F32 side IS the buses' image: the kernel writes the stage itself)
+  a.dst = reinterpret_cast<float *>(mc.pass_out ? *mc.bus_image : dst_base);
+  a.dst_pitch = bus_stride;
+  a.n_legs = mc.n_legs;
+  a.n_buses = mc.n_buses;
+  a.channels = mc.channels;
+  a.bus_frames = mc.bus_frames;
+  if (hip_failed(launch_bus_sum_legs(a, table, ms.stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+  count_mixer(2);
+  CallSide stage = mc.out;
+  stage.base = dst_base;
+  stage.stride = bus_stride;
+  stage.plane_stride = plane_stride;
+  uint32_t passes = 0;
+  const int prc = mixer_bus_pass(mc, stage, mc.pass_out ? *mc.bus_image : nullptr, bus_stride, ms.stream, &passes);
+  count_mixer(3, passes);
+  return prc;
+}
+
+// the buses back: the one copy of a call that is not small, the wait, and the stage's buses into the caller's buffers
+int Batch::ManyUnit::buses_out(size_t bus_stride, size_t plane_stride) {
+  const MixerCall &mc = *mixer;
+  const size_t es = sample_bytes(mc.out.fmt);
+  const size_t out_bytes = bus_stride * mc.n_buses * es;
+  if (mc.bus_frames != 0) {
+    if (!plan.small) HIP_TRY(hipMemcpyAsync(ms.h_out, ms.d_out, out_bytes, hipMemcpyDeviceToHost, ms.stream));
+    count_mixer(5);
+  }
+  if (plan.wait.sync || !plan.launches.empty()) {
+    const int wrc = wait_call(ms.stream, plan.wait, tail_word(ms.h_out, ms.h_out_cap), ++ms.seq);
+    if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
+  }
+  const bool planar = mc.out.layout == SPEEXHIP_LAYOUT_PLANAR;
+  for (uint32_t j = 0; j < mc.n_buses && mc.bus_frames != 0; j++) {
+    char *to = static_cast<char *>(mc.out.base) + j * mc.out.stride * es;
+    const char *from = ms.h_out + j * bus_stride * es;
+    if (!planar) {
+      std::memcpy(to, from, static_cast<size_t>(mc.bus_frames) * mc.channels * es);
+    } else {
+      for (uint32_t c = 0; c < mc.channels; c++)
+        std::memcpy(to + c * mc.out.plane_stride * es, from + c * plane_stride * es, static_cast<size_t>(mc.bus_frames) * es);
+    }
+  }
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+int Batch::many_mixer(MixerCall &mc, uint32_t n, ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *rcs) {
+  Unit unit{mc.device, 0, {}};
+  for (uint32_t i = 0; i < n; i++)
+    if (entries[i].leg && entries[i].rc == SPEEXHIP_ERR_SUCCESS && entries[i].b != nullptr) unit.idx.push_back(i);
+  return ManyUnit::run_mixer(unit, entries, in_len, out_len, rcs, mc);
 }
 
 // process_many_int / _float: the all-S16 / all-F32 case of many_run -- every entry the int16 call, or the float call, on

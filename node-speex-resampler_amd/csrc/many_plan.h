@@ -2,6 +2,7 @@
 // checks it against its tables and over random shapes).  many.cpp describes the fused entries of one unit -- the states of
 // one (device, lane) -- as ManyShapes and carries out what plan_many_unit answers; plan_many_lanes splits a device's
 // states into units, many_primes_copy_stream says which units get their copy stream before anything is copied.
+// A mixer call (mixer.cpp) plans its legs here as well: ManyShape::leg, ManyExtra, ManyKey::zero.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -23,13 +24,15 @@ inline size_t align128(size_t v) { return (v + 127) & ~static_cast<size_t>(127);
 
 // What the states of one launch share, in the order the launches are queued: the filter's tables (their address), the
 // mode, the window format (a float call has put samples into the history that an int16 window cannot hold) and the sample
-// type of the launch.
+// type of the launch -- and, among a mixer's legs, whether the state is in the zero fallback (its launch writes zeros; a
+// fused entry of the many-states calls never is: such a state takes its own call).
 struct ManyKey {
   uintptr_t tables = 0;
   int mode = 0;
   bool float_window = false, float_io = false;
+  bool zero = false;
   bool operator<(const ManyKey &o) const {
-    return std::tie(tables, mode, float_window, float_io) < std::tie(o.tables, o.mode, o.float_window, o.float_io);
+    return std::tie(tables, mode, float_window, float_io, zero) < std::tie(o.tables, o.mode, o.float_window, o.float_io, o.zero);
   }
 };
 
@@ -42,6 +45,15 @@ struct ManyShape {
   bool pass_in = false, pass_out = false;      // the side's storage goes through a float image ...
   size_t image_in = 0, image_out = 0;          // ... of this many bytes
   ManyKey key;
+  // a leg of a mixer call (mixer.cpp): its result STAYS its float image on the device, a range of its own among the output
+  // images -- no storage, no output pass, nothing that travels back (out_bytes 0, pass_out false)
+  bool leg = false;
+};
+// What a mixer call moves beside its legs' inputs: the table of the legs at the head of the range that travels in, the
+// buses (as their side stores them) at the head of the range that travels out.  They go the gathered way, whatever their
+// size: one copy each way, or the pinned stage of a small call.
+struct ManyExtra {
+  size_t in_bytes = 0, out_bytes = 0;
 };
 struct ManySwitches {     // the diagnostics build's: SPEEXHIP_PIN_IN_COPY (0 = read in place even then), _MANY_PIPELINE (0 = off)
   int pin_in_copy = 1, pipeline = -1;
@@ -67,9 +79,11 @@ struct ManyUnitPlan {
   std::vector<ManyLaunch> launches;  // entry indices, in the order the launches are queued
 };
 
-inline ManyUnitPlan plan_many_unit(const ManyShape *shapes, size_t n, const ManySwitches &sw) {
+inline ManyUnitPlan plan_many_unit(const ManyShape *shapes, size_t n, const ManySwitches &sw, const ManyExtra &extra = ManyExtra()) {
   ManyUnitPlan p;
   p.e.resize(n);
+  p.total_in = align64(extra.in_bytes);
+  p.total_out = align64(extra.out_bytes);
   for (size_t k = 0; k < n; k++) {
     const ManyShape &s = shapes[k];
     ManyEntryPlan &e = p.e[k];
@@ -81,7 +95,7 @@ inline ManyUnitPlan plan_many_unit(const ManyShape *shapes, size_t n, const Many
     e.img_in = p.images_in;
     e.img_out = p.images_out;
     if (s.pass_in) p.images_in += align128(s.image_in);
-    if (s.pass_out) p.images_out += align128(s.image_out);
+    if (s.pass_out || s.leg) p.images_out += align128(s.image_out);
     p.total_in += align64(s.in_pinned && !e.demoted ? 0 : s.in_bytes);
     p.total_out += align64(s.out_pinned ? 0 : s.out_bytes);
   }
@@ -94,7 +108,7 @@ inline ManyUnitPlan plan_many_unit(const ManyShape *shapes, size_t n, const Many
     const ManyShape &s = shapes[k];
     ManyEntryPlan &e = p.e[k];
     e.in = route_side(s.in_bytes, s.in_present, s.in_pinned && !e.demoted, p.small);
-    e.out = route_side(s.out_bytes, true, s.out_pinned, p.small);
+    e.out = s.leg ? Via::None : route_side(s.out_bytes, true, s.out_pinned, p.small);
     p.wait.add(e.in, s.in_bytes);
     p.wait.add(e.out, s.out_bytes);
     if (s.work && (e.in != Via::Copy || e.out != Via::Copy)) p.all_big = false;
@@ -102,7 +116,10 @@ inline ManyUnitPlan plan_many_unit(const ManyShape *shapes, size_t n, const Many
   // layout: the gathered buffers first (one contiguous range = one copy), then the Copy ones.  A small call's stage is
   // the pinned pair, a larger one's the device pair.
   auto through_stage = [&p](Via v, size_t bytes) { return align64(p.small ? pinned_part(v, bytes) : device_part(v, bytes)); };
-  size_t off_in = 0, off_out = 0;
+  // (a mixer call's table and buses lie at the head of the gathered ranges)
+  if (extra.in_bytes != 0) p.wait.add(p.small ? Via::Bounce : Via::Staged, extra.in_bytes);
+  if (extra.out_bytes != 0) p.wait.add(p.small ? Via::Bounce : Via::Staged, extra.out_bytes);
+  size_t off_in = p.gathered_in = align64(extra.in_bytes), off_out = p.gathered_out = align64(extra.out_bytes);
   for (int pass = 0; pass < 2; pass++)
     for (size_t k = 0; k < n; k++) {
       ManyEntryPlan &e = p.e[k];

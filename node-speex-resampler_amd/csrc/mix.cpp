@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "dither.h"
 #include "engine.h"
 #include "engine_detail.h"
 
@@ -101,6 +102,69 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
       e = launch_convert(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream, meter, gain);
     }
     if (hip_failed(e, "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+  }
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+// The output pass over the buses of a MIXER call (engine.h, MixerCall): side_pass's launches over items that belong to no
+// Batch -- bus j is mc.bus_frames frames of mc.channels floats at image + j * pitch (floats) and leaves for side.base +
+// j * side.stride (samples), dithered from the mixer's bus seeds at its bus position, judged into its cells, never gained.
+// A side that passes through no image (interleaved F32: bus_sum_legs wrote side.base) is only read, by meter_image, when
+// the meter is on.  *launches: the passes launched.
+int mixer_bus_pass(const MixerCall &mc, const CallSide &side, const char *image, size_t pitch, hipStream_t stream, uint32_t *launches) {
+  const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
+  const bool planar = side.layout == SPEEXHIP_LAYOUT_PLANAR;
+  const bool dithered = mc.dither_kind != SPEEXHIP_DITHER_NONE && dithered_fmt(side.fmt);
+  if (!mc.pass_out && mc.cells == nullptr) return SPEEXHIP_ERR_SUCCESS;
+  for (uint32_t first = 0; first < mc.n_buses && mc.bus_frames != 0; first += kChunk) {
+    const uint32_t n = std::min(kChunk, mc.n_buses - first);
+    DitherPack dith;
+    std::memset(&dith, 0, sizeof(dith));
+    dith.kind = mc.dither_kind;
+    MeterPack cells;
+    std::memset(&cells, 0, sizeof(cells));
+    for (uint32_t j = 0; j < n; j++) {
+      dith.s[j].seed = dither::stream_seed(mc.dither_seed, mc.n_legs + first + j);
+      dith.s[j].first = mc.bus_pos * (planar ? 1 : mc.channels);  // (mod 2^64, like idx)
+      if (mc.cells != nullptr) cells.cell[j] = mc.cells + first + j;
+    }
+    const MeterPack *meter = mc.cells != nullptr ? &cells : nullptr;
+    const size_t es = sample_bytes(side.fmt);
+    hipError_t e;
+    if (!mc.pass_out) {
+      ConvertPack pack;
+      std::memset(&pack, 0, sizeof(pack));
+      for (uint32_t j = 0; j < n; j++) {
+        pack.s[j].src = static_cast<const char *>(side.base) + (first + j) * side.stride * es;
+        pack.s[j].n = static_cast<uint64_t>(mc.bus_frames) * mc.channels;
+        pack.s[j].step = 1;
+      }
+      e = launch_meter_image(pack, cells, 1.0f, n, static_cast<uint64_t>(mc.bus_frames) * mc.channels, stream);
+    } else if (planar) {
+      PlanePack pack;
+      std::memset(&pack, 0, sizeof(pack));
+      pack.storage_channels = pack.image_channels = pack.image_pitch = mc.channels;
+      for (uint32_t j = 0; j < n; j++) {
+        pack.s[j].src = image + (first + j) * pitch * sizeof(float);
+        pack.s[j].dst = static_cast<char *>(side.base) + (first + j) * side.stride * es;
+        pack.s[j].plane_stride = side.plane_stride;
+        pack.s[j].frames = mc.bus_frames;
+      }
+      e = launch_planes(side.fmt, true, pack, dithered ? &dith : nullptr, n, mc.bus_frames, stream, meter, nullptr);
+    } else {
+      ConvertPack pack;
+      std::memset(&pack, 0, sizeof(pack));
+      for (uint32_t j = 0; j < n; j++) {
+        pack.s[j].src = image + (first + j) * pitch * sizeof(float);
+        pack.s[j].dst = static_cast<char *>(side.base) + (first + j) * side.stride * es;
+        pack.s[j].n = static_cast<uint64_t>(mc.bus_frames) * mc.channels;
+        pack.s[j].step = 1;
+      }
+      e = launch_convert(side.fmt, true, pack, dithered ? &dith : nullptr, n, static_cast<uint64_t>(mc.bus_frames) * mc.channels, stream, meter,
+                         nullptr);
+    }
+    if (hip_failed(e, "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+    if (launches != nullptr) (*launches)++;
   }
   return SPEEXHIP_ERR_SUCCESS;
 }

@@ -1,6 +1,6 @@
 // sides_route.h -- the route of a formatted, mixed or sides call: host only, a pure function of what the sides are and
 // what the state has on, checked row by row on the CPU (tools/san_host.cpp) like route_host_call (host_transfer.h) and
-// plan_many_unit (many_plan.h).  The entry points (formats.cpp, many.cpp, bus.cpp) describe their call and carry out the
+// plan_many_unit (many_plan.h).  The entry points (formats.cpp, many.cpp, bus.cpp, mixer.cpp) describe their call and carry out the
 // answer.  They differ in small ways that their histories chose; each difference is one commented line below and a
 // sentence in DESIGN.md ("The route of a formatted call").
 #pragma once
@@ -22,8 +22,8 @@ struct SidesState {
   bool repeated;             // ManyEntry: the state is named by an earlier entry of the call
 };
 // the entry point that asks: process_sides_device, process_sides_host, planes_host_call, process_sides_host_chunks, an
-// entry of many_run, process_bus_device
-enum class SidesForm { Device, Host, PlanesHost, Chunks, ManyEntry, Bus };
+// entry of many_run, process_bus_device, a leg of a mixer call (mixer.cpp: `out` is the leg's float image, interleaved F32)
+enum class SidesForm { Device, Host, PlanesHost, Chunks, ManyEntry, Bus, MixerLeg };
 
 struct SidesRoute {
   // SPEEXHIP_ERR_SUCCESS, or the code the call returns before it touches anything.  late (Host only): the code is returned
@@ -42,8 +42,8 @@ struct SidesRoute {
   float finish_scale = 1.0f;               // what the stored value is judged at: 32768 for F32N on its own bytes
   // what moves behind the call (Bus: the bus position and the bus totals in the place of the streams')
   bool moves_dither = false, counts_meter = false, moves_gain = false;
-  // ManyEntry: the entry joins a launch group.  Chunks: the chunks share their launches (a direct call whose state
-  // process_host_chunks serves chunk by chunk does not).
+  // ManyEntry, MixerLeg: the entry joins a launch group.  Chunks: the chunks share their launches (a direct call whose
+  // state process_host_chunks serves chunk by chunk does not).
   bool fusable = false;
 };
 
@@ -184,6 +184,23 @@ inline SidesRoute route_sides_call(SidesForm form, const SideKind &in, const Sid
       // gained before they were summed
       r.finish = !r.pass_out && st.meter ? SidesRoute::MeterImage : SidesRoute::Nothing;
       // Bus: gain moves; the bus position and the bus totals move in the place of the streams'
+      return r;
+    }
+    case SidesForm::MixerLeg: {
+      // MixerLeg: a leg is one interleaved host buffer (or one channel) without matrix, of a single-stream state that no
+      // earlier slot names -- argument errors, found with the arguments
+      if (in.mix || in.planar || in.planes || !st.single_stream || st.repeated) return refused(SPEEXHIP_ERR_INVALID_ARG);
+      // MixerLeg: a bus has no frame to sum channels that stand apart in
+      if (st.split) return refused(SPEEXHIP_ERR_BAD_STATE);
+      // MixerLeg: no same-bytes route -- the leg's result is always its float image of the call, where the bus-sum kernel
+      // reads it: no output pass, nothing finished in place (the kernel gains the leg as it sums it)
+      SidesRoute r;
+      r.kind = SidesRoute::Images;
+      r.pass_in = side_passes(in);
+      // MixerLeg: gain moves; the leg's own dither position and meter totals do not -- nothing of a leg is encoded.  The
+      // zero fallback joins its launch group like any leg
+      r.moves_gain = st.gain;
+      r.fusable = true;
       return r;
     }
   }

@@ -307,4 +307,32 @@ export declare class SpeexResamplerBatch {
     destroy(): void;
 }
 
+/**
+ * Mix buses over many separate SpeexResampler instances in one library call per tick: nLegs slots, nBuses buses, one
+ * channel count.  Bus j is the float64 sum, in ascending slot order and rounded once, of rows[j][i] times slot i's output
+ * of the call (behind that leg's own setGain), encoded in outFormat with the mixer's dither and meter.
+ */
+export declare class SpeexResamplerMixer {
+    nLegs: number;
+    nBuses: number;
+    channels: number;
+    legs: Array<SpeexResampler | null>;
+    constructor(nLegs: number, nBuses: number, channels: number, options?: { device?: number });
+    /** the instance in slot i (of the mixer's channel count), or null: an empty slot */
+    setLeg(i: number, resampler: SpeexResampler | null): void;
+    /** rows[j][i]: the weight of slot i in bus j; null: off.  Zeroes the bus meters and the buses' dither position */
+    setWeights(rows: number[][] | null): void;
+    setDither(kind: DitherKind, seed?: bigint | number, position?: bigint | number): void;
+    getDither(): { kind: DitherKind, seed: bigint, position: bigint };
+    setMeter(on: boolean): void;
+    getBusMeter(j: number, options?: { reset?: boolean }): MeterTotals;
+    /**
+     * One tick, synchronously: chunks[i] in inFormats[i] (one name for all slots or one per slot; null for an empty slot).
+     * codes[i] !== 0: a leg the library refused -- its state untouched, silence in the sum.
+     */
+    process(chunks: Array<Buffer | null>, inFormats: SampleFormat | SampleFormat[], outFormat: SampleFormat):
+        { buses: Buffer[], busFrames: number, produced: number[], codes: number[] };
+    destroy(): void;
+}
+
 export default SpeexResampler;

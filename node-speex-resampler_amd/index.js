@@ -943,6 +943,141 @@ class SpeexResamplerBatch {
   destroy() { for (const r of this.streams) r.destroy(); }
 }
 /**
+ * Extension.  A mixer: mix buses over many separate SpeexResampler instances in ONE library call per tick -- a conference
+ * bridge whose legs are G.711 at 8 kHz, wideband at 16 kHz and studio feeds at 48 kHz, every participant's mix-minus feed
+ * encoded on the GPU.  nLegs slots, nBuses buses, one channel count; every leg keeps its own rates, quality, gain and ramp
+ * (leg.setGain) and is fed in its own sample format.  Bus j is the sum, in ascending slot order and in float64, rounded
+ * once, of rows[j][i] times slot i's output of the call; it leaves in outFormat through the format's encoder, the mixer's
+ * dither and the mixer's meter.  Only the buses travel back: nothing of a leg is encoded.
+ */
+class SpeexResamplerMixer {
+  constructor(nLegs, nBuses, channels, options = undefined) {
+    for (const [v, name] of [[nLegs, 'nLegs'], [nBuses, 'nBuses'], [channels, 'channels']]) {
+      if (!Number.isInteger(v) || v < 1) throw new Error(name + ' must be a positive integer');
+    }
+    if (nLegs > 1024 || nBuses > 1024) throw new Error('a mixer has at most 1024 legs and 1024 buses');
+    this.nLegs = nLegs;
+    this.nBuses = nBuses;
+    this.channels = channels;
+    this.legs = new Array(nLegs).fill(null);
+    this._device = options && Number.isInteger(options.device) ? options.device : -1;
+    this._ptr = undefined;
+  }
+
+  _native() {
+    if (!speexModule) {
+      throw new Error('You need to wait for SpeexResampler.initPromise before calling this method');
+    }
+    if (!this._ptr) this._ptr = speexModule.mixerInit(this.nLegs, this.nBuses, this.channels, this._device);
+    return this._ptr;
+  }
+
+  /** the SpeexResampler in slot i (its channel count must be the mixer's), or null: an empty slot */
+  setLeg(i, resampler) {
+    if (!Number.isInteger(i) || i < 0 || i >= this.nLegs) throw new Error('no such slot: ' + i);
+    if (resampler !== null && !(resampler instanceof SpeexResampler)) throw new Error('a leg is a SpeexResampler or null');
+    if (resampler !== null && resampler.channels !== this.channels) throw new Error('a leg has the mixer\'s channel count: ' + this.channels);
+    this.legs[i] = resampler;
+  }
+
+  /** rows[j][i] = the weight of slot i in bus j (nBuses rows of nLegs finite numbers; mix-minus: 1 everywhere, 0 on the
+   *  diagonal); null turns the mixer off.  Zeroes the bus meters and the buses' dither position. */
+  setWeights(rows) {
+    if (rows === null) {
+      speexModule.mixerSetWeights(this._native(), null);
+      return;
+    }
+    if (!Array.isArray(rows) || rows.length !== this.nBuses) throw new Error('setWeights expects ' + this.nBuses + ' rows');
+    const w = new Float32Array(this.nBuses * this.nLegs);
+    rows.forEach((row, j) => {
+      if (!row || row.length !== this.nLegs) throw new Error('setWeights expects rows of ' + this.nLegs + ' weights');
+      for (let i = 0; i < this.nLegs; i++) {
+        if (typeof row[i] !== 'number' || !Number.isFinite(row[i])) throw new Error('a weight must be a finite number');
+        w[j * this.nLegs + i] = row[i];
+      }
+    });
+    speexModule.mixerSetWeights(this._native(), Buffer.from(w.buffer));
+  }
+
+  /** dither of the buses' integer and companded outputs: bus j draws from seed + (nLegs + j) * 0x9E3779B97F4A7C15 (mod 2^64) */
+  setDither(kind, seed = 0n, position = 0n) {
+    const code = DITHER_KINDS.indexOf(kind);
+    if (code < 0) throw new Error("dither must be 'none', 'rectangular' or 'triangular'");
+    const s = BigInt.asUintN(64, BigInt(seed));
+    const p = BigInt.asUintN(64, BigInt(position));
+    speexModule.mixerSetDither(this._native(), code, Number(s & 0xffffffffn), Number(s >> 32n), Number(p & 0xffffffffn), Number(p >> 32n));
+  }
+
+  /** { kind, seed, position }: the seed as given, the buses' one position (bigints) */
+  getDither() {
+    const [code, sLo, sHi, pLo, pHi] = speexModule.mixerGetDither(this._native());
+    return { kind: DITHER_KINDS[code], seed: (BigInt(sHi) << 32n) | BigInt(sLo), position: (BigInt(pHi) << 32n) | BigInt(pLo) };
+  }
+
+  setMeter(on) { speexModule.mixerSetMeter(this._native(), !!on); }
+
+  /** getMeter's object, of bus j's own cell; { reset: true } clears that bus only */
+  getBusMeter(j, options = undefined) {
+    const v = speexModule.mixerGetBusMeter(this._native(), j >>> 0, !!(options && options.reset));
+    const big = (i) => (BigInt(v[i + 1]) << 32n) | BigInt(v[i]);
+    return { on: v[0] !== 0, samples: big(1), clippedHigh: big(3), clippedLow: big(5), nan: big(7), peak: v[9] };
+  }
+
+  /**
+   * One tick, synchronously.  chunks[i]: the Buffer of slot i's interleaved frames in its input format (null / undefined
+   * for an empty slot; an empty Buffer: the leg runs on nothing); inFormats: one of processChunkFormat's names for all
+   * slots, or one per slot; outFormat: the buses' format.  Every leg advances as by processChunkFormat(chunk, inFormat,
+   * 'f32le') -- the same state, the same grow-only capacity rule -- and its gain ramp by the frames it produced.
+   * Returns { buses: Buffer[] (bus j: busFrames interleaved frames in outFormat), busFrames, produced: number[], codes:
+   * number[] }: codes[i] !== 0 is a leg the library refused -- its state untouched, silence in the sum, the tick not lost.
+   * Refuses while a leg has an asynchronous call pending, as SpeexResamplerBatch.processChunksFormat does.
+   */
+  process(chunks, inFormats, outFormat) {
+    if (!Array.isArray(chunks) || chunks.length !== this.nLegs) throw new Error('process expects one chunk (or null) per slot: ' + this.nLegs);
+    const names = Array.isArray(inFormats) ? inFormats : new Array(this.nLegs).fill(inFormats);
+    if (names.length !== this.nLegs) throw new Error('process expects one format name, or one per slot: ' + this.nLegs);
+    const fout = SAMPLE_FORMATS[outFormat];
+    if (!fout) throw new Error('Unknown sample format: ' + outFormat);
+    const ptr = this._native();
+    // formats and chunks are all checked before any leg's state is touched: a tick is refused whole
+    const fin = names.map((name, i) => {
+      if (!this.legs[i]) return null;
+      const f = SAMPLE_FORMATS[name];
+      if (!f) throw new Error('Unknown sample format: ' + name);
+      return f;
+    });
+    for (let i = 0; i < this.nLegs; i++) {
+      const leg = this.legs[i];
+      if (!leg) continue;
+      leg._refuseWhileAsyncPending('SpeexResamplerMixer.process');
+      if (chunks[i] === null || chunks[i] === undefined) throw new Error('slot ' + i + ' has a leg and no chunk');
+      if (chunks[i].length % (this.channels * fin[i].bytes) !== 0) {
+        throw new Error('Chunk length should be a multiple of channels * ' + fin[i].bytes + ' bytes');
+      }
+    }
+    const handles = [], bufs = [], inFrames = [], caps = [], fmts = [];
+    for (let i = 0; i < this.nLegs; i++) {
+      const leg = this.legs[i];
+      if (!leg) {
+        handles.push(null), bufs.push(null), inFrames.push(0), caps.push(0), fmts.push(fout.id);
+        continue;
+      }
+      // the capacity rule of leg.processChunkFloat on these frames
+      const frames = (chunks[i].length / this.channels / fin[i].bytes) | 0;
+      const [, cap] = leg._prepare({ length: frames * this.channels * Float32Array.BYTES_PER_ELEMENT }, Float32Array.BYTES_PER_ELEMENT);
+      handles.push(leg._resamplerPtr), bufs.push(chunks[i].length ? chunks[i] : null), inFrames.push(frames), caps.push(cap), fmts.push(fin[i].id);
+    }
+    const r = speexModule.mixerProcess(ptr, handles, bufs, inFrames, caps, fmts, fout.id);
+    return { buses: r.buses, busFrames: r.busFrames, produced: r.produced, codes: r.codes };
+  }
+
+  destroy() {
+    if (this._ptr) speexModule.mixerDestroy(this._ptr);
+    this._ptr = undefined;
+  }
+}
+
+/**
  * Extension.  Destroyed (or collected) states leave their device buffers, pinned staging buffers and
  * filter tables in a process-wide pool for the next `new SpeexResampler` (DESIGN 3.5); this hands
  * whatever is idle there back to the driver and returns the number of bytes.
@@ -1259,4 +1394,5 @@ class SpeexResamplerTransform extends Transform {
 
 exports.SpeexResamplerTransform = SpeexResamplerTransform;
 exports.SpeexResamplerBatch = SpeexResamplerBatch;
+exports.SpeexResamplerMixer = SpeexResamplerMixer;
 exports.default = SpeexResampler;

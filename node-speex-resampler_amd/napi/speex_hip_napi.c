@@ -1866,6 +1866,327 @@ static napi_value Stats(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+/* ---- the mixer (speexhip_mixer_*): mix buses over many separate states in one host call ---------------------------------
+ * A mixer handle is an external of its own; its calls are synchronous, on the calling thread.  The legs are ordinary
+ * resampler handles: mixerProcess holds the lock of every leg for the call, taken in address order like processMany. */
+typedef struct {
+  SpeexHipMixer *m;
+  uint32_t n_legs, n_buses, channels;
+} MixerHandle;
+
+static void finalize_mixer(napi_env env, void *data, void *hint) {
+  (void)env;
+  (void)hint;
+  MixerHandle *h = (MixerHandle *)data;
+  if (h->m != NULL) speexhip_mixer_destroy(h->m);
+  free(h);
+}
+static MixerHandle *unwrap_mixer(napi_env env, napi_value v) {
+  void *p = NULL;
+  if (napi_get_value_external(env, v, &p) != napi_ok || p == NULL) {
+    napi_throw_type_error(env, NULL, "expected a mixer handle");
+    return NULL;
+  }
+  MixerHandle *h = (MixerHandle *)p;
+  if (h->m == NULL) {
+    napi_throw_error(env, NULL, speexhip_resampler_strerror(SPEEXHIP_ERR_BAD_STATE));
+    return NULL;
+  }
+  return h;
+}
+
+/* mixerInit(nLegs, nBuses, channels[, device]) -> handle */
+static napi_value MixerInit(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 3) {
+    napi_throw_type_error(env, NULL, "mixerInit(nLegs, nBuses, channels[, device])");
+    return NULL;
+  }
+  uint32_t n_legs = 0, n_buses = 0, channels = 0;
+  int32_t device = -1;
+  NAPI_OK(napi_get_value_uint32(env, argv[0], &n_legs));
+  NAPI_OK(napi_get_value_uint32(env, argv[1], &n_buses));
+  NAPI_OK(napi_get_value_uint32(env, argv[2], &channels));
+  if (argc >= 4) {
+    napi_valuetype t;
+    if (napi_typeof(env, argv[3], &t) == napi_ok && t == napi_number) NAPI_OK(napi_get_value_int32(env, argv[3], &device));
+  }
+  int err = 0;
+  SpeexHipMixer *m = speexhip_mixer_init_on(device, n_legs, n_buses, channels, &err);
+  if (m == NULL) {
+    napi_throw_error(env, NULL, speexhip_resampler_strerror(err));
+    return NULL;
+  }
+  MixerHandle *h = (MixerHandle *)calloc(1, sizeof(MixerHandle));
+  if (h == NULL) {
+    speexhip_mixer_destroy(m);
+    napi_throw_error(env, NULL, speexhip_resampler_strerror(SPEEXHIP_ERR_ALLOC_FAILED));
+    return NULL;
+  }
+  h->m = m;
+  h->n_legs = n_legs, h->n_buses = n_buses, h->channels = channels;
+  napi_value handle;
+  NAPI_OK(napi_create_external(env, h, finalize_mixer, NULL, &handle));
+  return handle;
+}
+
+/* mixerDestroy(handle) */
+static napi_value MixerDestroy(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  void *p = NULL;
+  if (argc < 1 || napi_get_value_external(env, argv[0], &p) != napi_ok || p == NULL) {
+    napi_throw_type_error(env, NULL, "expected a mixer handle");
+    return NULL;
+  }
+  MixerHandle *h = (MixerHandle *)p;
+  if (h->m != NULL) speexhip_mixer_destroy(h->m);
+  h->m = NULL;
+  return NULL;
+}
+
+/* mixerSetWeights(handle, weights: Buffer of nBuses x nLegs float32, row-major | null) */
+static napi_value MixerSetWeights(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 2) {
+    napi_throw_type_error(env, NULL, "mixerSetWeights(handle, Buffer | null)");
+    return NULL;
+  }
+  MixerHandle *h = unwrap_mixer(env, argv[0]);
+  if (h == NULL) return NULL;
+  void *data = NULL;
+  size_t bytes = 0;
+  if (!buffer_or_null(env, argv[1], &data, &bytes) ||
+      (data != NULL && bytes != (size_t)h->n_buses * h->n_legs * sizeof(float))) {
+    napi_throw_type_error(env, NULL, "mixerSetWeights expects nBuses x nLegs float32 values, or null");
+    return NULL;
+  }
+  return control_result(env, speexhip_mixer_set_weights(h->m, (const float *)data));
+}
+
+/* mixerSetDither(handle, kind, seedLo, seedHi, positionLo, positionHi) */
+static napi_value MixerSetDither(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 6) {
+    napi_throw_type_error(env, NULL, "mixerSetDither(handle, kind, seedLo, seedHi, positionLo, positionHi)");
+    return NULL;
+  }
+  MixerHandle *h = unwrap_mixer(env, argv[0]);
+  if (h == NULL) return NULL;
+  int32_t kind = 0;
+  uint32_t v[4] = {0, 0, 0, 0};
+  NAPI_OK(napi_get_value_int32(env, argv[1], &kind));
+  for (size_t i = 0; i < 4; i++) NAPI_OK(napi_get_value_uint32(env, argv[2 + i], &v[i]));
+  return control_result(env, speexhip_mixer_set_dither(h->m, kind, ((uint64_t)v[1] << 32) | v[0], ((uint64_t)v[3] << 32) | v[2]));
+}
+
+/* mixerGetDither(handle) -> [kind, seedLo, seedHi, positionLo, positionHi] */
+static napi_value MixerGetDither(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  MixerHandle *h = argc >= 1 ? unwrap_mixer(env, argv[0]) : NULL;
+  if (h == NULL) return NULL;
+  int kind = 0;
+  uint64_t seed = 0, position = 0;
+  const int rc = speexhip_mixer_get_dither(h->m, &kind, &seed, &position);
+  if (rc != 0) return control_result(env, rc);
+  const uint32_t out[5] = {(uint32_t)kind, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)position, (uint32_t)(position >> 32)};
+  napi_value arr, v;
+  NAPI_OK(napi_create_array_with_length(env, 5, &arr));
+  for (uint32_t i = 0; i < 5; i++) {
+    NAPI_OK(napi_create_uint32(env, out[i], &v));
+    NAPI_OK(napi_set_element(env, arr, i, v));
+  }
+  return arr;
+}
+
+/* mixerSetMeter(handle, on) */
+static napi_value MixerSetMeter(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  MixerHandle *h = argc >= 2 ? unwrap_mixer(env, argv[0]) : NULL;
+  if (h == NULL) return NULL;
+  bool on = false;
+  NAPI_OK(napi_get_value_bool(env, argv[1], &on));
+  return control_result(env, speexhip_mixer_set_meter(h->m, on ? 1 : 0));
+}
+
+/* mixerGetBusMeter(handle, bus, reset) -> getMeter's array, of the bus's cell */
+static napi_value MixerGetBusMeter(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  MixerHandle *h = argc >= 3 ? unwrap_mixer(env, argv[0]) : NULL;
+  if (h == NULL) return NULL;
+  uint32_t bus = 0;
+  bool reset = false;
+  NAPI_OK(napi_get_value_uint32(env, argv[1], &bus));
+  NAPI_OK(napi_get_value_bool(env, argv[2], &reset));
+  SpeexHipMeter m;
+  memset(&m, 0, sizeof(m));
+  m.struct_size = (uint32_t)sizeof(m);
+  const int rc = speexhip_mixer_get_bus_meter(h->m, bus, &m, reset ? 1 : 0);
+  if (rc != 0) return control_result(env, rc);
+  const uint64_t counts[4] = {m.samples, m.clipped_high, m.clipped_low, m.nan};
+  napi_value arr, v;
+  NAPI_OK(napi_create_array_with_length(env, 10, &arr));
+  NAPI_OK(napi_create_uint32(env, m.on, &v));
+  NAPI_OK(napi_set_element(env, arr, 0, v));
+  for (uint32_t i = 0; i < 4; i++) {
+    NAPI_OK(napi_create_uint32(env, (uint32_t)counts[i], &v));
+    NAPI_OK(napi_set_element(env, arr, 1 + 2 * i, v));
+    NAPI_OK(napi_create_uint32(env, (uint32_t)(counts[i] >> 32), &v));
+    NAPI_OK(napi_set_element(env, arr, 2 + 2 * i, v));
+  }
+  NAPI_OK(napi_create_double(env, (double)m.peak, &v));
+  NAPI_OK(napi_set_element(env, arr, 9, v));
+  return arr;
+}
+
+/* mixerProcess(handle, legs: (handle | null)[], chunks: (Buffer | null)[], inFrames[], caps[], inFmts[], outFmt)
+ *   -> { buses: Buffer[], busFrames, consumed: number[], produced: number[], codes: number[] }
+ * One speexhip_mixer_process call; the buses come interleaved in outFmt, bus j a fresh Buffer of busFrames frames.  A leg
+ * whose code is not 0 was refused (its state untouched, +0.0 in the sum) -- the caller decides what that means. */
+static napi_value MixerProcess(napi_env env, napi_callback_info info) {
+  size_t argc = 7;
+  napi_value argv[7];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  const char *usage = "mixerProcess(handle, handle[], Buffer[], number[], number[], number[], number)";
+  MixerHandle *h = argc >= 7 ? unwrap_mixer(env, argv[0]) : NULL;
+  if (h == NULL) {
+    if (argc < 7) napi_throw_type_error(env, NULL, usage);
+    return NULL;
+  }
+  const uint32_t n = h->n_legs;
+  int32_t out_fmt = -1;
+  uint32_t len = 0;
+  if (napi_get_array_length(env, argv[1], &len) != napi_ok || len != n || napi_get_value_int32(env, argv[6], &out_fmt) != napi_ok ||
+      speexhip_sample_bytes(out_fmt) == 0) {
+    napi_throw_type_error(env, NULL, usage);
+    return NULL;
+  }
+  Handle **hs = (Handle **)calloc(n, sizeof(Handle *)), **locked = (Handle **)calloc(n, sizeof(Handle *));
+  SpeexHipResamplerState **st = (SpeexHipResamplerState **)calloc(n, sizeof(*st));
+  SpeexHipSide *sides = (SpeexHipSide *)calloc(n, sizeof(SpeexHipSide));
+  uint32_t *in_len = (uint32_t *)calloc(n, sizeof(uint32_t)), *out_len = (uint32_t *)calloc(n, sizeof(uint32_t));
+  int *codes = (int *)calloc(n, sizeof(int));
+  char *image = NULL;
+  napi_value result = NULL;
+  const char *fail = NULL;
+  int type_error = 0;
+  uint32_t n_locked = 0, most = 0;
+  if (!hs || !locked || !st || !sides || !in_len || !out_len || !codes) fail = speexhip_resampler_strerror(SPEEXHIP_ERR_ALLOC_FAILED);
+  for (uint32_t i = 0; fail == NULL && i < n; i++) {
+    napi_value hv, c, a, b, f;
+    napi_valuetype t;
+    void *p = NULL, *data = NULL;
+    size_t bytes = 0;
+    int32_t fi = -1;
+    if (napi_get_element(env, argv[1], i, &hv) != napi_ok || napi_typeof(env, hv, &t) != napi_ok ||
+        (t != napi_null && t != napi_undefined && (napi_get_value_external(env, hv, &p) != napi_ok || p == NULL)) ||
+        napi_get_element(env, argv[2], i, &c) != napi_ok || !buffer_or_null(env, c, &data, &bytes) ||
+        napi_get_element(env, argv[3], i, &a) != napi_ok || napi_get_value_uint32(env, a, &in_len[i]) != napi_ok ||
+        napi_get_element(env, argv[4], i, &b) != napi_ok || napi_get_value_uint32(env, b, &out_len[i]) != napi_ok ||
+        napi_get_element(env, argv[5], i, &f) != napi_ok || napi_get_value_int32(env, f, &fi) != napi_ok) {
+      fail = usage;
+      type_error = 1;
+      break;
+    }
+    hs[i] = (Handle *)p;
+    sides[i].struct_size = (uint32_t)sizeof(SpeexHipSide);
+    sides[i].fmt = fi;
+    sides[i].channels = h->channels;
+    sides[i].layout = SPEEXHIP_LAYOUT_INTERLEAVED;
+    sides[i].data = data;
+    if (p != NULL && data != NULL && (size_t)in_len[i] * h->channels * speexhip_sample_bytes(fi) > bytes) fail = "input frame count exceeds the chunk";
+    if (p != NULL) locked[n_locked++] = (Handle *)p;
+    if (p != NULL && out_len[i] > most) most = out_len[i];
+  }
+  if (fail == NULL) {
+    qsort(locked, n_locked, sizeof(Handle *), cmp_handle);
+    /* (a state in two slots is locked once; the library refuses its second slot) */
+    uint32_t kept = 0;
+    for (uint32_t k = 0; k < n_locked; k++)
+      if (kept == 0 || locked[k] != locked[kept - 1]) locked[kept++] = locked[k];
+    n_locked = kept;
+  }
+  const size_t frame_bytes = (size_t)h->channels * speexhip_sample_bytes(out_fmt);
+  const size_t bus_bytes = (size_t)(most ? most : 1) * frame_bytes;
+  if (fail == NULL && (image = (char *)malloc(bus_bytes * h->n_buses)) == NULL) fail = speexhip_resampler_strerror(SPEEXHIP_ERR_ALLOC_FAILED);
+  int rc = 0;
+  uint32_t bus_frames = 0;
+  if (fail == NULL) {
+    for (uint32_t k = 0; k < n_locked; k++) pthread_mutex_lock(&locked[k]->lock);
+    for (uint32_t i = 0; fail == NULL && i < n; i++) {
+      st[i] = hs[i] != NULL ? hs[i]->st : NULL;
+      if (hs[i] != NULL && st[i] == NULL) fail = speexhip_resampler_strerror(SPEEXHIP_ERR_BAD_STATE);  /* a destroyed leg */
+    }
+    if (fail == NULL) {
+      SpeexHipSide out;
+      memset(&out, 0, sizeof(out));
+      out.struct_size = (uint32_t)sizeof(out);
+      out.fmt = out_fmt;
+      out.channels = h->channels;
+      out.layout = SPEEXHIP_LAYOUT_INTERLEAVED;
+      out.data = image;
+      out.stream_stride = (uint64_t)(most ? most : 1) * h->channels;
+      bus_frames = 0xFFFFFFFFu;
+      rc = speexhip_mixer_process(h->m, st, sides, in_len, out_len, &out, &bus_frames, codes);
+      if (bus_frames == 0xFFFFFFFFu) fail = speexhip_resampler_strerror(rc);  /* a call-level error: nothing ran */
+    }
+    for (uint32_t k = n_locked; k-- > 0;) pthread_mutex_unlock(&locked[k]->lock);
+  }
+  if (fail == NULL) {
+    napi_value buses, used, made, cs, v;
+    if (napi_create_object(env, &result) != napi_ok || napi_create_array_with_length(env, h->n_buses, &buses) != napi_ok ||
+        napi_create_array_with_length(env, n, &used) != napi_ok || napi_create_array_with_length(env, n, &made) != napi_ok ||
+        napi_create_array_with_length(env, n, &cs) != napi_ok)
+      fail = "speexhip N-API failure: building the result";
+    for (uint32_t j = 0; fail == NULL && j < h->n_buses; j++) {
+      void *dst = NULL;
+      if (napi_create_buffer_copy(env, (size_t)bus_frames * frame_bytes, image + j * bus_bytes, &dst, &v) != napi_ok ||
+          napi_set_element(env, buses, j, v) != napi_ok)
+        fail = "speexhip N-API failure: building the result";
+    }
+    for (uint32_t i = 0; fail == NULL && i < n; i++) {
+      if (napi_create_uint32(env, in_len[i], &v) != napi_ok || napi_set_element(env, used, i, v) != napi_ok ||
+          napi_create_uint32(env, out_len[i], &v) != napi_ok || napi_set_element(env, made, i, v) != napi_ok ||
+          napi_create_int32(env, codes[i], &v) != napi_ok || napi_set_element(env, cs, i, v) != napi_ok)
+        fail = "speexhip N-API failure: building the result";
+    }
+    if (fail == NULL &&
+        (napi_create_uint32(env, bus_frames, &v) != napi_ok || napi_set_named_property(env, result, "busFrames", v) != napi_ok ||
+         napi_set_named_property(env, result, "buses", buses) != napi_ok || napi_set_named_property(env, result, "consumed", used) != napi_ok ||
+         napi_set_named_property(env, result, "produced", made) != napi_ok || napi_set_named_property(env, result, "codes", cs) != napi_ok))
+      fail = "speexhip N-API failure: building the result";
+  }
+  free(hs);
+  free(locked);
+  free(st);
+  free(sides);
+  free(in_len);
+  free(out_len);
+  free(codes);
+  free(image);
+  if (fail != NULL) {
+    if (type_error)
+      napi_throw_type_error(env, NULL, fail);
+    else
+      napi_throw_error(env, NULL, fail);
+    return NULL;
+  }
+  return result;
+}
+
 /* NAPI_MODULE_INIT: the well-known symbol napi_register_module_v1, so that every environment of the process -- the main
  * thread and each worker_threads Worker -- can load the addon (a module that registers itself from a static constructor
  * loads once per process).  The addon keeps no per-environment state: handles are externals, the counters above are
@@ -1912,6 +2233,14 @@ NAPI_MODULE_INIT() {
       {"warmup", NULL, Warmup, NULL, NULL, NULL, napi_default, NULL},
       {"stats", NULL, Stats, NULL, NULL, NULL, napi_default, NULL},
       {"allocChunk", NULL, AllocChunk, NULL, NULL, NULL, napi_default, NULL},
+      {"mixerInit", NULL, MixerInit, NULL, NULL, NULL, napi_default, NULL},
+      {"mixerDestroy", NULL, MixerDestroy, NULL, NULL, NULL, napi_default, NULL},
+      {"mixerSetWeights", NULL, MixerSetWeights, NULL, NULL, NULL, napi_default, NULL},
+      {"mixerSetDither", NULL, MixerSetDither, NULL, NULL, NULL, napi_default, NULL},
+      {"mixerGetDither", NULL, MixerGetDither, NULL, NULL, NULL, napi_default, NULL},
+      {"mixerSetMeter", NULL, MixerSetMeter, NULL, NULL, NULL, napi_default, NULL},
+      {"mixerGetBusMeter", NULL, MixerGetBusMeter, NULL, NULL, NULL, napi_default, NULL},
+      {"mixerProcess", NULL, MixerProcess, NULL, NULL, NULL, napi_default, NULL},
   };
   if (napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props) != napi_ok)
     napi_throw_error(env, NULL, "speexhip: cannot define exports");

@@ -128,7 +128,12 @@ EXPORTS = [
     # buses: weighted sums of a batch's streams in one device call
     "speexhip_batch_set_buses", "speexhip_batch_get_buses", "speexhip_batch_process_bus_device",
     "speexhip_batch_get_bus_meter", "speexhip_batch_get_bus_position", "speexhip_debug_bus",
+    # mixer: mix buses over many separate states in one host call
+    "speexhip_mixer_init", "speexhip_mixer_init_on", "speexhip_mixer_destroy", "speexhip_mixer_set_weights",
+    "speexhip_mixer_get_weights", "speexhip_mixer_set_dither", "speexhip_mixer_get_dither", "speexhip_mixer_set_meter",
+    "speexhip_mixer_get_bus_meter", "speexhip_mixer_process", "speexhip_debug_mixer_counters",
 ]
+MIXER_MAX_LEGS = MIXER_MAX_BUSES = 1024
 
 
 class Meter(C.Structure):
@@ -472,6 +477,30 @@ def lib():
             L.speexhip_batch_get_bus_position.argtypes = [p, C.POINTER(C.c_uint64)]
             L.speexhip_debug_bus.restype = i32
             L.speexhip_debug_bus.argtypes = [u32, u32, p, p, u32, p]
+        if hasattr(L, "speexhip_mixer_init") or "SPEEXHIP_LIB_PATH" not in os.environ:
+            pu64 = C.POINTER(C.c_uint64)
+            L.speexhip_mixer_init.restype = p
+            L.speexhip_mixer_init.argtypes = [u32, u32, u32, C.POINTER(i32)]
+            L.speexhip_mixer_init_on.restype = p
+            L.speexhip_mixer_init_on.argtypes = [i32, u32, u32, u32, C.POINTER(i32)]
+            L.speexhip_mixer_destroy.restype = None
+            L.speexhip_mixer_destroy.argtypes = [p]
+            L.speexhip_mixer_set_weights.restype = i32
+            L.speexhip_mixer_set_weights.argtypes = [p, p]
+            L.speexhip_mixer_get_weights.restype = i32
+            L.speexhip_mixer_get_weights.argtypes = [p, p]
+            L.speexhip_mixer_set_dither.restype = i32
+            L.speexhip_mixer_set_dither.argtypes = [p, i32, C.c_uint64, C.c_uint64]
+            L.speexhip_mixer_get_dither.restype = i32
+            L.speexhip_mixer_get_dither.argtypes = [p, C.POINTER(i32), pu64, pu64]
+            L.speexhip_mixer_set_meter.restype = i32
+            L.speexhip_mixer_set_meter.argtypes = [p, i32]
+            L.speexhip_mixer_get_bus_meter.restype = i32
+            L.speexhip_mixer_get_bus_meter.argtypes = [p, u32, C.POINTER(Meter), i32]
+            L.speexhip_mixer_process.restype = i32
+            L.speexhip_mixer_process.argtypes = [p, p, C.POINTER(Side), pu32, pu32, C.POINTER(Side), pu32, C.POINTER(i32)]
+            L.speexhip_debug_mixer_counters.restype = None
+            L.speexhip_debug_mixer_counters.argtypes = [pu64]
         _lib = L
     return _lib
 
@@ -703,6 +732,15 @@ def many_counters():
     v = (C.c_uint64 * 4)()
     lib().speexhip_debug_many_counters(v)
     return dict(zip(("fir_launches", "in_passes", "out_passes", "own_calls"), (int(x) for x in v)))
+
+
+def debug_mixer_counters():
+    """speexhip_debug_mixer_counters: process-wide counts of the mixer calls since start, as a dict -- fir_launches,
+    in_passes, bus_sum_launches, out_passes, transfers_in, transfers_out."""
+    v = (C.c_uint64 * 6)()
+    lib().speexhip_debug_mixer_counters(v)
+    return dict(zip(("fir_launches", "in_passes", "bus_sum_launches", "out_passes", "transfers_in", "transfers_out"),
+                    (int(x) for x in v)))
 
 
 def chunk_counters():
@@ -1864,6 +1902,137 @@ class Batch:
             self._h = None
 
     __del__ = close
+
+
+class Mixer:
+    """speexhip_mixer_*: mix buses over many separate Resampler states in one host call per tick.  A mixer has n_legs
+    slots, n_buses buses and one channel count; bus j is the weighted sum, in ascending slot order, of the slots' output
+    of the call (each behind its own state's gain), encoded, dithered and metered like a stream."""
+
+    def __init__(self, n_legs, n_buses, channels, device=None):
+        err = C.c_int(0)
+        if device is None:
+            self._h = lib().speexhip_mixer_init(n_legs, n_buses, channels, C.byref(err))
+        else:
+            self._h = lib().speexhip_mixer_init_on(int(device), n_legs, n_buses, channels, C.byref(err))
+        if not self._h:
+            raise (RuntimeError if err.value == ERR_DEVICE else ValueError)(strerror(err.value))
+        self.n_legs, self.n_buses, self.channels = n_legs, n_buses, channels
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().speexhip_mixer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_weights(self, weights):
+        """W (n_buses, n_legs): bus j = sum over the slots of weights[j][i] times slot i's gained output (mix-minus: ones -
+        identity).  None: off.  Zeroes the bus meters and the bus position.  Returns the C call's code."""
+        if weights is None:
+            return lib().speexhip_mixer_set_weights(self._h, None)
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        if w.shape != (self.n_buses, self.n_legs):
+            raise ValueError("weights must be (%d, %d)" % (self.n_buses, self.n_legs))
+        return lib().speexhip_mixer_set_weights(self._h, C.c_void_p(w.ctypes.data))
+
+    def get_weights(self):
+        """W (n_buses, n_legs) float32, or None while the mixer is off"""
+        w = np.zeros((self.n_buses, self.n_legs), np.float32)
+        rc = lib().speexhip_mixer_get_weights(self._h, C.c_void_p(w.ctypes.data))
+        if rc == ERR_BAD_STATE:
+            return None
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return w
+
+    def set_dither(self, kind, seed=0, position=0):
+        """Dither of the buses' integer outputs: bus j draws from seed + (n_legs + j) * 0x9E3779B97F4A7C15 (mod 2^64);
+        position = the buses' one position.  Returns the C call's code."""
+        return lib().speexhip_mixer_set_dither(self._h, int(kind), int(seed), int(position))
+
+    def get_dither(self):
+        """(kind, the seed as given, the bus position)"""
+        k, s, p_ = C.c_int(), C.c_uint64(), C.c_uint64()
+        rc = lib().speexhip_mixer_get_dither(self._h, C.byref(k), C.byref(s), C.byref(p_))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return k.value, s.value, p_.value
+
+    def set_meter(self, on):
+        return lib().speexhip_mixer_set_meter(self._h, int(on))
+
+    def get_bus_meter(self, bus, reset=False):
+        """The bus's {'on', 'samples', 'clipped_high', 'clipped_low', 'nan', 'peak'}; reset clears that bus only."""
+        m = Meter()
+        rc = lib().speexhip_mixer_get_bus_meter(self._h, int(bus), C.byref(m), int(bool(reset)))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return m.as_dict()
+
+    def bus_position(self):
+        return self.get_dither()[2]
+
+    def process_sides(self, legs, in_sides, in_lens, out_side, capacities):
+        """speexhip_mixer_process itself: legs[i] a Resampler or None, in_sides[i] its Side (make_side; None for an empty
+        slot), out_side the buses' Side over a host buffer the caller keeps alive.  Returns (rc, consumed, produced,
+        bus_frames, codes); bus_frames is None when the call did not set it."""
+        n = self.n_legs
+        hs = (C.c_void_p * n)()
+        a = (Side * n)()
+        for i in range(n):
+            hs[i] = None if legs[i] is None else legs[i]._h
+            if in_sides[i] is not None:
+                C.memmove(C.byref(a[i]), C.byref(in_sides[i]), C.sizeof(Side))
+        il, ol, codes = (C.c_uint32 * n)(*in_lens), (C.c_uint32 * n)(*capacities), (C.c_int * n)()
+        frames = C.c_uint32(0xFFFFFFFF)
+        rc = lib().speexhip_mixer_process(self._h, hs, a, il, ol, C.byref(out_side), C.byref(frames), codes)
+        return rc, list(il), list(ol), (None if frames.value == 0xFFFFFFFF else frames.value), list(codes)
+
+    def process(self, legs, chunks, in_formats, out_format, capacity, out_layout="interleaved"):
+        """One tick.  legs[i]: a Resampler or None (an empty slot); chunks[i]: a bytes-like of whole interleaved frames of
+        in_formats[i] (one FMT_* for all, or one per slot), or None -- a silent leg, with capacity[i] = (silent_frames,
+        capacity).  capacity: output frames each leg may produce, one for all or one per slot.  Returns (buses, bus_frames,
+        used, produced, codes): buses is (n_buses, bus_frames * channels) of out_format's storage type (the packed 24-bit
+        formats: three bytes a sample), or (n_buses, channels, bus_frames) for out_layout='planar'."""
+        n = self.n_legs
+        fi = _per_state(in_formats, n)
+        caps = [capacity] * n if isinstance(capacity, (int, np.integer)) else list(capacity)
+        keep, sides, il, ol = [], [], [], []
+        for i in range(n):
+            if legs[i] is None:
+                sides.append(None), il.append(0), ol.append(0)
+                continue
+            if chunks[i] is None:
+                frames, cap = (int(caps[i][0]), int(caps[i][1])) if isinstance(caps[i], (tuple, list)) else (0, int(caps[i]))
+                sides.append(make_side(fi[i], self.channels))
+            else:
+                a = np.frombuffer(chunks[i], dtype=np.uint8) if not isinstance(chunks[i], np.ndarray) else \
+                    np.ascontiguousarray(chunks[i]).reshape(-1).view(np.uint8)
+                frames, cap = a.nbytes // (fmt_bytes(fi[i]) * self.channels), int(caps[i])
+                if frames * fmt_bytes(fi[i]) * self.channels != a.nbytes:
+                    raise ValueError("chunk %d: whole frames only" % i)
+                keep.append(a)
+                sides.append(make_side(fi[i], self.channels, data=a.ctypes.data if a.nbytes else None))
+            il.append(frames), ol.append(cap)
+        most, es, layout = max(ol + [1]), fmt_bytes(out_format), _layout(out_layout)
+        planar = layout == LAYOUT_PLANAR and self.channels > 1
+        out = np.zeros((self.n_buses, most * self.channels * es), np.uint8)
+        side = make_side(out_format, self.channels, layout=layout, data=out.ctypes.data, plane_stride=most,
+                         stream_stride=most * self.channels)
+        rc, used, made, bus_frames, codes = self.process_sides(legs, sides, il, side, ol)
+        if bus_frames is None:
+            raise RuntimeError(strerror(rc))
+        dt = fmt_dtype(out_format)
+        if planar:
+            buses = out.reshape(self.n_buses, self.channels, most * es)[:, :, : bus_frames * es].copy().view(dt)
+        else:
+            buses = out[:, : bus_frames * self.channels * es].copy().view(dt)
+        return buses, bus_frames, used, made, codes
 
 
 class SpeexResampler:

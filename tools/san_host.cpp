@@ -245,6 +245,43 @@ bool check_many_plans(long *rows) {
   MANY_EXPECT(p.pipelined && (launches_of(p) == Launches{{0}, {1}}));
   p = many_plan_of(std::vector<ManyShape>(40, many_shape(1 * MB, 1 * MB)));  // (40 MiB: 2 pieces of 20 entries)
   MANY_EXPECT(p.pipelined && p.launches.size() == 2 && p.launches[0].entries.size() == 20);
+  // The legs of a mixer call (mixer.cpp, many.cpp: run_mixer): the table at the head of the range that travels in, the
+  // buses at the head of the range that travels out, every leg's result an image range of its own and no storage
+  name = "mixer legs, a small tick";
+  s.assign(3, many_shape(160, 0));
+  for (ManyShape &leg : s) leg.leg = true, leg.pass_in = true, leg.image_in = 640, leg.image_out = 3840;
+  s[1].pass_in = false;  // (an F32 leg: its storage is its input image)
+  s[2].key.zero = true;  // (the zero fallback: a launch of its own)
+  {
+    ManyExtra extra;
+    extra.in_bytes = 3 * 64, extra.out_bytes = 5 * 960 * 2;
+    p = plan_many_unit(s.data(), s.size(), no_pipeline, extra);
+    MANY_EXPECT(p.small && !p.pipelined && !p.wait.sync && (launches_of(p) == Launches{{0, 1}, {2}}));
+    MANY_EXPECT(p.e[0].in == B && p.e[0].out == N && p.e[0].in_off == 192 && p.e[1].in_off == 192 + 192 && p.e[2].in_off == 192 + 384);
+    MANY_EXPECT(p.e[0].img_out == 0 && p.e[1].img_out == 3840 && p.e[2].img_out == 7680 && p.images_out == 3 * 3840 && p.dev_img_out == 3 * 3840 + 256);
+    MANY_EXPECT(p.e[1].img_in == 640 && p.e[2].img_in == 640 && p.images_in == 1280);
+    MANY_EXPECT(p.gathered_in == 192 + 3 * 192 && p.pin_in == p.gathered_in && p.dev_in == 0);
+    MANY_EXPECT(p.gathered_out == 9600 && p.pin_out == 9600 + 128 && p.dev_out == 0 && p.total_out == 9600);
+    (*rows)++;
+    name = "mixer legs, buses too large for the pinned stage alone";
+    extra.out_bytes = 1 * MB;
+    p = plan_many_unit(s.data(), s.size(), no_pipeline, extra);
+    MANY_EXPECT(!p.small && !p.pipelined && p.wait.sync && p.e[0].in == S && p.e[0].out == N && p.e[0].in_off == 192);
+    MANY_EXPECT(p.gathered_in == 192 + 3 * 192 && p.dev_in == p.gathered_in && p.pin_in == p.gathered_in);
+    MANY_EXPECT(p.gathered_out == 1 * MB && p.dev_out == 1 * MB && p.pin_out == 1 * MB + 128);
+    (*rows)++;
+    name = "mixer legs, a payload that travels on its own";
+    s[0].in_bytes = Dc;
+    p = plan_many_unit(s.data(), s.size(), no_pipeline, extra);
+    MANY_EXPECT(!p.small && !p.pipelined && p.e[0].in == C && p.e[1].in == S && p.e[1].in_off == 192 && p.e[0].in_off == p.gathered_in);
+    MANY_EXPECT(p.gathered_in == 192 + 2 * 192 && p.dev_in == p.gathered_in + Dc);
+    (*rows)++;
+  }
+  {
+    const ManyKey zero_last[] = {{10, 0, true, true, false}, {10, 0, true, true, true}, {10, 1, false, false, false}};
+    for (size_t a = 0; a < 3; a++)
+      for (size_t b = 0; b < 3; b++) MANY_EXPECT((zero_last[a] < zero_last[b]) == (a < b));
+  }
   p = many_plan_of(std::vector<ManyShape>(130, many_shape(Dc, Dc)));  // (32.5 MiB: 2 pieces of 65, 32 per launch at most)
   MANY_EXPECT(p.pipelined && p.launches.size() == 5 && p.launches[0].entries.size() == 32 && p.launches[4].entries.size() == 2);
   (*rows)++;
@@ -385,7 +422,7 @@ bool check_sides_routes(long *rows, long *walked) {
     return s;
   };
   const SidesForm Dev = SidesForm::Device, Host = SidesForm::Host, Planes = SidesForm::PlanesHost, Chunks = SidesForm::Chunks,
-                  Many = SidesForm::ManyEntry, Bus = SidesForm::Bus;
+                  Many = SidesForm::ManyEntry, Bus = SidesForm::Bus, Leg = SidesForm::MixerLeg;
   const SidesRoute::Kind I16 = SidesRoute::Int16Call, Flt = SidesRoute::FloatCall, PFl = SidesRoute::PlanarFloatCall,
                          Img = SidesRoute::Images, Own = SidesRoute::OwnCalls;
   const SidesRoute::Finish None = SidesRoute::Nothing, MeterI = SidesRoute::MeterImage, GainI = SidesRoute::GainImage;
@@ -492,6 +529,20 @@ bool check_sides_routes(long *rows, long *walked) {
       {"bus f32n side metered: the pass, :142, :181-183", Bus, flat(F32), flat(F32N), with(batch, "m"), OK, n, Img, n, n, y, None, 1, n, y, n, n},
       {"bus matrix on the sum, :122", Bus, flat(S16), mix(S16), batch, ARG, n, Img, n, n, n, None, 1, n, n, n, n},
       {"bus split, :129-131", Bus, flat(S16), flat(S16), with(one, "s"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      // ---- MixerLeg: mixer.cpp, Mixer::process (written with the rule; `out` is the leg's float image)
+      {"leg s16: the input pass, no output pass", Leg, flat(S16), flat(F32), one, OK, n, Img, n, y, n, None, 1, n, n, n, y},
+      {"leg f32: no same-bytes route, no pass at all", Leg, flat(F32), flat(F32), one, OK, n, Img, n, n, n, None, 1, n, n, n, y},
+      {"leg f32n: the input pass", Leg, flat(F32N), flat(F32), one, OK, n, Img, n, y, n, None, 1, n, n, n, y},
+      {"leg gained: gain moves, never gain_image", Leg, flat(U8), flat(F32), with(one, "g"), OK, n, Img, n, y, n, None, 1, n, n, y, y},
+      {"leg dithered metered gained: only gain moves", Leg, flat(S24), flat(F32), with(one, "dmg"), OK, n, Img, n, y, n, None, 1, n, n, y, y},
+      {"leg in the zero fallback joins its group", Leg, flat(S16), flat(F32), with(one, "zg"), OK, n, Img, n, y, n, None, 1, n, n, y, y},
+      {"leg matrix", Leg, mix(S16), flat(F32), one, ARG, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"leg planar of several channels", Leg, planar(S16), flat(F32), one, ARG, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"leg plane pointers", Leg, ptrs(S16), flat(F32), one, ARG, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"leg of a batch of several streams", Leg, flat(S16), flat(F32), batch, ARG, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"leg named by an earlier slot", Leg, flat(S16), flat(F32), with(one, "r"), ARG, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"leg split", Leg, flat(S16), flat(F32), with(one, "s"), BAD, n, Img, n, n, n, None, 1, n, n, n, n},
+      {"leg split and named twice: the argument error first", Leg, flat(S16), flat(F32), with(one, "sr"), ARG, n, Img, n, n, n, None, 1, n, n, n, n},
   };
   for (const RouteRow &w : table) {
     const SidesRoute r = route_sides_call(w.form, w.in, w.out, w.st);
@@ -517,11 +568,11 @@ bool check_sides_routes(long *rows, long *walked) {
       return false;                                                                                                            \
     }                                                                                                                          \
   } while (0)
-  for (SidesForm form : {Dev, Host, Planes, Chunks, Many, Bus})
+  for (SidesForm form : {Dev, Host, Planes, Chunks, Many, Bus, Leg})
     for (int fi : fmts) for (int fo : fmts)
       for (int sides = 0; sides < 64; sides++)  // mix, planar, planes of either side
         for (int bits = 0; bits < 128; bits++) {
-          if (form != Many && (sides & (4 | 32)) != 0) continue;  // (only the many-states call asks for plane pointers)
+          if (form != Many && form != Leg && (sides & (4 | 32)) != 0) continue;  // (only the many-states and the mixer call ask for plane pointers)
           const SideKind in ={fi, (sides & 1) != 0, (sides & 2) != 0, (sides & 4) != 0};
           const SideKind out = {fo, (sides & 8) != 0, (sides & 16) != 0, (sides & 32) != 0};
           const SidesState st = {(bits & 1) != 0, (bits & 2) != 0, (bits & 4) != 0, (bits & 8) != 0, (bits & 16) != 0, (bits & 32) != 0, (bits & 64) != 0};
@@ -535,6 +586,16 @@ bool check_sides_routes(long *rows, long *walked) {
             continue;
           }
           ROUTE_EXPECT(!r.refuse_late);
+          if (form == Leg) {
+            // a leg that runs: one interleaved buffer of a single-stream state; the float call into its image behind at most
+            // an input pass -- never an output pass, never a finish: the bus-sum kernel reads the image and gains it; of
+            // the state only the gain moves
+            ROUTE_EXPECT(!in.mix && !in.planar && !in.planes && st.single_stream && !st.repeated && !st.split);
+            ROUTE_EXPECT(r.kind == SidesRoute::Images && !r.pass_out && r.finish == SidesRoute::Nothing && !r.direct && r.fusable);
+            ROUTE_EXPECT(r.pass_in == (fi != SPEEXHIP_FMT_F32));
+            ROUTE_EXPECT(!r.moves_dither && !r.counts_meter && r.moves_gain == st.gain && r.finish_scale == 1.0f);
+            continue;
+          }
           if (r.kind == SidesRoute::Int16Call)
             ROUTE_EXPECT(fi == SPEEXHIP_FMT_S16 && fo == SPEEXHIP_FMT_S16 && !st.dither && !st.meter && !st.gain && !in.mix && !out.mix);
           if (r.kind != SidesRoute::Images) ROUTE_EXPECT(!r.pass_in && !r.pass_out);
@@ -551,7 +612,7 @@ bool check_sides_routes(long *rows, long *walked) {
           ROUTE_EXPECT(r.moves_dither == st.dither);
           if (!r.direct) ROUTE_EXPECT(r.counts_meter == st.meter && r.moves_gain == st.gain);
           if (r.direct) ROUTE_EXPECT((form == Host || form == Chunks) && !st.meter && !st.gain && r.kind != SidesRoute::Images && r.kind != SidesRoute::PlanarFloatCall);
-          if (r.fusable) ROUTE_EXPECT(form == Chunks || form == Many);
+          if (r.fusable) ROUTE_EXPECT(form == Chunks || form == Many);  // (and a mixer's leg, above)
           if (form == Many) ROUTE_EXPECT(r.fusable && !in.planar && !out.planar && !in.mix && !out.mix && !in.planes && !out.planes && r.finish != SidesRoute::MeterImage);
           if (form == Bus) ROUTE_EXPECT(r.kind == SidesRoute::Images && r.finish != SidesRoute::GainImage);
         }
