@@ -332,6 +332,7 @@ int Batch::setup() {
     return SPEEXHIP_ERR_DEVICE;
   }
   ON_DEVICE();  // (everything below -- pool, tables, uploads -- runs on the state's device)
+  bus_out_.bind(device_, channels_, n_streams_);
   hipDeviceProp_t prop;
   trace.step("placement + hipSetDevice");
   HIP_TRY(hipGetDeviceProperties(&prop, devices::physical(device_)));
@@ -796,7 +797,7 @@ Batch::~Batch() {
   pool::device_put(device_, d_planar_out_);
   pool::device_put(device_, d_meter_);
   pool::device_put(device_, d_bus_);
-  pool::device_put(device_, d_bus_image_);
+  bus_out_.release();
   pool::pinned_put(h_pin_in_);
   pool::pinned_put(h_pin_out_);
   for (int i = 0; i < kMaxPieces; i++) pool::event_put(device_, piece_ev_[i]);
@@ -821,45 +822,20 @@ int Batch::set_meter(int on) {
       return rc;
     }
     d_meter_ = static_cast<MeterCell *>(cells);
-    meter_bytes_ = bytes;
     meter_samples_.assign(n_streams_, 0);
   }
   meter_on_ = on != 0;
+  bus_out_.set_meter(meter_on_);
   return SPEEXHIP_ERR_SUCCESS;
 }
 
 int Batch::get_meter(uint32_t stream, SpeexHipMeter *m, bool reset) {
-  if (stream >= n_streams_ || (m == nullptr && !reset)) return SPEEXHIP_ERR_INVALID_ARG;
-  if (m != nullptr && m->struct_size < sizeof(SpeexHipMeter)) return SPEEXHIP_ERR_INVALID_ARG;
-  SpeexHipMeter now;
-  std::memset(&now, 0, sizeof(now));
-  now.on = meter_on_ ? 1u : 0u;
-  if (d_meter_ != nullptr) {
-    ON_DEVICE();
-    int rc = quiesce();  // this state's own last call; its totals are in the cells behind it
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-    std::vector<MeterCell> cells(n_streams_);
-    rc = ctl_download(cells.data(), reinterpret_cast<const char *>(d_meter_), meter_bytes_, 0, sizeof(MeterCell) * n_streams_,
-                      own_stream_);
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-    const MeterCell &c = cells[stream];
-    now.samples = meter_samples_[stream];
-    now.clipped_high = c.hi;
-    now.clipped_low = c.lo;
-    now.nan = c.nan;
-    std::memcpy(&now.peak, &c.peak_bits, sizeof(now.peak));
-    if (reset) {  // (nothing of this state is in flight: the cells go back whole, this stream's zeroed)
-      std::memset(&cells[stream], 0, sizeof(MeterCell));
-      rc = ctl_upload(d_meter_, cells.data(), sizeof(MeterCell) * n_streams_, own_stream_);
-      if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-      meter_samples_[stream] = 0;
-    }
-  }
-  if (m != nullptr) {
-    now.struct_size = m->struct_size;
-    std::memcpy(m, &now, sizeof(now));
-  }
-  return SPEEXHIP_ERR_SUCCESS;
+  if (!meter_request_ok(stream, n_streams_, m, reset)) return SPEEXHIP_ERR_INVALID_ARG;
+  if (d_meter_ == nullptr) return read_meter(nullptr, n_streams_, stream, meter_on_, nullptr, m, reset, nullptr);
+  ON_DEVICE();
+  const int rc = quiesce();  // this state's own last call; its totals are in the cells behind it
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+  return read_meter(d_meter_, n_streams_, stream, meter_on_, meter_samples_.data(), m, reset, own_stream_);
 }
 
 MeterPack Batch::meter_pack(uint32_t s0, uint32_t n) const {
@@ -873,21 +849,13 @@ void Batch::meter_count(const uint32_t *produced, uint32_t per_frame) {
   for (uint32_t s = 0; s < n_streams_; s++) meter_samples_[s] += static_cast<uint64_t>(produced[s]) * per_frame;
 }
 
-int Batch::meter_result(const void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream, bool buses) {
-  const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams), items = buses ? n_buses_ : n_streams_;
-  for (uint32_t first = 0; first < items; first += kChunk) {
-    const uint32_t n = std::min(kChunk, items - first);
-    ConvertPack pack;
-    std::memset(&pack, 0, sizeof(pack));
+int Batch::meter_result(const void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream) {
+  const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
+  for (uint32_t first = 0; first < n_streams_; first += kChunk) {
+    const uint32_t n = std::min(kChunk, n_streams_ - first);
     uint64_t most = 0;
-    for (uint32_t j = 0; j < n; j++) {
-      pack.s[j].src = static_cast<const float *>(result) + (first + j) * stride;
-      pack.s[j].n = static_cast<uint64_t>(lens[first + j]) * channels_;
-      pack.s[j].step = 1;
-      most = std::max(most, pack.s[j].n);
-    }
-    const MeterPack cells = buses ? bus_meter_pack() : meter_pack(first, n);
-    if (hip_failed(launch_meter_image(pack, cells, scale, n, most, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
+    const ConvertPack pack = float_results_pack(static_cast<const float *>(result) + first * stride, stride, lens + first, n, channels_, &most);
+    if (hip_failed(launch_meter_image(pack, meter_pack(first, n), scale, n, most, stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
   }
   return SPEEXHIP_ERR_SUCCESS;
 }
@@ -951,15 +919,8 @@ int Batch::image_result(void *result, uint64_t stride, const uint32_t *lens, flo
   const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
   for (uint32_t first = 0; first < n_streams_; first += kChunk) {
     const uint32_t n = std::min(kChunk, n_streams_ - first);
-    ConvertPack pack;
-    std::memset(&pack, 0, sizeof(pack));
     uint64_t most = 0;
-    for (uint32_t j = 0; j < n; j++) {
-      pack.s[j].dst = static_cast<float *>(result) + (first + j) * stride;
-      pack.s[j].n = static_cast<uint64_t>(lens[first + j]) * channels_;
-      pack.s[j].step = 1;
-      most = std::max(most, pack.s[j].n);
-    }
+    const ConvertPack pack = float_results_pack(static_cast<const float *>(result) + first * stride, stride, lens + first, n, channels_, &most);
     MeterPack cells;
     if (meter_on_) cells = meter_pack(first, n);
     if (hip_failed(launch_gain_image(pack, gain_pack(first, n, channels_), meter_on_ ? &cells : nullptr, scale, n, most, stream),

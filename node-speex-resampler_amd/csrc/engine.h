@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/speexhip_resampler.h"
+#include "bus_out.h"
 #include "device_types.h"
 #include "engine_detail.h"
 #include "filter_design.h"
@@ -89,23 +90,18 @@ inline bool side_planar(const CallSide &side) { return side.layout == SPEEXHIP_L
 inline SideKind side_kind(const CallSide &side) { return SideKind{side.fmt, side.mix != nullptr, side_planar(side), side.planes != nullptr}; }
 
 // What a mixer call (mixer.h) hands the unit machinery of the many-states calls (many.cpp, Batch::many_mixer) beside its
-// legs: the buses that stand behind the legs' launches.  The mixer owns all of it; the unit reads it and leaves bus_frames.
+// legs: the sum that stands behind the legs' launches, and the buses' output stage (bus_out.h), which the unit grows the
+// image of and has encode the buses.  The mixer owns all of it; the unit leaves bus_frames.
 struct MixerCall {
   int device = 0;
-  uint32_t n_legs = 0, n_buses = 0, channels = 0;
+  uint32_t n_legs = 0;
   const float *d_w = nullptr;    // the resident copy of W as bus_sum_legs reads it (kernels.h)
   uint32_t w_pitch = 0;
   CallSide out = {};             // the buses in host memory
-  bool pass_out = false;         // the bus side passes through an image (SidesForm::Bus); else bus_sum_legs writes the stage
-  int dither_kind = SPEEXHIP_DITHER_NONE;  // NONE also where the format is not dithered
-  uint64_t dither_seed = 0, bus_pos = 0;
-  MeterCell *cells = nullptr;    // one per bus; NULL: the meter is off
-  char **bus_image = nullptr;    // the float image of the buses, grow-only
-  size_t *bus_image_cap = nullptr;
+  SidesRoute bus_route;          // of the bus side (SidesForm::Bus); pass_out false: bus_sum_legs writes the stage itself
+  BusOutput *buses = nullptr;
   uint32_t bus_frames = 0;       // out: the length of the buses
 };
-// mix.cpp: the output pass over the buses of a mixer call, beside Batch::side_pass
-int mixer_bus_pass(const MixerCall &mc, const CallSide &side, const char *image, size_t pitch, hipStream_t stream, uint32_t *launches);
 
 class Batch {
  public:
@@ -205,16 +201,16 @@ class Batch {
   int get_buses(uint32_t *n_buses, float *weights) const;  // (either may be null)
   // The bus call: the input side's pass -> process_device(float) into the state's image -> bus_sum (kernels_bus.hip: every
   // bus the fp64 sum of all streams' samples behind their gains, a stream that has ended supplying +0.0f) into a grow-only
-  // image of the buses -> side_pass over that image with the buses in the place of the streams, dithered from the bus
-  // seeds at the bus position and judged into the bus cells.  An interleaved F32 bus side is written by bus_sum itself
-  // (and read by meter_image when the meter is on).  Counters, history and positions of every stream are the float
+  // image of the buses -> the buses' output stage (bus_out.h), which encodes that image, dithered from the bus seeds at the
+  // bus position and judged into the bus cells.  An interleaved F32 bus side is written by bus_sum itself (and read by
+  // meter_image when the meter is on).  Counters, history and positions of every stream are the float
   // call's; the streams' gains move by what they produced, their dither positions and meter totals do not move: nothing
   // of theirs is encoded.  out_len: the streams' capacities in, their produced frames out; *bus_frames = the largest of
   // them, the length of every bus.  No buses set, or a stream whose channels stand apart: BAD_STATE; out.mix: INVALID_ARG.
   int process_bus_device(const CallSide &in, uint32_t *in_len, const CallSide &out, uint32_t *out_len, uint32_t *bus_frames,
                          hipStream_t stream);
   int get_bus_meter(uint32_t bus, SpeexHipMeter *m, bool reset);  // as get_meter, of a bus's cell
-  uint64_t bus_position() const { return bus_pos_; }             // the buses' one dither position
+  uint64_t bus_position() const { return bus_out_.position(); }  // the buses' one dither position
   // Host-buffer call for a single-stream batch; synchronous (H2D, kernels, D2H).
   int process_host(const void *in, uint32_t *in_len, void *out, uint32_t *out_len, bool float_io);
   // The same call with the result left in a pinned block of the pool that the caller then OWNS (release_block):
@@ -316,10 +312,8 @@ class Batch {
   // image -> storage, dithered when the state and the format say so.  Stream s is lens[s] frames at side.base + s *
   // side.stride and image + s * pitch (elements).  apart (an output side without a matrix): the plans of the one
   // stream's channels, which stand apart -- channel c is plans[c].produced samples, channels() elements from one to the next.
-  // buses (an output side of a bus call): the items are the state's buses in the place of its streams -- lens[j] frames
-  // of bus j, dithered from the bus seeds at the bus position, judged into the bus cells, never gained.
   int side_pass(const CallSide &side, bool to_image, char *image, size_t pitch, const uint32_t *lens, hipStream_t stream,
-                const CallPlan *apart = nullptr, bool buses = false);
+                const CallPlan *apart = nullptr);
   bool dither_on() const { return dither_kind_ != SPEEXHIP_DITHER_NONE; }
   // the DitherPack of streams [s0, s0 + n): first = position * per_frame (per_frame = 1: the position itself)
   DitherPack dither_pack(uint32_t s0, uint32_t n, uint32_t per_frame) const;
@@ -328,19 +322,14 @@ class Batch {
   MeterPack meter_pack(uint32_t s0, uint32_t n) const;
   void meter_count(const uint32_t *produced, uint32_t per_frame);  // after a formatted or mixed call with the meter on
   // meter_image over what a call without an output pass wrote: stream s is lens[s] frames of channels() floats at
-  // result + s * stride (floats), judged as stored * scale.  buses: the state's buses and their cells in the place of its
-  // streams, as in side_pass
-  int meter_result(const void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream, bool buses = false);
+  // result + s * stride (floats), judged as stored * scale
+  int meter_result(const void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream);
   // whether any stream's gain is on: the state's formatted calls then take the gained routes
   bool gain_on() const;
   // the gains of streams [s0, s0 + n), as a gained launch takes them: first = the stream's done; per_frame = the samples
   // of an output frame in a pass that walks samples, 1 in the passes that walk frames (a stream whose gain is off: 0)
   GainPack gain_pack(uint32_t s0, uint32_t n, uint32_t per_frame) const;
   void gain_advance(const uint32_t *produced);  // after a formatted or mixed call with gain on
-  // the packs of the buses, as an output pass over the bus image takes them: bus j draws from dither::stream_seed(seed,
-  // n_streams() + j), first = the bus position * per_frame; its cell is d_bus_ + j
-  DitherPack bus_dither_pack(uint32_t per_frame) const;
-  MeterPack bus_meter_pack() const;
   // What a call without an output pass wrote (meter_result's arguments), finished in place: gain_image when gain is on --
   // which judges its product too when the meter is on -- meter_image otherwise.
   int image_result(void *result, uint64_t stride, const uint32_t *lens, float scale, hipStream_t stream);
@@ -511,8 +500,7 @@ class Batch {
   uint64_t dither_seed_ = 0;
   std::vector<uint64_t> dither_pos_;        // per stream: index of its next output frame (empty until set_dither: 0)
   bool meter_on_ = false;                   // set_meter
-  MeterCell *d_meter_ = nullptr;            // one cell per stream (null until the meter is first turned on), meter_bytes_ in all
-  size_t meter_bytes_ = 0;
+  MeterCell *d_meter_ = nullptr;            // one cell per stream (null until the meter is first turned on)
   std::vector<uint64_t> meter_samples_;     // per stream: samples metered since the last reset
   struct Gain {                             // one stream's gain (gain.h)
     double step = 0.0;                      // (to - from) / total, formed by set_gain
@@ -520,15 +508,12 @@ class Batch {
     uint32_t total = 0, done = 0;
   };
   std::vector<Gain> gain_;                  // per stream (empty until set_gain: off)
-  // buses (bus.cpp): n_buses_ == 0 = off.  One device block, allocated by the first set_buses: the buses' 32 meter cells
-  // at its front, behind them the 32 x 32 floats of W as bus_sum reads it (BusPack::w).
+  // buses (bus.cpp): n_buses_ == 0 = off.  W, and behind the sum the buses' output stage: their dither, meter, cells,
+  // totals, position and image (bus_out.h)
   uint32_t n_buses_ = 0;
   std::vector<float> bus_w_;                // W as the caller gave it: n_buses_ x n_streams_, row-major
-  char *d_bus_ = nullptr;
-  uint64_t bus_pos_ = 0;                    // index of every bus's next output frame (set_dither, set_buses)
-  std::vector<uint64_t> bus_samples_;       // per bus: samples metered since the last reset
-  char *d_bus_image_ = nullptr;             // the float image of the buses, grow-only
-  size_t bus_image_cap_ = 0;                // bytes
+  char *d_bus_ = nullptr;                   // the 32 x 32 floats of W as bus_sum reads it (BusPack::w), from the first set_buses on
+  BusOutput bus_out_;
   uint32_t done_seq_ = 0;  // completion word of the small host-buffer calls (engine.cpp, process_host)
   size_t stage_in_cap_ = 0, stage_out_cap_ = 0, pin_in_cap_ = 0, pin_out_cap_ = 0;  // bytes
 };

@@ -73,7 +73,7 @@ int Batch::set_dither(int kind, uint64_t seed, uint64_t position) {
   dither_kind_ = kind;
   dither_seed_ = seed;
   dither_pos_.assign(n_streams_, position);
-  bus_pos_ = position;  // (the buses' one position: bus.cpp)
+  bus_out_.set_dither(kind, seed, position);  // (the buses' one position, whether or not buses are on: bus.cpp)
   return SPEEXHIP_ERR_SUCCESS;
 }
 int Batch::get_dither(uint32_t stream, int *kind, uint64_t *seed, uint64_t *position) const {
@@ -113,7 +113,7 @@ void Batch::sides_moved(const SidesRoute &r, const uint32_t *produced, uint32_t 
 // The float images of a call and its input pass: one stream after the other, whole 128-byte lines each, sized from what
 // this call moves.  (The zero fallback goes through them as well: its history still takes the converted input, and its
 // silence is whatever the float call writes, converted -- and dithered.)  bus: the streams' results always lie in the
-// state's image, whatever the route, and the image of the buses is sized here as well.
+// state's image, whatever the route.
 int Batch::prepare_images(const CallSide &in, const uint32_t *in_len, const uint32_t *out_len, const SidesRoute &r, bool split,
                           bool bus, hipStream_t stream, SideImages *im) {
   // what the float call will do, known before anything is launched (integer arithmetic)
@@ -132,13 +132,6 @@ int Batch::prepare_images(const CallSide &in, const uint32_t *in_len, const uint
   int rc = ensure_planar_scratch(pass_in ? in_pitch * n_streams_ * sizeof(float) : 0,
                                  bus || r.pass_out ? im->out_pitch * n_streams_ * sizeof(float) : 0);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  const size_t bus_bytes = bus && r.pass_out ? im->out_pitch * n_buses_ * sizeof(float) : 0;
-  if (bus_bytes > bus_image_cap_) {
-    rc = quiesce();  // (a grow waits for the state's own last call, which may still read the old image)
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-    rc = grow_stage(device_, &d_bus_image_, &bus_image_cap_, bus_bytes, false);
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  }
   if (bus || pass_in || (r.pass_out && im->most_out != 0)) {
     // (the images and the cells belong to the state: a call on another stream than the previous one waits for it first)
     rc = chain_to(stream);

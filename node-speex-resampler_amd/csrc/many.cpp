@@ -480,7 +480,7 @@ void mixer_counters(uint64_t out[6]) {
 // ---- the unit of a mixer call (engine.h, many_mixer; include/speexhip_resampler.h, "Mixer") -------------------------------
 // The legs are staged, grouped and launched as run_plain does it -- the table of ALL the call's slots at the head of the
 // range that travels in -- and stay float images on the device; behind the last launch bus_sum_legs (kernels_bus_legs.hip)
-// sums every slot into the buses, the existing output pass encodes them into the head of the range that travels out, and
+// sums every slot into the buses, their output stage (bus_out.h) encodes them into the head of the range that travels out, and
 // that range goes back as one copy (a small call: the kernels wrote the pinned stage) and from there into the caller's
 // bus buffers.  Never pipelined, never two lanes: a tick is small, and the buses need every leg.
 int Batch::ManyUnit::run_mixer(const Unit &unit, const ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *rcs, MixerCall &mc) {
@@ -499,17 +499,17 @@ int Batch::ManyUnit::run_mixer(const Unit &unit, const ManyEntry *entries, uint3
   // runs, so that every bus begins on a line whatever the format), a planar side's plane c another c * plane_stride.
   const bool planar = mc.out.layout == SPEEXHIP_LAYOUT_PLANAR;
   const size_t plane_stride = planar ? (static_cast<size_t>(mc.bus_frames) + 15) & ~static_cast<size_t>(15) : 0;
-  const size_t bus_samples = planar ? plane_stride * mc.channels : static_cast<size_t>(mc.bus_frames) * mc.channels;
+  const size_t bus_samples = planar ? plane_stride * mc.out.channels : static_cast<size_t>(mc.bus_frames) * mc.out.channels;
   const size_t bus_stride = (bus_samples + 63) & ~static_cast<size_t>(63);
   ManyExtra extra;
   extra.in_bytes = sizeof(BusLeg) * mc.n_legs;
-  extra.out_bytes = bus_stride * mc.n_buses * sample_bytes(mc.out.fmt);
+  extra.out_bytes = bus_stride * mc.buses->n_buses() * sample_bytes(mc.out.fmt);
   const ManySwitches switches = {1, 0};  // (no pipeline)
   u.plan = plan_many_unit(u.shapes.data(), u.shapes.size(), switches, extra);
   int rc = u.grow();
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  if (mc.pass_out) {
-    rc = grow_stage(unit.device, mc.bus_image, mc.bus_image_cap, bus_stride * mc.n_buses * sizeof(float), false);
+  if (mc.bus_route.pass_out) {  // (the mixer's last call has been waited for: nothing reads the old image)
+    rc = mc.buses->grow_image(bus_stride * mc.buses->n_buses() * sizeof(float));
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
   // The table: one record per SLOT, in slot order.  A slot without a leg that runs -- empty, refused -- stays zeros: no
@@ -521,7 +521,7 @@ int Batch::ManyUnit::run_mixer(const Unit &unit, const ManyEntry *entries, uint3
     BusLeg &leg = table[it.i];
     leg.src = reinterpret_cast<const float *>(ms.d_img_out + u.plan.e[k].img_out);
     leg.frames = it.plan.produced;
-    if (it.e->route.moves_gain) leg.gain = it.b->gain_pack(0, 1, mc.channels).s[0];
+    if (it.e->route.moves_gain) leg.gain = it.b->gain_pack(0, 1, mc.out.channels).s[0];
   }
   for (const Item &it : u.items) {
     it.b->float_seen_ = true;
@@ -557,11 +557,11 @@ int Batch::ManyUnit::sum_buses(size_t bus_stride, size_t plane_stride) {
   a.w = mc.d_w;
   a.w_pitch = mc.w_pitch;
   // (an interleaved F32 side IS the buses' image: the kernel writes the stage itself)
-  a.dst = reinterpret_cast<float *>(mc.pass_out ? *mc.bus_image : dst_base);
+  a.dst = reinterpret_cast<float *>(mc.bus_route.pass_out ? mc.buses->image() : dst_base);
   a.dst_pitch = bus_stride;
   a.n_legs = mc.n_legs;
-  a.n_buses = mc.n_buses;
-  a.channels = mc.channels;
+  a.n_buses = mc.buses->n_buses();
+  a.channels = mc.out.channels;
   a.bus_frames = mc.bus_frames;
   if (hip_failed(launch_bus_sum_legs(a, table, ms.stream), "kernel launch")) return SPEEXHIP_ERR_DEVICE;
   count_mixer(2);
@@ -570,7 +570,7 @@ int Batch::ManyUnit::sum_buses(size_t bus_stride, size_t plane_stride) {
   stage.stride = bus_stride;
   stage.plane_stride = plane_stride;
   uint32_t passes = 0;
-  const int prc = mixer_bus_pass(mc, stage, mc.pass_out ? *mc.bus_image : nullptr, bus_stride, ms.stream, &passes);
+  const int prc = mc.buses->encode(mc.bus_route, stage, mc.buses->image(), bus_stride, mc.bus_frames, ms.stream, &passes);
   count_mixer(3, passes);
   return prc;
 }
@@ -579,7 +579,7 @@ int Batch::ManyUnit::sum_buses(size_t bus_stride, size_t plane_stride) {
 int Batch::ManyUnit::buses_out(size_t bus_stride, size_t plane_stride) {
   const MixerCall &mc = *mixer;
   const size_t es = sample_bytes(mc.out.fmt);
-  const size_t out_bytes = bus_stride * mc.n_buses * es;
+  const size_t out_bytes = bus_stride * mc.buses->n_buses() * es;
   if (mc.bus_frames != 0) {
     if (!plan.small) HIP_TRY(hipMemcpyAsync(ms.h_out, ms.d_out, out_bytes, hipMemcpyDeviceToHost, ms.stream));
     count_mixer(5);
@@ -589,13 +589,13 @@ int Batch::ManyUnit::buses_out(size_t bus_stride, size_t plane_stride) {
     if (wrc != SPEEXHIP_ERR_SUCCESS) return wrc;
   }
   const bool planar = mc.out.layout == SPEEXHIP_LAYOUT_PLANAR;
-  for (uint32_t j = 0; j < mc.n_buses && mc.bus_frames != 0; j++) {
+  for (uint32_t j = 0; j < mc.buses->n_buses() && mc.bus_frames != 0; j++) {
     char *to = static_cast<char *>(mc.out.base) + j * mc.out.stride * es;
     const char *from = ms.h_out + j * bus_stride * es;
     if (!planar) {
-      std::memcpy(to, from, static_cast<size_t>(mc.bus_frames) * mc.channels * es);
+      std::memcpy(to, from, static_cast<size_t>(mc.bus_frames) * mc.out.channels * es);
     } else {
-      for (uint32_t c = 0; c < mc.channels; c++)
+      for (uint32_t c = 0; c < mc.out.channels; c++)
         std::memcpy(to + c * mc.out.plane_stride * es, from + c * plane_stride * es, static_cast<size_t>(mc.bus_frames) * es);
     }
   }

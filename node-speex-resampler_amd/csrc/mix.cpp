@@ -7,7 +7,6 @@
 #include <algorithm>
 #include <cstring>
 
-#include "dither.h"
 #include "engine.h"
 #include "engine_detail.h"
 
@@ -15,10 +14,9 @@ namespace speexhip {
 using namespace detail;
 
 int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pitch, const uint32_t *lens, hipStream_t stream,
-                     const CallPlan *apart, bool buses) {
-  // an item of the pass: a stream of the batch, or a channel of the one stream whose channels stand apart -- or a bus of
-  // a bus call's output side (bus.cpp), which takes the bus seeds, position and cells where a stream takes its own
-  const uint32_t items = buses ? n_buses_ : apart != nullptr ? channels_ : n_streams_;
+                     const CallPlan *apart) {
+  // an item of the pass: a stream of the batch, or a channel of the one stream whose channels stand apart
+  const uint32_t items = apart != nullptr ? channels_ : n_streams_;
   const size_t storage_step = (apart != nullptr ? 1 : side.stride) * sample_bytes(side.fmt);
   const size_t image_step = (apart != nullptr ? 1 : pitch) * sizeof(float);
   // With dither on (set_dither) the formats of dithered_fmt leave through the dithered instances of either pass, at the
@@ -31,15 +29,15 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
   // With a stream's gain on (set_gain) every format leaves through the gained instance of its pass, each stream at its own
   // g from its own frame index on; dither and meter ride along in the same instance.  (Channels that stand apart have no
   // output frame to index: the callers have refused them.)
-  const bool gained = !to_image && !buses && gain_on();  // (a bus's streams were gained before they were summed)
+  const bool gained = !to_image && gain_on();
   if (gained && apart != nullptr) return SPEEXHIP_ERR_BAD_STATE;
   const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
   for (uint32_t first = 0; first < items; first += kChunk) {
     const uint32_t n = std::min(kChunk, items - first);
     DitherPack dith;
-    if (dithered) dith = buses ? bus_dither_pack(channels_) : dither_pack(first, n, side.mix != nullptr ? 1 : channels_);
+    if (dithered) dith = dither_pack(first, n, side.mix != nullptr ? 1 : channels_);
     MeterPack cells;
-    if (metered) cells = buses ? bus_meter_pack() : meter_pack(first, n);
+    if (metered) cells = meter_pack(first, n);
     const MeterPack *meter = metered ? &cells : nullptr;
     GainPack gains;  // (the flat converting pass walks samples: it divides by channels(); the others walk frames)
     if (gained) gains = gain_pack(first, n, side.layout != SPEEXHIP_LAYOUT_PLANAR && side.mix == nullptr ? channels_ : 1);
@@ -74,7 +72,7 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
         pack.s[j].frames = apart != nullptr ? apart[item].produced : lens[item];
         most = std::max(most, pack.s[j].frames);
       }
-      if (dithered) dith = buses ? bus_dither_pack(1) : dither_pack(first, n, 1);
+      if (dithered) dith = dither_pack(first, n, 1);
       e = launch_planes(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream, meter, gain);
     } else if (side.mix != nullptr) {
       MixPack pack;
@@ -102,69 +100,6 @@ int Batch::side_pass(const CallSide &side, bool to_image, char *image, size_t pi
       e = launch_convert(side.fmt, !to_image, pack, dithered ? &dith : nullptr, n, most, stream, meter, gain);
     }
     if (hip_failed(e, "kernel launch")) return SPEEXHIP_ERR_DEVICE;
-  }
-  return SPEEXHIP_ERR_SUCCESS;
-}
-
-// The output pass over the buses of a MIXER call (engine.h, MixerCall): side_pass's launches over items that belong to no
-// Batch -- bus j is mc.bus_frames frames of mc.channels floats at image + j * pitch (floats) and leaves for side.base +
-// j * side.stride (samples), dithered from the mixer's bus seeds at its bus position, judged into its cells, never gained.
-// A side that passes through no image (interleaved F32: bus_sum_legs wrote side.base) is only read, by meter_image, when
-// the meter is on.  *launches: the passes launched.
-int mixer_bus_pass(const MixerCall &mc, const CallSide &side, const char *image, size_t pitch, hipStream_t stream, uint32_t *launches) {
-  const uint32_t kChunk = static_cast<uint32_t>(kMaxPackedStreams);
-  const bool planar = side.layout == SPEEXHIP_LAYOUT_PLANAR;
-  const bool dithered = mc.dither_kind != SPEEXHIP_DITHER_NONE && dithered_fmt(side.fmt);
-  if (!mc.pass_out && mc.cells == nullptr) return SPEEXHIP_ERR_SUCCESS;
-  for (uint32_t first = 0; first < mc.n_buses && mc.bus_frames != 0; first += kChunk) {
-    const uint32_t n = std::min(kChunk, mc.n_buses - first);
-    DitherPack dith;
-    std::memset(&dith, 0, sizeof(dith));
-    dith.kind = mc.dither_kind;
-    MeterPack cells;
-    std::memset(&cells, 0, sizeof(cells));
-    for (uint32_t j = 0; j < n; j++) {
-      dith.s[j].seed = dither::stream_seed(mc.dither_seed, mc.n_legs + first + j);
-      dith.s[j].first = mc.bus_pos * (planar ? 1 : mc.channels);  // (mod 2^64, like idx)
-      if (mc.cells != nullptr) cells.cell[j] = mc.cells + first + j;
-    }
-    const MeterPack *meter = mc.cells != nullptr ? &cells : nullptr;
-    const size_t es = sample_bytes(side.fmt);
-    hipError_t e;
-    if (!mc.pass_out) {
-      ConvertPack pack;
-      std::memset(&pack, 0, sizeof(pack));
-      for (uint32_t j = 0; j < n; j++) {
-        pack.s[j].src = static_cast<const char *>(side.base) + (first + j) * side.stride * es;
-        pack.s[j].n = static_cast<uint64_t>(mc.bus_frames) * mc.channels;
-        pack.s[j].step = 1;
-      }
-      e = launch_meter_image(pack, cells, 1.0f, n, static_cast<uint64_t>(mc.bus_frames) * mc.channels, stream);
-    } else if (planar) {
-      PlanePack pack;
-      std::memset(&pack, 0, sizeof(pack));
-      pack.storage_channels = pack.image_channels = pack.image_pitch = mc.channels;
-      for (uint32_t j = 0; j < n; j++) {
-        pack.s[j].src = image + (first + j) * pitch * sizeof(float);
-        pack.s[j].dst = static_cast<char *>(side.base) + (first + j) * side.stride * es;
-        pack.s[j].plane_stride = side.plane_stride;
-        pack.s[j].frames = mc.bus_frames;
-      }
-      e = launch_planes(side.fmt, true, pack, dithered ? &dith : nullptr, n, mc.bus_frames, stream, meter, nullptr);
-    } else {
-      ConvertPack pack;
-      std::memset(&pack, 0, sizeof(pack));
-      for (uint32_t j = 0; j < n; j++) {
-        pack.s[j].src = image + (first + j) * pitch * sizeof(float);
-        pack.s[j].dst = static_cast<char *>(side.base) + (first + j) * side.stride * es;
-        pack.s[j].n = static_cast<uint64_t>(mc.bus_frames) * mc.channels;
-        pack.s[j].step = 1;
-      }
-      e = launch_convert(side.fmt, true, pack, dithered ? &dith : nullptr, n, static_cast<uint64_t>(mc.bus_frames) * mc.channels, stream, meter,
-                         nullptr);
-    }
-    if (hip_failed(e, "kernel launch")) return SPEEXHIP_ERR_DEVICE;
-    if (launches != nullptr) (*launches)++;
   }
   return SPEEXHIP_ERR_SUCCESS;
 }

@@ -1,7 +1,7 @@
 // mixer.cpp -- the mixer of mixer.h (include/speexhip_resampler.h, "Mixer"): the object, its control calls and process.
 // A mixer call is the many-states call up to the float images of the legs; where that call encodes each state and sends
 // it back, bus_sum_legs (kernels_bus_legs.hip) sums the slots' images -- each behind its own state's gain -- into the float
-// images of the buses, and the existing output pass encodes those.  What process does here is what bus.cpp and
+// images of the buses, and the buses' output stage (bus_out.h) encodes those.  What process does here is what bus.cpp and
 // formats.cpp do for their calls: check the arguments, ask the route of every leg and of the bus side, hand the rest to
 // the unit machinery (many.cpp), and move what the call moved.
 #include "mixer.h"
@@ -21,7 +21,6 @@ namespace speexhip {
 using namespace detail;
 
 // the device blocks: control-plane data, moved whole through the copy engines (engine_detail.h, kCtlCopyMin)
-size_t Mixer::cells_bytes() const { return std::max(sizeof(MeterCell) * n_buses_, kCtlCopyMin); }
 size_t Mixer::weights_bytes() const { return std::max(sizeof(float) * n_legs_ * w_pitch_, kCtlCopyMin); }
 
 Mixer *Mixer::create(uint32_t n_legs, uint32_t n_buses, uint32_t channels, int *err, int device) {
@@ -54,20 +53,16 @@ Mixer *Mixer::create(uint32_t n_legs, uint32_t n_buses, uint32_t channels, int *
     m->channels_ = channels;
     m->device_ = device;
     m->w_pitch_ = (n_buses + kBusGroup - 1) / kBusGroup * kBusGroup;
-    m->bus_samples_.assign(n_buses, 0);
-    e = [m]() -> int {
+    m->buses_.bind(device, channels, n_legs);
+    e = [m, n_buses]() -> int {
       DeviceScope scope(m->device_);
       HIP_TRY(scope.error());
       HIP_TRY(pool::stream_get(m->device_, &m->stream_));
-      void *cells = nullptr, *w = nullptr;
-      int rc = dev_alloc(m->device_, &cells, m->cells_bytes());
-      if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-      m->d_cells_ = static_cast<char *>(cells);
-      rc = dev_alloc(m->device_, &w, m->weights_bytes());
+      void *w = nullptr;
+      const int rc = dev_alloc(m->device_, &w, m->weights_bytes());
       if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
       m->d_w_ = static_cast<char *>(w);
-      const std::vector<char> zeros(m->cells_bytes(), 0);
-      return ctl_upload(m->d_cells_, zeros.data(), zeros.size(), m->stream_);
+      return m->buses_.resize(n_buses, m->stream_);
     }();
   }
   if (e != SPEEXHIP_ERR_SUCCESS) {
@@ -81,9 +76,8 @@ Mixer *Mixer::create(uint32_t n_legs, uint32_t n_buses, uint32_t channels, int *
 Mixer::~Mixer() {
   DeviceScope scope(device_);
   // (process is synchronous and the control calls wait for their copies: nothing of the mixer's is in flight)
-  pool::device_put(device_, d_bus_image_);
+  buses_.release();
   pool::device_put(device_, d_w_);
-  pool::device_put(device_, d_cells_);
   pool::stream_put(device_, stream_);
 }
 
@@ -106,12 +100,9 @@ int Mixer::set_weights(const float *weights) {
   on_ = false;  // (a copy that fails leaves the mixer off until a set_weights succeeds)
   int rc = ctl_upload(d_w_, wt.data(), wt.size() * sizeof(float), stream_);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  const std::vector<char> zeros(cells_bytes(), 0);
-  rc = ctl_upload(d_cells_, zeros.data(), zeros.size(), stream_);
+  rc = buses_.reset(stream_);  // (the cells, the totals, the position)
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   w_.assign(weights, weights + n);
-  bus_samples_.assign(n_buses_, 0);
-  bus_pos_ = 0;
   on_ = true;
   return SPEEXHIP_ERR_SUCCESS;
 }
@@ -125,52 +116,28 @@ int Mixer::get_weights(float *weights) const {
 
 int Mixer::set_dither(int kind, uint64_t seed, uint64_t position) {
   if (!dither::known_kind(kind)) return SPEEXHIP_ERR_INVALID_ARG;
-  dither_kind_ = kind;
-  dither_seed_ = seed;
-  bus_pos_ = position;
+  buses_.set_dither(kind, seed, position);
   return SPEEXHIP_ERR_SUCCESS;
 }
 int Mixer::get_dither(int *kind, uint64_t *seed, uint64_t *position) const {
-  if (kind != nullptr) *kind = dither_kind_;
-  if (seed != nullptr) *seed = dither_seed_;
-  if (position != nullptr) *position = bus_pos_;
+  if (kind != nullptr) *kind = buses_.dither_kind();
+  if (seed != nullptr) *seed = buses_.dither_seed();
+  if (position != nullptr) *position = buses_.position();
   return SPEEXHIP_ERR_SUCCESS;
 }
 
 int Mixer::set_meter(int on) {
   if (on != 0 && on != 1) return SPEEXHIP_ERR_INVALID_ARG;
-  meter_on_ = on != 0;  // (the totals stay, as a state's do)
+  buses_.set_meter(on != 0);  // (the totals stay, as a state's do)
   return SPEEXHIP_ERR_SUCCESS;
 }
 
 int Mixer::get_bus_meter(uint32_t bus, SpeexHipMeter *m, bool reset) {
-  if (bus >= n_buses_ || (m == nullptr && !reset)) return SPEEXHIP_ERR_INVALID_ARG;
-  if (m != nullptr && m->struct_size < sizeof(SpeexHipMeter)) return SPEEXHIP_ERR_INVALID_ARG;
+  if (!meter_request_ok(bus, n_buses_, m, reset)) return SPEEXHIP_ERR_INVALID_ARG;
   DeviceScope scope(device_);
   HIP_TRY(scope.error());
-  std::vector<char> image(cells_bytes());
-  int rc = ctl_download(image.data(), d_cells_, image.size(), 0, image.size(), stream_);
-  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  MeterCell *cells = reinterpret_cast<MeterCell *>(image.data());
-  SpeexHipMeter now;
-  std::memset(&now, 0, sizeof(now));
-  now.on = meter_on_ ? 1u : 0u;
-  now.samples = bus_samples_[bus];
-  now.clipped_high = cells[bus].hi;
-  now.clipped_low = cells[bus].lo;
-  now.nan = cells[bus].nan;
-  std::memcpy(&now.peak, &cells[bus].peak_bits, sizeof(now.peak));
-  if (reset) {  // (nothing of the mixer's is in flight: the cells go back whole, this bus's zeroed)
-    std::memset(&cells[bus], 0, sizeof(MeterCell));
-    rc = ctl_upload(d_cells_, image.data(), image.size(), stream_);
-    if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-    bus_samples_[bus] = 0;
-  }
-  if (m != nullptr) {
-    now.struct_size = m->struct_size;
-    std::memcpy(m, &now, sizeof(now));
-  }
-  return SPEEXHIP_ERR_SUCCESS;
+  // (process is synchronous: nothing of the mixer's is in flight)
+  return buses_.get_meter(bus, m, reset, stream_);
 }
 
 int Mixer::process(Batch *const *legs, const CallSide *in, const uint8_t *bad, uint32_t *in_len, uint32_t *out_len,
@@ -185,8 +152,8 @@ int Mixer::process(Batch *const *legs, const CallSide *in, const uint8_t *bad, u
   // (the bus side's route is the Batch's bus call's: the same rule, with the mixer's switches for the state's)
   const SideKind image_kind = {SPEEXHIP_FMT_F32, false, false, false};
   SidesState bus_state = {};
-  bus_state.dither = dither_kind_ != SPEEXHIP_DITHER_NONE;
-  bus_state.meter = meter_on_;
+  bus_state.dither = buses_.dither_kind() != SPEEXHIP_DITHER_NONE;
+  bus_state.meter = buses_.meter_on();
   const SidesRoute bus_route = route_sides_call(SidesForm::Bus, image_kind, side_kind(out), bus_state);
   if (bus_route.refuse != SPEEXHIP_ERR_SUCCESS) return bus_route.refuse;
 
@@ -220,18 +187,11 @@ int Mixer::process(Batch *const *legs, const CallSide *in, const uint8_t *bad, u
   MixerCall mc;
   mc.device = device_;
   mc.n_legs = n_legs_;
-  mc.n_buses = n_buses_;
-  mc.channels = channels_;
   mc.d_w = reinterpret_cast<const float *>(d_w_);
   mc.w_pitch = w_pitch_;
   mc.out = out;
-  mc.pass_out = bus_route.pass_out;
-  mc.dither_kind = dithered_fmt(out.fmt) ? dither_kind_ : SPEEXHIP_DITHER_NONE;
-  mc.dither_seed = dither_seed_;
-  mc.bus_pos = bus_pos_;
-  mc.cells = bus_route.counts_meter ? reinterpret_cast<MeterCell *>(d_cells_) : nullptr;
-  mc.bus_image = &d_bus_image_;
-  mc.bus_image_cap = &bus_image_cap_;
+  mc.bus_route = bus_route;
+  mc.buses = &buses_;
   int unit_rc;
   try {
     unit_rc = Batch::many_mixer(mc, n_legs_, entries.data(), in_len, out_len, rcs.data());
@@ -244,9 +204,7 @@ int Mixer::process(Batch *const *legs, const CallSide *in, const uint8_t *bad, u
       if (entries[i].b != nullptr && entries[i].rc == SPEEXHIP_ERR_SUCCESS) rcs[i] = unit_rc;
   } else {
     // what the call moved beside its legs: the buses' totals and the one bus position
-    if (bus_route.counts_meter)
-      for (uint32_t j = 0; j < n_buses_; j++) bus_samples_[j] += static_cast<uint64_t>(mc.bus_frames) * channels_;
-    if (bus_route.moves_dither) bus_pos_ += mc.bus_frames;
+    buses_.moved(bus_route, mc.bus_frames);
     *bus_frames = mc.bus_frames;
   }
   int first = SPEEXHIP_ERR_SUCCESS;

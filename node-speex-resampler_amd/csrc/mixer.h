@@ -1,6 +1,6 @@
 // mixer.h -- the mixer (include/speexhip_resampler.h, "Mixer"): mix buses over many separate single-stream states in one
-// host call.  The object owns what a Batch owns for its buses (bus.cpp) -- W on the device, the buses' dither kind, seed
-// and one bus position, the buses' meter switch, cells and totals -- and nothing of a leg: the caller names the state in
+// host call.  The object owns W on the device and the buses' output stage (bus_out.h: their dither kind, seed and one bus
+// position, their meter switch, cells and totals, their image) -- and nothing of a leg: the caller names the state in
 // every slot with every call.  process describes its legs as entries of the many-states machinery (many.cpp,
 // Batch::many_mixer), which carries the call out; every decision is a pure host rule (sides_route.h: SidesForm::MixerLeg
 // for a leg, SidesForm::Bus for the bus side; many_plan.h: the stage and the launch groups).
@@ -29,7 +29,7 @@ class Mixer {
   int get_dither(int *kind, uint64_t *seed, uint64_t *position) const;  // the seed as given; the bus position
   int set_meter(int on);
   int get_bus_meter(uint32_t bus, SpeexHipMeter *m, bool reset);
-  uint64_t bus_position() const { return bus_pos_; }
+  uint64_t bus_position() const { return buses_.position(); }
   // One tick (the header's speexhip_mixer_process): legs[i] = the state in slot i or nullptr, in[i] its input side in
   // host memory, bad[i] != 0 (bad may be null) = a side the caller could not read.  Synchronous.
   int process(Batch *const *legs, const CallSide *in, const uint8_t *bad, uint32_t *in_len, uint32_t *out_len, const CallSide &out,
@@ -41,7 +41,6 @@ class Mixer {
 
  private:
   Mixer() = default;
-  size_t cells_bytes() const;
   size_t weights_bytes() const;
   uint32_t n_legs_ = 0, n_buses_ = 0, channels_ = 0;
   int device_ = 0;
@@ -50,13 +49,7 @@ class Mixer {
   bool on_ = false;                // weights are set
   std::vector<float> w_;           // W as the caller gave it
   char *d_w_ = nullptr;            // its transpose, padded (kernels.h, BusLegsArgs::w)
-  char *d_cells_ = nullptr;        // one MeterCell per bus, zeroed by init and by set_weights
-  int dither_kind_ = SPEEXHIP_DITHER_NONE;
-  uint64_t dither_seed_ = 0, bus_pos_ = 0;
-  bool meter_on_ = false;
-  std::vector<uint64_t> bus_samples_;  // per bus: samples metered since the last reset
-  char *d_bus_image_ = nullptr;    // the float image of the buses, grow-only
-  size_t bus_image_cap_ = 0;
+  BusOutput buses_;                // behind the sum (seed_base = n_legs); the cells zeroed by init and by set_weights
 };
 
 }  // namespace speexhip
