@@ -92,6 +92,111 @@ def buses(weights, y, defect=None, live=None):
     return out
 
 
+def buses_wide(weights, y):
+    """buses(weights, y), the rule alone, with the Python loop over the streams only and all buses at once as (n_buses, n)
+    float64 arrays: every product and every add still one IEEE operation per element, in the same order -- the same bits,
+    at a width (1024 x 1024) where the loop over the buses takes many times as long"""
+    w = np.asarray(weights, np.float32).astype(np.float64)
+    y = np.asarray(y, np.float32)
+    assert w.ndim == 2 and y.ndim == 2 and w.shape[1] == y.shape[0]
+    y64 = y.astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        acc = w[:, 0:1] * y64[0][None, :]
+        for s in range(1, w.shape[1]):
+            p = w[:, s: s + 1] * y64[s][None, :]
+            acc = acc + p
+        return acc.astype(np.float32)
+
+
+# ---- the mixer's kernel (bus_sum_legs): legs walked in blocks, a block's legs dealt to waves ---------------------------
+# What its structure invites, kept apart from ORDER_DEFECTS (the Batch's kernel has neither blocks nor waves):
+#   block_partials   each block of `block` legs summed in ascending order into its own fp64 partial (its first term the
+#                    product itself), the partials then added in ascending order
+#   wave_dealt       one accumulator, but within each block the legs added in the order their waves fetched them: block
+#                    slot wave + r * waves -- 0, 4, 8, 12, 1, 5, ... -- a ragged last block leaving out what it lacks
+LEG_DEFECTS = ("block_partials", "wave_dealt")
+LEG_BLOCK, LEG_WAVES = 16, 4
+
+
+def wave_dealt_order(n_legs, block=LEG_BLOCK, waves=LEG_WAVES):
+    assert block % waves == 0
+    order = []
+    for b0 in range(0, n_legs, block):
+        order += [b0 + wave + r * waves for wave in range(waves) for r in range(block // waves) if b0 + wave + r * waves < n_legs]
+    assert sorted(order) == list(range(n_legs))
+    return order
+
+
+def buses_legs(weights, y, defect, block=LEG_BLOCK, waves=LEG_WAVES):
+    """(n_buses, n) float32: the buses with one of LEG_DEFECTS planted"""
+    assert defect in LEG_DEFECTS, defect
+    w = np.asarray(weights, np.float32).astype(np.float64)
+    y64 = np.asarray(y, np.float32).astype(np.float64)
+    assert w.ndim == 2 and y64.ndim == 2 and w.shape[1] == y64.shape[0]
+    n_legs = w.shape[1]
+    term = lambda s: w[:, s: s + 1] * y64[s][None, :]
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        if defect == "wave_dealt":
+            order = wave_dealt_order(n_legs, block, waves)
+            acc = term(order[0])
+            for s in order[1:]:
+                acc = acc + term(s)
+            return acc.astype(np.float32)
+        total = None
+        for b0 in range(0, n_legs, block):
+            part = term(b0)
+            for s in range(b0 + 1, min(n_legs, b0 + block)):
+                part = part + term(s)
+            total = part if total is None else total + part
+        return total.astype(np.float32)
+
+
+def order_layout_legs(n_legs, pairs, frames, seed=1234):
+    """the order layout (below) for any leg count: (n_legs, frames) float32, mono.  Values of 2^12 everywhere; for pair k
+    = (a, a + 1) of `pairs` a 2^60-sized value in leg a over stretch k of the frames (len(pairs) equal stretches, the last
+    one taking the remainder), and leg a + 1 the exact negation of leg a throughout."""
+    rng = np.random.default_rng(seed)
+    x = (rng.uniform(-1.0, 1.0, (n_legs, frames)) * 2.0 ** 12).astype(np.float32)
+    huge = (rng.uniform(-1.0, 1.0, frames) * 2.0 ** 60).astype(np.float32)
+    for lo, hi, (a, b) in zip(*order_stretches(len(pairs), frames), pairs):
+        assert b == a + 1 and 0 <= a and b < n_legs
+        x[a, lo:hi] = huge[lo:hi]
+    for a, b in pairs:
+        x[b] = -x[a]
+    return x
+
+
+def order_stretches(n_pairs, frames):
+    """(the first frame of each stretch, the frame behind its last)"""
+    step = frames // n_pairs
+    return [k * step for k in range(n_pairs)], [(k + 1) * step if k + 1 < n_pairs else frames for k in range(n_pairs)]
+
+
+def order_weights_legs(n_legs, pairs, n_buses, seed=4321):
+    """(n_buses, n_legs) float32 for that layout: row 0 all ones, row 1 all minus ones, one row per pair with ones on the
+    pair alone (its bus: +0.0, never -0.0), then rows of random weights in [-1.5, 1.5]"""
+    assert n_buses >= 2 + len(pairs)
+    w = np.random.default_rng(seed).uniform(-1.5, 1.5, (n_buses, n_legs)).astype(np.float32)
+    w[0], w[1] = 1.0, -1.0
+    for k, (a, b) in enumerate(pairs):
+        w[2 + k] = 0.0
+        w[2 + k, [a, b]] = 1.0
+    return w
+
+
+# the two order layouts of the mixer's tests: 48 legs -- three blocks; the pair (15, 16) straddles the first block edge, which
+# only block_partials can see (15 is the last leg of its block in either order); (46, 47) ends the ragged walk of a wave --
+# and the mixer's limits, 1024 x 1024, with a slot that is empty and one that is silent (+0.0 throughout either way)
+LEGS_48, PAIRS_48 = 48, ((0, 1), (15, 16), (46, 47))
+LIMIT, LIMIT_PAIRS, LIMIT_EMPTY, LIMIT_SILENT = 1024, ((0, 1), (1007, 1008), (1022, 1023)), 500, 501
+
+
+def limits_layout(frames, seed=1234):
+    x = order_layout_legs(LIMIT, LIMIT_PAIRS, frames, seed)
+    x[[LIMIT_EMPTY, LIMIT_SILENT]] = 0.0
+    return x
+
+
 def live_of(lengths, n):
     """(n_streams, n) bool: sample i of stream s lies before the stream's end (lengths in samples)"""
     return np.arange(n)[None, :] < np.asarray(lengths)[:, None]

@@ -113,3 +113,73 @@ def test_debug_bus_equals_the_model_at_41_by_41_and_every_order_defect_shows():
         print("41 x 41 order layout, %-16s: up to %5.1f %% of a bus's samples change, %d of %d buses"
               % (defect, 100 * max(shares), sum(s > 0 for s in shares), N))
         assert max(shares) >= 0.01, defect
+
+
+# ---- the model's own additions for the mixer's kernel (bus_model.py: buses_wide, LEG_DEFECTS, the layouts for any leg count)
+def test_buses_wide_is_buses_bit_for_bit():
+    rng = np.random.default_rng(5)
+    for n_buses, n_legs, n in ((130, 70, 33), (41, 41, 257), (1, 1, 5), (3, 17, 64)):
+        w = rng.uniform(-1.5, 1.5, (n_buses, n_legs)).astype(np.float32)
+        w[n_buses // 2] = 0.0
+        y = (rng.uniform(-1.0, 1.0, (n_legs, n)) * 2.0 ** rng.integers(0, 40, (n_legs, 1))).astype(np.float32)
+        y[0, :2] = (-0.0, np.inf)
+        assert bm.buses_wide(w, y).tobytes() == bm.buses(w, y).tobytes(), (n_buses, n_legs)
+    y, w = wide_order_layout(100), wide_weights()
+    assert bm.buses_wide(w, y).tobytes() == bm.buses(w, y).tobytes()
+
+
+def test_the_wave_dealt_order_and_the_defects_on_an_input_that_cannot_tell():
+    assert bm.wave_dealt_order(20)[:16] == [0, 4, 8, 12, 1, 5, 9, 13, 2, 6, 10, 14, 3, 7, 11, 15]
+    assert bm.wave_dealt_order(20)[16:] == [16, 17, 18, 19] and bm.wave_dealt_order(22)[16:] == [16, 20, 17, 21, 18, 19]
+    # small integers sum exactly in any order: neither defect may change a bit there (they reorder, nothing else)
+    rng = np.random.default_rng(6)
+    w = rng.integers(-3, 4, (5, 37)).astype(np.float32)
+    y = rng.integers(-1000, 1000, (37, 50)).astype(np.float32)
+    for defect in bm.LEG_DEFECTS:
+        assert bm.buses_legs(w, y, defect).tobytes() == bm.buses(w, y).tobytes(), defect
+
+
+def stretch_shares(bad, want, frames, n_pairs):
+    """per stretch of the layout, the larger share of rows 0 and 1 that the defect changed"""
+    lo, hi = bm.order_stretches(n_pairs, frames)
+    return [max(bm.changed(bad[j][a:b], want[j][a:b]) for j in (0, 1)) for a, b in zip(lo, hi)]
+
+
+def test_every_order_defect_shows_on_the_48_leg_layout_and_debug_bus_equals_the_model():
+    frames = 402
+    y = bm.order_layout_legs(bm.LEGS_48, bm.PAIRS_48, frames)
+    w = bm.order_weights_legs(bm.LEGS_48, bm.PAIRS_48, 8)
+    assert np.isfinite(y).all() and y.shape == (48, frames) and w.shape == (8, 48)
+    for a, b in bm.PAIRS_48:
+        assert y[b].tobytes() == (-y[a]).tobytes()
+    want = bm.buses(w, y)
+    assert want[2:5].tobytes() == np.zeros((3, frames), np.float32).tobytes(), "a pair alone is not +0.0"
+    assert bm.buses_wide(w, y).tobytes() == want.tobytes()
+    assert speexhip.debug_bus(w, y).tobytes() == want.tobytes(), "speexhip_debug_bus differs from the model on the 48-leg layout"
+    shares = {}
+    for defect in bm.ORDER_DEFECTS + ("round_each_add",) + bm.LEG_DEFECTS:
+        bad = bm.buses_legs(w, y, defect) if defect in bm.LEG_DEFECTS else bm.buses(w, y, defect)
+        shares[defect] = stretch_shares(bad, want, frames, 3)
+        print("48-leg layout, %-16s: %s %% of rows 0 / 1 change per stretch" % (defect, " / ".join("%5.1f" % (100 * s) for s in shares[defect])))
+        assert bad[2:5].tobytes() == want[2:5].tobytes() or defect in ("fp32_accumulator", "round_each_add")
+    # the pair across the first block edge is block_partials' alone; wave_dealt sees the pair that begins a block
+    assert shares["block_partials"][1] == 1.0 and shares["block_partials"][2] == 1.0
+    assert shares["wave_dealt"][0] == 1.0 and shares["wave_dealt"][1] == 0.0 and shares["wave_dealt"][2] >= 0.2
+    for defect in bm.ORDER_DEFECTS + ("round_each_add",):
+        assert max(shares[defect]) >= 0.75, defect
+
+
+def test_the_order_defects_show_at_the_mixers_limits_and_debug_bus_equals_the_model():
+    frames = 160
+    y = bm.limits_layout(frames)
+    w = bm.order_weights_legs(bm.LIMIT, bm.LIMIT_PAIRS, bm.LIMIT)
+    assert y.shape == (1024, frames) and w.shape == (1024, 1024) and not y[[bm.LIMIT_EMPTY, bm.LIMIT_SILENT]].any()
+    want = bm.buses_wide(w, y)
+    assert np.isfinite(want).all() and want[2:5].tobytes() == np.zeros((3, frames), np.float32).tobytes()
+    assert want[:7].tobytes() == bm.buses(w[:7], y).tobytes()
+    assert speexhip.debug_bus(w, y).tobytes() == want.tobytes(), "speexhip_debug_bus differs from the model at 1024 x 1024"
+    for defect in ("descending",) + bm.LEG_DEFECTS:
+        bad = bm.buses_legs(w[:2], y, defect) if defect in bm.LEG_DEFECTS else bm.buses(w[:2], y, defect)
+        shares = stretch_shares(bad, want, frames, 3)
+        print("1024-leg layout, %-16s: %s %% of rows 0 / 1 change per stretch" % (defect, " / ".join("%5.1f" % (100 * s) for s in shares)))
+        assert max(shares) >= 0.01, defect
