@@ -1300,6 +1300,61 @@ SPEEXHIP_API int speexhip_mixer_process(SpeexHipMixer *m, SpeexHipResamplerState
                                         int *codes);
 SPEEXHIP_API void speexhip_debug_mixer_counters(uint64_t out[6]);
 
+/* ------------------------------------------------------------------------------------------
+ * Mixer levels: how loud each leg of a tick was, measured on the device while the legs' float images are resident --
+ * what active-speaker detection, "mix only the N loudest", the RFC 6464 / 6465 audio-level header extensions, a UI's
+ * talking indicators and silence suppression go by.  A mixer call sends nothing of a leg back, so without this a leg's
+ * level costs a second run of every leg through speexhip_resampler_process_many_fmt to F32.  Off by default; while it is
+ * off a mixer call is byte for byte and launch for launch what "Mixer" describes.
+ *
+ * One record per slot and call, over all C channels of the leg, measured on the leg's float value y: the float call's
+ * value in int16 units BEFORE the state's gain -- y_i, not y'_i of "Mixer".  Pre-gain is deliberate: the levels are for
+ * deciding gains (read tick t's levels, speexhip_resampler_set_gain for tick t + 1, never touch W), and a muted leg must
+ * still read as loud.
+ *
+ *   samples   produced[i] * C            (frames of THIS call; the +0.0f padding up to bus_frames is NOT measured)
+ *   per sample y:
+ *     y != y            nan += 1; nothing else for that sample
+ *     otherwise         peak = max(peak, |y|)                       fp32, +inf is a legal peak
+ *                       r = floor((double)y + 0.5)                  "Metering"'s S16 r with d = 0
+ *                       q = r < -32768 ? -32768 : r > 32767 ? 32767 : r
+ *                       energy += (uint64)(q * q)                   integer, exact; +-inf count at their rail
+ *
+ * energy is a sum of integers and peak a maximum: like the meter's totals they do not depend on the order of the
+ * reduction, on what shares a launch, or on the GPU.  A call of more than 2^34 samples in one leg wraps energy mod 2^64.
+ * An empty slot and a refused leg: all zeros.  A silent leg (data == NULL) and a leg in the zero fallback: samples
+ * counted, the rest 0 -- their images are zeros.  The RFC 6464 level of a record is
+ * min(127, max(0, round(-10 * log10(energy / (samples * 2^30))))), 127 when energy or samples is 0.
+ *
+ * speexhip_mixer_set_levels: on = 0 / 1, anything else INVALID_ARG; a CHANGE of the switch clears the snapshot.  With the
+ * switch on, speexhip_mixer_process measures every slot behind the legs' last FIR launch -- one more launch for a call
+ * whose every leg produced at most 65 536 samples, two otherwise -- and the records ride back behind the buses in the one
+ * transfer out the call makes anyway (none, where the call is small: the kernel writes the pinned stage); no atomics.
+ * speexhip_mixer_get_levels reports the LAST process call's records of the slots [first_slot, first_slot + count): record k
+ * at (char *)levels + k * struct_size, its first 32 bytes written.  struct_size < 32, a range beyond n_legs, or a NULL
+ * pointer: INVALID_ARG; levels off: BAD_STATE; before any call: zeros; after a call-level error (nothing touched): the
+ * snapshot as it was; after a call whose unit failed: cleared; after a call with bus_frames == 0: zeros (nothing was
+ * launched).  set_weights, set_dither and set_meter do not touch it.  The six speexhip_debug_mixer_counters keep their
+ * meaning and their values; speexhip_debug_mixer_level_launches counts the levels' launches apart (host only,
+ * process-wide since start).  speexhip_debug_levels: host only, no GPU -- the very lines the kernel compiles, over y[0 .. n),
+ * ACCUMULATED into *l (samples += n; zero the record first for a fresh one).
+ *
+ * Not part of this version: levels in the Batch's bus call; post-gain or per-channel levels; any selection policy
+ * (loudest-N, hold, hysteresis) inside the library; accumulation across calls -- the caller sums records if it wants that.
+ *
+ * ABI note: adds SpeexHipLevel and these four entry points; SpeexHipInfo, SpeexHipSide, SpeexHipMeter, the enums, the
+ * error codes, the eleven entry points of "Mixer" and the version string are unchanged. */
+typedef struct SpeexHipLevel {
+  uint64_t samples, energy, nan;
+  float peak;
+  uint32_t reserved;
+} SpeexHipLevel; /* 32 bytes */
+SPEEXHIP_API int speexhip_mixer_set_levels(SpeexHipMixer *m, int on);
+SPEEXHIP_API int speexhip_mixer_get_levels(SpeexHipMixer *m, uint32_t first_slot, uint32_t count, void *levels,
+                                           uint32_t struct_size);
+SPEEXHIP_API int speexhip_debug_levels(const float *y, uint32_t n, SpeexHipLevel *l);
+SPEEXHIP_API uint64_t speexhip_debug_mixer_level_launches(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@
 #include "devices.h"
 #include "dither.h"
 #include "gain.h"
+#include "levels.h"
 #include "meter.h"
 #include "engine.h"
 #include "mixer.h"
@@ -917,6 +918,23 @@ int speexhip_mixer_process(SpeexHipMixer *m, SpeexHipResamplerState *const *legs
 void speexhip_debug_mixer_counters(uint64_t out[6]) {
   if (out != nullptr) speexhip::mixer_counters(out);
 }
+int speexhip_mixer_set_levels(SpeexHipMixer *m, int on) {
+  return guarded([&] { return m ? m->mixer->set_levels(on) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_mixer_get_levels(SpeexHipMixer *m, uint32_t first_slot, uint32_t count, void *levels, uint32_t struct_size) {
+  return guarded([&] { return m ? m->mixer->get_levels(first_slot, count, levels, struct_size) : SPEEXHIP_ERR_INVALID_ARG; });
+}
+int speexhip_debug_levels(const float *y, uint32_t n, SpeexHipLevel *l) {
+  if (l == nullptr || (y == nullptr && n != 0)) return SPEEXHIP_ERR_INVALID_ARG;
+  for (uint32_t i = 0; i < n; i++) {
+    speexhip::levels::Lane one;  // (a lane's energy chain is exact up to 2^23 samples: folded sample by sample here)
+    speexhip::levels::add(one, y[i]);
+    speexhip::levels::fold(*l, one);
+  }
+  l->samples += n;
+  return SPEEXHIP_ERR_SUCCESS;
+}
+uint64_t speexhip_debug_mixer_level_launches(void) { return speexhip::mixer_level_launches(); }
 
 int speexhip_debug_g711_decode(int fmt, const uint8_t *codes, uint32_t n, float *x) {
   if ((fmt != SPEEXHIP_FMT_ULAW && fmt != SPEEXHIP_FMT_ALAW) || ((codes == nullptr || x == nullptr) && n != 0))

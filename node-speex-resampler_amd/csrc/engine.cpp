@@ -1549,6 +1549,7 @@ int warm_device(int device) {
   warm_unit_sides(s);
   warm_unit_bus(s);
   warm_unit_bus_legs(s);
+  warm_unit_levels(s);
   HIP_TRY(hipStreamSynchronize(s));
   return SPEEXHIP_ERR_SUCCESS;
 }

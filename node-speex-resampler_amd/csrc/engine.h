@@ -101,7 +101,15 @@ struct MixerCall {
   SidesRoute bus_route;          // of the bus side (SidesForm::Bus); pass_out false: bus_sum_legs writes the stage itself
   BusOutput *buses = nullptr;
   uint32_t bus_frames = 0;       // out: the length of the buses
+  // The legs' levels ("Mixer levels"; kernels_levels.hip), when the mixer has them on: n_legs records, which the unit
+  // fills from the range that travelled out -- all zeros on entry, and left so by a call of bus_frames 0 -- and the
+  // mixer's device block for the partials of a call whose legs span more than one launch row, grown by the unit.
+  SpeexHipLevel *levels = nullptr;   // nullptr: off -- nothing measured, nothing launched, not a byte more travels
+  char **level_parts = nullptr;
+  size_t *level_parts_cap = nullptr;
 };
+// speexhip_debug_mixer_level_launches: the launches of the levels' kernels since start (apart from mixer_counters)
+uint64_t mixer_level_launches();
 
 class Batch {
  public:

@@ -408,4 +408,25 @@ struct BusLegsArgs {
 hipError_t launch_bus_sum_legs(const BusLegsArgs &a, const BusLeg *host_legs, hipStream_t stream);
 void warm_unit_bus_legs(hipStream_t s);
 
+// ---- the levels of a mixer's legs (kernels_levels.hip; levels.h states the record): one SpeexHipLevel per slot over the
+// very table bus_sum_legs reads -- src and frames, BEFORE the gain.  legs: the table in device memory, host_legs: the same
+// records where the host can read them (the launcher checks them before it queues anything: a null table, a leg with
+// frames > bus_frames, a leg with frames but no src).  records: n_legs records where the kernel can write them -- device
+// memory, or the pinned stage of a small call; no atomic touches them.  A call in which every leg is at most one span of
+// kLevelSpan samples is ONE launch that writes the records; otherwise the spans' partials go to `partials` (device
+// memory, partials_room bytes >= n_legs * level_spans() records) and a second launch folds them.  bus_frames == 0:
+// nothing launched.  *launches (may be null): the launches queued, added.
+constexpr uint32_t kLevelSpan = 65536;
+struct LevelsArgs {
+  const BusLeg *legs;       // device memory, one record per workgroup row
+  SpeexHipLevel *dst;       // spans == 1: the records; else the partials, slot-major, `spans` a slot
+  uint32_t channels;
+  uint32_t spans;           // spans of the longest leg, >= 1
+};
+uint64_t level_spans(const BusLeg *host_legs, uint32_t n_legs, uint32_t channels);
+hipError_t launch_leg_levels(const BusLeg *legs, const BusLeg *host_legs, uint32_t n_legs, uint32_t channels, uint32_t bus_frames,
+                             SpeexHipLevel *records, SpeexHipLevel *partials, size_t partials_room, hipStream_t stream,
+                             uint32_t *launches);
+void warm_unit_levels(hipStream_t s);
+
 }  // namespace speexhip

@@ -44,6 +44,8 @@ inline void count_many(int which, uint64_t by = 1) { g_many_counters[which].fetc
 // speexhip_debug_mixer_counters: FIR launches, input passes, bus-sum launches, output passes, transfers in, transfers out
 std::atomic<uint64_t> g_mixer_counters[6];
 inline void count_mixer(int which, uint64_t by = 1) { g_mixer_counters[which].fetch_add(by, std::memory_order_relaxed); }
+// speexhip_debug_mixer_level_launches: the launches of the levels' kernels, apart from the six above
+std::atomic<uint64_t> g_mixer_level_launches;
 // (device, lane): a large call on one device runs as two halves side by side, each on a stage of its own (below)
 ManyStage &many_stage(int device, int lane) {
   static std::mutex mu;
@@ -147,8 +149,9 @@ struct Batch::ManyUnit {
   int inputs_in();
   int run_plain();
   static int run_mixer(const Unit &unit, const ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *rcs, MixerCall &mc);
+  int measure_legs(size_t records_off);
   int sum_buses(size_t bus_stride, size_t plane_stride);
-  int buses_out(size_t bus_stride, size_t plane_stride);
+  int buses_out(size_t bus_stride, size_t plane_stride, size_t records_off);
   int run_pipelined();
   void launch_behind_copies(HandOver &h);
   int launch_group(const std::vector<uint32_t> &g, hipStream_t stream);
@@ -476,6 +479,7 @@ void many_counters(uint64_t out[4]) {
 void mixer_counters(uint64_t out[6]) {
   for (int k = 0; k < 6; k++) out[k] = g_mixer_counters[k].load(std::memory_order_relaxed);
 }
+uint64_t mixer_level_launches() { return g_mixer_level_launches.load(std::memory_order_relaxed); }
 
 // ---- the unit of a mixer call (engine.h, many_mixer; include/speexhip_resampler.h, "Mixer") -------------------------------
 // The legs are staged, grouped and launched as run_plain does it -- the table of ALL the call's slots at the head of the
@@ -483,6 +487,9 @@ void mixer_counters(uint64_t out[6]) {
 // sums every slot into the buses, their output stage (bus_out.h) encodes them into the head of the range that travels out, and
 // that range goes back as one copy (a small call: the kernels wrote the pinned stage) and from there into the caller's
 // bus buffers.  Never pipelined, never two lanes: a tick is small, and the buses need every leg.
+// With the mixer's levels on ("Mixer levels") leg_levels (kernels_levels.hip) measures every slot's image behind the last
+// FIR launch and before the sum, which it does not wait for; its records lie behind the buses in the range that travels
+// out, on a 64-byte boundary, and leave with them.
 int Batch::ManyUnit::run_mixer(const Unit &unit, const ManyEntry *entries, uint32_t *in_len, uint32_t *out_len, int *rcs, MixerCall &mc) {
   ManyStage &ms = many_stage(unit.device, unit.lane);
   std::lock_guard<std::mutex> lock(ms.mu);
@@ -504,6 +511,9 @@ int Batch::ManyUnit::run_mixer(const Unit &unit, const ManyEntry *entries, uint3
   ManyExtra extra;
   extra.in_bytes = sizeof(BusLeg) * mc.n_legs;
   extra.out_bytes = bus_stride * mc.buses->n_buses() * sample_bytes(mc.out.fmt);
+  // (bus_stride is whole 64-sample runs: the buses end on a 64-byte boundary, where the records begin)
+  const size_t records_off = extra.out_bytes;
+  if (mc.levels != nullptr) extra.out_bytes += align64(sizeof(SpeexHipLevel) * mc.n_legs);
   const ManySwitches switches = {1, 0};  // (no pipeline)
   u.plan = plan_many_unit(u.shapes.data(), u.shapes.size(), switches, extra);
   int rc = u.grow();
@@ -523,6 +533,14 @@ int Batch::ManyUnit::run_mixer(const Unit &unit, const ManyEntry *entries, uint3
     leg.frames = it.plan.produced;
     if (it.e->route.moves_gain) leg.gain = it.b->gain_pack(0, 1, mc.out.channels).s[0];
   }
+  if (mc.levels != nullptr && mc.bus_frames != 0) {
+    // (the mixer's last call has been waited for: nothing reads the old block)
+    const uint64_t spans = level_spans(table, mc.n_legs, mc.out.channels);
+    if (spans > 1) {
+      rc = grow_stage(unit.device, mc.level_parts, mc.level_parts_cap, sizeof(SpeexHipLevel) * mc.n_legs * spans, false);
+      if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
+    }
+  }
   for (const Item &it : u.items) {
     it.b->float_seen_ = true;
     if (in_len[it.i] != 0 && out_len[it.i] != 0) it.b->started_[0] = 1;  // resample.c:886
@@ -539,11 +557,25 @@ int Batch::ManyUnit::run_mixer(const Unit &unit, const ManyEntry *entries, uint3
     if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   }
   u.commit_idle();
+  rc = u.measure_legs(records_off);
+  if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
   rc = u.sum_buses(bus_stride, plane_stride);
   if (rc != SPEEXHIP_ERR_SUCCESS) return rc;
-  rc = u.buses_out(bus_stride, plane_stride);
+  rc = u.buses_out(bus_stride, plane_stride, records_off);
   if (rc == SPEEXHIP_ERR_SUCCESS) drain.armed = false;
   return rc;
+}
+
+// leg_levels over the table, into the records behind the buses in the stage that travels out (levels off: nothing)
+int Batch::ManyUnit::measure_legs(size_t records_off) {
+  MixerCall &mc = *mixer;
+  if (mc.levels == nullptr || mc.bus_frames == 0) return SPEEXHIP_ERR_SUCCESS;
+  uint32_t launches = 0;
+  const hipError_t e = launch_leg_levels(reinterpret_cast<const BusLeg *>(src_base), reinterpret_cast<const BusLeg *>(ms.h_in), mc.n_legs,
+                                         mc.out.channels, mc.bus_frames, reinterpret_cast<SpeexHipLevel *>(dst_base + records_off),
+                                         reinterpret_cast<SpeexHipLevel *>(*mc.level_parts), *mc.level_parts_cap, ms.stream, &launches);
+  g_mixer_level_launches.fetch_add(launches, std::memory_order_relaxed);
+  return hip_failed(e, "kernel launch") ? SPEEXHIP_ERR_DEVICE : SPEEXHIP_ERR_SUCCESS;
 }
 
 // bus_sum_legs over the table, then the output pass over the buses, into the stage that travels out
@@ -575,11 +607,13 @@ int Batch::ManyUnit::sum_buses(size_t bus_stride, size_t plane_stride) {
   return prc;
 }
 
-// the buses back: the one copy of a call that is not small, the wait, and the stage's buses into the caller's buffers
-int Batch::ManyUnit::buses_out(size_t bus_stride, size_t plane_stride) {
+// the buses back: the one copy of a call that is not small (the legs' records behind the buses in it, when the levels
+// are on), the wait, and the stage's buses into the caller's buffers, the records into the mixer's snapshot
+int Batch::ManyUnit::buses_out(size_t bus_stride, size_t plane_stride, size_t records_off) {
   const MixerCall &mc = *mixer;
   const size_t es = sample_bytes(mc.out.fmt);
-  const size_t out_bytes = bus_stride * mc.buses->n_buses() * es;
+  const size_t records_bytes = mc.levels != nullptr ? sizeof(SpeexHipLevel) * mc.n_legs : 0;
+  const size_t out_bytes = records_bytes != 0 ? records_off + records_bytes : bus_stride * mc.buses->n_buses() * es;
   if (mc.bus_frames != 0) {
     if (!plan.small) HIP_TRY(hipMemcpyAsync(ms.h_out, ms.d_out, out_bytes, hipMemcpyDeviceToHost, ms.stream));
     count_mixer(5);
@@ -599,6 +633,7 @@ int Batch::ManyUnit::buses_out(size_t bus_stride, size_t plane_stride) {
         std::memcpy(to + c * mc.out.plane_stride * es, from + c * plane_stride * es, static_cast<size_t>(mc.bus_frames) * es);
     }
   }
+  if (records_bytes != 0 && mc.bus_frames != 0) std::memcpy(mc.levels, ms.h_out + records_off, records_bytes);
   return SPEEXHIP_ERR_SUCCESS;
 }
 

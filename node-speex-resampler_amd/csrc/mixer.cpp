@@ -77,6 +77,7 @@ Mixer::~Mixer() {
   DeviceScope scope(device_);
   // (process is synchronous and the control calls wait for their copies: nothing of the mixer's is in flight)
   buses_.release();
+  pool::device_put(device_, d_level_parts_);
   pool::device_put(device_, d_w_);
   pool::stream_put(device_, stream_);
 }
@@ -140,6 +141,22 @@ int Mixer::get_bus_meter(uint32_t bus, SpeexHipMeter *m, bool reset) {
   return buses_.get_meter(bus, m, reset, stream_);
 }
 
+int Mixer::set_levels(int on) {
+  if (on != 0 && on != 1) return SPEEXHIP_ERR_INVALID_ARG;
+  if ((on != 0) == levels_on_) return SPEEXHIP_ERR_SUCCESS;  // (no change: the snapshot stays)
+  levels_on_ = on != 0;
+  levels_.assign(levels_on_ ? n_legs_ : 0, SpeexHipLevel{});
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
+int Mixer::get_levels(uint32_t first, uint32_t count, void *levels, uint32_t struct_size) const {
+  if (levels == nullptr || struct_size < sizeof(SpeexHipLevel) || first > n_legs_ || count > n_legs_ - first) return SPEEXHIP_ERR_INVALID_ARG;
+  if (!levels_on_) return SPEEXHIP_ERR_BAD_STATE;
+  for (uint32_t k = 0; k < count; k++)
+    std::memcpy(static_cast<char *>(levels) + static_cast<size_t>(k) * struct_size, &levels_[first + k], sizeof(SpeexHipLevel));
+  return SPEEXHIP_ERR_SUCCESS;
+}
+
 int Mixer::process(Batch *const *legs, const CallSide *in, const uint8_t *bad, uint32_t *in_len, uint32_t *out_len,
                    const CallSide &out_side, uint32_t *bus_frames, int *codes) {
   // ---- the call's own errors: nothing touched, codes not written
@@ -192,6 +209,14 @@ int Mixer::process(Batch *const *legs, const CallSide *in, const uint8_t *bad, u
   mc.out = out;
   mc.bus_route = bus_route;
   mc.buses = &buses_;
+  if (levels_on_) {
+    // (from here on the call touches things: the snapshot is this call's -- zeros until the unit has filled it, and so
+    //  after a unit that failed and after a call of bus_frames 0)
+    levels_.assign(n_legs_, SpeexHipLevel{});
+    mc.levels = levels_.data();
+    mc.level_parts = &d_level_parts_;
+    mc.level_parts_cap = &level_parts_cap_;
+  }
   int unit_rc;
   try {
     unit_rc = Batch::many_mixer(mc, n_legs_, entries.data(), in_len, out_len, rcs.data());
@@ -202,6 +227,7 @@ int Mixer::process(Batch *const *legs, const CallSide *in, const uint8_t *bad, u
     // (as in the many-states calls: the unit's failure is the code of every leg it was to run)
     for (uint32_t i = 0; i < n_legs_; i++)
       if (entries[i].b != nullptr && entries[i].rc == SPEEXHIP_ERR_SUCCESS) rcs[i] = unit_rc;
+    if (levels_on_) levels_.assign(n_legs_, SpeexHipLevel{});
   } else {
     // what the call moved beside its legs: the buses' totals and the one bus position
     buses_.moved(bus_route, mc.bus_frames);

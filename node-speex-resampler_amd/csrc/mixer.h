@@ -30,6 +30,10 @@ class Mixer {
   int set_meter(int on);
   int get_bus_meter(uint32_t bus, SpeexHipMeter *m, bool reset);
   uint64_t bus_position() const { return buses_.position(); }
+  // "Mixer levels": the switch (a change clears the snapshot) and the last process call's records of the slots
+  // [first, first + count), struct_size bytes apart.  BAD_STATE while off.
+  int set_levels(int on);
+  int get_levels(uint32_t first, uint32_t count, void *levels, uint32_t struct_size) const;
   // One tick (the header's speexhip_mixer_process): legs[i] = the state in slot i or nullptr, in[i] its input side in
   // host memory, bad[i] != 0 (bad may be null) = a side the caller could not read.  Synchronous.
   int process(Batch *const *legs, const CallSide *in, const uint8_t *bad, uint32_t *in_len, uint32_t *out_len, const CallSide &out,
@@ -50,6 +54,10 @@ class Mixer {
   std::vector<float> w_;           // W as the caller gave it
   char *d_w_ = nullptr;            // its transpose, padded (kernels.h, BusLegsArgs::w)
   BusOutput buses_;                // behind the sum (seed_base = n_legs); the cells zeroed by init and by set_weights
+  bool levels_on_ = false;
+  std::vector<SpeexHipLevel> levels_;  // the snapshot: n_legs records of the last call, while the levels are on
+  char *d_level_parts_ = nullptr;      // the spans' partials of a call whose legs are longer than one span (kernels.h)
+  size_t level_parts_cap_ = 0;         // bytes; grow-only, like the buses' image
 };
 
 }  // namespace speexhip

@@ -326,6 +326,10 @@ export declare class SpeexResamplerMixer {
     getDither(): { kind: DitherKind, seed: bigint, position: bigint };
     setMeter(on: boolean): void;
     getBusMeter(j: number, options?: { reset?: boolean }): MeterTotals;
+    /** per-leg levels of every tick, measured on the device; off by default, a change clears the last tick's records */
+    setLevels(on: boolean): void;
+    /** the last tick's record of every slot, measured BEFORE the leg's gain; audioLevel is the RFC 6464 value (0 .. 127) */
+    getLevels(): { samples: BigUint64Array, energy: BigUint64Array, nan: BigUint64Array, peak: Float32Array, audioLevel: Uint8Array };
     /**
      * One tick, synchronously: chunks[i] in inFormats[i] (one name for all slots or one per slot; null for an empty slot).
      * codes[i] !== 0: a leg the library refused -- its state untouched, silence in the sum.

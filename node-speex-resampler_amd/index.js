@@ -1023,6 +1023,29 @@ class SpeexResamplerMixer {
     return { on: v[0] !== 0, samples: big(1), clippedHigh: big(3), clippedLow: big(5), nan: big(7), peak: v[9] };
   }
 
+  /** per-leg levels of every tick, measured on the device (off by default; a change clears the last tick's records) */
+  setLevels(on) { speexModule.mixerSetLevels(this._native(), !!on); }
+
+  /**
+   * The last tick's record of every slot, measured on the leg's output BEFORE its gain: { samples, energy, nan
+   * (BigUint64Array), peak (Float32Array, int16 units), audioLevel (Uint8Array: RFC 6464, 0 loudest .. 127) }.
+   */
+  getLevels() {
+    const raw = speexModule.mixerGetLevels(this._native());
+    const n = this.nLegs;
+    const view = new DataView(raw.buffer, raw.byteOffset, raw.byteLength);
+    const out = { samples: new BigUint64Array(n), energy: new BigUint64Array(n), nan: new BigUint64Array(n), peak: new Float32Array(n), audioLevel: new Uint8Array(n) };
+    for (let i = 0; i < n; i++) {
+      out.samples[i] = view.getBigUint64(32 * i, true);
+      out.energy[i] = view.getBigUint64(32 * i + 8, true);
+      out.nan[i] = view.getBigUint64(32 * i + 16, true);
+      out.peak[i] = view.getFloat32(32 * i + 24, true);
+      const e = Number(out.energy[i]), s = Number(out.samples[i]);
+      out.audioLevel[i] = e === 0 || s === 0 ? 127 : Math.min(127, Math.max(0, Math.round(-10 * Math.log10(e / (s * 2 ** 30)))));
+    }
+    return out;
+  }
+
   /**
    * One tick, synchronously.  chunks[i]: the Buffer of slot i's interleaved frames in its input format (null / undefined
    * for an empty slot; an empty Buffer: the leg runs on nothing); inFormats: one of processChunkFormat's names for all

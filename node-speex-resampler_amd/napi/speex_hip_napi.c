@@ -2052,6 +2052,33 @@ static napi_value MixerGetBusMeter(napi_env env, napi_callback_info info) {
   return arr;
 }
 
+/* mixerSetLevels(handle, on) */
+static napi_value MixerSetLevels(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  MixerHandle *h = argc >= 2 ? unwrap_mixer(env, argv[0]) : NULL;
+  if (h == NULL) return NULL;
+  bool on = false;
+  NAPI_OK(napi_get_value_bool(env, argv[1], &on));
+  return control_result(env, speexhip_mixer_set_levels(h->m, on ? 1 : 0));
+}
+
+/* mixerGetLevels(handle) -> Buffer of nLegs SpeexHipLevel records (32 bytes each, little-endian): the last call's */
+static napi_value MixerGetLevels(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  MixerHandle *h = argc >= 1 ? unwrap_mixer(env, argv[0]) : NULL;
+  if (h == NULL) return NULL;
+  void *data = NULL;
+  napi_value buf;
+  NAPI_OK(napi_create_buffer(env, (size_t)h->n_legs * sizeof(SpeexHipLevel), &data, &buf));
+  const int rc = speexhip_mixer_get_levels(h->m, 0, h->n_legs, data, (uint32_t)sizeof(SpeexHipLevel));
+  if (rc != 0) return control_result(env, rc);
+  return buf;
+}
+
 /* mixerProcess(handle, legs: (handle | null)[], chunks: (Buffer | null)[], inFrames[], caps[], inFmts[], outFmt)
  *   -> { buses: Buffer[], busFrames, consumed: number[], produced: number[], codes: number[] }
  * One speexhip_mixer_process call; the buses come interleaved in outFmt, bus j a fresh Buffer of busFrames frames.  A leg
@@ -2240,6 +2267,8 @@ NAPI_MODULE_INIT() {
       {"mixerGetDither", NULL, MixerGetDither, NULL, NULL, NULL, napi_default, NULL},
       {"mixerSetMeter", NULL, MixerSetMeter, NULL, NULL, NULL, napi_default, NULL},
       {"mixerGetBusMeter", NULL, MixerGetBusMeter, NULL, NULL, NULL, napi_default, NULL},
+      {"mixerSetLevels", NULL, MixerSetLevels, NULL, NULL, NULL, napi_default, NULL},
+      {"mixerGetLevels", NULL, MixerGetLevels, NULL, NULL, NULL, napi_default, NULL},
       {"mixerProcess", NULL, MixerProcess, NULL, NULL, NULL, napi_default, NULL},
   };
   if (napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props) != napi_ok)

@@ -132,8 +132,13 @@ EXPORTS = [
     "speexhip_mixer_init", "speexhip_mixer_init_on", "speexhip_mixer_destroy", "speexhip_mixer_set_weights",
     "speexhip_mixer_get_weights", "speexhip_mixer_set_dither", "speexhip_mixer_get_dither", "speexhip_mixer_set_meter",
     "speexhip_mixer_get_bus_meter", "speexhip_mixer_process", "speexhip_debug_mixer_counters",
+    # mixer levels: per-leg level records of every tick, measured on the device
+    "speexhip_mixer_set_levels", "speexhip_mixer_get_levels", "speexhip_debug_levels", "speexhip_debug_mixer_level_launches",
 ]
 MIXER_MAX_LEGS = MIXER_MAX_BUSES = 1024
+# SpeexHipLevel: one slot's record of one mixer call (32 bytes)
+LEVEL_DTYPE = np.dtype([("samples", np.uint64), ("energy", np.uint64), ("nan", np.uint64), ("peak", np.float32),
+                        ("reserved", np.uint32)])
 
 
 class Meter(C.Structure):
@@ -501,6 +506,16 @@ def lib():
             L.speexhip_mixer_process.argtypes = [p, p, C.POINTER(Side), pu32, pu32, C.POINTER(Side), pu32, C.POINTER(i32)]
             L.speexhip_debug_mixer_counters.restype = None
             L.speexhip_debug_mixer_counters.argtypes = [pu64]
+        if hasattr(L, "speexhip_mixer_set_levels") or "SPEEXHIP_LIB_PATH" not in os.environ:
+            # (as above: a build without the mixer's levels)
+            L.speexhip_mixer_set_levels.restype = i32
+            L.speexhip_mixer_set_levels.argtypes = [p, i32]
+            L.speexhip_mixer_get_levels.restype = i32
+            L.speexhip_mixer_get_levels.argtypes = [p, u32, u32, p, u32]
+            L.speexhip_debug_levels.restype = i32
+            L.speexhip_debug_levels.argtypes = [p, u32, p]
+            L.speexhip_debug_mixer_level_launches.restype = C.c_uint64
+            L.speexhip_debug_mixer_level_launches.argtypes = []
         _lib = L
     return _lib
 
@@ -741,6 +756,31 @@ def debug_mixer_counters():
     lib().speexhip_debug_mixer_counters(v)
     return dict(zip(("fir_launches", "in_passes", "bus_sum_launches", "out_passes", "transfers_in", "transfers_out"),
                     (int(x) for x in v)))
+
+
+def debug_mixer_level_launches():
+    """speexhip_debug_mixer_level_launches: launches of the mixer levels' kernels since start (apart from the six above)"""
+    return int(lib().speexhip_debug_mixer_level_launches())
+
+
+def debug_levels(y, into=None):
+    """host-only: the library's level statement (csrc/levels.h) over float32 values y in int16 units, accumulated into the
+    record `into` (a LEVEL_DTYPE array of one record; None: a fresh one).  Returns the record array."""
+    y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
+    rec = np.zeros(1, LEVEL_DTYPE) if into is None else into
+    rc = lib().speexhip_debug_levels(C.c_void_p(y.ctypes.data) if y.size else None, y.size, C.c_void_p(rec.ctypes.data))
+    if rc:
+        raise RuntimeError(strerror(rc))
+    return rec
+
+
+def audio_level(rec):
+    """The RFC 6464 audio level of a level record (a LEVEL_DTYPE record, or anything with 'energy' and 'samples'): -dBov
+    of the RMS, full scale = 2^15, as an integer 0 (loudest) .. 127; 127 for no energy or no samples."""
+    energy, samples = int(rec["energy"]), int(rec["samples"])
+    if energy == 0 or samples == 0:
+        return 127
+    return int(min(127, max(0, round(-10.0 * math.log10(energy / (samples * 2.0 ** 30))))))
 
 
 def chunk_counters():
@@ -1976,6 +2016,26 @@ class Mixer:
 
     def bus_position(self):
         return self.get_dither()[2]
+
+    def set_levels(self, on):
+        """Per-leg levels of every tick ("Mixer levels"): off by default; a change of the switch clears the snapshot.
+        Returns the C call's code."""
+        return lib().speexhip_mixer_set_levels(self._h, int(on))
+
+    def get_levels(self, first=0, count=None):
+        """The last process call's records of the slots [first, first + count) as a numpy structured array with the
+        fields samples, energy, nan, peak (LEVEL_DTYPE): the leg's float value BEFORE its gain.  ValueError for a range
+        beyond n_legs, RuntimeError while the levels are off."""
+        count = self.n_legs - first if count is None else count
+        if first < 0 or count < 0:
+            raise ValueError("a range of slots")
+        rec = np.zeros(max(count, 1), LEVEL_DTYPE)
+        rc = lib().speexhip_mixer_get_levels(self._h, int(first), int(count), C.c_void_p(rec.ctypes.data), LEVEL_DTYPE.itemsize)
+        if rc == ERR_INVALID_ARG:
+            raise ValueError(strerror(rc))
+        if rc:
+            raise RuntimeError(strerror(rc))
+        return rec[:count]
 
     def process_sides(self, legs, in_sides, in_lens, out_side, capacities):
         """speexhip_mixer_process itself: legs[i] a Resampler or None, in_sides[i] its Side (make_side; None for an empty

@@ -2,14 +2,19 @@
 // every rate pair of a grid incl. absurd ones, random positions / pending frames / capacities up to 2^32; and the
 // host-buffer calls' decisions (host_transfer.h, route_host_call; many_plan.h, plan_many_unit and plan_many_lanes -- the
 // functions the product calls; sides_route.h, route_sides_call) against their tables, the many-states one over random units
-// and the formatted calls' one over its whole input space as well.
+// and the formatted calls' one over its whole input space as well; and the statement of a mixer leg's level (levels.h) at
+// its decision points and over random floats.
 // Built and run by tests/test_cpu_sanitizers.py (GPU sanitizers are not available on the pool).
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <limits>
 #include <random>
 #include "devices.h"
 #include "filter_design.h"
 #include "host_transfer.h"
+#include "levels.h"
 #include "many_plan.h"
 #include "sides_route.h"
 #include "stream_plan.h"
@@ -619,6 +624,92 @@ bool check_sides_routes(long *rows, long *walked) {
 #undef ROUTE_EXPECT
   return true;
 }
+
+// ---- a mixer leg's level (levels.h: the lines the kernel leg_levels and speexhip_debug_levels compile) ----------------------
+// At its decision points against the step the header states, and over random floats -- every bit pattern, so NaNs of
+// either sign, infinities and denormals among them -- against a reference in integers: the step through long double, the
+// energy in uint64, the peak by comparing values.  Folded as the users fold: sample by sample (c_api.cpp) and a lane of
+// 256 at a time (the kernel).
+bool check_levels(std::mt19937 &rng, long *points, long *random) {
+  struct Point {
+    float y;
+    int q;  // the step; 1 << 30: a NaN
+  };
+  const float inf = std::numeric_limits<float>::infinity();
+  const Point at[] = {{0.5f, 1},          {-0.5f, 0},         {1.5f, 2},           {-1.5f, -1},   {0.49999997f, 0}, {-0.50000006f, -1},
+                      {32766.5f, 32767},  {32767.5f, 32767},  {-32768.5f, -32768}, {inf, 32767},  {-inf, -32768},   {-0.0f, 0},
+                      {1e30f, 32767},     {1e-42f, 0},        {-1e30f, -32768},    {32767.0f, 32767}, {-32768.0f, -32768},
+                      {std::numeric_limits<float>::quiet_NaN(), 1 << 30}};
+  for (const Point &p : at) {
+    levels::Lane lane;
+    levels::add(lane, p.y);
+    SpeexHipLevel rec = {};
+    levels::fold(rec, lane);
+    const bool nan = p.q == 1 << 30;
+    const uint64_t energy = nan ? 0 : static_cast<uint64_t>(static_cast<int64_t>(p.q) * p.q);
+    const float peak = nan ? 0.0f : std::fabs(p.y);
+    if (rec.energy != energy || rec.nan != (nan ? 1u : 0u) || rec.peak != peak || std::signbit(rec.peak) || rec.samples != 0 || rec.reserved != 0) {
+      printf("BAD level at %a: energy %llu nan %llu peak %a\n", p.y, static_cast<unsigned long long>(rec.energy),
+             static_cast<unsigned long long>(rec.nan), rec.peak);
+      return false;
+    }
+    (*points)++;
+  }
+  for (int round = 0; round < 200; round++) {
+    const uint32_t n = 1 + rng() % 3000;
+    const int kind = round % 3;  // every bit pattern; audio around the rails; whispers around the ties
+    SpeexHipLevel by_sample = {}, by_lane = {};
+    uint64_t energy = 0, nans = 0;
+    float peak = 0.0f;
+    levels::Lane lane;
+    uint32_t in_lane = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      float y;
+      if (kind == 0) {
+        const uint32_t bits = rng();
+        memcpy(&y, &bits, sizeof(y));
+      } else {
+        y = (static_cast<float>(rng()) / 4294967296.0f - 0.5f) * (kind == 1 ? 80000.0f : 6.0f);
+        if (kind == 2 && rng() % 8 == 0) y = std::floor(y) + 0.5f;  // (an exact tie)
+      }
+      if (y != y) {
+        nans++;
+      } else {
+        const long double r = std::floor(static_cast<long double>(y) + 0.5L);
+        const int64_t q = r < -32768.0L ? -32768 : r > 32767.0L ? 32767 : static_cast<int64_t>(r);
+        energy += static_cast<uint64_t>(q * q);
+        if (std::fabs(y) > peak) peak = std::fabs(y);
+      }
+      levels::Lane one;
+      levels::add(one, y);
+      levels::fold(by_sample, one);
+      levels::add(lane, y);
+      if (++in_lane == 256 || i + 1 == n) {
+        levels::fold(by_lane, lane);
+        lane = levels::Lane();
+        in_lane = 0;
+      }
+      (*random)++;
+    }
+    for (const SpeexHipLevel *rec : {&by_sample, &by_lane})
+      if (rec->energy != energy || rec->nan != nans || rec->peak != peak) {
+        printf("BAD level over %u random floats of kind %d: energy %llu (want %llu) nan %llu (%llu) peak %a (%a)\n", n, kind,
+               static_cast<unsigned long long>(rec->energy), static_cast<unsigned long long>(energy),
+               static_cast<unsigned long long>(rec->nan), static_cast<unsigned long long>(nans), rec->peak, peak);
+        return false;
+      }
+  }
+  // a lane at the limit of its chain: kLaneMost samples at the rail are 2^23 * 2^30 = 2^53, which fp64 still holds
+  levels::Lane full;
+  for (uint32_t i = 0; i < levels::kLaneMost; i++) levels::add(full, -40000.0f);
+  SpeexHipLevel rec = {};
+  levels::fold(rec, full);
+  if (rec.energy != (1ull << 53) || rec.peak != 40000.0f) {
+    printf("BAD level of a full lane: energy %llu\n", static_cast<unsigned long long>(rec.energy));
+    return false;
+  }
+  return true;
+}
 }  // namespace
 
 int main() {
@@ -818,8 +909,10 @@ int main() {
   if (!check_many_plans(&many_rows) || !check_many_invariants(rng, &many_random)) return 1;
   long sides_rows = 0, sides_walked = 0;
   if (!check_sides_routes(&sides_rows, &sides_walked)) return 1;
+  long level_points = 0, level_random = 0;
+  if (!check_levels(rng, &level_points, &level_random)) return 1;
   printf("sanitizer run ok: %ld filters, %ld plans, %ld placements, %ld routes, %ld many-states rows, %ld random many-states units, "
-         "%ld sides routes, %ld walked\n",
-         filters, plans, placements, routes, many_rows, many_random, sides_rows, sides_walked);
+         "%ld sides routes, %ld walked, %ld level points, %ld random level samples\n",
+         filters, plans, placements, routes, many_rows, many_random, sides_rows, sides_walked, level_points, level_random);
   return 0;
 }
